@@ -2,6 +2,7 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+    python bench.py ... --dump-outputs DIR                        (also writes the last timed step's scores as DIR/scores.npy)
 
 One "step" = one engine pass over one device-resident super-batch of synthetic (query, candidate) pairs of
 BASELINE.json's headline shape: Qwen2-7B dims, 96 video tokens + 32 text tokens per pair, top-16 candidates per
@@ -280,6 +281,23 @@ def build_step_plans(model, rank, n_plans, Q, K):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: writes each array of `arrays` ({name: numpy array}) as out_dir/<name>.npy in float32.  Past `limit` bytes in all, each array is cut
+    to a fixed, seeded sample of its flattened entries (the same positions on every run with the same arguments, so two builds stay comparable)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    room = limit - 128 * len(arrays)                                  # (one .npy header of 128 bytes per array)
+    for name, v in arrays.items():
+        if total > room:
+            keep = max(1, v.size * room // total)
+            v = v.reshape(-1)[np.sort(np.random.default_rng(seed).choice(v.size, size=keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), v)
+
+
 def launcher_command(gpus: int, argv, port: int = 0):
     """`python bench.py --gpus N` without a launcher around it: the command of the child that runs the ranks
     (torch.distributed.run, one process per GPU, rendezvous on 127.0.0.1 -- the reference's env:// init, util/misc.py:199-229)."""
@@ -318,9 +336,16 @@ def main():
     ap.add_argument("--no-strong", action="store_true", help="skip the fixed-size N = 1000 evaluation (strong-scaling leg)")
     ap.add_argument("--strong-only", action="store_true", help="only the strong-scaling leg (development aid; prints that object alone)")
     ap.add_argument("--strong-n", type=int, default=1000)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes the scores the last timed step returned (all ranks' rows when N > 1) as DIR/scores.npy (float32); "
+                         "the inputs are seeded, so two builds run with the same arguments can be compared entry by entry")
     ap.add_argument("--leg-timeout", type=int, default=420, help="seconds after which the legs behind the timed steps (strong scaling, compensated mode, CPU baseline) are given up: "
                                                                  "rank 0 prints the headline line with the timeout recorded in it (0 = no watchdog)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.strong_only:
+        ap.error("--dump-outputs writes what the timed steps computed; --strong-only runs none")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         # Invoked as plain `python bench.py --gpus N`: start the N ranks as a CHILD process group and exit with its code.  This
@@ -390,6 +415,10 @@ def main():
         dt = float(t.item())
         assert torch.equal(gathered[rank], mine), "all_gather returned other rows than this rank sent"
     assert torch.isfinite(mine).all(), "non-finite scores"
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after the last timed step: its score rows ([pairs]), all ranks' rows after the all-gather ([world, pairs])
+        last = torch.stack([g[-1] for g in gathered]) if pg else mine[-1]
+        dump_outputs(a.dump_outputs, {"scores": last.float().cpu().numpy()})
 
     # ---- per-kernel timing (HIP events on the launch stream) of one more step, for the roofline object
     model.engine.timing_enable(True)

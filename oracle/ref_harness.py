@@ -1,7 +1,8 @@
 """TEST INFRASTRUCTURE ONLY -- imports the reference's own modules from /root/reference, in place.
 
-Used by oracle/gen_golden.py (and by tests marked `needs_reference`, which skip when
-/root/reference is absent, i.e. on the GPU box).  Nothing from the reference is copied into this
+Used by the fixture generators oracle/gen_golden*.py; no test calls it (the tests read what the
+generators stored under tests/golden/; a test that imports a generator's case table imports this
+module with it, and it reads nothing at import time).  Nothing from the reference is copied into this
 repository: this file only sets up sys.path / stub modules so the reference's files import under
 the transformers version of this image (procedure of SURVEY.md Appendix A), and maps this repo's
 canonical weight names onto the reference's state_dict keys.

@@ -16,7 +16,15 @@ def _free_port():
     s = socket.socket(); s.bind(("127.0.0.1", 0)); p = s.getsockname()[1]; s.close(); return p
 
 
+def _cpu_rank():
+    """The ranks of these tests are CPU processes (gloo, host tensors).  torch's barrier() asks for the machine's accelerator before it picks the CPU
+    for a gloo group, and that question starts the GPU runtime: on a GPU machine every rank would hold the device.  Answer it with the CPU here."""
+    assert hasattr(torch._C, "_get_accelerator"), "torch no longer has _get_accelerator: find what barrier() asks now, or these ranks start the GPU runtime"
+    torch._C._get_accelerator = lambda: torch.device("cpu")
+
+
 def _worker(rank, world, port, n, m, out_q):
+    _cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     D.init_distributed_mode(backend="gloo")
     full = torch.from_numpy(np.random.RandomState(0).randn(n, m).astype(np.float32) - 5.0)
@@ -110,6 +118,7 @@ def _run_eval(n):
 
 
 def _eval_worker(rank, world, port, n, out_q):
+    _cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
     D.init_distributed_mode(backend="gloo")
     t2v, v2t, calls = _run_eval(n)
@@ -241,6 +250,7 @@ def test_pair_ownership_with_unequal_numbers_of_videos_and_texts():
 
 def _forced_worker(port, n, out_q):
     """World size 1 with a process group up and BLIM_FORCE_COLLECTIVE=1: the collective branches run (what the -m gpu tests do over RCCL on a one-GPU box)."""
+    _cpu_rank()
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", BLIM_FORCE_COLLECTIVE="1")
     D.init_distributed_mode(backend="gloo")
     assert D.force_collective()
@@ -277,6 +287,7 @@ def test_forced_collectives_at_world_size_one_change_no_bit():
 
 # ----------------------------------------------------------------------------- sharded calibration sample (`--vtg_precise` / `--tvg_precise auto` at W > 1)
 def _cal_worker(rank, world, port, out_q):
+    _cpu_rank()
     import types
     from blim_amd import retrieval_utils as RU
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))

@@ -346,15 +346,39 @@ def test_bench_launcher_command_plumbing():
     assert 1024 < port < 65536
 
 
+def test_bench_dump_outputs_keep_to_the_limit_with_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 files of what the timed path returned; past the byte limit a seeded sample of the same positions on every run.
+    Refused together with --strong-only (no timed steps to dump)."""
+    import importlib.util
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_dump_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec); spec.loader.exec_module(bench)
+    x = np.arange(4000, dtype=np.float64).reshape(40, 100)              # values name their positions
+    bench.dump_outputs(str(tmp_path / "whole"), {"scores": x[0]})
+    whole = np.load(tmp_path / "whole" / "scores.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, x[0])
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"sample{k}"
+        bench.dump_outputs(str(d), {"a": x, "b": x[:10]}, limit=8192)
+        assert sorted(f.name for f in d.iterdir()) == ["a.npy", "b.npy"] and sum(f.stat().st_size for f in d.iterdir()) <= 8192
+        runs.append({n: np.load(d / f"{n}.npy") for n in "ab"})
+    for n, src in (("a", x), ("b", x[:10])):
+        v = runs[0][n]
+        assert np.array_equal(v, runs[1][n]) and v.dtype == np.float32 and 0 < v.size < src.size
+        assert np.isin(v, src).all() and (np.diff(v) > 0).all()           # entries of the array, in position order, no repeats
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--strong-only", "--dump-outputs", str(tmp_path / "none")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--strong-only" in r.stderr and not (tmp_path / "none").exists()
+
+
 def test_coefficient_sweeps_match_the_reference_when_present():
-    """calculate_score / calculate_cpn_score (training_utils.py:106-140): brute-force property here; equality with the reference's own
-    functions when /root/reference is importable (build container only)."""
+    """calculate_score / calculate_cpn_score (training_utils.py:106-140): brute-force property here, and equality with what the reference's own
+    functions return on the same matrices (tests/golden/refcheck.npz, written by oracle/gen_golden_refcheck.py)."""
     from blim_amd import training_utils as TU
-    rs = np.random.RandomState(4)
-    n = 40
-    a, b = rs.randn(n, n).astype(np.float32) + 1.5 * np.eye(n, dtype=np.float32), rs.randn(n, n).astype(np.float32) + 0.5 * np.eye(n, dtype=np.float32)
-    c, d = rs.randn(n, n).astype(np.float32) + 1.0 * np.eye(n, dtype=np.float32), rs.randn(n, n).astype(np.float32)
-    ids = {i: i for i in range(n)}
+    from oracle.gen_golden_refcheck import coefficient_inputs
+    a, b, c, d, ids = coefficient_inputs()
     t2v, v2t, ct, cv = TU.calculate_score(a, b, c, d, ids, ids)
     grid = [round(float(x), 1) for x in np.linspace(0, 1, 11)]
     r1 = lambda m: TU.get_recall(m, m, ids, ids)["t2v_r1"]
@@ -362,12 +386,10 @@ def test_coefficient_sweeps_match_the_reference_when_present():
     assert np.allclose(t2v, ct * a + (1 - ct) * c) and np.allclose(v2t, cv * b + (1 - cv) * d)
     p2t, p2v, pt, pv = TU.calculate_cpn_score(a, b, c, d, ids, ids)
     assert np.allclose(p2t, a - pt * c) and np.allclose(p2v, b - pv * d)
-    from oracle import ref_harness
-    if ref_harness.available():
-        R = ref_harness.load().TU
-        for mine, ref in ((TU.calculate_score(a, b, c, d, ids, ids), R.calculate_score(a, b, c, d, ids, ids)),
-                          (TU.calculate_cpn_score(a, b, c, d, ids, ids), R.calculate_cpn_score(a, b, c, d, ids, ids))):
-            assert mine[2:] == ref[2:] and np.array_equal(mine[0], ref[0]) and np.array_equal(mine[1], ref[1])
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "refcheck.npz"))
+    for tag, mine in (("score", (t2v, v2t, ct, cv)), ("cpn", (p2t, p2v, pt, pv))):
+        assert list(mine[2:]) == list(g[f"{tag}_coef"]), tag
+        assert np.array_equal(mine[0], g[f"{tag}_m0"]) and np.array_equal(mine[1], g[f"{tag}_m1"]), tag
 
 
 def test_host_thread_cap_is_sane(monkeypatch):

@@ -102,11 +102,13 @@ def _same_npz(a, b, rtol=0.0):
         assert np.array_equal(a[k].view(np.uint32) if a[k].dtype == np.float32 else a[k], b[k].view(np.uint32) if b[k].dtype == np.float32 else b[k]), k
 
 
-@pytest.mark.parametrize("n, extra", [(19, []), (19, ["--no_dedup"]), (5, [])], ids=["N19-short-and-empty-blocks", "N19-six-passes", "N5-fewer-rows-than-ranks"])
-def test_eight_ranks_through_the_real_engine_give_the_single_process_matrices(tmp_path, n, extra):
-    """The 8-rank job the driver's scaling run starts, with the REAL engine in every rank: eight processes on cuda:0 (gloo in place of RCCL so that they can share the
-    device), `--cpn`, both settings of pair ownership.  N = 19 at W = 8 is the reference's `step = N // W + 1 = 3` (retrieval_utils.py:213-215): six blocks of three
-    rows, one of ONE row and an EMPTY one; N = 5: three ranks own nothing at all.  Calibration (`--vtg_precise / --tvg_precise auto`) is sharded over the eight ranks and
+@pytest.mark.parametrize("n, extra", [(5, []), (19, ["--no_dedup"]), (3, [])], ids=["N5-short-and-empty-blocks", "N19-six-passes", "N3-fewer-rows-than-ranks"])
+def test_four_ranks_through_the_real_engine_give_the_single_process_matrices(tmp_path, n, extra):
+    """A multi-rank job of the kind the driver's scaling run starts, with the REAL engine in every rank: four processes on cuda:0 (gloo in place of RCCL so that they can
+    share the device; at most four: with the launcher, whose torch.cuda.is_available() starts the GPU runtime, and the test process that is the six processes a
+    GPU may be held by), `--cpn`, both settings of pair ownership.
+    N = 5 at W = 4 is the reference's `step = N // W + 1 = 2` (retrieval_utils.py:213-215): two blocks of two rows, one of ONE row and an EMPTY one; N = 19: blocks
+    of 5, 5, 5 and 4 rows; N = 3: fewer rows than ranks.  Calibration (`--vtg_precise / --tvg_precise auto`) is sharded over the four ranks and
     gathered, the TVG clip features are projected per block and all-gathered, the prior is text-sharded, all matrices merge in one all-gather -- and the recall table
     and every score matrix must equal the one-process run bit for bit (/root/reference/retrieval_utils.py:213-215, 233-235, 252-262).  `--no_dedup` keeps the reference's
     six row-sharded passes: there a v2t TVG pair shares its merged sequence (PairScorer._plan_tvg: the candidates of one text, segments of ONE sequence) with whichever
@@ -120,38 +122,40 @@ def test_eight_ranks_through_the_real_engine_give_the_single_process_matrices(tm
     r1 = subprocess.run([sys.executable, "-m", "blim_amd.main"] + common + ["--output_dir", str(tmp_path / "w1"), "--dump_scores", str(tmp_path / "w1.npz")], cwd=root, env=env,
                         capture_output=True, text=True, timeout=600)
     assert r1.returncode == 0, r1.stderr[-2000:]
-    env8 = dict(env, BLIM_DIST_BACKEND="gloo", BLIM_FORCE_DEVICE="0", OMP_NUM_THREADS="1")
-    r8 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
-                         "--master-port", str({(19, 0): 29571, (19, 1): 29573, (5, 0): 29575}[(n, len(extra))]), "-m", "blim_amd.main"] + common + ["--output_dir", str(tmp_path / "w8"), "--dump_scores", str(tmp_path / "w8.npz")],
-                        cwd=root, env=env8, capture_output=True, text=True, timeout=900)
-    assert r8.returncode == 0, r8.stderr[-3000:]
-    assert "world size 8" in r8.stdout
-    t1, t8 = open(tmp_path / "w1" / "log.txt").read(), open(tmp_path / "w8" / "log.txt").read()
-    assert "blim" in t1 and t1 == t8
-    _same_npz(np.load(tmp_path / "w1.npz"), np.load(tmp_path / "w8.npz"), rtol=2e-6 if extra else 0.0)
+    env4 = dict(env, BLIM_DIST_BACKEND="gloo", BLIM_FORCE_DEVICE="0", OMP_NUM_THREADS="1")
+    r4 = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+                         "--master-port", str({(5, 0): 29571, (19, 1): 29573, (3, 0): 29575}[(n, len(extra))]), "-m", "blim_amd.main"] + common + ["--output_dir", str(tmp_path / "w4"), "--dump_scores", str(tmp_path / "w4.npz")],
+                        cwd=root, env=env4, capture_output=True, text=True, timeout=900)
+    assert r4.returncode == 0, r4.stderr[-3000:]
+    assert "world size 4" in r4.stdout
+    t1, t4 = open(tmp_path / "w1" / "log.txt").read(), open(tmp_path / "w4" / "log.txt").read()
+    assert "blim" in t1 and t1 == t4
+    _same_npz(np.load(tmp_path / "w1.npz"), np.load(tmp_path / "w4.npz"), rtol=2e-6 if extra else 0.0)
 
 
-def test_bench_gpus_8_on_one_gpu_keeps_the_json_contract(tmp_path):
-    """`python bench.py --gpus 8` as the driver's scaling run invokes it -- the parent starts torch.distributed.run with eight ranks -- here with all eight on cuda:0
-    over gloo (the 7B replica is 15 GB: eight fit one MI355X): one JSON line from rank 0, `n_gpus: 8`, whole-job pairs/s = 8 ranks' pairs / the slowest rank's time,
-    weak scaling, the strong-scaling leg's fixed job run by all eight ranks with its collectives."""
+def test_bench_gpus_4_on_one_gpu_keeps_the_json_contract(tmp_path):
+    """`python bench.py --gpus N` as the driver's scaling run invokes it -- the parent starts torch.distributed.run with N ranks -- here N = 4 with all four on cuda:0
+    over gloo (the 7B replica is 15 GB; at most four ranks: with the launcher, whose torch.cuda.is_available() starts the GPU runtime, and the test process that is
+    the six processes a GPU may be held by): one JSON line from
+    rank 0, `n_gpus: 4`, whole-job pairs/s = 4 ranks' pairs / the slowest rank's time, weak scaling, the strong-scaling leg's fixed job run by all four ranks with
+    its collectives."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PYTHONPATH=root, BLIM_DIST_BACKEND="gloo", BLIM_FORCE_DEVICE="0", OMP_NUM_THREADS="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96"], cwd=root, env=env,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96"], cwd=root, env=env,
                        capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     d = json.loads(lines[0])
-    assert d["n_gpus"] == 8 and d["scaling"] == "weak" and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["higher_is_better"] is True
-    assert abs(d["value"] - 8 * d["config"]["pairs_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]        # whole-job aggregate over the 8 ranks
+    assert d["n_gpus"] == 4 and d["scaling"] == "weak" and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["higher_is_better"] is True
+    assert abs(d["value"] - 4 * d["config"]["pairs_per_step_per_gpu"] / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]        # whole-job aggregate over the 4 ranks
     assert "cpu_baseline" not in d and "roofline" in d and d["roofline"]["frac"] > 0
     ss = d["strong_scaling"]
-    assert ss["world"] == 8 and ss["finite"] is True and ss["pairs"] == 6 * 96 * 16 and "emulated_world" not in ss
+    assert ss["world"] == 4 and ss["finite"] is True and ss["pairs"] == 6 * 96 * 16 and "emulated_world" not in ss
 
 
 def _rccl_env(root, port):

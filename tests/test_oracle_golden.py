@@ -137,26 +137,18 @@ def test_cpn_prior_is_query_independent(tiny):
             assert np.ptp(vals) < 1e-5
 
 
-@pytest.mark.needs_reference
 def test_reference_importable_and_agrees_on_one_layer(tiny):
-    """Build container only: run the reference itself on one ragged batch and compare with the oracle."""
-    import torch
-    from oracle import ref_harness
-    m, prob, cfg, w = tiny["m"], tiny["prob"], tiny["cfg"], tiny["w"]
-    ref = ref_harness.build_model(cfg, w)
+    """One ragged batch (VTG rows 1 and 4 of the tiny case) against the reference's own sequence assembly and decoder output on it: oracle/gen_golden_refcheck.py
+    imports and runs the reference and stores what it returns in tests/golden/refcheck.npz, so the check runs wherever the repository does."""
+    from oracle.gen_golden_refcheck import LAYER_ROWS
+    g = np.load(os.path.join(GOLD, "refcheck.npz"))
+    m, prob = tiny["m"], tiny["prob"]
     ids, lab, msk = tiny["vtg"]
-    sel = [1, 4]
+    sel = LAYER_ROWS
     mask, cpn, emb, lab2 = m.prepare_inputs_labels_for_multimodal(ids[sel], msk[sel], lab[sel], [prob.video[i] for i in sel])
-    T = lambda a: torch.from_numpy(np.asarray(a))
-    with torch.no_grad():
-        # the reference's own sequence assembly (it also sets model.llm_compress_layer_list, which forward reads)
-        r = ref.prepare_inputs_labels_for_multimodal(T(ids[sel]), None, T(msk[sel]), None, T(lab[sel]), [T(prob.video[i]) for i in sel],
-                                                     ["video"] * 2, image_sizes=None, video_feature=True, cpn=True)
-        (_, _, (m_r, c_r), _, e_r, l_r) = r
-        assert np.array_equal(m_r.numpy(), mask) and np.array_equal(c_r.numpy(), cpn) and np.array_equal(l_r.numpy(), lab2)
-        np.testing.assert_allclose(e_r.numpy(), emb, atol=1e-6)
-        out = ref(inputs_embeds=e_r, attention_mask=m_r)
-    np.testing.assert_allclose(m.forward_hidden(emb, mask), out.hidden_states.numpy(), atol=2e-5)
+    assert np.array_equal(g["layer_mask"], mask) and np.array_equal(g["layer_cpn"], cpn) and np.array_equal(g["layer_labels"], lab2)
+    np.testing.assert_allclose(g["layer_embeds"], emb, atol=1e-6)
+    np.testing.assert_allclose(m.forward_hidden(emb, mask), g["layer_hidden"], atol=2e-5)
 
 
 def test_oracle_at_depth_28_layers_h1024():
