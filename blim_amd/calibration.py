@@ -8,6 +8,7 @@ item 7): `predicted_max_deviation` (the tail extrapolation), `calibration_pairs`
 from __future__ import annotations
 
 import math
+import time
 from typing import Optional
 
 import numpy as np
@@ -19,7 +20,29 @@ TVG_MODES = ("attn", "full")     # compensation of the TVG calls (always hi + lo
 VTG_MODES = ("none", "full")     # compensation of the VTG calls: plain 16-bit, or every activation as hi + lo (0.67x the plain rate on fp16 engines with the e2m3 second
                                  # pass).  Round 4 had four modes between the two (qk, qkx, attn, act0: 0.975 ... 0.70x); on the weight sets where plain fails they
                                  # either failed too or sat at the edge of the bar, and each was a kernel variant, an engine option and a calibration pass: removed.
-VTG_SPLIT_MODES = ("full",)      # modes whose VTG rows (embeddings, features) travel as [hi | lo]
+VTG_SPLIT_MODES = ("full", "select")   # modes whose VTG rows (embeddings, features) travel as [hi | lo]
+VTG_UNIT_CLASSES = "AOGD"        # `--vtg_precise select`: bit k of a layer's mask = unit class k -- QKV + attention, o_proj, gate|up, down (include/blim.h)
+
+
+def vtg_select_units(num_layers: int, group: int = 4):
+    """The units calibrate_vtg_select decides on: every GEMM class x every group of `group` consecutive layers -> [(class bit, first layer, end layer)], class-major."""
+    return [(c, g0, min(num_layers, g0 + group)) for c in range(4) for g0 in range(0, num_layers, group)]
+
+
+def vtg_unit_mask(num_layers: int, plain_units) -> np.ndarray:
+    """uint8 [num_layers]: all four bits set except the classes of `plain_units` in their layers."""
+    m = np.full(num_layers, 15, dtype=np.uint8)
+    for c, a, b in plain_units:
+        m[a:b] &= np.uint8(15 & ~(1 << c))
+    return m
+
+
+def vtg_unit_flops(dims, unit) -> float:
+    """Second-pass GEMM FLOPs per token that leaving `unit` plain saves (the attention's extra products are left out: a few % of the QKV unit's)."""
+    c, a, b = unit
+    H, I = dims.hidden_size, dims.intermediate_size
+    per = (2.0 * H * (dims.num_heads + 2 * dims.num_kv_heads) * dims.head_dim, 2.0 * H * H, 4.0 * H * I, 2.0 * H * I)[c]
+    return per * (b - a)
 
 
 def predicted_max_deviation(dev, n_eval: Optional[int]) -> float:
@@ -109,7 +132,7 @@ class CalibrationMixin:
         limit = tail_margin * bar if (n_eval or 0) > n_sampled else bar
         return bool(finite and st["max"] <= bar and z * st["rms"] <= bar), bool(st["pred"] <= limit)
 
-    def _decide(self, measure, pairs, confirm_pairs, share, n_eval, bar, z, tail_margin, cheap, full, adopt=None):
+    def _decide(self, measure, pairs, confirm_pairs, share, n_eval, bar, z, tail_margin, cheap, full, adopt=None, force_confirm=False):
         """The decision both calibrations share.  measure(block) -> list of deviation arrays (one per law: VTG one, TVG likelihood and prior) of the CHEAP mode from the
         fully compensated one on this rank's block, already gathered over the ranks.
 
@@ -123,7 +146,8 @@ class CalibrationMixin:
         entries is already ~ 2e-3.  Every rank sees the same gathered deviations, so every rank takes the same branch (the stage-2 gathers are collective).
         adopt = (mode, confirmed): one process PLAYING a rank of a W-process job (`--shard`, bench.py's emulated ranks) has nobody to gather from and would decide on
         1 / W of the sample; handed the job-wide outcome, it measures its block of the same stages the job ran -- the cost a rank's share stands for -- and takes the
-        job's decision."""
+        job's decision.  force_confirm: stage 2 runs whenever the sample passes, not only when its extrapolation misses (calibrate_vtg_select: a mask that
+        was picked AS the largest one passing the sample is confirmed on the larger one before it is trusted)."""
         n_all = len(pairs)
         block, sh = self._my_block(pairs, share)
         devs = measure(block, sh)
@@ -133,7 +157,7 @@ class CalibrationMixin:
         ok_sample, ok_tail = self._passes(devs, st, n_eval, n_all, bar, z, tail_margin)
         entry = dict(st)
         chosen = cheap if (ok_sample and ok_tail) else full
-        go_on = (ok_sample and not ok_tail) if adopt is None else bool(adopt[1])
+        go_on = (ok_sample and (force_confirm or not ok_tail)) if adopt is None else bool(adopt[1])
         if go_on and confirm_pairs is not None and len(confirm_pairs):
             seen = {(int(a), int(b)) for a, b in np.asarray(pairs)}
             extra = np.array([p for p in np.asarray(confirm_pairs, dtype=np.int64) if (int(p[0]), int(p[1])) not in seen], dtype=np.int64).reshape(-1, 2)
@@ -180,6 +204,114 @@ class CalibrationMixin:
         self.set_vtg_mode(chosen)
         resolve(chosen)
         return chosen, {"none": entry}
+
+    def _vtg_select_measure(self, mask, block) -> np.ndarray:
+        """calibrate_vtg_select's default measurement: relative deviation of this rank's `block` of pairs from the fully compensated mode, with the per-layer mask `mask`
+        (uint8 [num_layers]) or plain (None).  The compensated reference of a block is scored once."""
+        cache = self.__dict__.setdefault("_select_ref", {})
+        key = np.ascontiguousarray(block).tobytes()
+        if key not in cache:
+            self.set_vtg_mode("full")
+            cache[key] = self.vtg(block).astype(np.float64)
+        ref = cache[key]
+        if mask is None:
+            self.set_vtg_mode(None)
+        else:
+            self.engine.set_layer_mask(mask)
+            self.set_vtg_mode("select")
+        return np.abs(self.vtg(block).astype(np.float64) - ref) / np.abs(ref)
+
+    def calibrate_vtg_select(self, pairs, bar: float = 1e-3, z: float = 4.5, n_eval: Optional[int] = None, tail_margin: float = 0.8, share=None, confirm_pairs=None,
+                             group: int = 4, n_sens: int = 64, max_probes: int = 5, measure=None):
+        """`--vtg_precise select`: which (layer group, GEMM class) units of the VTG calls may run plain on the loaded weights, measured on the evaluation's own pairs.
+        1. plain against fully compensated, exactly as calibrate_vtg: if plain passes, it is taken ("none").
+        2. Sensitivity: 4 classes x ceil(L / group) layer groups; on the first `n_sens` pairs of the sample, the deviation from `full` with only that unit plain.
+        3. The units in order of rms deviation per second-pass FLOP saved, lowest first (ties: class-major unit order).
+        4. Bisection on k, the number of leading units left plain (k = 0 is `full`), each candidate judged on the whole sample by `_passes`, in <= max_probes calls
+           (the deviation grows with k on the weight sets seen; the bisection assumes it).
+        5. The chosen mask goes through `_decide` with its stage 2 forced (the confirmation sample); a reject halves k, at most twice, then the mask is all ones.
+        Every rank sees the same gathered deviations and takes the same branches, so every rank picks the same mask.  measure(mask | None, block) -> relative
+        deviations of this rank's block (default: _vtg_select_measure).  Returns ("none" | "select", table); the table holds the mask, the per-unit sensitivities,
+        the probes and the calibration seconds."""
+        t0 = time.time()
+        pairs = np.asarray(pairs, dtype=np.int64)
+        resolve = getattr(self.m, "resolve_vtg", lambda mode, mask=None: None)
+        if not bool(getattr(self.engine, "can_precise", False)):
+            self.set_vtg_mode(None)
+            resolve("none")
+            return "none", {}
+        L = int(self.m.dims.num_layers)
+        ones = np.full(L, 15, dtype=np.uint8)
+        self.engine.set_layer_mask(ones)                     # whatever an earlier measurement left: the full form first
+        if measure is None:
+            self.__dict__["_select_ref"] = {}
+            measure = self._vtg_select_measure
+
+        def gathered(mask, block, sh):
+            return self._gather_dev(measure(mask, block) if len(block) else np.zeros(0), sh)
+
+        chosen, entry = self._decide(lambda b, sh: [gathered(None, b, sh)], pairs, confirm_pairs, share, n_eval, bar, z, tail_margin, "none", "full")
+        table = {"none": entry}
+        if chosen == "none":
+            self.set_vtg_mode(None)
+            resolve("none")
+            table["seconds"] = time.time() - t0
+            return "none", table
+
+        units = vtg_select_units(L, group)
+        blk, sh = self._my_block(pairs[:n_sens], share)
+        rows = []
+        for u in units:
+            d = gathered(vtg_unit_mask(L, [u]), blk, sh)
+            st = self._stats(d, None)
+            rms = st["rms"] if np.all(np.isfinite(d)) else math.inf
+            rows.append({"unit": f"{VTG_UNIT_CLASSES[u[0]]}{u[1]}-{u[2] - 1}", "max": st["max"], "rms": rms, "flops": vtg_unit_flops(self.m.dims, u)})
+        order = sorted(range(len(units)), key=lambda i: (rows[i]["rms"] / rows[i]["flops"], i))
+        table["units"] = rows
+        table["order"] = [rows[i]["unit"] for i in order]
+        mask_of = lambda k: vtg_unit_mask(L, [units[i] for i in order[:k]])
+
+        memo = {}
+
+        def measure_k(k):
+            def m_(block, sh_):
+                key = (k, np.ascontiguousarray(block).tobytes())
+                if key not in memo:
+                    memo[key] = gathered(mask_of(k), block, sh_)
+                return [memo[key]]
+            return m_
+
+        blk_all, sh_all = self._my_block(pairs, share)
+        probes = []
+        lo, hi = 0, len(units) + 1                          # k = lo passes (the full form); k = hi is a sentinel above every candidate
+        while hi - lo > 1 and len(probes) < max_probes:
+            k = (lo + hi) // 2
+            d = measure_k(k)(blk_all, sh_all)[0]
+            st = self._stats(d, n_eval)
+            ok_s, ok_t = self._passes([d], st, n_eval, len(pairs), bar, z, tail_margin)
+            probes.append(dict(st, k=k, passed=bool(ok_s and ok_t)))
+            if ok_s and ok_t:
+                lo = k
+            else:
+                hi = k
+        table["probes"] = probes
+        k, confirms = lo, []
+        for attempt in range(3):
+            if k == 0:
+                break
+            c_, e_ = self._decide(measure_k(k), pairs, confirm_pairs, share, n_eval, bar, z, tail_margin, k, 0, force_confirm=True)
+            confirms.append(dict(e_, k=k, accepted=c_ == k))
+            if c_ == k:
+                break
+            k = k // 2 if attempt < 2 else 0
+        table["confirm"] = confirms
+        mask = mask_of(k)
+        table["k"], table["mask"] = int(k), [int(b) for b in mask]
+        self.engine.set_layer_mask(mask)
+        self.set_vtg_mode("select")
+        resolve("select", mask)
+        table["seconds"] = time.time() - t0
+        return "select", table
 
     def calibrate_tvg(self, pairs, bar: float = 1e-3, z: float = 4.5, n_eval: Optional[int] = None, tail_margin: float = 0.8, share=None, confirm_pairs=None, adopt=None):
         """The TVG calls' counterpart of calibrate_vtg (same criterion, same yardstick = the fully compensated mode).  Every TVG call of a 16-bit engine carries its

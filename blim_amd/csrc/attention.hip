@@ -24,7 +24,10 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 // the head grouping (G >= 4: up to 512 threads; G = 2, 3: <= 192; G = 1: 64), so the few-thread variants -- whose threads each stage a large share of
 // the tile -- get the registers of the waves that are not there instead of spilling (MHA, compensated: 450 VGPRs spilled under a 512-thread bound).
 template <int MAXC, bool SPLIT> struct attn_bound { static constexpr int value = MAXC <= (SPLIT ? 8 : 4) ? 512 : MAXC <= (SPLIT ? 16 : 8) ? 256 : 64; };
-template <bool USE_TR, int MAXC, int DT, bool SPLIT = false>
+// SPLIT: three-term products over Q, K, V = hi + lo (compensated mode); OUT_LO: the output leaves as hi + lo.  Both or neither is the whole-call form; the two mixed forms
+// are the per-layer mask's (engine option "precise_layers"): plain products with a [hi | lo] output store (QKV plain, o_proj compensated) and split products with a
+// hi-only store (QKV compensated, o_proj plain)
+template <bool USE_TR, int MAXC, int DT, bool SPLIT = false, bool OUT_LO = SPLIT>
 __global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(const AttnParams p) {
     __shared__ __attribute__((aligned(16))) bf16_t k_lds[(SPLIT ? 2 : 1) * KT * HD];   // SPLIT: K_hi tile, then K_lo tile
     __shared__ __attribute__((aligned(16))) bf16_t v_lds[(SPLIT ? 2 : 1) * KT * HD];   // SPLIT: V_hi tile, then V_lo tile
@@ -319,7 +322,7 @@ __global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(
                 const int d = 32 * db + 8 * g + 4 * hf;
                 const float x0 = o[db][4 * g] * inv, x1 = o[db][4 * g + 1] * inv, x2 = o[db][4 * g + 2] * inv, x3 = o[db][4 * g + 3] * inv;
                 *(uint2*)(orow + d) = make_uint2(pack2<DT>(x0, x1), pack2<DT>(x2, x3));
-                if constexpr (SPLIT)
+                if constexpr (OUT_LO)
                     *(uint2*)(orow + p.out_lo_off + d) = make_uint2(pack2<DT>(x0 - from16<DT>(to16<DT>(x0)), x1 - from16<DT>(to16<DT>(x1))),
                                                                     pack2<DT>(x2 - from16<DT>(to16<DT>(x2)), x3 - from16<DT>(to16<DT>(x3))));
             }
@@ -333,12 +336,18 @@ int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream) {
     const int G = p.num_heads / p.num_kv_heads;
     if (G > 8) { blim_set_error("attention: %d query heads per kv head > 8 unsupported", G); return BLIM_ERR_ARG; }
     const dim3 grid(p.n_blocks, p.num_kv_heads), block(64 * G);
-    if (p.v_lo_off != 0 || p.out_lo_off != 0) {   // compensated mode (fp16 engines): transposed-read path only
-        ARG_CHECK((p.dtype == DT_F16 || p.dtype == DT_BF16) && p.v_lo_off > 0 && p.out_lo_off > 0 && p.v_lo_off % 8 == 0 && p.out_lo_off % 4 == 0);
-#define ATTN_SPLIT(MC, BLOCK)                                                                                          \
-        do {                                                                                                         \
-            if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, MC, DT_F16, true>), grid, BLOCK, 0, stream, p);  \
-            else hipLaunchKernelGGL((attn_kernel<true, MC, DT_BF16, true>), grid, BLOCK, 0, stream, p);               \
+    if (p.v_lo_off != 0 || p.out_lo_off != 0)      // compensated forms (16-bit engines): transposed-read path only
+        ARG_CHECK((p.dtype == DT_F16 || p.dtype == DT_BF16) && p.v_lo_off >= 0 && p.out_lo_off >= 0 && p.v_lo_off % 8 == 0 && p.out_lo_off % 4 == 0 && !p.out8);
+    if (p.v_lo_off != 0) {     // split products; the output as hi + lo (out_lo_off > 0) or hi only (0: the per-layer mask's QKV-compensated, o_proj-plain form)
+#define ATTN_SPLIT(MC, BLOCK)                                                                                                       \
+        do {                                                                                                                      \
+            if (p.out_lo_off) {                                                                                                   \
+                if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, MC, DT_F16, true>), grid, BLOCK, 0, stream, p);       \
+                else hipLaunchKernelGGL((attn_kernel<true, MC, DT_BF16, true>), grid, BLOCK, 0, stream, p);                    \
+            } else {                                                                                                              \
+                if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, MC, DT_F16, true, false>), grid, BLOCK, 0, stream, p); \
+                else hipLaunchKernelGGL((attn_kernel<true, MC, DT_BF16, true, false>), grid, BLOCK, 0, stream, p);              \
+            }                                                                                                                     \
         } while (0)
         if (G >= 7) ATTN_SPLIT(5, block);           // 2,048 chunks / 448 (512) threads: five per thread, not eight (the 7B model's grouping)
         else ATTN_SPLIT(4, dim3(512));              // fewer heads per group: eight waves, G of them compute and the rest only help staging (four chunks per thread;
@@ -348,12 +357,27 @@ int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream) {
         if (e2 != hipSuccess) { blim_set_error("attention launch failed: %s", hipGetErrorString(e2)); return BLIM_ERR_HIP; }
         return BLIM_OK;
     }
+    static const int g_split = getenv("BLIM_ATTN_HEAD_GROUPS") ? atoi(getenv("BLIM_ATTN_HEAD_GROUPS")) : 2;
+    if (p.out_lo_off != 0) {   // plain products, output as hi + lo (the per-layer mask's QKV-plain, o_proj-compensated form): the plain kernels' grouping, transposed reads
+#define ATTN_LO(MC, GRID, BLOCK)                                                                                                   \
+        do {                                                                                                                     \
+            if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, MC, DT_F16, false, true>), GRID, BLOCK, 0, stream, p);   \
+            else hipLaunchKernelGGL((attn_kernel<true, MC, DT_BF16, false, true>), GRID, BLOCK, 0, stream, p);                \
+        } while (0)
+        if (G >= 5 && g_split > 1) ATTN_LO(4, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        else if (G >= 4) ATTN_LO(4, grid, block);
+        else if (G >= 2) ATTN_LO(8, grid, block);
+        else ATTN_LO(16, grid, block);
+#undef ATTN_LO
+        hipError_t e3 = hipGetLastError();
+        if (e3 != hipSuccess) { blim_set_error("attention launch failed: %s", hipGetErrorString(e3)); return BLIM_ERR_HIP; }
+        return BLIM_OK;
+    }
 #define ATTN_LAUNCH(TR, MC)                                                                             \
     do {                                                                                            \
         if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<TR, MC, DT_F16>), grid, block, 0, stream, p); \
         else hipLaunchKernelGGL((attn_kernel<TR, MC, DT_BF16>), grid, block, 0, stream, p);                \
     } while (0)
-    static const int g_split = getenv("BLIM_ATTN_HEAD_GROUPS") ? atoi(getenv("BLIM_ATTN_HEAD_GROUPS")) : 2;
     if (G >= 5 && g_split > 1 && use_tr_read && !p.out8) {
         // two workgroups of ceil(G / 2) waves per (block, KV head): 1,024 chunks / 256 threads = four per thread
         const int hpg = (G + 1) / 2;

@@ -145,6 +145,7 @@ extern "C" int blim_create(const blim_config* cfg, blim_engine** out) {
     const int H = cfg->hidden_size, I = cfg->intermediate_size, V = cfg->vocab_size, M = cfg->mm_hidden_size;
     e->qkv_n = (cfg->num_heads + 2 * cfg->num_kv_heads) * 128;
     e->L.resize(cfg->num_layers);
+    e->layer_bits.assign(cfg->num_layers, 15);
     int rc = BLIM_OK;
 #define A(ptr, count, type) do { if (rc == BLIM_OK) rc = dev_alloc(e, (void**)&(ptr), (size_t)(count) * sizeof(type)); } while (0)
     A(e->embed, (int64_t)V * H, bf16_t);
@@ -649,6 +650,14 @@ static GemmParams gp2(const blim_engine* e, const void* A, int64_t K1, const voi
     return p;
 }
 
+// one unit of a layer (option "precise_layers"): the rows are `lay` halves wide ([hi | lo] for lay = 2, whether or not this unit reads the lo half); split = the product
+// takes both halves (gp2), lo_out = 16-bit outputs leave as hi at C and lo at C + n_out1; a plain unit over [hi | lo] rows reads their hi halves only (lda = lay * K1)
+static GemmParams gp3(const blim_engine* e, const void* A, int64_t K1, const void* W, int64_t M, int N, void* C, int64_t ldc1, int64_t n_out1, int lay, bool split, bool lo_out) {
+    GemmParams p = split ? gp2(e, A, K1, W, M, N, C, ldc1, n_out1, true) : gp(e->c.compute_dtype, A, lay * K1, W, M, N, (int)K1, C, lay * ldc1);
+    p.lo_off = lo_out ? n_out1 : 0;
+    return p;
+}
+
 extern "C" int blim_project_video(blim_engine* e, const void* feats, int64_t n_rows, int32_t which, void* out, void* stream) {
     ARG_CHECK(e && feats && out && n_rows > 0 && (which == 0 || which == 1));
     TRY(blim_weights_ready(e));
@@ -747,9 +756,13 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
         int64_t stride = 0;
         TRY(engine_rope_rows(e, b, s, &rope_rows, &stride));
     }
-    const int pf = e->precise ? 2 : 1;                              // attention branch
+    const int pf = e->precise ? 2 : 1;                              // attention branch: row layout
+    const bool masked = e->precise && e->layer_mask_on;             // options "precise_layers" / "precise_layer_bits": compensation per (layer, GEMM class)
     const bool pm = e->precise && e->precise_mlp;                   // MLP branch (option "precise_mlp")
-    const int pfm = pm ? 2 : 1;
+    const int pfm = (pm || masked) ? 2 : 1;                         // MLP branch: row layout
+    // the compensated units of layer li: bit 0 QKV + attention products, 1 o_proj, 2 gate|up, 3 down.  A unit's producer writes the lo part it reads (RMSNorm 1 -> QKV,
+    // QKV epilogue -> attention, attention -> o_proj, RMSNorm 2 -> gate|up, SwiGLU epilogue -> down); a plain unit reads the hi halves of the same layout
+    auto unit_bits = [&](int li) -> int { return masked ? (int)e->layer_bits[li] : e->precise ? (pm ? 15 : 3) : 0; };
     if (e->precise && e->f8) { blim_set_error("option 'precise' needs a 16-bit engine (fp16 or bf16)"); return BLIM_ERR_STATE; }
     // option "precise_lo6": a compensated GEMM = its plain fp16 pass over the hi part + an e2m3 pass over the lo part, in one kernel and into the same accumulators
     // (gemm.hip, phase 2).  `rows` are [hi | lo] rows (lo at +K elements, row stride ld): the lo halves are written as e2m3 operand tiles into the a6 workspace
@@ -757,13 +770,15 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
     // adapters apart the adapted projections use the augmented weights' images.
     const bool lo6 = e->lo6 && e->precise;
     if (lo6) TRY(ensure(e->a6, f6_tiles_bytes(T, (int)std::max<int64_t>(I, Hq))));
-    const bool fuse6 = lo6 && pm && e->lo6_fuse && (e->lo6_fuse_mask & 1) && (2 * I) % 256 == 0;         // the gate | up epilogue writes the down GEMM's A6 tiles (gemm.hpp: out6) into a second buffer
-    if (fuse6) TRY(ensure(e->a6b, f6_tiles_bytes(T, (int)I)));
+    const bool fuse6_ok = lo6 && e->lo6_fuse && (e->lo6_fuse_mask & 1) && (2 * I) % 256 == 0;    // the gate | up epilogue writes the down GEMM's A6 tiles (gemm.hpp: out6) into a second buffer
+    bool any_fuse6 = false;                                                                        // (layers whose gate | up and down both run compensated)
+    for (int li = 0; li < c.num_layers; ++li) any_fuse6 |= (unit_bits(li) & 12) == 12;
+    if (fuse6_ok && any_fuse6) TRY(ensure(e->a6b, f6_tiles_bytes(T, (int)I)));
     // ... and the RMSNorm kernels write the tiles of their own output's lo part (kernels.hpp: launch_rmsnorm out6) -- the rows' lo halves are then stored only for
     // the adapters' rank-r inputs: norm1 -> QKV input when no adapter is apart (with adapters the GEMM input carries their u columns, written after the norm);
     // norm2 -> gate | up input (no adapters on the MLP)
-    const bool n1_tiles = lo6 && e->lo6_fuse && (e->lo6_fuse_mask & 2) && !G && rmsnorm_can_write_tiles((int)H, H, pf * Hq);
-    const bool n2_tiles = lo6 && pm && e->lo6_fuse && (e->lo6_fuse_mask & 2) && rmsnorm_can_write_tiles((int)H, H, pfm * H);
+    const bool n1_tiles_ok = lo6 && e->lo6_fuse && (e->lo6_fuse_mask & 2) && !G && rmsnorm_can_write_tiles((int)H, H, pf * Hq);
+    const bool n2_tiles_ok = lo6 && e->lo6_fuse && (e->lo6_fuse_mask & 2) && rmsnorm_can_write_tiles((int)H, H, pfm * H);
     auto attach_lo6_ready = [&](GemmParams& p, int K, const uint8_t* w6) { p.A6 = (const uint8_t*)e->a6.p; p.W6 = w6; p.K6 = K; };
     auto attach_lo6 = [&](GemmParams& p, const bf16_t* rows, int64_t ld, int64_t n, int K, const uint8_t* w6) -> int {
         { SpanGuard gq(e, s, TC_QUANT, 0); TRY(launch_f6_tiles(rows + K, ld, n, K, c.compute_dtype, false, (uint8_t*)e->a6.p, s)); }
@@ -772,20 +787,23 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
     };
     for (int li = 0; li < c.num_layers; ++li) {
         const LayerW& l = e->L[li];
+        const int ub = unit_bits(li);
+        const bool cA = ub & 1, cO = ub & 2, cG = ub & 4, cD = ub & 8;
+        const bool fuse6 = fuse6_ok && cG && cD, n1_tiles = n1_tiles_ok && cA, n2_tiles = n2_tiles_ok && cG;
         {
             SpanGuard g(e, s, TC_NORM, 0);
             if (q8) TRY(launch_rmsnorm_f8(resid, H, T, H, l.norm1, c.rms_eps, x8, sx, s));
 #ifdef ENGINE_ABLATE_NORMFOLD   // timing-only build (make ablate_normfold; profiles/r06_normfold_bound.md): plain calls skip every RMSNorm pass a residual epilogue could have produced
             else if (!e->precise && !G && li > 0 && e->lse_part.p) { }
 #endif
-            else TRY(launch_rmsnorm(resid, H, nullptr, T, H, l.norm1, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pf * Hq, (e->precise && !n1_tiles) ? xn + Hq : nullptr, true, n1_tiles ? (uint8_t*)e->a6.p : nullptr));
-            if (G) TRY(adapter_u(e, xn, pf * Hq, e->precise ? Hq : 0, T, H, &e->AD[li].ad[0], &e->AD[li].ad[1], &e->AD[li].ad[2], s));
+            else TRY(launch_rmsnorm(resid, H, nullptr, T, H, l.norm1, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pf * Hq, (cA && !n1_tiles) ? xn + Hq : nullptr, true, n1_tiles ? (uint8_t*)e->a6.p : nullptr));
+            if (G) TRY(adapter_u(e, xn, pf * Hq, cA ? Hq : 0, T, H, &e->AD[li].ad[0], &e->AD[li].ad[1], &e->AD[li].ad[2], s));
         }
         {
-            SpanGuard g(e, s, TC_GEMM_QKV, 2.0 * tok * Hq * e->qkv_n * pf);
+            SpanGuard g(e, s, TC_GEMM_QKV, 2.0 * tok * Hq * e->qkv_n * (cA ? 2 : 1));
             GemmParams p = q8 ? gp8(x8, H, sx, l.wqkv8, l.sqkv, T, e->qkv_n, H, qkv, e->qkv_n)
-                              : gp2(e, xn, Hq, G ? (const void*)e->AD[li].wqkv_aug : (const void*)l.wqkv, T, e->qkv_n, qkv, e->qkv_n, e->qkv_n, e->precise);
-            if (lo6) {                                                                    // hi part in fp16, lo part in e2m3; [hi | lo] outputs as before
+                              : gp3(e, xn, Hq, G ? (const void*)e->AD[li].wqkv_aug : (const void*)l.wqkv, T, e->qkv_n, qkv, e->qkv_n, e->qkv_n, pf, cA, cA);
+            if (lo6 && cA) {                                                                    // hi part in fp16, lo part in e2m3; [hi | lo] outputs as before
                 p = gp(c.compute_dtype, xn, 2 * Hq, G ? (const void*)e->AD[li].wqkv_aug : (const void*)l.wqkv, T, e->qkv_n, (int)Hq, qkv, 2 * (int64_t)e->qkv_n); p.lo_off = e->qkv_n;
                 if (n1_tiles) attach_lo6_ready(p, (int)Hq, l.wqkv6); else TRY(attach_lo6(p, xn, 2 * Hq, T, (int)Hq, G ? e->AD[li].wqkv_aug6 : l.wqkv6));
             }
@@ -799,7 +817,7 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
             a.qkv = qkv; a.ldq = (int64_t)pf * e->qkv_n; a.num_heads = c.num_heads; a.num_kv_heads = c.num_kv_heads;
             a.key_visible = b->key_visible; a.seq_start = b->seq_start; a.seq_len = b->seq_len; a.pfx_start = b->pfx_start; a.pfx_len = b->pfx_len;
             a.blk_seq = b->blk_seq; a.blk_q0 = b->blk_q0; a.own_start = b->own_start; a.n_blocks = b->n_blocks; a.out = attn; a.ldo = (int64_t)pf * Hq; a.scale = 0.08838834764831845f;
-            a.v_lo_off = pf == 2 ? e->qkv_n : 0; a.out_lo_off = pf == 2 ? Hq : 0;
+            a.v_lo_off = cA ? e->qkv_n : 0; a.out_lo_off = cO ? Hq : 0;            // (four forms: attention.hpp)
             a.out8 = nullptr; a.ldo8 = 0; a.out_mx = nullptr; a.mx_stride = 0; a.lse_out = nullptr;
             if (o8 && e->f8_fuse) { a.out8 = a8; a.ldo8 = H; a.out_mx = (uint8_t*)e->attn_mx.p; a.mx_stride = Tp; }   // fp8: e4m3 + E8M0 per (token, head)
             TRY(launch_attention(a, e->attn_tr, s));
@@ -814,37 +832,37 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
             {
                 SpanGuard g0(e, s, TC_MISC, 0);
                 TRY(launch_gather_rows(attn_live, attn, live_rows, n_live, (int64_t)pf * Hq * 2, T, 0u, s));
-                if (G) TRY(adapter_u(e, attn_live, (int64_t)pf * Hq, e->precise ? Hq : 0, n_live, H, &e->AD[li].ad[3], nullptr, nullptr, s));
+                if (G) TRY(adapter_u(e, attn_live, (int64_t)pf * Hq, cO ? Hq : 0, n_live, H, &e->AD[li].ad[3], nullptr, nullptr, s));
                 TRY(launch_gather_rows(rl, resid, live_rows, n_live, (int64_t)H * 4, T, 0x7fc00000u, s));      // a row outside the batch: NaN (poisoned score)
             }
             const double tl = (double)n_live;
-            { SpanGuard g(e, s, TC_GEMM_O, 2.0 * tl * Hq * H * pf);
-              GemmParams p = gp2(e, attn_live, Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, n_live, H, rl, H, 0, e->precise); p.ldc = H; p.lo_off = 0;
-              if (lo6) { p = gp(c.compute_dtype, attn_live, 2 * Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, n_live, H, (int)Hq, rl, H);
+            { SpanGuard g(e, s, TC_GEMM_O, 2.0 * tl * Hq * H * (cO ? 2 : 1));
+              GemmParams p = gp3(e, attn_live, Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, n_live, H, rl, H, 0, pf, cO, false); p.ldc = H; p.lo_off = 0;
+              if (lo6 && cO) { p = gp(c.compute_dtype, attn_live, 2 * Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, n_live, H, (int)Hq, rl, H);
                          TRY(attach_lo6(p, attn_live, 2 * Hq, n_live, (int)Hq, G ? e->AD[li].wo_aug6 : l.wo6)); }
               TRY(launch_gemm(EPI_RESID, p, s)); }
             { SpanGuard g(e, s, TC_NORM, 0);
-              TRY(launch_rmsnorm(rl, H, nullptr, n_live, H, l.norm2, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pfm * H, (pm && !n2_tiles) ? xn + H : nullptr, true, n2_tiles ? (uint8_t*)e->a6.p : nullptr)); }
+              TRY(launch_rmsnorm(rl, H, nullptr, n_live, H, l.norm2, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pfm * H, (cG && !n2_tiles) ? xn + H : nullptr, true, n2_tiles ? (uint8_t*)e->a6.p : nullptr)); }
             // SwiGLU output [n_live, pfm * I]: `act` holds attn_live only until o_proj above has run (stream order), so it is free again here
-            { SpanGuard g(e, s, TC_GEMM_GATEUP, 4.0 * tl * H * I * pfm);
-              GemmParams p = gp2(e, xn, H, l.wgu, n_live, 2 * I, act, I, I, pm);
-              if (lo6 && pm) { p = gp(c.compute_dtype, xn, 2 * (int64_t)H, l.wgu, n_live, 2 * I, H, act, 2 * (int64_t)I); p.lo_off = I; if (n2_tiles) attach_lo6_ready(p, (int)H, l.wgu6); else TRY(attach_lo6(p, xn, 2 * (int64_t)H, n_live, H, l.wgu6)); if (fuse6) p.out6 = (uint8_t*)e->a6b.p; }
+            { SpanGuard g(e, s, TC_GEMM_GATEUP, 4.0 * tl * H * I * (cG ? 2 : 1));
+              GemmParams p = gp3(e, xn, H, l.wgu, n_live, 2 * I, act, I, I, pfm, cG, cD);
+              if (lo6 && cG) { p = gp(c.compute_dtype, xn, 2 * (int64_t)H, l.wgu, n_live, 2 * I, H, act, 2 * (int64_t)I); p.lo_off = cD ? I : 0; if (n2_tiles) attach_lo6_ready(p, (int)H, l.wgu6); else TRY(attach_lo6(p, xn, 2 * (int64_t)H, n_live, H, l.wgu6)); if (fuse6) p.out6 = (uint8_t*)e->a6b.p; }
               TRY(launch_gemm(EPI_SWIGLU, p, s)); }
-            { SpanGuard g(e, s, TC_GEMM_DOWN, 2.0 * tl * H * I * pfm);
-              GemmParams p = gp2(e, act, I, l.wd, n_live, H, rl, H, 0, pm); p.ldc = H; p.lo_off = 0;
-              if (lo6 && pm) { p = gp(c.compute_dtype, act, 2 * (int64_t)I, l.wd, n_live, H, I, rl, H); if (fuse6) { p.A6 = (const uint8_t*)e->a6b.p; p.W6 = l.wd6; p.K6 = (int)I; } else TRY(attach_lo6(p, act, 2 * (int64_t)I, n_live, I, l.wd6)); }
+            { SpanGuard g(e, s, TC_GEMM_DOWN, 2.0 * tl * H * I * (cD ? 2 : 1));
+              GemmParams p = gp3(e, act, I, l.wd, n_live, H, rl, H, 0, pfm, cD, false); p.ldc = H; p.lo_off = 0;
+              if (lo6 && cD) { p = gp(c.compute_dtype, act, 2 * (int64_t)I, l.wd, n_live, H, I, rl, H); if (fuse6) { p.A6 = (const uint8_t*)e->a6b.p; p.W6 = l.wd6; p.K6 = (int)I; } else TRY(attach_lo6(p, act, 2 * (int64_t)I, n_live, I, l.wd6)); }
               TRY(launch_gemm(EPI_RESID, p, s)); }
             *final_resid = rl; *final_is_live = true;
             break;
         }
-        if (G) { SpanGuard g(e, s, TC_MISC, 0); TRY(adapter_u(e, attn, (int64_t)pf * Hq, e->precise ? Hq : 0, T, H, &e->AD[li].ad[3], nullptr, nullptr, s)); }
+        if (G) { SpanGuard g(e, s, TC_MISC, 0); TRY(adapter_u(e, attn, (int64_t)pf * Hq, cO ? Hq : 0, T, H, &e->AD[li].ad[3], nullptr, nullptr, s)); }
         {
-            SpanGuard g(e, s, TC_GEMM_O, 2.0 * tok * Hq * H * pf);
+            SpanGuard g(e, s, TC_GEMM_O, 2.0 * tok * Hq * H * (cO ? 2 : 1));
             GemmParams p = o8 ? gp8(a8, H, fuse_o ? nullptr : sa, l.wo8, l.so, T, H, H, resid, H)
-                              : gp2(e, attn, Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, T, H, resid, H, 0, e->precise);
+                              : gp3(e, attn, Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, T, H, resid, H, 0, pf, cO, false);
             if (fuse_o) { p.a_mx = (const uint8_t*)e->attn_mx.p; p.mx_stride = Tp; }
             p.ldc = H; p.lo_off = 0;
-            if (lo6) {
+            if (lo6 && cO) {
                 p = gp(c.compute_dtype, attn, 2 * Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, T, H, (int)Hq, resid, H);
                 TRY(attach_lo6(p, attn, 2 * Hq, T, (int)Hq, G ? e->AD[li].wo_aug6 : l.wo6));
             }
@@ -859,15 +877,15 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
 #ifdef ENGINE_ABLATE_NORMFOLD
             else if (!e->precise && !G && e->lse_part.p) { }
 #endif
-            else TRY(launch_rmsnorm(resid, H, nullptr, T, H, l.norm2, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pfm * H, (pm && !n2_tiles) ? xn + H : nullptr, true, n2_tiles ? (uint8_t*)e->a6.p : nullptr));
+            else TRY(launch_rmsnorm(resid, H, nullptr, T, H, l.norm2, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pfm * H, (cG && !n2_tiles) ? xn + H : nullptr, true, n2_tiles ? (uint8_t*)e->a6.p : nullptr));
         }
         const bool fuse = g8 && d8 && e->f8_fuse;      // fp8: the gate|up epilogue emits e4m3 + one E8M0 scale per (token, 128 outputs) itself
         {
-            SpanGuard g(e, s, TC_GEMM_GATEUP, 4.0 * tok * H * I * pfm);
-            GemmParams p = g8 ? gp8(x8, H, sx, l.wgu8, l.sgu, T, 2 * I, H, act, I) : gp2(e, xn, H, l.wgu, T, 2 * I, act, I, I, pm);
+            SpanGuard g(e, s, TC_GEMM_GATEUP, 4.0 * tok * H * I * (cG ? 2 : 1));
+            GemmParams p = g8 ? gp8(x8, H, sx, l.wgu8, l.sgu, T, 2 * I, H, act, I) : gp3(e, xn, H, l.wgu, T, 2 * I, act, I, I, pfm, cG, cD);
             if (fuse) { p.C = act8; p.ldc = I; p.out_mx = (uint8_t*)e->act_mx.p; p.mx_stride = Tp; }
-            if (lo6 && pm) {
-                p = gp(c.compute_dtype, xn, 2 * (int64_t)H, l.wgu, T, 2 * I, H, act, 2 * (int64_t)I); p.lo_off = I;
+            if (lo6 && cG) {
+                p = gp(c.compute_dtype, xn, 2 * (int64_t)H, l.wgu, T, 2 * I, H, act, 2 * (int64_t)I); p.lo_off = cD ? I : 0;
                 if (n2_tiles) attach_lo6_ready(p, (int)H, l.wgu6); else TRY(attach_lo6(p, xn, 2 * (int64_t)H, T, H, l.wgu6));
                 if (fuse6) p.out6 = (uint8_t*)e->a6b.p;
             }
@@ -875,11 +893,11 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
         }
         if (d8 && !fuse) { SpanGuard g(e, s, TC_QUANT, 0); TRY(launch_quant_rows(act, I, T, I, c.compute_dtype, act8, sact, s)); }
         {
-            SpanGuard g(e, s, TC_GEMM_DOWN, 2.0 * tok * H * I * pfm);
-            GemmParams p = d8 ? gp8(act8, I, fuse ? nullptr : sact, l.wd8, l.sd, T, H, I, resid, H) : gp2(e, act, I, l.wd, T, H, resid, H, 0, pm);
+            SpanGuard g(e, s, TC_GEMM_DOWN, 2.0 * tok * H * I * (cD ? 2 : 1));
+            GemmParams p = d8 ? gp8(act8, I, fuse ? nullptr : sact, l.wd8, l.sd, T, H, I, resid, H) : gp3(e, act, I, l.wd, T, H, resid, H, 0, pfm, cD, false);
             if (fuse) { p.a_mx = (const uint8_t*)e->act_mx.p; p.mx_stride = Tp; }
             p.ldc = H; p.lo_off = 0;
-            if (lo6 && pm) {
+            if (lo6 && cD) {
                 p = gp(c.compute_dtype, act, 2 * (int64_t)I, l.wd, T, H, I, resid, H);
                 if (fuse6) { p.A6 = (const uint8_t*)e->a6b.p; p.W6 = l.wd6; p.K6 = (int)I; }
                 else TRY(attach_lo6(p, act, 2 * (int64_t)I, T, I, l.wd6));
@@ -1259,6 +1277,17 @@ extern "C" int blim_set_option(blim_engine* e, const char* key, int32_t value) {
         e->lo6 = value != 0; return BLIM_OK;
     }
     if (!strcmp(key, "precise_mlp")) { e->precise_mlp = value != 0; return BLIM_OK; }
+    if (!strcmp(key, "precise_layers")) {
+        if (value && e->f8) { blim_set_error("option 'precise_layers' needs a 16-bit engine (fp16 or bf16)"); return BLIM_ERR_ARG; }
+        e->layer_mask_on = value != 0; return BLIM_OK;
+    }
+    if (!strcmp(key, "precise_layer_bits")) {
+        if (e->f8) { blim_set_error("option 'precise_layer_bits' needs a 16-bit engine (fp16 or bf16)"); return BLIM_ERR_ARG; }
+        const int32_t layer = value >> 4;
+        if (value < 0 || layer >= e->c.num_layers) {
+            blim_set_error("option 'precise_layer_bits': value = (layer << 4) | bits with 0 <= layer < %d (got %d)", e->c.num_layers, (int)value); return BLIM_ERR_ARG; }
+        e->layer_bits[layer] = (uint8_t)(value & 15); return BLIM_OK;
+    }
     if (!strcmp(key, "precise")) {
         if (value && e->f8) { blim_set_error("option 'precise' needs a 16-bit engine (fp16 or bf16)"); return BLIM_ERR_ARG; }
         e->precise = value != 0;

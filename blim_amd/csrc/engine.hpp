@@ -78,6 +78,11 @@ struct blim_engine {
     // cheap TVG calls only (their scores are ~10x smaller in magnitude than the VTG ones: DESIGN.md section 4).
     bool precise = false;
     bool precise_mlp = true;       // option "precise_mlp": compensate the MLP branch too (87 % of the flops, ~20 % of the error variance)
+    // options "precise_layers" / "precise_layer_bits" (--vtg_precise select): in precise mode, which (layer, GEMM class) units run compensated -- 4 bits per layer,
+    // bit 0 QKV + attention products, 1 o_proj, 2 gate|up, 3 down (include/blim.h).  Buffers keep the compensated [hi | lo] layout; a plain unit runs the plain kernel
+    // over the hi halves and its producer writes no lo part.  Off (or unset): every unit follows precise / precise_mlp
+    bool layer_mask_on = false;
+    std::vector<uint8_t> layer_bits;
     bool masked_query_zero = false; // option "masked_query_zero" (PARITY-UNPINNED): query positions the key mask hides write a zero attention output -- what the reference's
                                    // flash-attention-2 class does (modeling_qwen2_flash.py:526-563: dropped before flash_attn_varlen_func, zero-padded back) where its
                                    // eager / SDPA classes, the pinned semantics, compute such rows like any other

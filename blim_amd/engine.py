@@ -229,6 +229,8 @@ class Engine:
         self.lo6 = lo6_ok and ((dtype == "f16" and os.environ.get("BLIM_PRECISE_LO6", "1") != "0") or (dtype == "bf16" and os.environ.get("BLIM_PRECISE_LO6", "0") == "1"))
         self._precise_mlp = os.environ.get("BLIM_PRECISE_MLP", "1") != "0"
         self.weights_version = 0          # bumped by every weight / adapter change: what a measured numeric mode was measured on (modeling.py: resolve_*)
+        self._layer_mask = None           # set_layer_mask: per-layer compensation bits of the VTG calls under `--vtg_precise select` (None: no mask)
+        self._layer_bits_live = None      # what the engine's "precise_layer_bits" hold (None: its default, all set)
 
     def close(self):
         if getattr(self, "h", None):
@@ -248,7 +250,7 @@ class Engine:
         assert tuple(arr.shape) == tuple(shape), (name, arr.shape, shape)
         a = np.ascontiguousarray(arr, dtype=np.float32)
         _check(self.lib.blim_load_weight(self.h, name.encode(), a.ctypes.data, DTYPE_F32, 0), f"blim_load_weight({name})")
-        self.weights_version += 1
+        self._weights_changed()
 
     def load_weights(self, weights: Dict[str, np.ndarray]):
         """weights: canonical name -> float32 numpy array; every tensor of the model must be present."""
@@ -261,7 +263,7 @@ class Engine:
 
     def init_synthetic_weights(self, seed: int):
         _check(self.lib.blim_init_synthetic_weights(self.h, seed), "blim_init_synthetic_weights")
-        self.weights_version += 1
+        self._weights_changed()
 
     # ---- LoRA adapters kept apart (blim.h: blim_load_adapter; the reference's --resume flow, main.py:96-105, 125-128)
     def load_adapter(self, weight_name: str, A: np.ndarray, B: np.ndarray, lora_r: int, lora_alpha: float):
@@ -270,11 +272,18 @@ class Engine:
         assert tuple(A.shape) == (lora_r, n_in) and tuple(B.shape) == (n_out, lora_r), (weight_name, A.shape, B.shape, (n_out, n_in), lora_r)
         a = np.ascontiguousarray(A, dtype=np.float32); b = np.ascontiguousarray(B, dtype=np.float32)
         _check(self.lib.blim_load_adapter(self.h, weight_name.encode(), a.ctypes.data, b.ctypes.data, int(lora_r), float(lora_alpha)), f"blim_load_adapter({weight_name})")
-        self.weights_version += 1
+        self._weights_changed()
 
     def clear_adapters(self):
         _check(self.lib.blim_clear_adapters(self.h), "blim_clear_adapters")
+        self._weights_changed()
+
+    def _weights_changed(self):
+        """Every weight / adapter change: a mask measured on the old weights says nothing about the new ones -- it goes back to all ones (the `full` form) until a
+        calibration measures again (modeling.py: vtg_select_mask)."""
         self.weights_version += 1
+        if self._layer_mask is not None:
+            self.set_layer_mask(np.full(self.dims.num_layers, 15, dtype=np.uint8))
 
     def num_adapters(self) -> int:
         return int(self.lib.blim_num_adapters(self.h))
@@ -301,7 +310,7 @@ class Engine:
     def can_precise(self) -> bool:
         return self.dtype in ("f16", "bf16")
 
-    def set_precise(self, on: bool, embeds: bool = False, mlp: bool = True, tvg: bool = False):
+    def set_precise(self, on: bool, embeds: bool = False, mlp: bool = True, tvg: bool = False, layers: bool = False):
         """Compensated mode for the following calls (16-bit engines; a no-op request on others): every 16-bit activation travels as hi + lo and the GEMMs take
         both parts (fp16 engines: the lo part on the e2m3 MFMA, option "precise_lo6").  The host turns it on for the TVG calls, whose scores are ~10x smaller in
         magnitude than the VTG ones, and for the VTG calls of checkpoints that need it (`--vtg_precise`).
@@ -309,7 +318,8 @@ class Engine:
         are produced in this mode; the literal forward() keeps [B, L, H] embeddings.  mlp=False: only the attention branch (QKV, attention, o_proj) and the
         scored rows are compensated -- the TVG calls' "attn" mode.  tvg=True: the call is a TVG call -- on a bf16 engine that was asked for the e2m3 second pass
         (`second_pass = "e2m3"`, round 6) it still takes the bf16 second pass: TVG scores are ~10x smaller in magnitude, read 1.7 - 2.6e-4 with the e2m3 pass against
-        1 - 2.4e-5 with the bf16 one at 7B depth, and cost a few percent of an evaluation either way."""
+        1 - 2.4e-5 with the bf16 one at 7B depth, and cost a few percent of an evaluation either way.  layers=True (VTG calls under `--vtg_precise select`): the call
+        follows the per-layer mask of set_layer_mask (when one is set) instead of `mlp`."""
         on = bool(on) and self.can_precise
         embeds = bool(embeds) and on
         want6 = bool(self.lo6) and not (bool(tvg) and on and self.dtype == "bf16")
@@ -326,6 +336,32 @@ class Engine:
         if on and mlp != getattr(self, "_precise_mlp", True):
             self.set_option("precise_mlp", int(mlp))
             self._precise_mlp = mlp
+        masked = bool(layers) and on and self._layer_mask is not None and not bool(tvg)
+        if masked != getattr(self, "_precise_layers", False):
+            self.set_option("precise_layers", int(masked))
+            self._precise_layers = masked
+
+    def set_layer_mask(self, bits):
+        """Per-layer compensation mask of the VTG calls (`--vtg_precise select`; engine options "precise_layers" / "precise_layer_bits", include/blim.h): bits[l] says
+        which units of layer l run compensated -- bit 0 QKV + attention, 1 o_proj, 2 gate|up, 3 down; uint8 [num_layers], or None for no mask.  Takes effect on the
+        calls that set_precise(..., layers=True) brackets (the VTG calls); the TVG calls never use it."""
+        if bits is None:
+            self._layer_mask = None
+            return
+        if not self.can_precise:
+            raise BlimError("set_layer_mask: fp8 engines have no compensated modes")
+        bits = np.asarray(bits).astype(np.int64).reshape(-1)
+        if bits.shape != (self.dims.num_layers,) or np.any(bits < 0) or np.any(bits > 15):
+            raise ValueError(f"set_layer_mask: {self.dims.num_layers} values in 0 .. 15 expected, got {bits.tolist()}")
+        live = self._layer_bits_live if self._layer_bits_live is not None else np.full(self.dims.num_layers, 15, dtype=np.int64)
+        for li in np.nonzero(bits != live)[0]:
+            _check(self.lib.blim_set_option(self.h, b"precise_layer_bits", int((int(li) << 4) | int(bits[li]))), "blim_set_option")
+        self._layer_bits_live = bits.copy()
+        self._layer_mask = bits.astype(np.uint8)
+
+    @property
+    def layer_mask(self):
+        return None if self._layer_mask is None else self._layer_mask.copy()
 
     # ---- component ops (torch device tensors in/out)
     def project_video(self, feats, which: int):

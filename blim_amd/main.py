@@ -67,13 +67,16 @@ def get_args_parser():
                    help="fp8 mode: which GEMMs take e4m3 operands (bit 0 qkv, 1 o_proj, 2 gate|up, 3 down, 4 lm_head).  Default 31 (all) on a base checkpoint, "
                         "12 (the MLP only) when --resume names a fine-tuned checkpoint: LoRA adapts q/k/v/o_proj and lm_head, whose merged rank-8 update is below one "
                         "e4m3 step of the base weight -- those GEMMs stay in fp16, the MLP (87 %% of a layer's flops, not adapted) runs in fp8")
-    p.add_argument("--vtg_precise", default="auto", choices=["auto", "none", "full"],
+    p.add_argument("--vtg_precise", default="auto", choices=["auto", "none", "full", "select"],
                    help="compensated (hi + lo) activations on the VTG calls.  auto (default): measured on the loaded checkpoint before the first pass -- up to 256 pairs of the "
                         "evaluation are scored plain and fully compensated (which sits at 2e-6 .. 1e-4 of the fp32 reference) and plain is kept if its largest deviation, 4.5 x its "
                         "RMS deviation and the largest deviation predicted for the whole evaluation's entries are inside 1e-3 (PairScorer.calibrate_vtg; the table is printed; measured "
                         "again whenever weights or adapters change).  none = plain 16-bit: the reference's own numerics, and what auto keeps on an fp16 engine unless the "
                         "checkpoint has massive activations (tests/golden/sink.npz, heavy7b.npz: plain fp16 is 3 - 5e-3 from the fp32 result there).  full = every activation "
-                        "(fp16 engines: second pass on the e2m3 MFMA, 0.67x the plain rate; the mode in which a bf16 engine holds 1e-3 at 7B depth, at 0.5x)")
+                        "(fp16 engines: second pass on the e2m3 MFMA, 0.67x the plain rate; the mode in which a bf16 engine holds 1e-3 at 7B depth, at 0.5x).  select = "
+                        "per layer and GEMM: if plain fails, the (4-layer group, GEMM class) units -- QKV + attention, o_proj, gate|up, down -- are ranked by their deviation "
+                        "per second-pass FLOP and the largest leading set that keeps the same bar runs plain, the rest compensated (PairScorer.calibrate_vtg_select; the mask "
+                        "is printed and measured again whenever weights or adapters change)")
     p.add_argument("--tvg_precise", default="auto", choices=["auto", "attn", "full"],
                    help="how much of the TVG calls' MLP branch runs compensated (their embeddings, QKV, attention, o_proj and head always do on a 16-bit engine).  auto (default): "
                         "measured like --vtg_precise auto, on the TVG likelihood and prior of up to 256 pairs; attn = MLP plain (1.6x faster than full), "

@@ -37,7 +37,8 @@ class BlimModel:
         # Numeric modes.  What the USER asks for:
         #   vtg_precise: None = plain 16-bit VTG calls (what the reference's autocast computes; holds 1e-3 at 28 layers of the 7B configuration on N(0, 0.02^2) weights),
         #                "full" = every activation as hi + lo (what weights with a trained checkpoint's massive activations need; bf16 engines' default: 8-bit
-        #                mantissas miss the bar when plain), "auto" = measured on the loaded checkpoint by evaluation() (PairScorer.calibrate_vtg);
+        #                mantissas miss the bar when plain), "auto" = measured on the loaded checkpoint by evaluation() (PairScorer.calibrate_vtg), "select" = a per-layer,
+        #                per-GEMM mask of the units that need compensation, measured likewise (PairScorer.calibrate_vtg_select; engine.set_layer_mask);
         #   tvg_precise: the TVG calls always carry hi + lo embeddings, QKV, attention, o_proj and head; "attn" leaves their MLP branch plain (1.6x faster),
         #                "full" (library default) compensates it too, "auto" = measured (PairScorer.calibrate_tvg).
         # What "auto" RESOLVED to is kept apart (resolve_vtg / resolve_tvg) together with the engine's weights_version it was measured on: new weights or adapters --
@@ -58,9 +59,11 @@ class BlimModel:
     @vtg_precise.setter
     def vtg_precise(self, mode):
         mode = None if mode in (None, "none", "0", "") else mode
-        if mode not in (None, "full", "auto"):
-            raise ValueError(f"vtg_precise = {mode!r}: one of none, full, auto (round 5 removed the intermediate modes qk / qkx / attn / act0)")
+        if mode not in (None, "full", "auto", "select"):
+            raise ValueError(f"vtg_precise = {mode!r}: one of none, full, auto, select (round 5 removed the intermediate modes qk / qkx / attn / act0)")
         self._vtg_request, self._vtg_resolved = mode, None
+        if getattr(self.engine, "layer_mask", None) is not None:    # a mask measured for an earlier request: back to the full form until measured again
+            self.engine.set_layer_mask(np.full(self.dims.num_layers, 15, dtype=np.uint8))
 
     @property
     def tvg_precise(self):
@@ -115,16 +118,30 @@ class BlimModel:
         self.engine.set_option("masked_query_zero", int(bool(on)))
         self._masked_query_zero = bool(on)
 
-    def resolve_vtg(self, mode) -> None:
-        """Records what `vtg_precise = "auto"` was measured to need on the weights now loaded (evaluation() -> PairScorer.calibrate_vtg)."""
-        self._vtg_resolved = (None if mode in (None, "none") else mode, self.engine.weights_version)
+    def resolve_vtg(self, mode, mask=None) -> None:
+        """Records what `vtg_precise = "auto"` / "select" was measured to need on the weights now loaded (evaluation() -> PairScorer.calibrate_vtg /
+        calibrate_vtg_select).  mode "select" comes with its mask (uint8 [num_layers]), which goes to the engine (Engine.set_layer_mask)."""
+        mode = None if mode in (None, "none") else mode
+        if mode == "select":
+            if mask is None:
+                raise ValueError("resolve_vtg('select') needs the measured mask")
+            self.engine.set_layer_mask(mask)
+        self._vtg_resolved = (mode, self.engine.weights_version)
+
+    def vtg_select_mask(self):
+        """The per-layer mask `vtg_precise = "select"` resolved to on the CURRENT weights (uint8 [num_layers]), or None (another mode, not measured yet, or resolved to
+        plain).  A weight or adapter change sets the engine's mask back to all ones (Engine._weights_changed) and makes this None until measured again."""
+        if self._vtg_request != "select" or self.vtg_mode() != "select":
+            return None
+        return self.engine.layer_mask
 
     def resolve_tvg(self, mode) -> None:
         self._tvg_resolved = (mode, self.engine.weights_version)
 
     def vtg_mode(self):
-        """The mode VTG calls run in: the request, or -- for "auto" -- what it resolved to on the CURRENT weights; "auto" itself while unresolved."""
-        if self._vtg_request != "auto":
+        """The mode VTG calls run in: the request, or -- for "auto" / "select" -- what it resolved to on the CURRENT weights ("none" as None, "select", "full");
+        "auto" while a measured request is unresolved."""
+        if self._vtg_request not in ("auto", "select"):
             return self._vtg_request
         r = self._vtg_resolved
         return r[0] if (r is not None and r[1] == self.engine.weights_version) else "auto"
@@ -307,8 +324,8 @@ class BlimModel:
         tvg_rows = (kind == "tvg") if kind is not None else (self._tvg_rows or (inputs_embeds.dtype == torch.float32 and self.engine.dtype == "f16" and self.engine.can_precise))
         vmode = self.vtg_mode()
         if vmode == "auto" and not tvg_rows:
-            raise RuntimeError("vtg_precise = 'auto' has not been resolved on the weights now loaded: evaluation() measures it before its first pass "
-                               "(PairScorer.calibrate_vtg); set BlimModel.vtg_precise to none / full to call forward() directly")
+            raise RuntimeError(f"vtg_precise = {self._vtg_request!r} has not been resolved on the weights now loaded: evaluation() measures it before its first pass "
+                               "(PairScorer.calibrate_vtg / calibrate_vtg_select); set BlimModel.vtg_precise to none / full to call forward() directly")
         wide = inputs_embeds.dtype == torch.float32 and self.engine.can_precise and (self.engine.dtype == "bf16" or tvg_rows)
         if wide:                                                          # float32 embeddings of prepare_inputs_labels_for_multimodal (bf16 engines; TVG rows on fp16 ones): back to [hi | lo]
             hi = inputs_embeds.to(self.dtype)
@@ -324,8 +341,8 @@ class BlimModel:
         if tvg_rows:
             self.engine.set_precise(True, embeds=wide, mlp=self.tvg_mode() != "attn", tvg=True)       # (an unresolved "auto" runs fully compensated)
         else:
-            on = vmode == "full"
-            self.engine.set_precise(on, embeds=wide and on, mlp=True)
+            on = vmode in ("full", "select")
+            self.engine.set_precise(on, embeds=wide and on, mlp=True, layers=vmode == "select")
             if wide and not on:                                           # plain bf16 VTG forward asked for (vtg_precise none): plain embeddings
                 emb = inputs_embeds.to(self.dtype).contiguous()
         try:

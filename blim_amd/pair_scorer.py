@@ -48,39 +48,51 @@ def _split_prompt_response(ids: np.ndarray, labels: np.ndarray):
     return ids[:n_prompt], ids[n_prompt:]
 
 
-def executed_flops(dims, n_tokens: int, n_rows: int, kind: str, mode=None, n_vocab: int = 0, prune: bool = True) -> float:
+def _select_factors(layer_bits):
+    """`--vtg_precise select`: the mean compensation factor (1 plain, 2 compensated) of the QKV, o_proj, gate|up and down GEMMs over the layers of a mask."""
+    b = np.asarray(layer_bits, dtype=np.int64).reshape(-1)
+    return tuple(1.0 + float(np.mean((b >> k) & 1)) for k in range(4))
+
+
+def executed_flops(dims, n_tokens: int, n_rows: int, kind: str, mode=None, n_vocab: int = 0, prune: bool = True, layer_bits=None) -> float:
     """GEMM FLOPs one engine call EXECUTES (the per-token constants applied to the token counts actually launched; attention,
     < 1 - 3 %, excluded): decoder layers over n_tokens packed tokens + the head over n_rows scored rows.  `mode`: compensation of the call (None: plain;
     "attn": QKV, o_proj and the head take hi + lo inputs; "full": every GEMM -- a TVG call of a 16-bit engine runs in one of the last two, TVG_MODES; a VTG
-    call plain or "full", VTG_MODES).  prune: the last layer's o_proj / MLP run on the scored rows only (engine option prune_last) when they are < 15/16 of the tokens."""
+    call plain, "full" or "select", VTG_MODES).  prune: the last layer's o_proj / MLP run on the scored rows only (engine option prune_last) when they are < 15/16 of
+    the tokens.  "select" with its per-layer mask `layer_bits`: each GEMM class at its mean factor over the layers, the head compensated."""
     H, I = dims.hidden_size, dims.intermediate_size
     q = 2.0 * H * (dims.num_heads + 2 * dims.num_kv_heads) * dims.head_dim
     o, gu, d = 2.0 * H * H, 4.0 * H * I, 2.0 * H * I
     fq = fo = 2.0 if mode in ("attn", "full") else 1.0      # "attn" (TVG calls only): the attention branch and the scored rows compensated, the MLP branch plain
     fg = fd = 2.0 if mode == "full" else 1.0
+    if mode == "select":
+        fq, fo, fg, fd = _select_factors(layer_bits if layer_bits is not None else [15] * dims.num_layers)
     per_tok = fq * q + fo * o + fg * gu + fd * d
     total = dims.num_layers * per_tok * n_tokens
     if prune and n_rows <= n_tokens - n_tokens // 16:
         total -= (fo * o + fg * gu + fd * d) * (n_tokens - n_rows)
     if kind == "vtg":
-        total += fo * 2.0 * H * dims.vocab_size * n_rows
+        total += (2.0 if mode == "select" else fo) * 2.0 * H * dims.vocab_size * n_rows
     else:
         # the visual head and the product with the video vocabulary: three-term compensated products (one GEMM of depth 3 K each) on a compensated call
         total += (3.0 if fo == 2.0 else 1.0) * (2.0 * H * dims.mm_hidden_size + 2.0 * dims.mm_hidden_size * n_vocab) * n_rows
     return total
 
 
-def lo6_pass_flops(dims, n_tokens: int, n_rows: int, kind: str, mode=None, prune: bool = True) -> float:
+def lo6_pass_flops(dims, n_tokens: int, n_rows: int, kind: str, mode=None, prune: bool = True, layer_bits=None) -> float:
     """The part of executed_flops() that runs on the e2m3 MFMA when the engine's option "precise_lo6" is on (fp16 engines, default): the second walk over K of the
     decoder GEMMs and of lm_head in the compensated modes (the TVG head's three-term products are 16-bit GEMMs of depth 3 K).  A roofline for such a call prices
     these flops at the fp6 peak (4x the 16-bit one) and the rest at the 16-bit one."""
-    if mode not in ("attn", "full"):
+    if mode not in ("attn", "full", "select"):
         return 0.0
     H, I = dims.hidden_size, dims.intermediate_size
     q = 2.0 * H * (dims.num_heads + 2 * dims.num_kv_heads) * dims.head_dim
     o, gu, d = 2.0 * H * H, 4.0 * H * I, 2.0 * H * I
     g2 = gu if mode == "full" else 0.0
     d2 = d if mode == "full" else 0.0
+    if mode == "select":
+        fq, fo, fg, fd = _select_factors(layer_bits if layer_bits is not None else [15] * dims.num_layers)
+        q, o, g2, d2 = (fq - 1.0) * q, (fo - 1.0) * o, (fg - 1.0) * gu, (fd - 1.0) * d
     total = dims.num_layers * (q + o + g2 + d2) * n_tokens
     if prune and n_rows <= n_tokens - n_tokens // 16:
         total -= (o + g2 + d2) * (n_tokens - n_rows)
@@ -445,12 +457,13 @@ class PairScorer(CalibrationMixin):
         self.exec_tokens += plan.n_tokens
         f8 = getattr(self.engine, "dtype", "") == "f8"
         if plan.kind == "vtg":
-            mode = self.vtg_mode                                             # None | "full"
-            self.exec_flops += executed_flops(self.m.dims, plan.n_tokens, plan.n_rows, "vtg", mode, prune=not f8)
+            mode = self.vtg_mode                                             # None | "full" | "select"
+            bits = getattr(self.engine, "layer_mask", None) if mode == "select" else None
+            self.exec_flops += executed_flops(self.m.dims, plan.n_tokens, plan.n_rows, "vtg", mode, prune=not f8, layer_bits=bits)
             if getattr(self.engine, "lo6", False):
-                self.exec_flops_lo6 += lo6_pass_flops(self.m.dims, plan.n_tokens, plan.n_rows, "vtg", mode, prune=not f8)
+                self.exec_flops_lo6 += lo6_pass_flops(self.m.dims, plan.n_tokens, plan.n_rows, "vtg", mode, prune=not f8, layer_bits=bits)
             comp = mode in VTG_SPLIT_MODES
-            self.engine.set_precise(comp, embeds=comp, mlp=True)
+            self.engine.set_precise(comp, embeds=comp, mlp=True, layers=mode == "select")
             try:
                 embeds = self.engine.assemble(plan.src_index, plan.feats)
                 return self.engine.score_vtg(plan.batch, embeds, plan.rows, plan.labels, plan.row_start)
@@ -500,10 +513,10 @@ class PairScorer(CalibrationMixin):
 
     # ---- which compensation the VTG calls need (`--vtg_precise auto`) ---------------------------------------------------------------
     def set_vtg_mode(self, mode) -> None:
-        """Compensation of this scorer's following VTG calls: None | "full".  The cached VTG feature rows are dropped when their layout changes ([hi | lo] rows in
+        """Compensation of this scorer's following VTG calls: None | "full" | "select" (the engine's per-layer mask: Engine.set_layer_mask).  The cached VTG feature rows are dropped when their layout changes ([hi | lo] rows in
         the compensated mode).  (The model's own record of what `auto` resolved to is BlimModel.resolve_vtg: calibrate_vtg and evaluation() write it.)"""
         mode = None if mode in (None, "none") else mode
-        if mode not in (None,) + VTG_MODES[1:]:
+        if mode not in (None,) + VTG_MODES[1:] + ("select",):
             raise ValueError(f"vtg mode {mode!r}: one of {VTG_MODES}")
         if not bool(getattr(self.engine, "can_precise", False)):
             mode = None

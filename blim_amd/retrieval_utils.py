@@ -260,14 +260,33 @@ def evaluation(model, data_loader, device, tokenizer, args):
 
     mod = model.module
     t_cal = time.time()
-    if getattr(mod, "vtg_precise", None) == "auto":
+    if getattr(mod, "vtg_precise", None) in ("auto", "select"):
         # `--vtg_precise auto` (the driver's default): which compensation the VTG calls need is MEASURED on this checkpoint (PairScorer.calibrate_vtg) -- once per set
         # of weights: what an earlier evaluation() resolved stands while the engine's weights and adapters are unchanged (BlimModel.vtg_mode) and is measured again
         # after every change (the training loop's validation loads new adapters every epoch: main.py:166)
+        # `--vtg_precise select`: the same, but what is measured is a per-layer, per-GEMM mask (PairScorer.calibrate_vtg_select)
         if hasattr(mod, "vtg_mode") and mod.vtg_mode() != "auto":
             stats["vtg_precise"] = mod.vtg_mode() or "none"
             if isinstance(scorer, PairScorer):
                 scorer.set_vtg_mode(mod.vtg_mode())
+            if mod.vtg_mode() == "select":
+                stats["vtg_select_mask"] = [int(b) for b in mod.vtg_select_mask()]
+        elif mod.vtg_precise == "select":
+            cal = scorer if isinstance(scorer, PairScorer) else new_scorer()
+            kt_, kv_ = min(args.topk, num_texts), min(args.topk, num_videos)
+            n_eval_vtg = num_videos * kt_ * (2 if args.cpn else 1) + num_texts * kv_
+            # a real multi-rank job splits the sample and gathers the deviations: every rank then picks the same mask (no agreement round needed); an emulated rank
+            # measures the whole sample
+            cal_share = (W, rank) if (collective and dist_utils.is_dist_avail_and_initialized()) else None
+            chosen, table = cal.calibrate_vtg_select(calibration_pairs(v2t_iv2, args.topk, n_queries=32, per_query=8), n_eval=n_eval_vtg, share=cal_share,
+                                                     confirm_pairs=calibration_pairs(v2t_iv2, args.topk, n_queries=256, per_query=8))
+            stats["vtg_precise"] = chosen; stats["vtg_precise_table"] = table
+            if chosen == "select":
+                stats["vtg_select_mask"] = table["mask"]
+            if rank == 0:
+                print(f"vtg_precise select: plain {fmt_table({'none': table['none']})}; "
+                      + (f"{table['k']} of {len(table['units'])} units plain, mask {''.join(f'{b:x}' for b in table['mask'])} (hex per layer: bit 0 QKV + attention, "
+                         f"1 o_proj, 2 gate|up, 3 down) in {table['seconds']:.2f} s" if chosen == "select" else "-> none"), file=sys.stderr, flush=True)
         else:
             cal = scorer if isinstance(scorer, PairScorer) else new_scorer()
             kt_, kv_ = min(args.topk, num_texts), min(args.topk, num_videos)

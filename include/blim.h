@@ -230,6 +230,12 @@ int blim_debug_gemm_stamps(void* device_buf);
  * "precise_embeds" (0/1): in precise mode the input embeddings / projector outputs are [hi | lo] rows of width 2 * hidden as well;
  * "precise_mlp" (0/1, default 1): 0 leaves the MLP branch plain in precise mode -- the TVG calls' "attn" mode (1.6x faster than fully compensated; TVG deviation at
  *   7B depth 8e-4 instead of 4e-5 on Gaussian weights, 3e-3 on weights with massive activations: `--tvg_precise auto` measures which one a checkpoint needs);
+ * "precise_layers" (0/1, default 0; 16-bit engines) and "precise_layer_bits" (value = (layer << 4) | bits, 0 <= layer < num_layers; every layer starts at 15):
+ *   a per-layer compensation mask for precise mode (`--vtg_precise select`).  With "precise_layers" = 1, layer `layer`'s units run compensated where its bits are
+ *   set -- bit 0 the QKV GEMM and the attention's three-term products, bit 1 o_proj, bit 2 gate|up, bit 3 down -- and plain elsewhere: the call keeps precise
+ *   mode's [hi | lo] buffer layout, a plain unit's GEMM reads only the hi halves and the unit's producer (RMSNorm, QKV epilogue, attention, SwiGLU epilogue)
+ *   writes no lo part for it.  The embeddings, the final norm and lm_head stay compensated; "precise_mlp" is ignored while the mask is on.  All bits set
+ *   computes what precise mode computes, bit for bit.  fp8 engines refuse both;
  * "precise_lo6" (0/1; 16-bit engines with hidden / intermediate sizes that are multiples of 128.  fp16 engines: default 1, env BLIM_PRECISE_LO6=0 turns it off.  bf16 engines
  *   (round 6): default 0 -- their parity mode walks K a second time in bf16, 1 - 3e-6 at 7B depth -- and 1 is an opt-in (env BLIM_PRECISE_LO6=1, `--second_pass e2m3 | auto`):
  *   a bf16 value's lo part is 2^-9 of it, hi + e2m3(lo) carry about what one fp16 rounding keeps: VTG scores 3 - 7e-5 from the fp32 reference at 7B depth on N(0, 0.02^2)
