@@ -313,6 +313,48 @@ class CalibrationMixin:
         table["seconds"] = time.time() - t0
         return "select", table
 
+    def verify_vtg_select(self, stored, pairs, bar: float = 1e-3, z: float = 4.5, n_eval: Optional[int] = None, tail_margin: float = 0.8, share=None, confirm_pairs=None,
+                          measure=None):
+        """A stored `--vtg_precise select` decision (`--calibration_store`, calibration_store.py) checked on THIS evaluation's pairs against the fully compensated
+        yardstick, by the rule the cold path decides with (`_decide`): a plain resolution ("none") exactly as calibrate_vtg_select's first step; a mask by one probe of
+        it on the sample, plus the forced confirmation on `confirm_pairs` when this evaluation's n_eval exceeds the one the mask was decided at.  stored = {"mode": "none"
+        | "select", "mask", "n_eval"}.  Accepted: the engine, this scorer and the model are set as calibrate_vtg_select sets them.  Rejected: nothing is resolved (the
+        caller runs the cold calibration).  measure: as calibrate_vtg_select's.  Returns (accepted, mode | None, {"verify": the stage table + accepted, "seconds"})."""
+        t0 = time.time()
+        pairs = np.asarray(pairs, dtype=np.int64)
+        resolve = getattr(self.m, "resolve_vtg", lambda mode, mask=None: None)
+        L = int(self.m.dims.num_layers)
+        mask = None
+        if stored.get("mode") == "select":
+            mask = np.asarray(stored.get("mask") or [], dtype=np.int64)
+            if mask.shape != (L,) or np.any(mask < 0) or np.any(mask > 15):
+                return False, None, {"verify": {"accepted": False, "reason": "the stored mask does not fit this model"}, "seconds": time.time() - t0}
+            mask = mask.astype(np.uint8)
+        elif stored.get("mode") != "none":
+            return False, None, {"verify": {"accepted": False, "reason": f"stored mode {stored.get('mode')!r}"}, "seconds": time.time() - t0}
+        if not bool(getattr(self.engine, "can_precise", False)):
+            return False, None, {"verify": {"accepted": False, "reason": "no compensated modes on this engine"}, "seconds": time.time() - t0}
+        self.engine.set_layer_mask(np.full(L, 15, dtype=np.uint8))
+        if measure is None:
+            self.__dict__["_select_ref"] = {}
+            measure = self._vtg_select_measure
+
+        def m_(block, sh):
+            return [self._gather_dev(measure(mask, block) if len(block) else np.zeros(0), sh)]
+
+        cheap = "none" if mask is None else "select"
+        grown = mask is not None and int(n_eval or 0) > int(stored.get("n_eval") or 0)
+        chosen, entry = self._decide(m_, pairs, confirm_pairs if (mask is None or grown) else None, share, n_eval, bar, z, tail_margin, cheap, "full", force_confirm=grown)
+        ok = chosen == cheap
+        if ok and mask is None:
+            self.set_vtg_mode(None)
+            resolve("none")
+        elif ok:
+            self.engine.set_layer_mask(mask)
+            self.set_vtg_mode("select")
+            resolve("select", mask)
+        return ok, (cheap if ok else None), {"verify": dict(entry, accepted=bool(ok), forced_confirm=bool(grown)), "seconds": time.time() - t0}
+
     def calibrate_tvg(self, pairs, bar: float = 1e-3, z: float = 4.5, n_eval: Optional[int] = None, tail_margin: float = 0.8, share=None, confirm_pairs=None, adopt=None):
         """The TVG calls' counterpart of calibrate_vtg (same criterion, same yardstick = the fully compensated mode).  Every TVG call of a 16-bit engine carries its
         embeddings, QKV, attention, o_proj and head as hi + lo; what is decided here is the MLP branch (87 % of the flops): `attn` leaves it plain (1.6x faster than

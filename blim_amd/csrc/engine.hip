@@ -7,6 +7,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <map>
 #include <string>
 #include <vector>
@@ -346,6 +347,116 @@ extern "C" int blim_weights_ready(const blim_engine* e) {
         auto it = e->loaded.find(n);
         if (it == e->loaded.end()) { blim_set_error("weight '%s' not loaded", n.c_str()); return BLIM_ERR_STATE; }
     }
+    return BLIM_OK;
+}
+
+// ---------------------------------------------------------------------------- content fingerprints (kernels.hpp: launch_hash_device, the definition)
+static AdapterW* find_adapter(blim_engine* e, const std::string& name, int* n_out, int* n_in);
+struct HashItem { std::string name; std::vector<int64_t> shape; const void* p; int64_t bytes; };
+
+// digests of device buffers: every buffer's two sums in one device array, one copy back, hash_finalize on the host -> dig[2 i], dig[2 i + 1]
+static int hash_items(const std::vector<HashItem>& items, hipStream_t s, std::vector<uint64_t>& dig) {
+    const size_t n = items.size();
+    dig.assign(2 * n, 0);
+    if (!n) return BLIM_OK;
+    unsigned long long* acc = nullptr;
+    HIP_TRY(hipMalloc((void**)&acc, 16 * n));
+    std::vector<uint64_t> sums(2 * n, 0);
+    int rc = BLIM_OK;
+    if (hipMemsetAsync(acc, 0, 16 * n, s) != hipSuccess) { blim_set_error("hash: hipMemsetAsync failed"); rc = BLIM_ERR_HIP; }
+    for (size_t i = 0; i < n && rc == BLIM_OK; ++i) rc = launch_hash_device(items[i].p, items[i].bytes, acc + 2 * i, 0, s);
+    if (rc == BLIM_OK && (hipMemcpyAsync(sums.data(), acc, 16 * n, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
+        blim_set_error("hash: copying the sums back failed");
+        rc = BLIM_ERR_HIP;
+    }
+    hipFree(acc);
+    if (rc != BLIM_OK) return rc;
+    for (size_t i = 0; i < n; ++i) hash_finalize(&sums[2 * i], items[i].bytes, &dig[2 * i]);
+    return BLIM_OK;
+}
+// the same definition over a host buffer (the fingerprint's manifest)
+static void hash_host(const std::vector<uint8_t>& b, uint64_t out[2]) {
+    uint64_t sums[2] = {0, 0};
+    const int64_t n = (int64_t)b.size();
+    for (int64_t i = 0; i < (n + 7) / 8; ++i) {
+        uint64_t w = 0;
+        for (int k = 0; k < 8 && 8 * i + k < n; ++k) w |= (uint64_t)b[8 * i + k] << (8 * k);
+        sums[0] += hash_mix1(w ^ ((uint64_t)(i + 1) * HASH_C1));
+        sums[1] += hash_mix2(w ^ ((uint64_t)(i + 1) * HASH_C2));
+    }
+    hash_finalize(sums, n, out);
+}
+
+extern "C" int blim_hash_device(const void* p, int64_t bytes, uint64_t out[2], void* stream) {
+    ARG_CHECK(out && bytes >= 0 && (p || bytes == 0));
+    std::vector<uint64_t> d;
+    TRY(hash_items({HashItem{"", {bytes}, p, bytes}}, (hipStream_t)stream, d));
+    out[0] = d[0]; out[1] = d[1];
+    return BLIM_OK;
+}
+
+// Everything the scores depend on, as the kernels read it: the placed base tensors (fused q|k|v, interleaved gate|up, 16-bit copies; norms and biases in f32), the
+// visual head's [hi | lo | hi] rows, the f32 A / B of every adapter kept apart, and the config.  Not the derived images (e4m3 / e2m3 copies, augmented weights: rebuilt
+// from these) nor the video vocabulary (per evaluation).  Per-tensor digests in name order, each with its name and shape, then the hash of that manifest.
+extern "C" int blim_weights_fingerprint(blim_engine* e, uint64_t out[2], void* stream) {
+    ARG_CHECK(e && out);
+    TRY(blim_weights_ready(e));
+    const blim_config& c = e->c;
+    const int64_t H = c.hidden_size, I = c.intermediate_size, V = c.vocab_size, M = c.mm_hidden_size;
+    std::vector<HashItem> items;
+    auto add = [&](const std::string& name, const void* p, std::vector<int64_t> shape, int64_t elem) {
+        int64_t bytes = elem;
+        for (int64_t d : shape) bytes *= d;
+        items.push_back(HashItem{name, shape, p, bytes});
+    };
+    add("embed_tokens", e->embed, {V, H}, 2);
+    add("lm_head", e->lm_head, {V, H}, 2);
+    add("visual_head", e->visual_head, {M, H}, 2);
+    if (e->visual_head3.p) add("visual_head:hilo", e->visual_head3.p, {M, 3 * H}, 2);
+    add("final_norm", e->final_norm, {H}, 4);
+    for (int w = 0; w < 2; ++w) {
+        const std::string p = w ? "tvg_mlp." : "mlp.";
+        add(p + "0.w", e->mlp_w0[w], {H, M}, 2); add(p + "0.b", e->mlp_b0[w], {H}, 4);
+        add(p + "2.w", e->mlp_w2[w], {H, H}, 2); add(p + "2.b", e->mlp_b2[w], {H}, 4);
+    }
+    for (int i = 0; i < c.num_layers; ++i) {
+        const std::string p = "layers." + std::to_string(i) + ".";
+        const LayerW& l = e->L[i];
+        add(p + "input_norm", l.norm1, {H}, 4); add(p + "post_norm", l.norm2, {H}, 4);
+        add(p + "qkv.w", l.wqkv, {e->qkv_n, H}, 2); add(p + "qkv.b", l.bqkv, {e->qkv_n}, 4);
+        add(p + "o_proj.w", l.wo, {H, H}, 2); add(p + "gate_up.w", l.wgu, {2 * I, H}, 2); add(p + "down_proj.w", l.wd, {H, I}, 2);
+    }
+    std::vector<std::string> adapted = {"lm_head", "mlp.0.w", "mlp.2.w", "tvg_mlp.0.w", "tvg_mlp.2.w"};
+    if (!e->AD.empty())
+        for (int i = 0; i < c.num_layers; ++i)
+            for (const char* t : {"q_proj.w", "k_proj.w", "v_proj.w", "o_proj.w"}) adapted.push_back("layers." + std::to_string(i) + "." + t);
+    for (const std::string& n : adapted) {
+        int n_out = 0, n_in = 0;
+        const AdapterW* a = find_adapter(e, n, &n_out, &n_in);
+        if (!a || !a->A) continue;
+        add(n + ":lora_A", a->A, {e->lora_r, a->n_in}, 4);
+        add(n + ":lora_B", a->B, {a->n_out, e->lora_r}, 4);
+    }
+    std::sort(items.begin(), items.end(), [](const HashItem& a, const HashItem& b) { return a.name < b.name; });
+    std::vector<uint64_t> dig;
+    TRY(hash_items(items, (hipStream_t)stream, dig));
+    std::vector<uint8_t> m;
+    auto put = [&](const void* p, size_t n) { m.insert(m.end(), (const uint8_t*)p, (const uint8_t*)p + n); };
+    const char tag[] = "blim weights fingerprint v1";
+    put(tag, sizeof(tag));
+    const int32_t cfg[] = {c.vocab_size, c.hidden_size, c.intermediate_size, c.num_layers, c.num_heads, c.num_kv_heads, c.mm_hidden_size, c.num_clips,
+                           e->f8 ? BLIM_COMPUTE_F8 : c.compute_dtype, e->lora_r};
+    const float cfg_f[] = {c.rms_eps, c.rope_theta, e->lora_scale};
+    put(cfg, sizeof(cfg));
+    put(cfg_f, sizeof(cfg_f));
+    for (size_t i = 0; i < items.size(); ++i) {
+        put(items[i].name.c_str(), items[i].name.size() + 1);
+        const int64_t nd = (int64_t)items[i].shape.size();
+        put(&nd, 8);
+        put(items[i].shape.data(), 8 * items[i].shape.size());
+        put(&dig[2 * i], 16);
+    }
+    hash_host(m, out);
     return BLIM_OK;
 }
 

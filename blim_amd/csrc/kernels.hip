@@ -661,3 +661,79 @@ int launch_f6_tiles(const bf16_t* in, int64_t ld, int64_t n_rows, int K, int dty
     LAUNCH_CHECK("f6_tiles");
     return BLIM_OK;
 }
+
+// ---------------------------------------------------------------------------- content hash (kernels.hpp: hash_mix1 / hash_mix2, the definition)
+__device__ __forceinline__ void hash_word(uint64_t w, uint64_t i, uint64_t& s1, uint64_t& s2) {
+    s1 += hash_mix1(w ^ ((i + 1) * HASH_C1));
+    s2 += hash_mix2(w ^ ((i + 1) * HASH_C2));
+}
+// word i read byte by byte, bytes past the end as zeros (the tail; buffers whose address is not 16-B aligned)
+__device__ __forceinline__ uint64_t hash_word_bytes(const uint8_t* p, int64_t bytes, int64_t i) {
+    uint64_t w = 0;
+    for (int b = 0; b < 8; ++b) {
+        const int64_t k = 8 * i + b;
+        if (k < bytes) w |= (uint64_t)p[k] << (8 * b);
+    }
+    return w;
+}
+// grid-stride over 16-B chunks (two words), four dwordx4 loads in flight per lane; per-thread u64 partials -> wave -> workgroup -> one atomic add per sum
+template <bool ALIGNED>
+__global__ void __launch_bounds__(256) hash_kernel(const uint8_t* p, int64_t bytes, unsigned long long* acc) {
+    uint64_t s1 = 0, s2 = 0;
+    const int64_t n_words = (bytes + 7) / 8;
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    int64_t first = 0;                                                      // words below `first` were read by the vector loop
+    if (ALIGNED) {
+        const int64_t n16 = bytes / 16;
+        const uint4* q = (const uint4*)p;
+        int64_t c = tid;
+        for (; c + 3 * nth < n16; c += 4 * nth) {
+            uint4 v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = q[c + u * nth];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const uint64_t i = 2 * (uint64_t)(c + u * nth);
+                hash_word(((uint64_t)v[u].y << 32) | v[u].x, i, s1, s2);
+                hash_word(((uint64_t)v[u].w << 32) | v[u].z, i + 1, s1, s2);
+            }
+        }
+        for (; c < n16; c += nth) {
+            const uint4 v = q[c];
+            hash_word(((uint64_t)v.y << 32) | v.x, 2 * (uint64_t)c, s1, s2);
+            hash_word(((uint64_t)v.w << 32) | v.z, 2 * (uint64_t)c + 1, s1, s2);
+        }
+        first = 2 * n16;
+    }
+    for (int64_t i = first + tid; i < n_words; i += nth) hash_word(hash_word_bytes(p, bytes, i), (uint64_t)i, s1, s2);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s1 += (uint64_t)__shfl_xor((unsigned long long)s1, o);
+        s2 += (uint64_t)__shfl_xor((unsigned long long)s2, o);
+    }
+    __shared__ uint64_t part[2][4];
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { part[0][wave] = s1; part[1][wave] = s2; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t a = 0, b = 0;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) { a += part[0][w]; b += part[1][w]; }
+        atomicAdd(acc, (unsigned long long)a);
+        atomicAdd(acc + 1, (unsigned long long)b);
+    }
+}
+int launch_hash_device(const void* p, int64_t bytes, unsigned long long* acc, int grid, hipStream_t s) {
+    ARG_CHECK(acc && bytes >= 0 && (p || bytes == 0));
+    if (bytes == 0) return BLIM_OK;
+    if (grid <= 0 && getenv("BLIM_HASH_GRID")) grid = atoi(getenv("BLIM_HASH_GRID"));
+    if (grid <= 0) {
+        int dev = 0, cus = 256;
+        HIP_TRY(hipGetDevice(&dev));
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+        grid = grid_for(bytes, 16 * 1024, 8 * cus);                        // >= 16 KiB per workgroup, at most 8 workgroups per CU
+    }
+    if (((uintptr_t)p & 15) == 0) hipLaunchKernelGGL(hash_kernel<true>, dim3(grid), dim3(256), 0, s, (const uint8_t*)p, bytes, acc);
+    else hipLaunchKernelGGL(hash_kernel<false>, dim3(grid), dim3(256), 0, s, (const uint8_t*)p, bytes, acc);
+    LAUNCH_CHECK("hash");
+    return BLIM_OK;
+}

@@ -48,6 +48,29 @@ int launch_quant_rows(const bf16_t* in, int64_t ld, int64_t n_rows, int K, int d
 // RMSNorm whose output is quantised per row (same arithmetic as launch_rmsnorm, then the rule above)
 int launch_rmsnorm_f8(const float* x, int64_t ldx, int64_t n_rows, int H, const float* w, float eps, uint8_t* out8, float* scale, hipStream_t s);
 
+// ---- content hash of a device buffer (blim_hash_device, blim_weights_fingerprint).  NOT cryptographic: a fingerprint against accidental change (another
+// checkpoint, an edited tensor), not against an adversary.  Definition (restated in numpy by blim_amd/calibration_store.py:hash_bytes): the buffer's `bytes`
+// bytes as little-endian 64-bit words w_i, the last one zero-padded; two sums mod 2^64, S_k = sum_i mix_k(w_i ^ (i + 1) C_k), k = 1, 2; the digest is
+// (mix_1(S_1 ^ (bytes + 1) C_1), mix_2(S_2 ^ (bytes + 1) C_2)).  Modular addition is exact and commutative, so the digest does not depend on the launch grid.
+// launch_hash_device ADDS S_1, S_2 to acc[0], acc[1] (device u64; the caller zeroes them).  grid = 0: 8 workgroups per CU (env BLIM_HASH_GRID overrides, tests).
+#define HASH_C1 0x9E3779B97F4A7C15ull
+#define HASH_C2 0xD1B54A32D192ED03ull
+__host__ __device__ __forceinline__ uint64_t hash_mix1(uint64_t x) {      // splitmix64's finaliser
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+__host__ __device__ __forceinline__ uint64_t hash_mix2(uint64_t x) {      // MurmurHash3's fmix64
+    x = (x ^ (x >> 33)) * 0xFF51AFD7ED558CCDull;
+    x = (x ^ (x >> 33)) * 0xC4CEB9FE1A85EC53ull;
+    return x ^ (x >> 33);
+}
+static inline void hash_finalize(const uint64_t sums[2], int64_t bytes, uint64_t out[2]) {
+    out[0] = hash_mix1(sums[0] ^ (((uint64_t)bytes + 1) * HASH_C1));
+    out[1] = hash_mix2(sums[1] ^ (((uint64_t)bytes + 1) * HASH_C2));
+}
+int launch_hash_device(const void* p, int64_t bytes, unsigned long long* acc, int grid, hipStream_t s);
+
 // ---- "lo6" (gemm.hpp: A6 / W6 / K6): the operands of the compensated GEMMs' second pass, e2m3 with one E8M0 (power-of-two) scale per 32 values that the block-scaled
 // MFMA applies itself, written as the LDS image of the pass's operand tiles (layout: gemm.hpp).
 // in: 16-bit [n_rows, K] (row stride ld) -> out: f6_tiles_bytes(n_rows, K) bytes; rows n_rows .. the next multiple of 256 are written as zeros.  K % 128 == 0.

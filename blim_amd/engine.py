@@ -114,6 +114,8 @@ def load_library(path: str = LIB_PATH):
         "blim_set_option": ([vp, C.c_char_p, i32], C.c_int),
         "blim_debug_read": ([vp, C.c_char_p, vp, i64, vp], C.c_int),
         "blim_debug_gemm_stamps": ([vp], C.c_int),
+        "blim_hash_device": ([vp, i64, vp, vp], C.c_int),
+        "blim_weights_fingerprint": ([vp, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -287,6 +289,16 @@ class Engine:
 
     def num_adapters(self) -> int:
         return int(self.lib.blim_num_adapters(self.h))
+
+    def fingerprint(self) -> str:
+        """Content fingerprint (32 hex digits) of everything the scores depend on -- placed weights as the kernels read them, adapters kept apart, visual head,
+        config (blim_weights_fingerprint; NOT cryptographic) -- the key of `--calibration_store` (calibration_store.py).  Computed once per weights_version."""
+        fp = getattr(self, "_fingerprint", None)
+        if fp is None or fp[0] != self.weights_version:
+            out = (C.c_uint64 * 2)()
+            _check(self.lib.blim_weights_fingerprint(self.h, out, _stream()), "blim_weights_fingerprint")
+            fp = self._fingerprint = (self.weights_version, f"{out[0]:016x}{out[1]:016x}")
+        return fp[1]
 
     def reserve(self, max_tokens: int, max_rows: int, compensated: bool = False):
         """Pre-size the workspaces.  compensated=True (16-bit engines): size them for compensated calls ([hi | lo] rows) and, on a "precise_lo6" engine, build the weights'
@@ -524,6 +536,16 @@ def segment_mean(logprob, row_start, mode: int = 0):
     out = torch.empty(n, dtype=torch.float32, device=logprob.device)
     _check(lib.blim_segment_mean(None, _ptr(logprob), _ptr(row_start), n, mode, _ptr(out), _stream()), "blim_segment_mean")
     return out
+
+
+def hash_device(t, nbytes: Optional[int] = None):
+    """(d1, d2): content hash of a contiguous device tensor's bytes (or its first `nbytes`), blim_hash_device -- calibration_store.hash_bytes states it in numpy."""
+    lib = load_library()
+    n = t.numel() * t.element_size() if nbytes is None else int(nbytes)
+    assert t.is_cuda and t.is_contiguous() and 0 <= n <= t.numel() * t.element_size()
+    out = (C.c_uint64 * 2)()
+    _check(lib.blim_hash_device(_ptr(t), n, out, _stream()), "blim_hash_device")
+    return int(out[0]), int(out[1])
 
 
 def fill_bell_bf16(out, seed: int, name: str, std: float, mean: float = 0.0):

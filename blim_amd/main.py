@@ -86,6 +86,11 @@ def get_args_parser():
                         "opt-in, 0.69x the plain rate with about one fp16 rounding's accuracy).  16bit: a second walk in the engine's own format (bf16 engines: the default and the "
                         "parity mode, 0.5x the plain rate at 1 - 3e-6).  auto (bf16 engines): measured on the loaded checkpoint like --vtg_precise auto -- the e2m3 form is kept "
                         "when its scores stay inside the bar of the 16-bit form's on the evaluation's own calibration pairs")
+    p.add_argument("--calibration_store", default=None, type=str, metavar="DIR",
+                   help="keep what --vtg_precise auto | select, --tvg_precise auto and --second_pass auto measure in DIR, one JSON record per weights fingerprint "
+                        "(blim_weights_fingerprint: weights, adapters, visual head, config) + numeric options + library build.  A later run on the same key checks the "
+                        "stored decision on its own calibration sample (select: one probe of the stored mask instead of the whole search) and measures again when the "
+                        "check fails.  Default: off")
     p.add_argument("--masked_query_zero", action="store_true",
                    help="PARITY-UNPINNED: masked query positions write a zero attention output, as the reference's flash-attention-2 class does (modeling_qwen2_flash.py:526-563) "
                         "where its eager / SDPA classes -- the semantics this engine's parity is pinned to -- compute them like any other row.  Changes the TVG-CPN prior only "

@@ -21,6 +21,7 @@ import time
 
 import numpy as np
 
+from . import calibration_store as cal_store
 from . import distributed as dist_utils
 from . import engine as eng
 from .calibration import TVG_MODES, VTG_MODES, VTG_SPLIT_MODES, calibration_pairs, predicted_max_deviation      # noqa: F401  (re-exported: the names callers import from here)
@@ -260,6 +261,24 @@ def evaluation(model, data_loader, device, tokenizer, args):
 
     mod = model.module
     t_cal = time.time()
+    store_state = {}
+
+    def store_session():
+        """`--calibration_store DIR` (calibration_store.py): this evaluation's record, opened at the first calibration that runs (None without the flag or on an engine
+        with nothing to measure).  A real job's ranks compare fingerprints and take rank 0's record; only rank 0 of a real job writes."""
+        if "s" not in store_state:
+            d = getattr(args, "calibration_store", None)
+            real_job = collective and dist_utils.is_dist_avail_and_initialized()
+            store_state["s"] = cal_store.open_session(d, mod, args, device, collective=real_job, rank=rank, writer=(rank == 0 and emulate is None)) \
+                if (d and bool(getattr(mod.engine, "can_precise", False))) else None
+        return store_state["s"]
+
+    def store_note(kind, request, chosen, table, n_eval):
+        """An `auto` decision: its check IS the cold calibration, so the record is compared with what was measured (and replaced when they differ)."""
+        ses = store_session()
+        if ses is not None:
+            ses.record(kind, request, chosen, table, n_eval)
+
     if getattr(mod, "vtg_precise", None) in ("auto", "select"):
         # `--vtg_precise auto` (the driver's default): which compensation the VTG calls need is MEASURED on this checkpoint (PairScorer.calibrate_vtg) -- once per set
         # of weights: what an earlier evaluation() resolved stands while the engine's weights and adapters are unchanged (BlimModel.vtg_mode) and is measured again
@@ -278,12 +297,22 @@ def evaluation(model, data_loader, device, tokenizer, args):
             # a real multi-rank job splits the sample and gathers the deviations: every rank then picks the same mask (no agreement round needed); an emulated rank
             # measures the whole sample
             cal_share = (W, rank) if (collective and dist_utils.is_dist_avail_and_initialized()) else None
-            chosen, table = cal.calibrate_vtg_select(calibration_pairs(v2t_iv2, args.topk, n_queries=32, per_query=8), n_eval=n_eval_vtg, share=cal_share,
-                                                     confirm_pairs=calibration_pairs(v2t_iv2, args.topk, n_queries=256, per_query=8))
+            first_p = calibration_pairs(v2t_iv2, args.topk, n_queries=32, per_query=8)
+            confirm_p = calibration_pairs(v2t_iv2, args.topk, n_queries=256, per_query=8)
+            ses = store_session()
+            if ses is not None:        # `--calibration_store`: a stored decision is verified on this sample; a miss or a failed verification measures as below
+                chosen, table = cal_store.vtg_select_with_store(cal, ses, first_p, confirm_p, n_eval_vtg, cal_share)
+            else:
+                chosen, table = cal.calibrate_vtg_select(first_p, n_eval=n_eval_vtg, share=cal_share, confirm_pairs=confirm_p)
             stats["vtg_precise"] = chosen; stats["vtg_precise_table"] = table
             if chosen == "select":
                 stats["vtg_select_mask"] = table["mask"]
-            if rank == 0:
+            if rank == 0 and table.get("source") == "store":
+                v_ = table["verify"]
+                print(f"vtg_precise select: stored decision verified on this evaluation's sample (max / rms {v_['max']:.1e} / {v_['rms']:.1e}, predicted max "
+                      f"{v_['pred']:.1e}) -> " + (f"mask {''.join(f'{b:x}' for b in table['mask'])}" if chosen == "select" else "none")
+                      + f" in {table['seconds']:.2f} s", file=sys.stderr, flush=True)
+            elif rank == 0:
                 print(f"vtg_precise select: plain {fmt_table({'none': table['none']})}; "
                       + (f"{table['k']} of {len(table['units'])} units plain, mask {''.join(f'{b:x}' for b in table['mask'])} (hex per layer: bit 0 QKV + attention, "
                          f"1 o_proj, 2 gate|up, 3 down) in {table['seconds']:.2f} s" if chosen == "select" else "-> none"), file=sys.stderr, flush=True)
@@ -297,6 +326,7 @@ def evaluation(model, data_loader, device, tokenizer, args):
             chosen, table = cal.calibrate_vtg(calibration_pairs(v2t_iv2, args.topk, n_queries=32, per_query=8), n_eval=n_eval_vtg, share=cal_share,
                                               confirm_pairs=calibration_pairs(v2t_iv2, args.topk, n_queries=256, per_query=8), adopt=adopt_of("vtg"))
             chosen = agree(chosen, VTG_MODES, lambda m_: (cal.set_vtg_mode(m_), getattr(mod, "resolve_vtg", lambda x: None)(m_)))
+            store_note("vtg", "auto", chosen, table, n_eval_vtg)
             stats["vtg_precise"] = chosen; stats["vtg_precise_table"] = table
             if rank == 0:
                 print("vtg_precise auto: deviation from the fully compensated mode on the calibration pairs (max / rms): "
@@ -308,10 +338,12 @@ def evaluation(model, data_loader, device, tokenizer, args):
         else:
             cal = scorer if isinstance(scorer, PairScorer) else new_scorer()
             kt_, kv_ = min(args.topk, num_texts), min(args.topk, num_videos)
+            n_eval_2 = num_videos * kt_ * (2 if args.cpn else 1) + num_texts * kv_
             chosen, table = cal.calibrate_second_pass(calibration_pairs(v2t_iv2, args.topk, n_queries=32, per_query=8),
-                                                      n_eval=num_videos * kt_ * (2 if args.cpn else 1) + num_texts * kv_, share=share_of("second"),
+                                                      n_eval=n_eval_2, share=share_of("second"),
                                                       confirm_pairs=calibration_pairs(v2t_iv2, args.topk, n_queries=256, per_query=8), adopt=adopt_of("second"))
             chosen = agree(chosen, ("e2m3", "16bit"), lambda m_: mod.resolve_second_pass(m_))
+            store_note("second", "auto", chosen, table, n_eval_2)
             stats["second_pass"] = chosen; stats["second_pass_table"] = table
             if rank == 0:
                 print("second_pass auto: deviation of the e2m3 second pass from the bf16 one on the calibration pairs (max / rms): " + fmt_table(table) + f" -> {chosen}", file=sys.stderr, flush=True)
@@ -330,9 +362,11 @@ def evaluation(model, data_loader, device, tokenizer, args):
             kt_, kv_ = min(args.topk, num_texts), min(args.topk, num_videos)
             cal_share = share_of("tvg")
             tc = calibration_pairs(t2v_iv2, args.topk, n_queries=256, per_query=4)     # the confirmation sample, should the first one's extrapolation alone miss the bar
-            chosen, table = cal.calibrate_tvg(np.stack([tp[:, 1], tp[:, 0]], axis=1), n_eval=num_videos * kt_ + num_texts * kv_ * (2 if args.cpn else 1), share=cal_share,
+            n_eval_t = num_videos * kt_ + num_texts * kv_ * (2 if args.cpn else 1)
+            chosen, table = cal.calibrate_tvg(np.stack([tp[:, 1], tp[:, 0]], axis=1), n_eval=n_eval_t, share=cal_share,
                                               confirm_pairs=np.stack([tc[:, 1], tc[:, 0]], axis=1), adopt=adopt_of("tvg"))
             chosen = agree(chosen, TVG_MODES, lambda m_: (cal.set_tvg_mode(m_), getattr(mod, "resolve_tvg", lambda x: None)(m_)))
+            store_note("tvg", "auto", chosen, table, n_eval_t)
             stats["tvg_precise"] = chosen; stats["tvg_precise_table"] = table
             if rank == 0:
                 print("tvg_precise auto: deviation from the fully compensated mode on the calibration pairs, likelihood + prior (max / rms): "
@@ -342,6 +376,13 @@ def evaluation(model, data_loader, device, tokenizer, args):
         stats["calibration_seconds"] = round(time.time() - t_cal, 4)
         # an emulated rank with no decision handed in measured the job's WHOLE sample (share_of): W times a real rank's share of this time
         stats["calibration_whole_sample"] = bool(emulate is not None and getattr(args, "agreed_modes", None) is None and W > 1)
+    if store_state.get("s") is not None:
+        ses = store_state["s"]
+        stats["calibration_source"] = ses.finish()
+        stats["weights_fingerprint"] = ses.fingerprint
+        if rank == 0:
+            print(f"calibration store: {stats['calibration_source']} (weights {ses.fingerprint}, {', '.join(sorted(ses.decisions))}) in "
+                  f"{stats.get('calibration_seconds', time.time() - t_cal):.2f} s", file=sys.stderr, flush=True)
     mark("setup")
 
     def run_pass(S, sims_rows, start, query_is_video, ftype, cpn):

@@ -101,6 +101,18 @@ int blim_init_synthetic_weights(blim_engine* e, uint64_t seed);
 /* 0 when every tensor has been loaded, BLIM_ERR_STATE (message lists a missing tensor) otherwise. */
 int blim_weights_ready(const blim_engine* e);
 
+/* ---- content fingerprints (additive in ABI v9; `--calibration_store`, blim_amd/calibration_store.py).  NOT cryptographic: they tell another checkpoint or an
+ * edited tensor apart, they do not resist an adversary.  The hash of `bytes` bytes: little-endian 64-bit words w_i (the last one zero-padded), two sums mod 2^64
+ * S_k = sum_i mix_k(w_i ^ (i + 1) C_k) with two independent 64-bit finalisers, the byte length mixed in at the end (csrc/kernels.hpp states it; the sums are exact
+ * and commutative, so the digest does not depend on the launch grid).  Reads at HBM rate, 64-bit indexing (buffers beyond 4 GiB).
+ * blim_hash_device: `p` a DEVICE pointer (any alignment), `out` a HOST array; the call synchronises `stream`.
+ * blim_weights_fingerprint: every tensor the scores depend on as the kernels read it -- each tensor placed by blim_load_weight / blim_init_synthetic_weights in its
+ * kernel layout (and as blim_train_merge left it), the fp32 visual head's hi + lo rows, the A / B / scaling of every adapter loaded apart -- and the config (dims,
+ * compute dtype); not the derived images (e4m3 / e2m3 copies, augmented weights) nor the video vocabulary.  The per-tensor digests are combined in name order with
+ * each name and shape: the result does not depend on the order of loading.  BLIM_ERR_STATE until every weight is loaded.  Synchronises `stream`. */
+int blim_hash_device(const void* p, int64_t bytes, uint64_t out[2], void* stream);
+int blim_weights_fingerprint(blim_engine* e, uint64_t out[2], void* stream);
+
 /* ---- LoRA adapters of a fine-tuned checkpoint, KEPT APART as the reference keeps them.  Replaces main.py:96-105 (peft get_peft_model on the
  * projector `mlp` / `tvg_mlp` Linear "0" / "2", on every q/k/v/o_proj and on lm_head) + main.py:125-128 (load_state_dict of the resume file): the
  * reference evaluates y = W x + b + (alpha / r) B (A x) with A, B as separate matrices; so does the engine for every `weight_name` an adapter was
