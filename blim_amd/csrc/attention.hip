@@ -14,6 +14,8 @@
 
 #include <stdlib.h>
 
+#include <type_traits>
+
 #define HD 128
 #define KT 32  // keys per tile
 #define QB 32  // queries per block
@@ -27,8 +29,10 @@ template <int MAXC, bool SPLIT> struct attn_bound { static constexpr int value =
 // SPLIT: three-term products over Q, K, V = hi + lo (compensated mode); OUT_LO: the output leaves as hi + lo.  Both or neither is the whole-call form; the two mixed forms
 // are the per-layer mask's (engine option "precise_layers"): plain products with a [hi | lo] output store (QKV plain, o_proj compensated) and split products with a
 // hi-only store (QKV compensated, o_proj plain)
-template <bool USE_TR, int MAXC, int DT, bool SPLIT = false, bool OUT_LO = SPLIT>
-__global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(const AttnParams p) {
+// PC: the prefix tiles of a sequence that names a cache slot (AttnParams::pfx_slot) come from the gallery's persistent K/V cache -- the same values in the same
+// tile order as the in-batch prefix they were captured from, so the result is bit for bit that of the uncached call (blim.h: blim_score_vtg_cached)
+template <bool USE_TR, int MAXC, int DT, bool SPLIT = false, bool OUT_LO = SPLIT, bool PC = false>
+__global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(const typename std::conditional<PC, AttnPcParams, AttnParams>::type p) {
     __shared__ __attribute__((aligned(16))) bf16_t k_lds[(SPLIT ? 2 : 1) * KT * HD];   // SPLIT: K_hi tile, then K_lo tile
     __shared__ __attribute__((aligned(16))) bf16_t v_lds[(SPLIT ? 2 : 1) * KT * HD];   // SPLIT: V_hi tile, then V_lo tile
     __shared__ uint32_t vis_lds[KT / 4];  // 32 visibility bytes
@@ -51,8 +55,13 @@ __global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(
     const int blk = blockIdx.x;
     const int s = p.blk_seq[blk], q0 = p.blk_q0[blk];
     const int sstart = p.seq_start[s], slen = p.seq_len[s];
-    const int plen = p.pfx_len[s];
+    int plen = p.pfx_len[s];
     const int pstart = plen > 0 ? p.pfx_start[s] : 0;
+    const bf16_t* cbase = nullptr;           // PC: this sequence's cache slot (nullptr: in-batch prefix)
+    if constexpr (PC) {
+        const int slot = p.pfx_slot[s];
+        if (slot >= 0 && slot < p.pc_n_slots) { cbase = p.pfx_cache + (int64_t)slot * p.pc_slot_stride; plen = min(plen, p.pc_max_len); }
+    }
 
     const int qi = lane & 31, hf = lane >> 5;
     const int qtok = sstart + min(q0 + qi, slen - 1);
@@ -107,6 +116,22 @@ __global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(
     auto load_tile = [&](int t) __attribute__((always_inline)) {
         int base_tok, k0, seg_len; bool causal;
         tile_desc(t, base_tok, k0, seg_len, causal);
+        if constexpr (PC) {
+            if (cbase != nullptr && t < n_ptiles) {      // (workgroup-uniform) a cached prefix tile: the same chunks from the slot's rows, every key visible
+                const int ck = kh * HD, cv = p.num_kv_heads * HD + kh * HD;
+#pragma unroll
+                for (int i = 0; i < MAXC; ++i) {
+                    const int idx = tid + i * nthreads;
+                    if (idx < NCHUNK) {
+                        const int isv = idx >> 9, row = (idx >> 4) & 31, ch = idx & 15;
+                        const int kk = min(k0 + row, seg_len - 1);
+                        st[i] = *(const uint4*)(cbase + (int64_t)kk * p.pc_ld + (isv == 0 ? ck : isv == 1 ? cv : isv == 2 ? cv + p.pc_lo_off : ck + p.pc_lo_off) + 8 * ch);
+                    }
+                }
+                if (tid < KT) st_vis = (k0 + tid < seg_len) ? (uint8_t)1 : (uint8_t)0;
+                return;
+            }
+        }
 #pragma unroll
         for (int i = 0; i < MAXC; ++i) {
             const int idx = tid + i * nthreads;
@@ -327,6 +352,49 @@ __global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(
                                                                     pack2<DT>(x2 - from16<DT>(to16<DT>(x2)), x3 - from16<DT>(to16<DT>(x3))));
             }
     }
+}
+
+// The cached forms (p.pfx_cache != nullptr): the four forms of launch_attention below with the prefix read from the cache, launched with the same grids and
+// blocks (transposed V reads, 16-bit engines).  A separate function, so that the uncached dispatch stays as it was.
+static int launch_attention_pc(const AttnPcParams& p, int G, hipStream_t stream) {
+    const dim3 grid(p.n_blocks, p.num_kv_heads), block(64 * G);
+    static const int g_split = getenv("BLIM_ATTN_HEAD_GROUPS") ? atoi(getenv("BLIM_ATTN_HEAD_GROUPS")) : 2;
+#define ATTN_PC(MC, SP, OL, GRID, BLOCK)                                                                                           \
+    do {                                                                                                                       \
+        if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, MC, DT_F16, SP, OL, true>), GRID, BLOCK, 0, stream, p);      \
+        else hipLaunchKernelGGL((attn_kernel<true, MC, DT_BF16, SP, OL, true>), GRID, BLOCK, 0, stream, p);                   \
+    } while (0)
+    if (p.v_lo_off != 0) {
+        if (p.out_lo_off) { if (G >= 7) ATTN_PC(5, true, true, grid, block); else ATTN_PC(4, true, true, grid, dim3(512)); }
+        else { if (G >= 7) ATTN_PC(5, true, false, grid, block); else ATTN_PC(4, true, false, grid, dim3(512)); }
+    } else if (p.out_lo_off != 0) {
+        if (G >= 5 && g_split > 1) ATTN_PC(4, false, true, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        else if (G >= 4) ATTN_PC(4, false, true, grid, block);
+        else if (G >= 2) ATTN_PC(8, false, true, grid, block);
+        else ATTN_PC(16, false, true, grid, block);
+    } else {
+        if (G >= 5 && g_split > 1) ATTN_PC(4, false, false, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        else if (G >= 4) ATTN_PC(4, false, false, grid, block);
+        else if (G >= 2) ATTN_PC(8, false, false, grid, block);
+        else ATTN_PC(16, false, false, grid, block);
+    }
+#undef ATTN_PC
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { blim_set_error("attention launch failed: %s", hipGetErrorString(e)); return BLIM_ERR_HIP; }
+    return BLIM_OK;
+}
+
+int launch_attention_cached(const AttnPcParams& p, hipStream_t stream) {
+    ARG_CHECK(p.qkv && p.out && p.key_visible && p.seq_start && p.seq_len && p.pfx_start && p.pfx_len && p.blk_seq && p.blk_q0);
+    ARG_CHECK(p.n_blocks > 0 && p.num_kv_heads > 0 && p.num_heads % p.num_kv_heads == 0);
+    ARG_CHECK(p.ldq % 8 == 0 && p.ldo % 4 == 0);
+    ARG_CHECK(p.pfx_cache && p.pfx_slot && p.pc_n_slots > 0 && p.pc_max_len > 0 && p.pc_ld % 8 == 0 && p.pc_lo_off % 8 == 0 && p.pc_slot_stride % 8 == 0 && p.pc_lo_off >= 0);
+    ARG_CHECK((p.dtype == DT_F16 || p.dtype == DT_BF16) && p.v_lo_off >= 0 && p.out_lo_off >= 0 && p.v_lo_off % 8 == 0 && p.out_lo_off % 4 == 0);
+    if (p.out8 || p.lse_out) { blim_set_error("attention: the prefix-cache forms write a 16-bit output and no lse"); return BLIM_ERR_ARG; }
+    if (p.v_lo_off != 0 && p.pc_lo_off == 0) { blim_set_error("attention: a compensated call needs a prefix cache that holds lo parts"); return BLIM_ERR_ARG; }
+    const int G = p.num_heads / p.num_kv_heads;
+    if (G > 8) { blim_set_error("attention: %d query heads per kv head > 8 unsupported", G); return BLIM_ERR_ARG; }
+    return launch_attention_pc(p, G, stream);
 }
 
 int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream) {

@@ -40,3 +40,16 @@ struct AttnParams {
 };
 
 int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream);
+
+// The gallery's cached forms (blim.h: blim_score_vtg_cached): sequence s with pfx_slot[s] >= 0 reads its prefix tiles from slot pfx_slot[s] of a persistent K/V
+// cache instead of `qkv` rows [pfx_start[s], +pfx_len[s]); -1 keeps the in-batch prefix.  pfx_cache = THIS layer's block of slot 0; a slot's rows are pc_slot_stride
+// values apart, its positions pc_ld apart, each [K heads | V heads (| K_lo | V_lo at +pc_lo_off)].  Every cached key is visible; pfx_len is clamped to pc_max_len and
+// a slot >= pc_n_slots reads the in-batch prefix.  The same four forms as launch_attention (transposed V reads, 16-bit output, no lse_out); a kernel argument of its
+// own, so that the uncached kernels keep their argument layout and code.
+struct AttnPcParams : AttnParams {
+    const bf16_t* pfx_cache;
+    const int32_t* pfx_slot;
+    int64_t pc_slot_stride, pc_ld, pc_lo_off;
+    int pc_n_slots, pc_max_len;
+};
+int launch_attention_cached(const AttnPcParams& p, hipStream_t stream);

@@ -306,6 +306,7 @@ extern "C" int blim_load_weight(blim_engine* e, const char* name, const void* da
         HIP_TRY(hipMemcpy(e->stage.p, data, bytes, hipMemcpyHostToDevice));
         src = e->stage.p;
     }
+    e->weights_epoch++;
     TRY(place_weight(e, name, src, dtype));
     HIP_TRY(hipDeviceSynchronize());
     return BLIM_OK;
@@ -320,6 +321,7 @@ static const double kSigma4 = 37837.22723328507;  // sqrt(4 * (65536^2 - 1) / 12
 
 extern "C" int blim_init_synthetic_weights(blim_engine* e, uint64_t seed) {
     ARG_CHECK(e);
+    e->weights_epoch++;
     for (const std::string& name : all_weight_names(e)) {
         WeightSlot s;
         if (!find_slot(e, name, s)) { blim_set_error("internal: no slot for %s", name.c_str()); return BLIM_ERR_STATE; }
@@ -581,6 +583,7 @@ static void free_aug(blim_engine* e) {
 
 extern "C" int blim_clear_adapters(blim_engine* e) {
     ARG_CHECK(e);
+    e->weights_epoch++;
     HIP_TRY(hipDeviceSynchronize());
     free_aug(e);
     for (void* p : e->ad_owned) hipFree(p);
@@ -606,6 +609,7 @@ extern "C" int blim_num_adapters(blim_engine* e) {
 
 extern "C" int blim_load_adapter(blim_engine* e, const char* weight_name, const float* A, const float* B, int32_t lora_r, float lora_alpha) {
     ARG_CHECK(e && weight_name && A && B && lora_r > 0 && lora_r <= 16 && lora_alpha > 0.f);
+    e->weights_epoch++;
     const float scale = lora_alpha / (float)lora_r;
     if (e->lora_r && (e->lora_r != lora_r || e->lora_scale != scale)) {
         blim_set_error("adapter '%s': r = %d, alpha / r = %g, but the engine's adapters have r = %d, alpha / r = %g (one LoraConfig per model, main.py:96-101)", weight_name, lora_r,
@@ -921,6 +925,13 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
             p.bias = l.bqkv; p.rope_cols = (c.num_heads + c.num_kv_heads) * 128; p.rope_rows = rope_rows; p.rope_stride = round_up(T, 256);
             TRY(launch_gemm(EPI_QKV, p, s));
         }
+        if (e->pc_fill) {      // gallery fill: this layer's K / V heads of the prefix rows (+ their lo parts where the attention reads them) into the cache slots
+            SpanGuard g(e, s, TC_MISC, 0);
+            const blim_prefix_cache* pc = e->pc_fill;
+            const int kvh = 2 * c.num_kv_heads * 128;
+            TRY(launch_kv_capture(qkv, (int64_t)pf * e->qkv_n, (int64_t)c.num_heads * 128, (cA && pc->comp) ? e->qkv_n : 0, kvh, e->pc_cap_row, T,
+                                  pc->kv + (int64_t)li * pc->max_len * pc->kv_w, pc->slot_stride, pc->kv_w, kvh, pc->max_len, pc->n_slots, s));
+        }
         {
             SpanGuard g(e, s, TC_ATTN, 0);
             AttnParams a;
@@ -931,7 +942,16 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
             a.v_lo_off = cA ? e->qkv_n : 0; a.out_lo_off = cO ? Hq : 0;            // (four forms: attention.hpp)
             a.out8 = nullptr; a.ldo8 = 0; a.out_mx = nullptr; a.mx_stride = 0; a.lse_out = nullptr;
             if (o8 && e->f8_fuse) { a.out8 = a8; a.ldo8 = H; a.out_mx = (uint8_t*)e->attn_mx.p; a.mx_stride = Tp; }   // fp8: e4m3 + E8M0 per (token, head)
-            TRY(launch_attention(a, e->attn_tr, s));
+            if (e->pc_read) {      // gallery scoring: sequences that name a slot read their prefix tiles from it (attention.hpp: the cached forms)
+                const blim_prefix_cache* pc = e->pc_read;
+                AttnPcParams pa;
+                static_cast<AttnParams&>(pa) = a;
+                pa.pfx_cache = pc->kv + (int64_t)li * pc->max_len * pc->kv_w; pa.pfx_slot = e->pc_slot; pa.pc_slot_stride = pc->slot_stride; pa.pc_ld = pc->kv_w;
+                pa.pc_lo_off = pc->comp ? 2 * c.num_kv_heads * 128 : 0; pa.pc_n_slots = pc->n_slots; pa.pc_max_len = pc->max_len;
+                TRY(launch_attention_cached(pa, s));
+            } else {
+                TRY(launch_attention(a, e->attn_tr, s));
+            }
             if (e->masked_query_zero) TRY(launch_zero_rows(attn, (int64_t)pf * Hq, b->key_visible, T, (int)(pf * Hq), s));
         }
         const bool fuse_o = o8 && e->f8_fuse;
@@ -1251,6 +1271,161 @@ extern "C" int blim_score_vtg(blim_engine* e, const blim_batch* b, const void* e
     ARG_CHECK(e && rows && labels && row_start && score && n_rows > 0 && n_pairs > 0);
     TRY(reserve_rows(e, n_rows));
     TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream, e->c.hidden_size + e->aug));     // rows laid out for the adapted lm_head
+    TRY(vtg_logprobs_impl(e, e->hsel.p, e->precise, labels, n_rows, (float*)e->logprob.p, stream, true));
+    return blim_segment_mean(e, (const float*)e->logprob.p, row_start, n_pairs, 0, score, stream);
+}
+
+// ---------------------------------------------------------------------------- gallery prefix cache (blim.h: blim_prefix_cache_*)
+static PcSnap pc_snap(const blim_engine* e) {
+    PcSnap s;
+    s.epoch = e->weights_epoch;
+    s.mqz = e->masked_query_zero;
+    s.precise = e->precise;
+    if (e->precise) {
+        s.embeds = e->precise_embeds; s.lo6 = e->lo6; s.layers = e->layer_mask_on;
+        if (e->layer_mask_on) s.bits = e->layer_bits; else s.mlp = e->precise_mlp;
+    }
+    return s;
+}
+static const char* pc_diff(const PcSnap& a, const PcSnap& b) {
+    if (a.epoch != b.epoch) return "the weights (a weight, adapter or merge changed them since the fill)";
+    if (a.precise != b.precise) return "option 'precise'";
+    if (a.embeds != b.embeds) return "option 'precise_embeds'";
+    if (a.mlp != b.mlp) return "option 'precise_mlp'";
+    if (a.layers != b.layers) return "option 'precise_layers'";
+    if (a.bits != b.bits) return "option 'precise_layer_bits'";
+    if (a.lo6 != b.lo6) return "option 'precise_lo6'";
+    if (a.mqz != b.mqz) return "option 'masked_query_zero'";
+    return nullptr;
+}
+static int pc_dims(const blim_engine* e, int32_t n_slots, int32_t max_len, int32_t compensated, int* kv_w, int* hid_w, int64_t* bytes) {
+    ARG_CHECK(e && n_slots > 0 && max_len > 0);
+    const blim_config& c = e->c;
+    *kv_w = 2 * c.num_kv_heads * 128 * (compensated ? 2 : 1);
+    *hid_w = c.hidden_size * (compensated ? 2 : 1);
+    *bytes = (int64_t)n_slots * ((int64_t)c.num_layers * max_len * *kv_w + *hid_w) * 2;
+    return BLIM_OK;
+}
+extern "C" int64_t blim_prefix_cache_bytes(const blim_engine* e, int32_t n_slots, int32_t max_len, int32_t compensated) {
+    int kv_w = 0, hid_w = 0; int64_t bytes = 0;
+    return pc_dims(e, n_slots, max_len, compensated, &kv_w, &hid_w, &bytes) == BLIM_OK ? bytes : -1;
+}
+extern "C" int blim_prefix_cache_create(blim_engine* e, int32_t n_slots, int32_t max_len, int32_t compensated, blim_prefix_cache** out) {
+    ARG_CHECK(out);
+    *out = nullptr;
+    int kv_w = 0, hid_w = 0; int64_t bytes = 0;
+    TRY(pc_dims(e, n_slots, max_len, compensated, &kv_w, &hid_w, &bytes));
+    if (e->f8) { blim_set_error("prefix cache: fp8 engines are not supported"); return BLIM_ERR_STATE; }
+    if (e->c.hidden_size % 8) { blim_set_error("prefix cache: hidden_size %% 8 != 0"); return BLIM_ERR_ARG; }
+    blim_prefix_cache* pc = new blim_prefix_cache();
+    pc->e = e; pc->n_slots = n_slots; pc->max_len = max_len; pc->comp = compensated != 0; pc->kv_w = kv_w; pc->hid_w = hid_w;
+    pc->slot_stride = (int64_t)e->c.num_layers * max_len * kv_w;
+    const size_t kv_bytes = (size_t)n_slots * pc->slot_stride * 2;
+    if (hipMalloc((void**)&pc->kv, kv_bytes) != hipSuccess || hipMalloc((void**)&pc->hid, (size_t)n_slots * hid_w * 2) != hipSuccess) {
+        (void)hipGetLastError();
+        if (pc->kv) hipFree(pc->kv);
+        delete pc;
+        blim_set_error("prefix cache: out of device memory for %d slots of %d positions (%lld MB)", n_slots, max_len, (long long)(bytes >> 20));
+        return BLIM_ERR_NOMEM;
+    }
+    pc->len.assign(n_slots, -1);
+    pc->snap.assign(n_slots, PcSnap());
+    *out = pc;
+    return BLIM_OK;
+}
+extern "C" void blim_prefix_cache_destroy(blim_prefix_cache* pc) {
+    if (!pc) return;
+    (void)hipDeviceSynchronize();
+    if (pc->kv) hipFree(pc->kv);
+    if (pc->hid) hipFree(pc->hid);
+    if (pc->map.p) hipFree(pc->map.p);
+    delete pc;
+}
+extern "C" int blim_prefix_cache_slot_len(const blim_prefix_cache* pc, int32_t slot) {
+    ARG_CHECK(pc && slot >= 0 && slot < pc->n_slots);
+    return pc->len[slot];
+}
+// lends the cache to run_layers for one call and takes it back on every exit path
+struct PcLease {
+    blim_engine* e;
+    ~PcLease() { e->pc_fill = nullptr; e->pc_cap_row = nullptr; e->pc_read = nullptr; e->pc_slot = nullptr; }
+};
+extern "C" int blim_prefix_cache_fill(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const void* embeds, const int32_t* slot_of_seq, void* stream) {
+    ARG_CHECK(e && pc && pc->e == e && embeds && slot_of_seq);
+    TRY(check_batch(b));
+    if (b->own_start) { blim_set_error("prefix cache fill: segmented sequences (own_start) are not prefixes"); return BLIM_ERR_ARG; }
+    if (e->precise && !pc->comp) { blim_set_error("prefix cache fill: a compensated call needs a cache created with compensated = 1"); return BLIM_ERR_STATE; }
+    if (!e->attn_tr) { blim_set_error("prefix cache: option 'attn_tr' must be 1"); return BLIM_ERR_STATE; }
+    hipStream_t s = (hipStream_t)stream;
+    const int n = b->n_seqs;
+    const int64_t T = b->n_tokens;
+    std::vector<int32_t> h(3 * (size_t)n);
+    HIP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipMemcpy(h.data(), b->seq_start, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.data() + n, b->seq_len, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(h.data() + 2 * n, b->pfx_len, (size_t)n * 4, hipMemcpyDeviceToHost));
+    // device map: [T] destination row per token | [n] last token per sequence | [n] slot per sequence
+    std::vector<int32_t> m((size_t)T + 2 * (size_t)n, -1);
+    std::vector<bool> seen(pc->n_slots, false);
+    for (int q = 0; q < n; ++q) {
+        const int st = h[q], ln = h[n + q], slot = slot_of_seq[q];
+        if (h[2 * n + q] != 0) { blim_set_error("prefix cache fill: sequence %d names a prefix of its own", q); return BLIM_ERR_ARG; }
+        if (slot < 0 || slot >= pc->n_slots) { blim_set_error("prefix cache fill: slot %d of sequence %d outside 0 .. %d", slot, q, pc->n_slots - 1); return BLIM_ERR_ARG; }
+        if (seen[slot]) { blim_set_error("prefix cache fill: slot %d named twice", slot); return BLIM_ERR_ARG; }
+        seen[slot] = true;
+        if (ln < 1 || ln > pc->max_len || st < 0 || (int64_t)st + ln > T) {
+            blim_set_error("prefix cache fill: sequence %d of %d tokens (at %d) does not fit a slot of %d positions in a batch of %lld tokens", q, ln, st, pc->max_len, (long long)T);
+            return BLIM_ERR_ARG;
+        }
+        for (int k = 0; k < ln; ++k) m[(size_t)st + k] = slot * pc->max_len + k;
+        m[(size_t)T + q] = st + ln - 1;
+        m[(size_t)T + n + q] = slot;
+    }
+    TRY(ensure(pc->map, m.size() * 4));
+    HIP_TRY(hipMemcpy(pc->map.p, m.data(), m.size() * 4, hipMemcpyHostToDevice));
+    const int32_t* cap = (const int32_t*)pc->map.p;
+    const int32_t* last = cap + T;
+    const int32_t* slots = last + n;
+    for (int q = 0; q < n; ++q) pc->len[slot_of_seq[q]] = -1;        // a failed fill leaves its slots empty
+    TRY(reserve_rows(e, n));
+    {
+        PcLease lease{e};
+        e->pc_fill = pc; e->pc_cap_row = cap;
+        TRY(decode_impl(e, b, embeds, last, n, e->hsel.p, e->precise, nullptr, stream));     // rows [hi | lo] of width 2 H (precise) or H
+    }
+    // the last prefix row's final-norm hidden state (it predicts the first response token): hi (| lo) into the slot's hidden row
+    TRY(launch_rows_by_index((uint16_t*)pc->hid, pc->hid_w, (const uint16_t*)e->hsel.p, (int64_t)(e->precise ? 2 : 1) * e->c.hidden_size, slots, n,
+                             (e->precise ? 2 : 1) * e->c.hidden_size, pc->n_slots, 0, 0, s));
+    const PcSnap now = pc_snap(e);
+    for (int q = 0; q < n; ++q) { pc->len[slot_of_seq[q]] = h[n + q]; pc->snap[slot_of_seq[q]] = now; }
+    return BLIM_OK;
+}
+extern "C" int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                                     const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* row_start, int32_t n_pairs,
+                                     float* score, void* stream) {
+    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && row_start && score && n_rows > 0 && n_pairs > 0);
+    if (!e->attn_tr) { blim_set_error("prefix cache: option 'attn_tr' must be 1"); return BLIM_ERR_STATE; }
+    const PcSnap now = pc_snap(e);
+    for (int k = 0; k < n_used; ++k) {
+        const int slot = slots_used[k];
+        if (slot < 0 || slot >= pc->n_slots) { blim_set_error("prefix cache: slot %d outside 0 .. %d", slot, pc->n_slots - 1); return BLIM_ERR_ARG; }
+        if (pc->len[slot] < 0) { blim_set_error("prefix cache: slot %d was never filled", slot); return BLIM_ERR_STATE; }
+        if (const char* what = pc_diff(pc->snap[slot], now)) { blim_set_error("prefix cache: slot %d is stale: %s differs from its fill", slot, what); return BLIM_ERR_STATE; }
+    }
+    if (e->precise && !pc->comp) { blim_set_error("prefix cache: a compensated call needs a cache created with compensated = 1"); return BLIM_ERR_STATE; }
+    hipStream_t s = (hipStream_t)stream;
+    TRY(reserve_rows(e, n_rows));
+    const int H = e->c.hidden_size;
+    const int64_t W = H + e->aug, pf = e->precise ? 2 : 1;
+    {
+        PcLease lease{e};
+        e->pc_read = pc; e->pc_slot = pfx_slot;
+        TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream, W));   // (a cached row -- rows[r] < 0 -- leaves a poisoned row here ...)
+    }
+    // ... which the slot's stored hidden state replaces: hi, then lo (H values each; adapters apart: lm_head_input forms the u columns from them)
+    const uint16_t nan16 = e->c.compute_dtype == DT_F16 ? 0x7E00 : 0x7FC0;
+    TRY(launch_rows_by_index((uint16_t*)e->hsel.p, pf * W, (const uint16_t*)pc->hid, pc->hid_w, rows, n_rows, H, pc->n_slots, 1, nan16, s));
+    if (e->precise) TRY(launch_rows_by_index((uint16_t*)e->hsel.p + W, pf * W, (const uint16_t*)pc->hid + H, pc->hid_w, rows, n_rows, H, pc->n_slots, 1, 0, s));
     TRY(vtg_logprobs_impl(e, e->hsel.p, e->precise, labels, n_rows, (float*)e->logprob.p, stream, true));
     return blim_segment_mean(e, (const float*)e->logprob.p, row_start, n_pairs, 0, score, stream);
 }

@@ -45,6 +45,27 @@ struct AdapterW { float* A = nullptr; float* B = nullptr; uint16_t* A16 = nullpt
 struct LayerAd { AdapterW ad[4]; uint16_t* wqkv_aug = nullptr; uint16_t* wo_aug = nullptr;           // ad: q, k, v, o
                  uint8_t* wqkv_aug6 = nullptr; uint8_t* wo_aug6 = nullptr; };   // option "precise_lo6": e2m3 tile images of the augmented matrices
 
+// ---- gallery prefix cache (blim.h: blim_prefix_cache_*).  What a slot's values were computed under: the weights epoch and every option that changes a K/V or
+// hidden value, normalised (an option without effect in the recorded state is not recorded: e.g. the precise_* sub-options of a plain fill)
+struct PcSnap {
+    uint64_t epoch = 0;
+    int precise = 0, embeds = 0, mlp = 0, layers = 0, lo6 = 0, mqz = 0;
+    std::vector<uint8_t> bits;
+};
+struct blim_prefix_cache {
+    blim_engine* e = nullptr;
+    int n_slots = 0, max_len = 0;
+    bool comp = false;                 // the slots hold the lo parts of K / V and of the hidden row (compensated calls)
+    int kv_w = 0;                      // values per (layer, position): K heads | V heads (| K_lo | V_lo)
+    int hid_w = 0;                     // values per cached hidden row: hi (| lo), H each
+    int64_t slot_stride = 0;           // num_layers * max_len * kv_w
+    bf16_t* kv = nullptr;              // [n_slots][num_layers][max_len][kv_w]
+    bf16_t* hid = nullptr;             // [n_slots][hid_w]
+    DevBuf map;                        // fill: per-token destination rows, per-sequence last rows and slots (uploaded per call)
+    std::vector<int> len;              // filled length per slot (-1: never filled)
+    std::vector<PcSnap> snap;
+};
+
 struct blim_engine {
     blim_config c;
     int hd = 128;
@@ -118,6 +139,12 @@ struct blim_engine {
     int n_vocab = 0;
     // visual_head (a full fp32 tensor of the resume file, main.py:104-107) as [hi | lo | hi] rows of width 3 H for the three-term product in compensated calls
     DevBuf visual_head3, hs3;
+    // ---- gallery prefix cache: the weights epoch (bumped by every weight / adapter change and blim_train_merge) that a slot records at fill time, and the cache a
+    // call of blim_prefix_cache_fill (pc_fill: K / V captured after each QKV GEMM into rows pc_cap_row[t]) or blim_score_vtg_cached (pc_read: prefix tiles read from
+    // slots pc_slot[s]) has lent run_layers for its duration
+    uint64_t weights_epoch = 0;
+    blim_prefix_cache* pc_fill = nullptr; const int32_t* pc_cap_row = nullptr;
+    blim_prefix_cache* pc_read = nullptr; const int32_t* pc_slot = nullptr;
 };
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }

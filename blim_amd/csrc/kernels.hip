@@ -180,6 +180,60 @@ int launch_gather_rows(void* dst, const void* src, const int32_t* rows, int64_t 
     return BLIM_OK;
 }
 
+// ---------------------------------------------------------------------------- gallery prefix cache (engine.hip: blim_prefix_cache_*)
+__global__ void kv_capture_kernel(const uint4* qkv, int64_t ldq8, int64_t col8, int64_t src_lo8, int w8, const int32_t* dst_row, int64_t n_tokens, uint4* cache,
+                                  int64_t slot_stride8, int64_t ld8, int64_t dst_lo8, int max_len, int n_slots) {
+    const int parts = src_lo8 > 0 ? 2 : 1;
+    const int64_t per = (int64_t)w8 * parts;
+    const int64_t total = n_tokens * per;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int64_t t = i / per;
+        const int c = (int)(i - t * per);
+        const int d = dst_row[t];
+        if (d < 0 || (int64_t)d >= (int64_t)n_slots * max_len) continue;
+        const int part = c >= w8, cc = c - part * w8;
+        const int slot = d / max_len, pos = d - slot * max_len;
+        cache[slot * slot_stride8 + pos * ld8 + part * dst_lo8 + cc] = qkv[t * ldq8 + col8 + part * src_lo8 + cc];
+    }
+}
+int launch_kv_capture(const bf16_t* qkv, int64_t ldq, int64_t col, int64_t src_lo_off, int width, const int32_t* dst_row, int64_t n_tokens, bf16_t* cache,
+                      int64_t slot_stride, int64_t ld, int64_t dst_lo_off, int max_len, int n_slots, hipStream_t s) {
+    ARG_CHECK(qkv && dst_row && cache && n_tokens > 0 && width > 0 && max_len > 0 && n_slots > 0);
+    ARG_CHECK(ldq % 8 == 0 && col % 8 == 0 && src_lo_off % 8 == 0 && width % 8 == 0 && slot_stride % 8 == 0 && ld % 8 == 0 && dst_lo_off % 8 == 0 && src_lo_off >= 0);
+    const int64_t total = n_tokens * (width / 8) * (src_lo_off > 0 ? 2 : 1);
+    hipLaunchKernelGGL(kv_capture_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, (const uint4*)qkv, ldq / 8, col / 8, src_lo_off / 8, width / 8, dst_row, n_tokens,
+                       (uint4*)cache, slot_stride / 8, ld / 8, dst_lo_off / 8, max_len, n_slots);
+    LAUNCH_CHECK("kv_capture");
+    return BLIM_OK;
+}
+
+__global__ void rows_by_index_kernel(uint4* dst, int64_t ld_dst8, const uint4* src, int64_t ld_src8, const int32_t* idx, int64_t n_rows, int w8, int64_t n_bound,
+                                     int gather, uint32_t fill) {
+    const int64_t total = n_rows * w8;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int64_t r = i / w8;
+        const int c = (int)(i - r * w8);
+        const int64_t k = idx[r];
+        if (!gather) {
+            if (k >= 0 && k < n_bound) dst[k * ld_dst8 + c] = src[r * ld_src8 + c];
+        } else if (k < 0) {
+            const int64_t j = -(k + 1);
+            dst[r * ld_dst8 + c] = j < n_bound ? src[j * ld_src8 + c] : make_uint4(fill, fill, fill, fill);
+        }
+    }
+}
+int launch_rows_by_index(uint16_t* dst, int64_t ld_dst, const uint16_t* src, int64_t ld_src, const int32_t* idx, int64_t n_rows, int width, int64_t n_bound, int gather,
+                         uint16_t fill, hipStream_t s) {
+    ARG_CHECK(dst && src && idx && n_rows > 0 && width > 0 && width % 8 == 0 && ld_dst % 8 == 0 && ld_src % 8 == 0);
+    const int64_t total = n_rows * (width / 8);
+    hipLaunchKernelGGL(rows_by_index_kernel, dim3(grid_for(total, 256)), dim3(256), 0, s, (uint4*)dst, ld_dst / 8, (const uint4*)src, ld_src / 8, idx, n_rows, width / 8,
+                       n_bound, gather, (uint32_t)fill * 0x10001u);
+    LAUNCH_CHECK("rows_by_index");
+    return BLIM_OK;
+}
+
 // ---------------------------------------------------------------------------- RMSNorm (K3/K9)
 // One wave per row; the row (H f32) is read once in float4 pieces and kept in registers when H <= 64*4*16.
 template <int MAXV, int DT>

@@ -14,6 +14,15 @@ int launch_assemble(bf16_t* out, const int32_t* src_index, int64_t n_tokens, int
 // resid[t, :] = f32(embeds[t, :])   (16-bit input of the engine's compute dtype)
 int launch_h16_to_f32(float* out, const bf16_t* in, int64_t n, int dtype, hipStream_t s);
 int launch_gather_rows(void* dst, const void* src, const int32_t* rows, int64_t n_rows, int64_t row_bytes, int64_t n_src, uint32_t fill, hipStream_t s);   // dst[r] = src[rows[r]]
+// gallery prefix cache (engine.hip: blim_prefix_cache_*).  K/V capture after a layer's QKV GEMM: for every token t with dst_row[t] = slot * max_len + pos >= 0 (and
+// < n_slots * max_len), the `width` values at qkv[t, col ..] -- the K heads | V heads of the token -- go to cache[slot * slot_stride + pos * ld ..], and with
+// src_lo_off > 0 also the lo parts at qkv[t, col + src_lo_off ..] to dst_lo_off further.  16-byte chunks; width, col, ld, offsets multiples of 8 values.
+int launch_kv_capture(const bf16_t* qkv, int64_t ldq, int64_t col, int64_t src_lo_off, int width, const int32_t* dst_row, int64_t n_tokens, bf16_t* cache,
+                      int64_t slot_stride, int64_t ld, int64_t dst_lo_off, int max_len, int n_slots, hipStream_t s);
+// 16-bit row copies by index, `width` values per row (a multiple of 8).  gather = 0: dst[idx[r]] = src[r] for 0 <= idx[r] < n_bound (the cached hidden rows of a fill);
+// gather = 1: for idx[r] < 0, dst[r] = src[-(idx[r] + 1)] when that is < n_bound, else `fill` words (a poisoned score); rows with idx[r] >= 0 are left alone
+int launch_rows_by_index(uint16_t* dst, int64_t ld_dst, const uint16_t* src, int64_t ld_src, const int32_t* idx, int64_t n_rows, int width, int64_t n_bound, int gather,
+                         uint16_t fill, hipStream_t s);
 int launch_hilo_to_f32(float* out, const bf16_t* in, int64_t n_rows, int H, int dtype, hipStream_t s);   // [hi | lo] 16-bit rows of width 2H -> f32 [n_rows, H]
 int launch_f32_to_bf16(bf16_t* out, const float* in, int64_t n, hipStream_t s);
 int launch_zero_rows(bf16_t* x, int64_t ld, const uint8_t* keep, int64_t n_rows, int width, hipStream_t s);      // x[r, :width] = 0 where keep[r] == 0

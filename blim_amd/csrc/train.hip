@@ -233,6 +233,7 @@ extern "C" int blim_train_merge(blim_trainer* t, void* stream) {
         blim_set_error("blim_train_merge: the engine holds adapters apart (blim_load_adapter); merging into its base weights as well would apply the update twice -- blim_clear_adapters first");
         return BLIM_ERR_STATE;
     }
+    e->weights_epoch++;       // (from here on the base weights change: every prefix-cache slot filled before is stale)
     const blim_config& c = e->c;
     const int H = c.hidden_size, M = c.mm_hidden_size, dt = c.compute_dtype, r = t->r;
     const int64_t qn = (int64_t)c.num_heads * 128, kn = (int64_t)c.num_kv_heads * 128;

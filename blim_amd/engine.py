@@ -116,6 +116,12 @@ def load_library(path: str = LIB_PATH):
         "blim_debug_gemm_stamps": ([vp], C.c_int),
         "blim_hash_device": ([vp, i64, vp, vp], C.c_int),
         "blim_weights_fingerprint": ([vp, vp, vp], C.c_int),
+        "blim_prefix_cache_bytes": ([vp, i32, i32, i32], C.c_int64),
+        "blim_prefix_cache_create": ([vp, i32, i32, i32, C.POINTER(vp)], C.c_int),
+        "blim_prefix_cache_destroy": ([vp], None),
+        "blim_prefix_cache_fill": ([vp, vp, C.POINTER(Batch), vp, vp, vp], C.c_int),
+        "blim_prefix_cache_slot_len": ([vp, i32], C.c_int),
+        "blim_score_vtg_cached": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, vp, vp, i64, vp, i32, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -478,6 +484,13 @@ class Engine:
                                        _ptr(out), _stream()), "blim_score_vtg")
         return out
 
+    # ---- gallery prefix cache (blim.h: blim_prefix_cache_*; blim_amd/gallery.py)
+    def prefix_cache_bytes(self, n_slots: int, max_len: int, compensated: bool) -> int:
+        return int(self.lib.blim_prefix_cache_bytes(self.h, int(n_slots), int(max_len), int(bool(compensated))))
+
+    def prefix_cache(self, n_slots: int, max_len: int, compensated: bool) -> "PrefixCache":
+        return PrefixCache(self, n_slots, max_len, compensated)
+
     def score_tvg(self, batch: PackedBatch, embeds, rows, vocab_clip_major, labels):
         """vocab_clip_major None: the vocabulary registered with set_video_vocab()."""
         import torch
@@ -516,6 +529,50 @@ class Engine:
         ms = (C.c_double * n)(); calls = (C.c_int64 * n)(); fl = (C.c_double * n)()
         _check(self.lib.blim_timing_report(self.h, ms, calls, fl), "blim_timing_report")
         return {self.lib.blim_timing_class_name(i).decode(): {"ms": ms[i], "calls": int(calls[i]), "flops": fl[i]} for i in range(n)}
+
+
+class PrefixCache:
+    """Device-resident K / V + last-row hidden state of VTG prefixes (blim.h: blim_prefix_cache_*), one slot per prefix."""
+
+    def __init__(self, engine: Engine, n_slots: int, max_len: int, compensated: bool):
+        self.engine, self.lib = engine, engine.lib
+        self.n_slots, self.max_len, self.compensated = int(n_slots), int(max_len), bool(compensated)
+        self.bytes = engine.prefix_cache_bytes(n_slots, max_len, compensated)
+        h = C.c_void_p()
+        _check(self.lib.blim_prefix_cache_create(engine.h, self.n_slots, self.max_len, int(self.compensated), C.byref(h)), "blim_prefix_cache_create")
+        self.h = h
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.lib.blim_prefix_cache_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def fill(self, batch: PackedBatch, embeds, slot_of_seq):
+        """batch: prefix sequences only; slot_of_seq: host int [n_seqs]."""
+        sl = np.ascontiguousarray(slot_of_seq, dtype=np.int32)
+        assert len(sl) == batch.n_seqs
+        bs = batch.struct(self.engine.max_positions)
+        _check(self.lib.blim_prefix_cache_fill(self.engine.h, self.h, C.byref(bs), _ptr(embeds), sl.ctypes.data, _stream()), "blim_prefix_cache_fill")
+
+    def slot_len(self, slot: int) -> int:
+        return int(self.lib.blim_prefix_cache_slot_len(self.h, int(slot)))
+
+    def score_vtg(self, batch: PackedBatch, pfx_slot, slots_used, embeds, rows, labels, row_start):
+        """blim_score_vtg_cached: pfx_slot device int32 [n_seqs] (-1: in-batch prefix); slots_used host ints (every slot read); rows[r] < 0: slot -(rows[r] + 1)'s hidden row."""
+        import torch
+        n_pairs = row_start.shape[0] - 1
+        out = torch.empty(n_pairs, dtype=torch.float32, device=self.engine.device)
+        su = np.ascontiguousarray(slots_used, dtype=np.int32)
+        bs = batch.struct(self.engine.max_positions)
+        _check(self.lib.blim_score_vtg_cached(self.engine.h, self.h, C.byref(bs), _ptr(pfx_slot), su.ctypes.data if len(su) else None, len(su), _ptr(embeds), _ptr(rows),
+                                              _ptr(labels), rows.shape[0], _ptr(row_start), n_pairs, _ptr(out), _stream()), "blim_score_vtg_cached")
+        return out
 
 
 def ce_rows(logits, labels):

@@ -196,6 +196,39 @@ int blim_score_vtg(blim_engine* e, const blim_batch* b, const void* embeds, cons
 int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, const void* vocab_bf16,
                    int32_t n_vocab, const int32_t* labels, int32_t n_pairs, float* score, void* stream);
 
+/* ---- Gallery prefix cache (additive in ABI v9; blim_amd/gallery.py): the K / V of every layer and the last row's final-norm hidden state of VTG prefixes
+ * ([header][video][instruction] of one gallery video and prompt split), computed once and kept in device memory, so that a new text query is scored on its own
+ * response tokens alone.  Layout: slot-major K / V, [n_slots][num_layers][max_len][K heads | V heads (| K_lo | V_lo)] 16-bit values (the lo parts: caches created
+ * with compensated = 1, written for the layers whose QKV unit runs compensated), then one hidden row per slot [hi (| lo)], hidden_size values each.
+ * blim_prefix_cache_bytes: the device bytes of such a cache (-1 on bad arguments) = n_slots * (num_layers * max_len * 256 * num_kv_heads * (1 + compensated)
+ *   + hidden_size * (1 + compensated)) * 2.
+ * blim_prefix_cache_create: BLIM_ERR_STATE on an fp8 engine, BLIM_ERR_NOMEM when the device memory is not there.  A cache belongs to one engine.
+ * blim_prefix_cache_fill: `b` holds prefix sequences only -- no prefix of their own (pfx_len 0), own_start NULL, every key visible -- and slot_of_seq (HOST, [n_seqs])
+ *   names the slot of each (distinct, seq_len <= max_len).  Runs the decoder over the batch as blim_score_vtg would, copies each layer's K / V of the rows into the
+ *   slots after its QKV GEMM, and stores the last row's final-norm hidden state.  Each slot records the engine's weights epoch (bumped by blim_load_weight,
+ *   blim_init_synthetic_weights, blim_load_adapter, blim_clear_adapters, blim_train_merge) and every option that changes a K / V or hidden value (precise,
+ *   precise_embeds, precise_mlp, precise_layers and the layer bits, precise_lo6, masked_query_zero).  Synchronises `stream`.
+ * blim_prefix_cache_slot_len: filled length of a slot, -1 when empty (or after a failed fill).
+ * blim_score_vtg_cached: blim_score_vtg where sequence s with pfx_slot[s] >= 0 (DEVICE, [n_seqs]) reads its prefix from that slot instead of from packed rows
+ *   (b->pfx_len[s] must equal the slot's filled length; pfx_start[s] is then ignored) and -1 keeps the in-batch prefix: one call mixes cached and uncached candidates.
+ *   rows[r] < 0 names the cached last-row hidden state of slot -(rows[r] + 1).  slots_used (HOST, n_used entries) lists every slot the call reads through pfx_slot
+ *   or rows: a slot that is empty or whose record differs from the engine's present state is refused (BLIM_ERR_STATE, the message names what differs).  The
+ *   scores are bit for bit those of blim_score_vtg on the same pairs with the prefixes packed in the batch.  Option "attn_tr" must be 1.
+ *   What the library checks is slots_used (host): the device arrays pfx_slot, pfx_len and rows are not read back.  A caller that names a slot in pfx_slot or rows
+ *   without listing it in slots_used, or passes a pfx_len other than the slot's filled length, gets WRONG SCORES, not an error -- never a read outside the cache:
+ *   pfx_len is clamped to max_len (positions beyond the filled length hold whatever an earlier fill left, or uninitialised values), a pfx_slot >= n_slots reads
+ *   the in-batch prefix at pfx_start, a cached row of a slot >= n_slots is a NaN score.  blim_amd/gallery.py derives slots_used from the same plan as the
+ *   device arrays. */
+typedef struct blim_prefix_cache blim_prefix_cache;
+int64_t blim_prefix_cache_bytes(const blim_engine* e, int32_t n_slots, int32_t max_len, int32_t compensated);
+int blim_prefix_cache_create(blim_engine* e, int32_t n_slots, int32_t max_len, int32_t compensated, blim_prefix_cache** out);
+void blim_prefix_cache_destroy(blim_prefix_cache* c);
+int blim_prefix_cache_fill(blim_engine* e, blim_prefix_cache* c, const blim_batch* b, const void* embeds, const int32_t* slot_of_seq, void* stream);
+int blim_prefix_cache_slot_len(const blim_prefix_cache* c, int32_t slot);
+int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* c, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                          const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* row_start, int32_t n_pairs,
+                          float* score, void* stream);
+
 /* ---- Literal model.forward(inputs_embeds=[B,L,H] bf16, attention_mask=[B,L] u8) -> logits f32 [B,L,V] (may be NULL),
  * hidden f32 [B,L,H] (may be NULL).  Replaces VideoChatFlashQwenForCausalLM.forward, modeling_videochat_flash.py:601-629. */
 int blim_forward(blim_engine* e, const void* embeds, const uint8_t* mask, int32_t B, int32_t L, float* logits, float* hidden, void* stream);
