@@ -3,11 +3,15 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without a launcher: spawns the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
     python bench.py ... --dump-outputs DIR                        (also writes the last timed step's scores as DIR/scores.npy)
+    python bench.py ... --full                                    (also the measurements that take runs of their own, see below)
 
 One "step" = one engine pass over one device-resident super-batch of synthetic (query, candidate) pairs of
 BASELINE.json's headline shape: Qwen2-7B dims, 96 video tokens + 32 text tokens per pair, top-16 candidates per
 video query (v2t VTG pass).  The 96-token video prefix of a query is computed once and its K/V reused by the 16
 candidates (identical scores, fewer executed FLOPs); `roofline` is priced on the FLOPs actually executed.
+A plain run sets up, warms up, times the steps, dumps (--dump-outputs) and prints the headline line.  --full then
+adds, after and outside the timed steps: one more step under per-kernel HIP-event timing (`roofline`,
+`kernel_classes_ms`), the strong-scaling leg, the compensated-mode leg and, on one GPU, the CPU baseline.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -331,16 +335,19 @@ def main():
                          "job's own pairs inside the timed region, as main.py's default does (blim_amd/retrieval_utils.py: PairScorer.calibrate_tvg)")
     ap.add_argument("--second-pass", default=None, choices=["e2m3", "16bit"], help="second walk over K of the compensated calls (default: e2m3 on fp16 engines, 16bit on bf16 engines; "
                                                                                    "bf16 + e2m3 is the fast form of the bf16 engine's compensated mode)")
-    ap.add_argument("--no-compensated", action="store_true", help="skip the extra timing of the same step with fully compensated VTG calls (reported as `compensated_mode`)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-strong", action="store_true", help="skip the fixed-size N = 1000 evaluation (strong-scaling leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps, also run what takes runs of its own: one step under per-kernel timing (`roofline`, `kernel_classes_ms`), "
+                         "the strong-scaling leg, the compensated-mode leg and (one GPU) the CPU baseline.  Off: the run ends after the timed steps")
+    ap.add_argument("--no-compensated", action="store_true", help="with --full: skip the extra timing of the same step with fully compensated VTG calls (reported as `compensated_mode`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-strong", action="store_true", help="with --full: skip the fixed-size N = 1000 evaluation (strong-scaling leg)")
     ap.add_argument("--strong-only", action="store_true", help="only the strong-scaling leg (development aid; prints that object alone)")
     ap.add_argument("--strong-n", type=int, default=1000)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, rank 0 writes the scores the last timed step returned (all ranks' rows when N > 1) as DIR/scores.npy (float32); "
                          "the inputs are seeded, so two builds run with the same arguments can be compared entry by entry")
-    ap.add_argument("--leg-timeout", type=int, default=420, help="seconds after which the legs behind the timed steps (strong scaling, compensated mode, CPU baseline) are given up: "
-                                                                 "rank 0 prints the headline line with the timeout recorded in it (0 = no watchdog)")
+    ap.add_argument("--leg-timeout", type=int, default=420, help="with --full: seconds after which the legs behind the timed steps (strong scaling, compensated mode, CPU baseline) "
+                                                                 "are given up: rank 0 prints the headline line with the timeout recorded in it (0 = no watchdog)")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
@@ -420,16 +427,19 @@ def main():
         last = torch.stack([g[-1] for g in gathered]) if pg else mine[-1]
         dump_outputs(a.dump_outputs, {"scores": last.float().cpu().numpy()})
 
-    # ---- per-kernel timing (HIP events on the launch stream) of one more step, for the roofline object
-    model.engine.timing_enable(True)
-    step(0)
-    rep = model.engine.timing_report()
-    model.engine.timing_enable(False)
+    # ---- --full: per-kernel timing (HIP events on the launch stream) of one more step, for the roofline object
+    rep = None
+    if a.full:
+        model.engine.timing_enable(True)
+        step(0)
+        rep = model.engine.timing_report()
+        model.engine.timing_enable(False)
 
     vtg_headline = model.vtg_precise                            # (the compensated leg below switches the model's mode for its own timing)
 
     def emit(ss, comp, cpu=True):
-        """Rank 0's ONE JSON line (everything in it but `strong_scaling`, `compensated_mode` and `cpu_baseline` was measured above)."""
+        """Rank 0's ONE JSON line (everything in it but `strong_scaling`, `compensated_mode` and `cpu_baseline` was measured above; `roofline` and
+        `kernel_classes_ms` only with --full)."""
         if rank == 0:
             total_pairs = n_pairs * a.steps * world
             value = total_pairs / dt
@@ -438,9 +448,6 @@ def main():
             exec_flops_step = RU.executed_flops(dims, n_tok, n_rows, "vtg", vtg_headline, prune=model.engine.dtype != "f8")
             assert vtg_headline is not None or model.engine.dtype == "f8" or \
                 abs(exec_flops_step - (LAYERS * FLOP_TOKEN_LAYER * n_tok + FLOP_HEAD_ROW * n_rows - (FLOP_TOKEN_LAYER - 2 * H * (H + 2 * 512)) * (n_tok - n_rows))) < 1e6
-            dom = max((k for k in rep if rep[k]["flops"] > 0), key=lambda k: rep[k]["ms"])
-            d = rep[dom]
-            ach = d["flops"] / d["calls"] / (d["ms"] / d["calls"] * 1e-3) / 1e12
             peak = PEAK_FP8_TFLOPS if model.engine.dtype == "f8" else PEAK_BF16_TFLOPS
             # compensated mode on an fp16 engine (option "precise_lo6", default): the second walk over K runs on the e2m3 MFMA -- those flops are priced at the fp6
             # peak, the rest at the 16-bit one: peak_mixed = flops / (flops16 / P16 + flops6 / P6).  Plain mode (the headline): share 0, nothing changes.
@@ -448,14 +455,6 @@ def main():
             lo6_step = RU.lo6_pass_flops(dims, n_tok, n_rows, "vtg", vtg_headline, prune=True) if lo6 else 0.0
             mixed = lambda total, f6: total / ((total - f6) / PEAK_BF16_TFLOPS + f6 / PEAK_FP6_TFLOPS) if total > 0 else PEAK_BF16_TFLOPS
             peak_step = mixed(exec_flops_step, lo6_step) if model.engine.dtype != "f8" else peak
-            dom_lo6 = 0.5 if (lo6_step > 0 and rep[dom]["flops"] > 0 and dom != "attention") else 0.0       # fully compensated: half of every GEMM's flops are its second pass
-            if model.engine.dtype != "f8":
-                peak = mixed(1.0, dom_lo6)
-            tr = measured_traffic(dom, model.engine.dtype, compensated=vtg_headline == "full")
-            es = 1 if model.engine.dtype == "f8" else 2
-            alg_bytes = {"gemm_gateup_swiglu": n_tok * H * es + 2 * I * H * es + n_tok * I * 2, "gemm_down_resid": n_tok * I * es + H * I * es + 2 * n_tok * H * 4,
-                         "gemm_qkv_rope": n_tok * H * es + 4608 * H * es + n_tok * 4608 * 2, "gemm_o_resid": n_tok * H * es + H * H * es + 2 * n_tok * H * 4,
-                         "lm_head_lse": n_rows * H * es + V * H * es}.get(dom)
             out = {
                 "metric": "candidate-pairs/sec (7B, 96+32 tok)", "value": round(value, 2), "unit": "pairs/s", "n_gpus": world, "steps": a.steps,
                 "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -469,16 +468,28 @@ def main():
                 "executed_tflops_per_gpu": round(exec_flops_step * a.steps / dt / 1e12, 1),
                 "executed_gflop_per_pair_e2m3": round(lo6_step / n_pairs / 1e9, 1),
                 "frac_mfma_peak_whole_step": round(exec_flops_step * a.steps / dt / 1e12 / peak_step, 4),
-                "roofline": {"kernel": dom, "bound": "mfma", "achieved": round(ach, 1), "peak": round(peak, 1), "unit": "TFLOP/s",
-                             "peak_note": None if dom_lo6 == 0.0 else "half of this kernel's flops are the e2m3 second pass of the compensated mode: peak = 2 / (1 / 2500 + 1 / 10000)",
-                             "frac": round(ach / peak, 4), "traffic": tr[0] if tr else None,
-                             "traffic_source": (f"{tr[1]}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (2 x FETCH_SIZE + WRITE_SIZE, "
-                                                "fabric side of L2, Infinity-Cache hits included); looked up, not re-measured in this run") if tr else None,
-                             "algorithmic_bytes_per_launch": alg_bytes,
-                             "traffic_over_algorithmic": round(tr[0] / alg_bytes, 2) if (tr and alg_bytes) else None,
-                             "avg_launch_ms": round(d["ms"] / d["calls"], 4), "flop_per_launch": d["flops"] / d["calls"]},
-                "kernel_classes_ms": {k: round(v["ms"], 3) for k, v in rep.items() if v["calls"]},
             }
+            if rep is not None:
+                dom = max((k for k in rep if rep[k]["flops"] > 0), key=lambda k: rep[k]["ms"])
+                d = rep[dom]
+                ach = d["flops"] / d["calls"] / (d["ms"] / d["calls"] * 1e-3) / 1e12
+                dom_lo6 = 0.5 if (lo6_step > 0 and rep[dom]["flops"] > 0 and dom != "attention") else 0.0       # fully compensated: half of every GEMM's flops are its second pass
+                if model.engine.dtype != "f8":
+                    peak = mixed(1.0, dom_lo6)
+                tr = measured_traffic(dom, model.engine.dtype, compensated=vtg_headline == "full")
+                es = 1 if model.engine.dtype == "f8" else 2
+                alg_bytes = {"gemm_gateup_swiglu": n_tok * H * es + 2 * I * H * es + n_tok * I * 2, "gemm_down_resid": n_tok * I * es + H * I * es + 2 * n_tok * H * 4,
+                             "gemm_qkv_rope": n_tok * H * es + 4608 * H * es + n_tok * 4608 * 2, "gemm_o_resid": n_tok * H * es + H * H * es + 2 * n_tok * H * 4,
+                             "lm_head_lse": n_rows * H * es + V * H * es}.get(dom)
+                out["roofline"] = {"kernel": dom, "bound": "mfma", "achieved": round(ach, 1), "peak": round(peak, 1), "unit": "TFLOP/s",
+                                   "peak_note": None if dom_lo6 == 0.0 else "half of this kernel's flops are the e2m3 second pass of the compensated mode: peak = 2 / (1 / 2500 + 1 / 10000)",
+                                   "frac": round(ach / peak, 4), "traffic": tr[0] if tr else None,
+                                   "traffic_source": (f"{tr[1]}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (2 x FETCH_SIZE + WRITE_SIZE, "
+                                                      "fabric side of L2, Infinity-Cache hits included); looked up, not re-measured in this run") if tr else None,
+                                   "algorithmic_bytes_per_launch": alg_bytes,
+                                   "traffic_over_algorithmic": round(tr[0] / alg_bytes, 2) if (tr and alg_bytes) else None,
+                                   "avg_launch_ms": round(d["ms"] / d["calls"], 4), "flop_per_launch": d["flops"] / d["calls"]}
+                out["kernel_classes_ms"] = {k: round(v["ms"], 3) for k, v in rep.items() if v["calls"]}
             if comp is not None:
                 out["compensated_mode"] = comp
             if ss is not None:
@@ -486,6 +497,13 @@ def main():
             if cpu and world == 1 and not a.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline()
             print(json.dumps(out), flush=True)
+
+    if not a.full:                                                # a plain run: the headline line alone
+        emit(None, None, cpu=False)
+        if pg:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
 
     # ---- watchdog: the legs below run AFTER the headline was measured, and the strong-scaling leg is the only part of this file whose collectives have never met more than
     # one GPU (no multi-GPU box was available to the builder).  Should it hang, every rank leaves after --leg-timeout seconds and rank 0 still prints the headline line

@@ -145,8 +145,8 @@ def test_bench_gpus_4_on_one_gpu_keeps_the_json_contract(tmp_path):
     env = dict(os.environ, PYTHONPATH=root, BLIM_DIST_BACKEND="gloo", BLIM_FORCE_DEVICE="0", OMP_NUM_THREADS="1")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96"], cwd=root, env=env,
-                       capture_output=True, text=True, timeout=1200)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96", "--full"], cwd=root,
+                       env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -202,8 +202,8 @@ def test_rccl_runs_the_bench_collectives_at_world_size_one(tmp_path, capsys):
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96", "--no-cpu-baseline"], cwd=root,
-                       env=_rccl_env(root, 29563), capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96", "--full", "--no-cpu-baseline"],
+                       cwd=root, env=_rccl_env(root, 29563), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     m = re.search(r"(RCCL|NCCL) version[^\n]*", r.stdout + r.stderr)
     with capsys.disabled():
@@ -223,8 +223,8 @@ def test_bench_watchdog_keeps_the_headline_line_when_a_later_leg_does_not_finish
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "1000", "--leg-timeout", "1"], cwd=root,
-                       capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "1000", "--full", "--leg-timeout", "1"],
+                       cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, r.stdout[-1500:]
@@ -233,13 +233,42 @@ def test_bench_watchdog_keeps_the_headline_line_when_a_later_leg_does_not_finish
     assert "watchdog" in r.stderr
 
 
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_bench_plain_run_prints_the_headline_line_alone(tmp_path, gpus):
+    """`bench.py` without --full: exactly one JSON line with the headline keys, and nothing of what takes runs of its own (the per-kernel timing step behind
+    `roofline`, the strong-scaling, compensated-mode and CPU-baseline legs); --dump-outputs still writes the last timed step's scores.  With --gpus 2 the
+    parent spawns the two ranks (on one visible device both share cuda:0 over gloo, as in test_bench_gpus_n_launches_its_own_ranks)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    if gpus > 1 and torch.cuda.device_count() < gpus:
+        env.update(BLIM_DIST_BACKEND="gloo", BLIM_FORCE_DEVICE="0")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--queries", "8",
+                        "--dump-outputs", str(tmp_path / "dump")], cwd=root, env=env, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert k in d, k
+    for k in ("roofline", "kernel_classes_ms", "strong_scaling", "compensated_mode", "cpu_baseline"):
+        assert k not in d, k
+    assert d["metric"].startswith("candidate-pairs/sec") and d["unit"] == "pairs/s" and d["higher_is_better"] is True and d["dtype"] == "f16"
+    assert d["n_gpus"] == gpus and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    pairs = d["config"]["pairs_per_step_per_gpu"]
+    assert abs(d["value"] - gpus * pairs / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    scores = np.load(tmp_path / "dump" / "scores.npy")              # [pairs] on one GPU, every rank's rows [gpus, pairs] after the all-gather
+    assert scores.dtype == np.float32 and scores.shape == ((pairs,) if gpus == 1 else (gpus, pairs)) and np.isfinite(scores).all()
+
+
 def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
-    """bench.py's output contract: exactly one JSON line on stdout with the driver's keys, the roofline and (at N = 1) the CPU
+    """bench.py --full's output contract: exactly one JSON line on stdout with the driver's keys, the roofline and (at N = 1) the CPU
     baseline objects.  Small workload (8 queries) so that the test takes seconds; the numbers themselves are not checked."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96"], cwd=root,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96", "--full"], cwd=root,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -275,7 +304,7 @@ def test_bench_prints_one_json_line_with_the_contract_fields(tmp_path):
 
 
 def test_bench_gpus_n_launches_its_own_ranks(tmp_path):
-    """`python bench.py --gpus 2` exactly as the driver invokes it (no launcher around it): the parent spawns the two ranks, rank 0
+    """`python bench.py --gpus 2 --full` with no launcher around it (the way the driver starts bench.py): the parent spawns the two ranks, rank 0
     prints the single JSON line with n_gpus = 2 and the all-gather inside the timed region.  With one visible device both ranks share
     cuda:0 (gloo stands in for RCCL, which needs one device per rank); with >= 2 devices it is the real RCCL path."""
     import subprocess
@@ -284,7 +313,7 @@ def test_bench_gpus_n_launches_its_own_ranks(tmp_path):
     env = dict(os.environ)
     if torch.cuda.device_count() < 2:
         env.update(BLIM_DIST_BACKEND="gloo", BLIM_FORCE_DEVICE="0")
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--queries", "8", "--strong-n", "96", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
