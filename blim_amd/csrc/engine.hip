@@ -1400,10 +1400,8 @@ extern "C" int blim_prefix_cache_fill(blim_engine* e, blim_prefix_cache* pc, con
     for (int q = 0; q < n; ++q) { pc->len[slot_of_seq[q]] = h[n + q]; pc->snap[slot_of_seq[q]] = now; }
     return BLIM_OK;
 }
-extern "C" int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
-                                     const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* row_start, int32_t n_pairs,
-                                     float* score, void* stream) {
-    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && row_start && score && n_rows > 0 && n_pairs > 0);
+// What the two cached scoring entry points share: the checks of the slots a call reads, and the gather of the slots' stored last-row hidden states.
+static int pc_check_read(const blim_engine* e, const blim_prefix_cache* pc, const int32_t* slots_used, int32_t n_used) {
     if (!e->attn_tr) { blim_set_error("prefix cache: option 'attn_tr' must be 1"); return BLIM_ERR_STATE; }
     const PcSnap now = pc_snap(e);
     for (int k = 0; k < n_used; ++k) {
@@ -1413,21 +1411,50 @@ extern "C" int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* pc, cons
         if (const char* what = pc_diff(pc->snap[slot], now)) { blim_set_error("prefix cache: slot %d is stale: %s differs from its fill", slot, what); return BLIM_ERR_STATE; }
     }
     if (e->precise && !pc->comp) { blim_set_error("prefix cache: a compensated call needs a cache created with compensated = 1"); return BLIM_ERR_STATE; }
-    hipStream_t s = (hipStream_t)stream;
-    TRY(reserve_rows(e, n_rows));
+    return BLIM_OK;
+}
+// a cached row -- rows[r] < 0 -- left a poisoned row in hsel (rows of pf halves of width W): the slot's stored hidden state replaces it, hi, then lo (H values each)
+static int pc_gather_rows(blim_engine* e, const blim_prefix_cache* pc, const int32_t* rows, int64_t n_rows, int64_t W, hipStream_t s) {
     const int H = e->c.hidden_size;
-    const int64_t W = H + e->aug, pf = e->precise ? 2 : 1;
-    {
-        PcLease lease{e};
-        e->pc_read = pc; e->pc_slot = pfx_slot;
-        TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream, W));   // (a cached row -- rows[r] < 0 -- leaves a poisoned row here ...)
-    }
-    // ... which the slot's stored hidden state replaces: hi, then lo (H values each; adapters apart: lm_head_input forms the u columns from them)
+    const int64_t pf = e->precise ? 2 : 1;
     const uint16_t nan16 = e->c.compute_dtype == DT_F16 ? 0x7E00 : 0x7FC0;
     TRY(launch_rows_by_index((uint16_t*)e->hsel.p, pf * W, (const uint16_t*)pc->hid, pc->hid_w, rows, n_rows, H, pc->n_slots, 1, nan16, s));
     if (e->precise) TRY(launch_rows_by_index((uint16_t*)e->hsel.p + W, pf * W, (const uint16_t*)pc->hid + H, pc->hid_w, rows, n_rows, H, pc->n_slots, 1, 0, s));
+    return BLIM_OK;
+}
+extern "C" int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                                     const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* row_start, int32_t n_pairs,
+                                     float* score, void* stream) {
+    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && row_start && score && n_rows > 0 && n_pairs > 0);
+    TRY(pc_check_read(e, pc, slots_used, n_used));
+    TRY(reserve_rows(e, n_rows));
+    const int64_t W = e->c.hidden_size + e->aug;
+    {
+        PcLease lease{e};
+        e->pc_read = pc; e->pc_slot = pfx_slot;
+        TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream, W));   // rows laid out for the adapted lm_head: lm_head_input forms the u columns
+    }
+    TRY(pc_gather_rows(e, pc, rows, n_rows, W, (hipStream_t)stream));
     TRY(vtg_logprobs_impl(e, e->hsel.p, e->precise, labels, n_rows, (float*)e->logprob.p, stream, true));
     return blim_segment_mean(e, (const float*)e->logprob.p, row_start, n_pairs, 0, score, stream);
+}
+// blim_score_tvg over cached caption prompts: a pair's first row (it predicts clip 0) is the prompt's last row -- of the batch, or of a slot
+extern "C" int blim_score_tvg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                                     const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab, const int32_t* labels, int32_t n_pairs,
+                                     float* score, void* stream) {
+    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && score && n_pairs > 0);
+    TRY(pc_check_read(e, pc, slots_used, n_used));
+    const int64_t n_rows = (int64_t)n_pairs * e->c.num_clips;
+    TRY(reserve_rows(e, n_rows));
+    TRY(ensure(e->vh, (size_t)round_up(n_rows, 256) * e->c.mm_hidden_size * 2 * (e->precise ? 2 : 1)));
+    {
+        PcLease lease{e};
+        e->pc_read = pc; e->pc_slot = pfx_slot;
+        TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream));
+    }
+    TRY(pc_gather_rows(e, pc, rows, n_rows, e->c.hidden_size, (hipStream_t)stream));
+    TRY(visual_head_impl(e, e->hsel.p, e->precise, n_rows, e->vh.p, stream));
+    return tvg_scores_impl(e, e->vh.p, e->precise, vocab_bf16, n_vocab, labels, n_pairs, score, stream);
 }
 
 extern "C" int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, const void* vocab_bf16,

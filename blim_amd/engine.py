@@ -122,6 +122,7 @@ def load_library(path: str = LIB_PATH):
         "blim_prefix_cache_fill": ([vp, vp, C.POINTER(Batch), vp, vp, vp], C.c_int),
         "blim_prefix_cache_slot_len": ([vp, i32], C.c_int),
         "blim_score_vtg_cached": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, vp, vp, i64, vp, i32, vp, vp], C.c_int),
+        "blim_score_tvg_cached": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -532,7 +533,7 @@ class Engine:
 
 
 class PrefixCache:
-    """Device-resident K / V + last-row hidden state of VTG prefixes (blim.h: blim_prefix_cache_*), one slot per prefix."""
+    """Device-resident K / V + last-row hidden state of prefixes (blim.h: blim_prefix_cache_*), one slot per prefix: VTG video prefixes or TVG caption prompts."""
 
     def __init__(self, engine: Engine, n_slots: int, max_len: int, compensated: bool):
         self.engine, self.lib = engine, engine.lib
@@ -572,6 +573,18 @@ class PrefixCache:
         bs = batch.struct(self.engine.max_positions)
         _check(self.lib.blim_score_vtg_cached(self.engine.h, self.h, C.byref(bs), _ptr(pfx_slot), su.ctypes.data if len(su) else None, len(su), _ptr(embeds), _ptr(rows),
                                               _ptr(labels), rows.shape[0], _ptr(row_start), n_pairs, _ptr(out), _stream()), "blim_score_vtg_cached")
+        return out
+
+    def score_tvg(self, batch: PackedBatch, pfx_slot, slots_used, embeds, rows, vocab_clip_major, labels):
+        """blim_score_tvg_cached: Engine.score_tvg with the slot conventions of score_vtg above (a slot holds a caption prompt; its hidden row predicts clip 0)."""
+        import torch
+        n_pairs = labels.shape[0]
+        out = torch.empty(n_pairs, dtype=torch.float32, device=self.engine.device)
+        su = np.ascontiguousarray(slots_used, dtype=np.int32)
+        bs = batch.struct(self.engine.max_positions)
+        n_vocab = self.engine.n_vocab if vocab_clip_major is None else vocab_clip_major.shape[1]
+        _check(self.lib.blim_score_tvg_cached(self.engine.h, self.h, C.byref(bs), _ptr(pfx_slot), su.ctypes.data if len(su) else None, len(su), _ptr(embeds), _ptr(rows),
+                                              _ptr(vocab_clip_major), n_vocab, _ptr(labels), n_pairs, _ptr(out), _stream()), "blim_score_tvg_cached")
         return out
 
 

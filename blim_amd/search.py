@@ -5,6 +5,10 @@ are test captions (`--query_ids`) and / or free text (`--query TEXT`, tokenised 
 takes each dataset query's top-k of the first-stage t2v row, `--candidates all` scores the whole gallery.  One JSON line per query: the ranked video ids and their
 blended t2v scores (training_utils.combine_and_rank's t2v half: `--cpn --alpha --c`; zero-shot runs blend the query likelihood with the first stage only).
 `--synthetic N [--synthetic_7b]`: a dry run on synth.make_problem, as main.py's.
+
+`--direction v2t` is the other half: the gallery is the dataset's test captions and the queries are test videos (`--video_ids`).  The candidate likelihood (VTG) is
+served from the same video cache; a fine-tuned checkpoint's query likelihood (TVG) reads the captions' prompts from a second cache (TextGalleryIndex,
+`--text_gallery_gb`), and the CPN prior is kept per text.  One JSON line per query video: the ranked text indices and their blended v2t scores.
 """
 from __future__ import annotations
 
@@ -27,15 +31,19 @@ def get_args_parser():
     p.add_argument("--calibration_store", default=None, type=str, metavar="DIR", help="refused: the index's mode resolution does not use the store")
     p.add_argument("--cpn", action="store_true")
     p.add_argument("--alpha", default=[0.0, 0.0], type=float, nargs="+")
-    p.add_argument("--c", default=[1.0, 0.0, 1.0, 0.0], type=float, nargs="+",
-                   help="ensemble weights as main.py's; only c0 (query vs candidate likelihood) and c2 (likelihood vs first stage) act on t2v.  Default: the query likelihood alone")
+    p.add_argument("--c", default=None, type=float, nargs="+",
+                   help="ensemble weights as main.py's; only c0 (query vs candidate likelihood) and c2 (likelihood vs first stage) act on t2v, only c1 and c3 (likewise) "
+                        "on v2t.  Default: t2v 1 0 1 0 (the query likelihood alone), v2t 1 0 1 1 (c1 = 0, c3 = 1: the VTG likelihood alone)")
     p.add_argument("--topk", default=10, type=int)
     p.add_argument("--lora_r", default=8, type=int)
     p.add_argument("--lora_alpha", default=32, type=int)
     p.add_argument("--query_ids", default=[], type=int, nargs="*", help="test captions (indices) used as queries")
     p.add_argument("--query", default=[], type=str, action="append", help="a free-text query (repeatable)")
+    p.add_argument("--direction", default="t2v", choices=["t2v", "v2t"], help="t2v: text queries over the videos; v2t: video queries (--video_ids) over the captions")
+    p.add_argument("--video_ids", default=[], type=int, nargs="*", help="test videos (indices) used as queries (--direction v2t)")
     p.add_argument("--candidates", default="iv2", choices=["iv2", "all"])
     p.add_argument("--gallery_gb", default=None, type=float, help="device memory for the prefix cache (default: every video)")
+    p.add_argument("--text_gallery_gb", default=None, type=float, help="v2t: device memory for the caption-prompt cache (default: every distinct prompt)")
     p.add_argument("--max_tokens", default=24576, type=int)
     p.add_argument("--shard", default=None, type=int, nargs=2, metavar=("W", "RANK"))
     p.add_argument("--synthetic", default=0, type=int)
@@ -52,15 +60,28 @@ def check_args(args, world: int = 1) -> None:
         raise SystemExit("search: --shard is not supported (a gallery is not sharded over ranks)")
     if world > 1:
         raise SystemExit(f"search: world size {world} > 1 is not supported (run one process)")
-    if not args.query_ids and not args.query:
-        raise SystemExit("search: give --query_ids and / or --query")
+    v2t = getattr(args, "direction", "t2v") == "v2t"
+    if args.c is None:                        # the likelihood of the direction alone: t2v c0 = c2 = 1; v2t c1 = 0, c3 = 1
+        args.c = [1.0, 0.0, 1.0, 1.0] if v2t else [1.0, 0.0, 1.0, 0.0]
+    if v2t:
+        if args.query or args.query_ids:
+            raise SystemExit("search: --direction v2t takes video queries (--video_ids), not --query / --query_ids")
+        if not args.video_ids:
+            raise SystemExit("search: --direction v2t needs --video_ids")
+    else:
+        if getattr(args, "video_ids", None):
+            raise SystemExit("search: --video_ids are the queries of --direction v2t (t2v takes --query_ids and / or --query)")
+        if not args.query_ids and not args.query:
+            raise SystemExit("search: give --query_ids and / or --query")
     if args.query and args.candidates == "iv2":
         raise SystemExit("search: free-text queries have no first-stage row: use --candidates all")
     if args.query and args.synthetic:
         raise SystemExit("search: free-text queries need the dataset's tokenizer (not --synthetic)")
     if len(args.c) != 4 or len(args.alpha) != 2:
         raise SystemExit("search: --c takes 4 values, --alpha 2")
-    if args.c[2] == 0:
+    if v2t and args.c[3] == 0:
+        raise SystemExit("search: --c with c3 = 0 ranks by the first-stage scores alone (the likelihood would have no effect): give c3 > 0, e.g. the v2t default 1 0 1 1")
+    if not v2t and args.c[2] == 0:
         raise SystemExit("search: --c with c2 = 0 ranks by the first-stage scores alone (the likelihood would have no effect): give c2 > 0, e.g. the default 1 0 1 0")
     if args.calibration_store:
         raise SystemExit("search: --calibration_store is not supported: the gallery resolves --vtg_precise auto | select on its own sample without the store; "
@@ -96,7 +117,7 @@ def main(args):
         vtg_ids, vtg_lab, vtg_msk = prob.vtg_ids, prob.vtg_labels, prob.vtg_masks
         tvg_ids, tvg_lab, tvg_msk = prob.tvg_ids, prob.tvg_labels, prob.tvg_masks
         video, vocab, vlab = [T(v) for v in prob.video], T(prob.video_vocab), T(prob.tvg_video_labels)
-        t2v_iv2 = prob.t2v_sims
+        t2v_iv2, v2t_iv2 = prob.t2v_sims, prob.v2t_sims
         vids = [str(j) for j in range(len(video))]
         model.set_tvg_prefix_length(prob.tvg_prefix_length)
         vtg_ids, vtg_lab, vtg_msk, tvg_ids, tvg_lab, tvg_msk = (rows(x) for x in (vtg_ids, vtg_lab, vtg_msk, tvg_ids, tvg_lab, tvg_msk))
@@ -124,8 +145,9 @@ def main(args):
         vocab, vlab = ds.video_vocab, torch.tensor([it["tvg_video_labels"] for it in items])
         model.set_tvg_prefix_length(ds.tvg_prefix_length)
         finetuned_ = bool(args.resume)
-        t2v_iv2 = torch.load(f"./scores/{args.dataset.lower()}{'' if finetuned_ else '_zeroshot'}.pth", weights_only=True)["t2v"].numpy() \
-            if args.candidates == "iv2" else None
+        first = torch.load(f"./scores/{args.dataset.lower()}{'' if finetuned_ else '_zeroshot'}.pth", weights_only=True) if args.candidates == "iv2" else None
+        t2v_iv2 = None if first is None else first["t2v"].numpy()
+        v2t_iv2 = None if first is None else first["v2t"].numpy()
     if model.engine.can_precise:
         model.tvg_precise = args.tvg_precise
         model.vtg_precise = None if args.vtg_precise == "none" else args.vtg_precise
@@ -136,6 +158,8 @@ def main(args):
     scorer = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, vocab, vlab, args.num_clips, max_tokens=args.max_tokens)
     budget = None if args.gallery_gb is None else int(args.gallery_gb * 2**30)
     gal = GalleryIndex(scorer, budget_bytes=budget)
+    if args.direction == "v2t":
+        return _main_v2t(args, model, scorer, gal, v2t_iv2, vids, len(tvg_ids), t0)
     gal.build(first_stage=None if t2v_iv2 is None else np.ascontiguousarray(np.asarray(t2v_iv2, dtype=np.float32).T))     # v2t first stage: calibration sample
     print(f"gallery: {len(video)} videos, {len(gal.slot_of)} cached slots of {gal.cache.bytes // max(len(gal.slot_of), 1) if gal.cache else 0} bytes, "
           f"mode {scorer.vtg_mode or 'none'}, built in {gal.build_seconds:.2f}s (ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
@@ -161,6 +185,48 @@ def main(args):
             out.write(line + "\n")
     if out:
         out.close()
+    gal.close()
+    model.engine.close()
+    return 0
+
+
+def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) -> int:
+    """Video queries over the captions: the VTG leg from the video cache, the fine-tuned TVG leg from the caption-prompt cache."""
+    import numpy as np
+
+    from .gallery import TextGalleryIndex
+    n_videos = len(vids)
+    first = None if v2t_iv2 is None else np.ascontiguousarray(np.asarray(v2t_iv2, dtype=np.float32))
+    gal.build(first_stage=first)
+    finetuned = bool(args.resume)
+    tbudget = None if args.text_gallery_gb is None else int(args.text_gallery_gb * 2**30)
+    tg = TextGalleryIndex(scorer, budget_bytes=tbudget, video_index=gal)
+    if finetuned:                                     # a zero-shot blend has no TVG term: no caption cache
+        tg.build(first_stage=first)
+    print(f"gallery: {n_videos} videos, {len(gal.slot_of)} cached slots, mode {scorer.vtg_mode or 'none'}, built in {gal.build_seconds:.2f}s; "
+          f"{n_texts} texts, {len(tg.slot_of)} caption slots of {tg.per_slot_bytes()} bytes, tvg mode {scorer.tvg_mode}, built in {tg.build_seconds:.2f}s "
+          f"(ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
+    bad = [v for v in args.video_ids if not 0 <= v < n_videos]
+    if bad:
+        raise SystemExit(f"search: --video_ids {bad} outside 0 .. {n_videos - 1}")
+    k = min(args.topk, n_texts)
+    out = open(args.output, "w") if args.output else None
+    for v in args.video_ids:
+        if args.candidates == "iv2":
+            row = np.asarray(v2t_iv2[v], dtype=np.float32)
+            cand = np.argsort(-row, kind="stable")[:k][None]
+            fs = row[cand]
+        else:
+            cand = np.arange(n_texts)[None]
+            fs = None if v2t_iv2 is None else np.asarray(v2t_iv2[v], dtype=np.float32)[cand]
+        order, blended = tg.rerank([v], cand, first_stage=fs, cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
+        line = json.dumps({"query": f"video:{vids[v]}", "texts": [int(i) for i in order[0]], "scores": [float(x) for x in blended[0]]})
+        print(line, flush=True)
+        if out:
+            out.write(line + "\n")
+    if out:
+        out.close()
+    tg.close()
     gal.close()
     model.engine.close()
     return 0

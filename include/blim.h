@@ -196,9 +196,11 @@ int blim_score_vtg(blim_engine* e, const blim_batch* b, const void* embeds, cons
 int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, const void* vocab_bf16,
                    int32_t n_vocab, const int32_t* labels, int32_t n_pairs, float* score, void* stream);
 
-/* ---- Gallery prefix cache (additive in ABI v9; blim_amd/gallery.py): the K / V of every layer and the last row's final-norm hidden state of VTG prefixes
- * ([header][video][instruction] of one gallery video and prompt split), computed once and kept in device memory, so that a new text query is scored on its own
- * response tokens alone.  Layout: slot-major K / V, [n_slots][num_layers][max_len][K heads | V heads (| K_lo | V_lo)] 16-bit values (the lo parts: caches created
+/* ---- Gallery prefix cache (additive in ABI v9; blim_amd/gallery.py): the K / V of every layer and the last row's final-norm hidden state of prefixes,
+ * computed once and kept in device memory, so that a new query is scored on its own continuation tokens alone.  A cache holds prefixes of either kind: a VTG slot
+ * is [header][video][instruction] of one gallery video and prompt split (a new text query then packs its response tokens only), a TVG slot is the caption prompt
+ * of one gallery text (a new video query then packs its num_clips - 1 clip tokens only).  The fill is kind-neutral: it runs under the options of the calls that
+ * will read the slot, and records them.  Layout: slot-major K / V, [n_slots][num_layers][max_len][K heads | V heads (| K_lo | V_lo)] 16-bit values (the lo parts: caches created
  * with compensated = 1, written for the layers whose QKV unit runs compensated), then one hidden row per slot [hi (| lo)], hidden_size values each.
  * blim_prefix_cache_bytes: the device bytes of such a cache (-1 on bad arguments) = n_slots * (num_layers * max_len * 256 * num_kv_heads * (1 + compensated)
  *   + hidden_size * (1 + compensated)) * 2.
@@ -218,7 +220,10 @@ int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* embeds, cons
  *   without listing it in slots_used, or passes a pfx_len other than the slot's filled length, gets WRONG SCORES, not an error -- never a read outside the cache:
  *   pfx_len is clamped to max_len (positions beyond the filled length hold whatever an earlier fill left, or uninitialised values), a pfx_slot >= n_slots reads
  *   the in-batch prefix at pfx_start, a cached row of a slot >= n_slots is a NaN score.  blim_amd/gallery.py derives slots_used from the same plan as the
- *   device arrays. */
+ *   device arrays.
+ * blim_score_tvg_cached: blim_score_tvg with the same conventions (pfx_slot, slots_used, the checks and their messages).  rows[p * num_clips + c] < 0 names the
+ *   cached last-row hidden state of slot -(rows + 1): the prompt's last row, which predicts clip 0; it is gathered into the visual head's input after the decode.
+ *   Sequences may be segmented (own_start) over a cached prompt: several videos' clip tokens for one text, all naming the text's slot. */
 typedef struct blim_prefix_cache blim_prefix_cache;
 int64_t blim_prefix_cache_bytes(const blim_engine* e, int32_t n_slots, int32_t max_len, int32_t compensated);
 int blim_prefix_cache_create(blim_engine* e, int32_t n_slots, int32_t max_len, int32_t compensated, blim_prefix_cache** out);
@@ -227,6 +232,9 @@ int blim_prefix_cache_fill(blim_engine* e, blim_prefix_cache* c, const blim_batc
 int blim_prefix_cache_slot_len(const blim_prefix_cache* c, int32_t slot);
 int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* c, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
                           const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* row_start, int32_t n_pairs,
+                          float* score, void* stream);
+int blim_score_tvg_cached(blim_engine* e, blim_prefix_cache* c, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                          const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab, const int32_t* labels, int32_t n_pairs,
                           float* score, void* stream);
 
 /* ---- Literal model.forward(inputs_embeds=[B,L,H] bf16, attention_mask=[B,L] u8) -> logits f32 [B,L,V] (may be NULL),

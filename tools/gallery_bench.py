@@ -2,7 +2,15 @@
 against the uncached PairScorer.vtg on the SAME pairs, alternated `--reps` times each in one process; the build time and bytes per slot; single-query latency
 for k = 16 and k = N; in the plain and the fully compensated VTG mode.  Scores of the two paths are checked bit-equal on every repetition.
 
-    python tools/gallery_bench.py --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r09_gallery.json"""
+    python tools/gallery_bench.py --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r09_gallery.json
+
+`--direction v2t`: the text gallery (TextGalleryIndex).  Per TVG mode (`--tvg_modes`): the TVG leg alone -- TextGalleryIndex.tvg_pairs against PairScorer.tvg on the
+same Q x top-k (video, text) pairs, alternated -- with packed tokens, build time and bytes per slot; the whole fine-tuned v2t blend (VTG from cached video slots +
+cached TVG + memoised prior against PairScorer.vtg + .tvg + .vtg(cpn=True)); single-query latency for k = 16 and k = N; the engine's timing classes of one cached
+and one uncached TVG pass.  Several videos share a text in the Q x top-k set, so its scores are checked within 1e-5 x max(1, |score|) on every repetition; the
+single-query sets (one video per text) are checked bit-equal.
+
+    python tools/gallery_bench.py --direction v2t --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r10_text_gallery.json"""
 import argparse
 import json
 import os
@@ -15,7 +23,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from blim_amd import retrieval_utils as RU  # noqa: E402
 from blim_amd import synth  # noqa: E402
-from blim_amd.gallery import GalleryIndex  # noqa: E402
+from blim_amd.gallery import GalleryIndex, TextGalleryIndex  # noqa: E402
 from blim_amd.modeling import BlimModel, DDPLike  # noqa: E402
 
 
@@ -38,6 +46,8 @@ def main():
     ap.add_argument("--modes", default="none,full")
     ap.add_argument("--dtype", default="f16")
     ap.add_argument("--max_tokens", type=int, default=24576)
+    ap.add_argument("--direction", default="t2v", choices=["t2v", "v2t"])
+    ap.add_argument("--tvg_modes", default="attn,full", help="v2t: the TVG calls' modes to measure")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -53,6 +63,8 @@ def main():
     tvg = RU.padding_ids(Tt(prob.tvg_ids), Tt(prob.tvg_labels), Tt(prob.tvg_masks), tok)
     video = [torch.from_numpy(v) for v in prob.video]
     q = np.linspace(0, a.n - 1, a.queries).round().astype(np.int64)
+    if a.direction == "v2t":
+        return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
     cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
     pairs = np.stack([cand.reshape(-1), np.repeat(q, a.k)], axis=1)
     res = {"n": a.n, "queries": a.queries, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc, "modes": {}}
@@ -88,6 +100,89 @@ def main():
         res["modes"][mode] = r
         print(json.dumps({mode: r}), flush=True)
         gal.close()
+        del sc
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    cand = np.argsort(-prob.v2t_sims[q], axis=1, kind="stable")[:, :a.k]
+    fs = np.take_along_axis(prob.v2t_sims[q].astype(np.float32), cand, 1)
+    pairs = np.stack([np.repeat(q, a.k), cand.reshape(-1)], axis=1)
+    P = len(pairs)
+    close = lambda got, want: bool(np.all(np.abs(got - want) <= 1e-5 * np.maximum(1.0, np.abs(want))))
+    alpha, c = (0.8, 0.3), (0.5, 0.5, 0.5, 0.5)
+    res = {"direction": "v2t", "n": a.n, "queries": a.queries, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc,
+           "pairs": P, "distinct_texts": int(len(np.unique(pairs[:, 1]))), "vtg_mode": "none", "tvg_modes": {}}
+    model.vtg_precise = None
+    for mode in a.tvg_modes.split(","):
+        model.tvg_precise = mode
+        model.clear_cache()
+        sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, torch.from_numpy(prob.video_vocab),
+                           torch.from_numpy(prob.tvg_video_labels), dims.num_clips, max_tokens=a.max_tokens)
+        sc.set_vtg_mode(model.vtg_mode()); sc.set_tvg_mode(model.tvg_mode())
+        sc.tvg(pairs[:8]); sc.vtg(pairs[:8])                              # warm-up: features projected, workspaces sized
+        gal = GalleryIndex(sc)
+        t_vbuild, _ = timed(gal.build)
+        tg = TextGalleryIndex(sc, video_index=gal)
+        t_build, _ = timed(tg.build)
+        tg.tvg_pairs(pairs[:8])
+        tok_unc = sum(p.n_tokens for p in sc.iter_tvg(pairs))
+        tok_cac = sum(p.n_tokens for p in tg.iter_plans(pairs))
+        # 1. the TVG leg alone
+        t_unc, t_cac, dmax, biteq = [], [], 0.0, True
+        for _ in range(a.reps):
+            dt, ref = timed(lambda: sc.tvg(pairs)); t_unc.append(dt)
+            dt, got = timed(lambda: tg.tvg_pairs(pairs)); t_cac.append(dt)
+            assert close(got, ref), "cached TVG scores differ from PairScorer.tvg by more than 1e-5"
+            dmax = max(dmax, float(np.max(np.abs(got - ref)))); biteq = biteq and bool(np.array_equal(got, ref))
+        # 2. the whole fine-tuned blend
+        def uncached_blend():
+            cl, ql, pr = sc.vtg(pairs), sc.tvg(pairs), sc.vtg(pairs, cpn=True)
+            return 0.5 * (0.5 * ql + 0.5 * (cl - alpha[1] * pr)).reshape(cand.shape) + 0.5 * fs
+        rr = lambda: tg.rerank(q, cand, first_stage=fs, cpn=True, alpha=alpha, c=c, finetuned=True)
+        t_cold, _ = timed(rr)                                             # the prior memo is empty on this call
+        b_unc, b_cac = [], []
+        for _ in range(a.reps):
+            dt, want = timed(uncached_blend); b_unc.append(dt)
+            dt, (order, blended) = timed(rr); b_cac.append(dt)
+            assert close(blended, -np.sort(-want, axis=1)), "cached blend differs from the uncached one by more than 1e-5"
+        # 3. single-query latency: one video per text, bit-equal
+        lat = {}
+        for kk in (16, a.n):
+            c1 = np.argsort(-prob.v2t_sims[q[0]], kind="stable")[:kk]
+            p1 = np.stack([np.full(kk, q[0]), c1], axis=1)
+            f1 = prob.v2t_sims[q[0]].astype(np.float32)[c1][None]
+            assert np.array_equal(tg.tvg_pairs(p1), sc.tvg(p1)), "single-query cached TVG scores are not bit-equal"
+            r1 = lambda: tg.rerank([q[0]], c1[None], first_stage=f1, cpn=True, alpha=alpha, c=c, finetuned=True)
+            r1()
+            med = lambda fn: 1e3 * float(np.median([timed(fn)[0] for _ in range(3)]))
+            lat[f"k{kk}"] = {"tvg_cached_ms": med(lambda: tg.tvg_pairs(p1)), "tvg_uncached_ms": med(lambda: sc.tvg(p1)), "blend_cached_ms": med(r1),
+                             "blend_uncached_ms": med(lambda: (sc.vtg(p1), sc.tvg(p1), sc.vtg(p1, cpn=True))),
+                             "tokens_cached": sum(p.n_tokens for p in tg.iter_plans(p1)), "tokens_uncached": sum(p.n_tokens for p in sc.iter_tvg(p1))}
+        # where the time goes: the engine's timing classes of one pass each
+        cls = {}
+        for name, fn in (("cached", lambda: tg.tvg_pairs(pairs)), ("uncached", lambda: sc.tvg(pairs))):
+            model.engine.timing_enable(True)
+            model.engine.timing_report()
+            wall, _ = timed(fn)
+            rep = model.engine.timing_report()
+            model.engine.timing_enable(False)
+            cls[name] = {"wall_ms": 1e3 * wall, "classes_ms": {k: round(v["ms"], 3) for k, v in rep.items() if v["calls"]}, "launches": int(sum(v["calls"] for v in rep.values()))}
+        spread = lambda t: float((max(t) - min(t)) / np.median(t))
+        r = {"build_s": t_build, "video_build_s": t_vbuild, "slots": len(tg.slot_of), "slot_positions": tg.slot_positions(), "bytes_per_slot": tg.cache.bytes // len(tg.slot_of),
+             "tokens_uncached": tok_unc, "tokens_cached": tok_cac, "uncached_s": t_unc, "cached_s": t_cac, "uncached_pairs_per_s": P / float(np.median(t_unc)),
+             "cached_pairs_per_s": P / float(np.median(t_cac)), "speedup": float(np.median(t_unc) / np.median(t_cac)), "spread_uncached": spread(t_unc),
+             "spread_cached": spread(t_cac), "max_abs_diff": dmax, "bit_equal_every_rep": biteq, "within_1e-5_every_rep": True,
+             "blend": {"uncached_s": b_unc, "cached_s": b_cac, "cached_cold_prior_s": t_cold, "speedup": float(np.median(b_unc) / np.median(b_cac)),
+                       "uncached_pairs_per_s": P / float(np.median(b_unc)), "cached_pairs_per_s": P / float(np.median(b_cac))},
+             "latency": lat, "timing": cls}
+        res["tvg_modes"][mode] = r
+        print(json.dumps({mode: r}), flush=True)
+        tg.close(); gal.close()
         del sc
         torch.cuda.empty_cache()
     if a.out:
