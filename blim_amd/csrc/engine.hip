@@ -1265,16 +1265,6 @@ extern "C" int blim_tvg_scores(blim_engine* e, const void* vh_bf16, const void* 
     return tvg_scores_impl(e, vh_bf16, false, vocab_bf16, n_vocab, labels, n_pairs, score, stream);
 }
 
-// ---------------------------------------------------------------------------- fused scoring
-extern "C" int blim_score_vtg(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, const int32_t* labels,
-                              int64_t n_rows, const int32_t* row_start, int32_t n_pairs, float* score, void* stream) {
-    ARG_CHECK(e && rows && labels && row_start && score && n_rows > 0 && n_pairs > 0);
-    TRY(reserve_rows(e, n_rows));
-    TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream, e->c.hidden_size + e->aug));     // rows laid out for the adapted lm_head
-    TRY(vtg_logprobs_impl(e, e->hsel.p, e->precise, labels, n_rows, (float*)e->logprob.p, stream, true));
-    return blim_segment_mean(e, (const float*)e->logprob.p, row_start, n_pairs, 0, score, stream);
-}
-
 // ---------------------------------------------------------------------------- gallery prefix cache (blim.h: blim_prefix_cache_*)
 static PcSnap pc_snap(const blim_engine* e) {
     PcSnap s;
@@ -1422,50 +1412,63 @@ static int pc_gather_rows(blim_engine* e, const blim_prefix_cache* pc, const int
     if (e->precise) TRY(launch_rows_by_index((uint16_t*)e->hsel.p + W, pf * W, (const uint16_t*)pc->hid + H, pc->hid_w, rows, n_rows, H, pc->n_slots, 1, 0, s));
     return BLIM_OK;
 }
-extern "C" int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
-                                     const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* row_start, int32_t n_pairs,
-                                     float* score, void* stream) {
-    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && row_start && score && n_rows > 0 && n_pairs > 0);
-    TRY(pc_check_read(e, pc, slots_used, n_used));
+
+// ---------------------------------------------------------------------------- fused scoring
+// blim_score_vtg (pc == nullptr), or the same over cached video prefixes: the lease and the gather of the slots' rows around the same three calls
+static int score_vtg_impl(blim_engine* e, blim_prefix_cache* pc, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used, const blim_batch* b,
+                          const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* row_start, int32_t n_pairs,
+                          float* score, void* stream) {
+    if (pc) TRY(pc_check_read(e, pc, slots_used, n_used));
     TRY(reserve_rows(e, n_rows));
     const int64_t W = e->c.hidden_size + e->aug;
     {
         PcLease lease{e};
-        e->pc_read = pc; e->pc_slot = pfx_slot;
+        if (pc) { e->pc_read = pc; e->pc_slot = pfx_slot; }
         TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream, W));   // rows laid out for the adapted lm_head: lm_head_input forms the u columns
     }
-    TRY(pc_gather_rows(e, pc, rows, n_rows, W, (hipStream_t)stream));
+    if (pc) TRY(pc_gather_rows(e, pc, rows, n_rows, W, (hipStream_t)stream));
     TRY(vtg_logprobs_impl(e, e->hsel.p, e->precise, labels, n_rows, (float*)e->logprob.p, stream, true));
     return blim_segment_mean(e, (const float*)e->logprob.p, row_start, n_pairs, 0, score, stream);
 }
-// blim_score_tvg over cached caption prompts: a pair's first row (it predicts clip 0) is the prompt's last row -- of the batch, or of a slot
-extern "C" int blim_score_tvg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
-                                     const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab, const int32_t* labels, int32_t n_pairs,
+extern "C" int blim_score_vtg(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, const int32_t* labels,
+                              int64_t n_rows, const int32_t* row_start, int32_t n_pairs, float* score, void* stream) {
+    ARG_CHECK(e && rows && labels && row_start && score && n_rows > 0 && n_pairs > 0);
+    return score_vtg_impl(e, nullptr, nullptr, nullptr, 0, b, embeds, rows, labels, n_rows, row_start, n_pairs, score, stream);
+}
+extern "C" int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                                     const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* row_start, int32_t n_pairs,
                                      float* score, void* stream) {
-    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && score && n_pairs > 0);
-    TRY(pc_check_read(e, pc, slots_used, n_used));
+    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && row_start && score && n_rows > 0 && n_pairs > 0);
+    return score_vtg_impl(e, pc, pfx_slot, slots_used, n_used, b, embeds, rows, labels, n_rows, row_start, n_pairs, score, stream);
+}
+
+// blim_score_tvg (pc == nullptr), or the same over cached caption prompts: a pair's first row (it predicts clip 0) is the prompt's last row -- of the batch, or of a slot
+static int score_tvg_impl(blim_engine* e, blim_prefix_cache* pc, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used, const blim_batch* b,
+                          const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab, const int32_t* labels, int32_t n_pairs,
+                          float* score, void* stream) {
+    if (pc) TRY(pc_check_read(e, pc, slots_used, n_used));
     const int64_t n_rows = (int64_t)n_pairs * e->c.num_clips;
     TRY(reserve_rows(e, n_rows));
     TRY(ensure(e->vh, (size_t)round_up(n_rows, 256) * e->c.mm_hidden_size * 2 * (e->precise ? 2 : 1)));
     {
         PcLease lease{e};
-        e->pc_read = pc; e->pc_slot = pfx_slot;
+        if (pc) { e->pc_read = pc; e->pc_slot = pfx_slot; }
         TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream));
     }
-    TRY(pc_gather_rows(e, pc, rows, n_rows, e->c.hidden_size, (hipStream_t)stream));
+    if (pc) TRY(pc_gather_rows(e, pc, rows, n_rows, e->c.hidden_size, (hipStream_t)stream));
     TRY(visual_head_impl(e, e->hsel.p, e->precise, n_rows, e->vh.p, stream));
     return tvg_scores_impl(e, e->vh.p, e->precise, vocab_bf16, n_vocab, labels, n_pairs, score, stream);
 }
-
 extern "C" int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, const void* vocab_bf16,
                               int32_t n_vocab, const int32_t* labels, int32_t n_pairs, float* score, void* stream) {
     ARG_CHECK(e && rows && labels && score && n_pairs > 0);       // vocab_bf16 == NULL: the vocabulary registered with blim_set_video_vocab
-    const int64_t n_rows = (int64_t)n_pairs * e->c.num_clips;
-    TRY(reserve_rows(e, n_rows));
-    TRY(ensure(e->vh, (size_t)round_up(n_rows, 256) * e->c.mm_hidden_size * 2 * (e->precise ? 2 : 1)));
-    TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream));
-    TRY(visual_head_impl(e, e->hsel.p, e->precise, n_rows, e->vh.p, stream));
-    return tvg_scores_impl(e, e->vh.p, e->precise, vocab_bf16, n_vocab, labels, n_pairs, score, stream);
+    return score_tvg_impl(e, nullptr, nullptr, nullptr, 0, b, embeds, rows, vocab_bf16, n_vocab, labels, n_pairs, score, stream);
+}
+extern "C" int blim_score_tvg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                                     const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab, const int32_t* labels, int32_t n_pairs,
+                                     float* score, void* stream) {
+    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && score && n_pairs > 0);
+    return score_tvg_impl(e, pc, pfx_slot, slots_used, n_used, b, embeds, rows, vocab_bf16, n_vocab, labels, n_pairs, score, stream);
 }
 
 // ---------------------------------------------------------------------------- literal forward

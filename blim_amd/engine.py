@@ -476,14 +476,21 @@ class Engine:
                                         _ptr(out), _stream()), "blim_tvg_scores")
         return out
 
-    def score_vtg(self, batch: PackedBatch, embeds, rows, labels, row_start):
+    def _score(self, name: str, batch: PackedBatch, embeds, rows, tail, n_pairs: int, cache=None, pfx_slot=None, slots_used=()):
+        """blim_score_<vtg | tvg>, or its _cached form when a PrefixCache is given: the output buffer and the arguments the forms share.  tail: the entry's own
+        arguments between `rows` and `n_pairs`."""
         import torch
-        n_pairs = row_start.shape[0] - 1
         out = torch.empty(n_pairs, dtype=torch.float32, device=self.device)
         bs = batch.struct(self.max_positions)
-        _check(self.lib.blim_score_vtg(self.h, C.byref(bs), _ptr(embeds), _ptr(rows), _ptr(labels), rows.shape[0], _ptr(row_start), n_pairs,
-                                       _ptr(out), _stream()), "blim_score_vtg")
+        head = (self.h, C.byref(bs))
+        if cache is not None:
+            su = np.ascontiguousarray(slots_used, dtype=np.int32)
+            name, head = name + "_cached", (self.h, cache.h, C.byref(bs), _ptr(pfx_slot), su.ctypes.data if len(su) else None, len(su))
+        _check(getattr(self.lib, name)(*head, _ptr(embeds), _ptr(rows), *tail, n_pairs, _ptr(out), _stream()), name)
         return out
+
+    def score_vtg(self, batch: PackedBatch, embeds, rows, labels, row_start, **cached):
+        return self._score("blim_score_vtg", batch, embeds, rows, (_ptr(labels), rows.shape[0], _ptr(row_start)), row_start.shape[0] - 1, **cached)
 
     # ---- gallery prefix cache (blim.h: blim_prefix_cache_*; blim_amd/gallery.py)
     def prefix_cache_bytes(self, n_slots: int, max_len: int, compensated: bool) -> int:
@@ -492,16 +499,10 @@ class Engine:
     def prefix_cache(self, n_slots: int, max_len: int, compensated: bool) -> "PrefixCache":
         return PrefixCache(self, n_slots, max_len, compensated)
 
-    def score_tvg(self, batch: PackedBatch, embeds, rows, vocab_clip_major, labels):
+    def score_tvg(self, batch: PackedBatch, embeds, rows, vocab_clip_major, labels, **cached):
         """vocab_clip_major None: the vocabulary registered with set_video_vocab()."""
-        import torch
-        n_pairs = labels.shape[0]
-        out = torch.empty(n_pairs, dtype=torch.float32, device=self.device)
-        bs = batch.struct(self.max_positions)
         n_vocab = self.n_vocab if vocab_clip_major is None else vocab_clip_major.shape[1]
-        _check(self.lib.blim_score_tvg(self.h, C.byref(bs), _ptr(embeds), _ptr(rows), _ptr(vocab_clip_major), n_vocab,
-                                       _ptr(labels), n_pairs, _ptr(out), _stream()), "blim_score_tvg")
-        return out
+        return self._score("blim_score_tvg", batch, embeds, rows, (_ptr(vocab_clip_major), n_vocab, _ptr(labels)), labels.shape[0], **cached)
 
     def forward(self, embeds, mask, want_logits=True, want_hidden=True):
         """Literal forward: embeds [B,L,H] bf16, mask [B,L] uint8 -> (logits f32 [B,L,V] | None, hidden f32 [B,L,H] | None)."""
@@ -566,26 +567,11 @@ class PrefixCache:
 
     def score_vtg(self, batch: PackedBatch, pfx_slot, slots_used, embeds, rows, labels, row_start):
         """blim_score_vtg_cached: pfx_slot device int32 [n_seqs] (-1: in-batch prefix); slots_used host ints (every slot read); rows[r] < 0: slot -(rows[r] + 1)'s hidden row."""
-        import torch
-        n_pairs = row_start.shape[0] - 1
-        out = torch.empty(n_pairs, dtype=torch.float32, device=self.engine.device)
-        su = np.ascontiguousarray(slots_used, dtype=np.int32)
-        bs = batch.struct(self.engine.max_positions)
-        _check(self.lib.blim_score_vtg_cached(self.engine.h, self.h, C.byref(bs), _ptr(pfx_slot), su.ctypes.data if len(su) else None, len(su), _ptr(embeds), _ptr(rows),
-                                              _ptr(labels), rows.shape[0], _ptr(row_start), n_pairs, _ptr(out), _stream()), "blim_score_vtg_cached")
-        return out
+        return self.engine.score_vtg(batch, embeds, rows, labels, row_start, cache=self, pfx_slot=pfx_slot, slots_used=slots_used)
 
     def score_tvg(self, batch: PackedBatch, pfx_slot, slots_used, embeds, rows, vocab_clip_major, labels):
         """blim_score_tvg_cached: Engine.score_tvg with the slot conventions of score_vtg above (a slot holds a caption prompt; its hidden row predicts clip 0)."""
-        import torch
-        n_pairs = labels.shape[0]
-        out = torch.empty(n_pairs, dtype=torch.float32, device=self.engine.device)
-        su = np.ascontiguousarray(slots_used, dtype=np.int32)
-        bs = batch.struct(self.engine.max_positions)
-        n_vocab = self.engine.n_vocab if vocab_clip_major is None else vocab_clip_major.shape[1]
-        _check(self.lib.blim_score_tvg_cached(self.engine.h, self.h, C.byref(bs), _ptr(pfx_slot), su.ctypes.data if len(su) else None, len(su), _ptr(embeds), _ptr(rows),
-                                              _ptr(vocab_clip_major), n_vocab, _ptr(labels), n_pairs, _ptr(out), _stream()), "blim_score_tvg_cached")
-        return out
+        return self.engine.score_tvg(batch, embeds, rows, vocab_clip_major, labels, cache=self, pfx_slot=pfx_slot, slots_used=slots_used)
 
 
 def ce_rows(logits, labels):

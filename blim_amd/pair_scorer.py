@@ -8,6 +8,7 @@ candidate.  Replaces the per-query / per-batch loops of /root/reference/retrieva
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -17,6 +18,8 @@ from . import distributed as dist_utils
 from .calibration import TVG_MODES, VTG_MODES, VTG_SPLIT_MODES, CalibrationMixin
 from .engine import PackedBatch
 from .synth import IGNORE_INDEX, IMAGE_TOKEN_INDEX
+
+SEG_MAX = 256            # bound of a merged TVG sequence (PairScorer._plan_tvg: own-segment tiles below a query's segment are computed and masked)
 
 
 def _clip_major_vocab(video_vocab, device, dtype):
@@ -38,6 +41,8 @@ class Plan:
     out_index: np.ndarray      # host: which requested pair each scored pair answers (many-to-one allowed)
     n_tokens: int
     n_rows: int
+    pfx_slot: Optional[object] = None            # planned over a prefix source (blim_amd/gallery.py): device int32 per sequence, the cache slot of its prefix (-1: in the batch)
+    slots_used: Optional[np.ndarray] = None      # ... host int32: every slot the call reads
 
 
 def _split_prompt_response(ids: np.ndarray, labels: np.ndarray):
@@ -273,16 +278,16 @@ class PairScorer(CalibrationMixin):
         Yields one Plan per engine call, so that packing call k+1 (host) overlaps call k (device)."""
         return self.iter_vtg_jobs([(pairs, cpn)])
 
-    def iter_vtg_jobs(self, jobs):
+    def iter_vtg_jobs(self, jobs, slots=None):
         """Several VTG passes -- [(pairs, cpn), ...] -- planned into the SAME engine calls (outputs concatenated in job order): a plan does not know which pass a
         sequence belongs to (a prior's prompt is its own sequence with the video's positions left out), so a rank's text-block prior rides in the last, partly
-        filled call of its likelihood pass instead of being a latency-bound call of its own (iter_tvg_jobs: the TVG counterpart)."""
+        filled call of its likelihood pass instead of being a latency-bound call of its own (iter_tvg_jobs: the TVG counterpart).  slots: a prefix source (_pack_vtg)."""
         items, base = [], 0
         for pairs, cpn in jobs:
             pairs = np.asarray(pairs, dtype=np.int64)
             items += self._vtg_items(pairs, bool(cpn), base)
             base += len(pairs)
-        yield from self._pack_vtg(items)
+        yield from self._pack_vtg(items, slots)
 
     def _vtg_items(self, pairs: np.ndarray, cpn: bool, base: int):
         """Groups of one VTG pass: (video j or None for a prior, its token count, texts, output slots per text), output slot of pair p = base + p."""
@@ -313,28 +318,42 @@ class PairScorer(CalibrationMixin):
             cur[2].append(i); cur[3].append(np.array([base + idx]))
         return items
 
-    def _pack_vtg(self, items):
-        # pack groups into super-batches
-        st = _PackState(self, "vtg")
+    def _pack_vtg(self, items, slots=None):
+        """Packs groups into super-batches.  slots: a prefix source (blim_amd/gallery.py: `slot_of` {(video, pre, post): slot} and `cache.slot_len`) -- a group whose
+        prefix it holds packs no prefix sequence: its sequences name the slot and each pair's first row is -(slot + 1)."""
+        st = _PackState(self, "vtg", slots)
         for (j, nv, texts_g, outs_g) in items:
             pre, post, _ = self.vtg_split[texts_g[0]]
-            n_vid = nv if j is None else int(self.video_feat(j, False).shape[0])
-            need = len(pre) + (0 if j is None else n_vid) + len(post) + sum(max(len(self.vtg_split[i][2]) - 1, 0) for i in texts_g)
-            if st.n_tok and st.n_tok + need > self.max_tokens:
-                yield st.finish(); st = _PackState(self, "vtg")
-            # prefix sequence
+            slot = -1 if slots is None or j is None else slots.slot_of.get((j, pre.tobytes(), post.tobytes()), -1)
             if j is None:
-                if len(pre) + len(post) == 0:
-                    # the reference's rows always open with the ChatML header; with no visible token in front of the response the
-                    # prior's first factor would be read from a fully masked video position (undefined attention row)
-                    raise ValueError("VTG candidate prior (cpn=True) needs at least one prompt token besides the <image> placeholder")
-                ptoks = np.concatenate([pre, post]); ppos = np.concatenate([np.arange(len(pre)), len(pre) + n_vid + np.arange(len(post))])
-                p0 = st.add_seq(ptoks, ppos, np.ones(len(ptoks), np.uint8), None)
+                n_vid = nv
+            elif slot >= 0:                                                # a cached video is not projected at query time: its token count is its shape's
+                n_vid = int(np.prod(self.video[j].shape[-3:-1]))
             else:
-                fo = st.add_feat(self.video_feat(j, False))
-                ptoks = np.concatenate([pre, -(1 + fo + np.arange(n_vid)), post])
-                p0 = st.add_seq(ptoks, np.arange(len(ptoks)), np.ones(len(ptoks), np.uint8), None)
-            plen = len(ptoks); ppos_end = len(pre) + n_vid + len(post)
+                n_vid = int(self.video_feat(j, False).shape[0])
+            ppos_end = len(pre) + n_vid + len(post)
+            need = (0 if slot >= 0 else ppos_end - (n_vid if j is None else 0)) + sum(max(len(self.vtg_split[i][2]) - 1, 0) for i in texts_g)
+            if st.n_tok and st.n_tok + need > self.max_tokens:
+                yield st.finish(); st = _PackState(self, "vtg", slots)
+            # prefix sequence
+            if slot >= 0:
+                plen = slots.cache.slot_len(slot)
+                if plen != ppos_end:
+                    raise RuntimeError(f"gallery slot {slot} holds {plen} positions, the prefix of video {j} has {ppos_end}")
+                st.used.add(slot)
+                p0, last = 0, -(slot + 1)
+            else:
+                if j is None:
+                    if len(pre) + len(post) == 0:
+                        # the reference's rows always open with the ChatML header; with no visible token in front of the response the
+                        # prior's first factor would be read from a fully masked video position (undefined attention row)
+                        raise ValueError("VTG candidate prior (cpn=True) needs at least one prompt token besides the <image> placeholder")
+                    ptoks = np.concatenate([pre, post]); ppos = np.concatenate([np.arange(len(pre)), len(pre) + n_vid + np.arange(len(post))])
+                else:
+                    fo = st.add_feat(self.video_feat(j, False))
+                    ptoks = np.concatenate([pre, -(1 + fo + np.arange(n_vid)), post]); ppos = np.arange(len(ptoks))
+                p0 = st.add_seq(ptoks, ppos, np.ones(len(ptoks), np.uint8), None)
+                plen = len(ptoks); last = p0 + plen - 1
             for i, outs in zip(texts_g, outs_g):
                 resp = self.vtg_split[i][2]
                 if self.max_row_len is not None and ppos_end + len(resp) > self.max_row_len:
@@ -342,9 +361,9 @@ class PairScorer(CalibrationMixin):
                         raise ValueError(f"tokenizer_model_max_length = {self.max_row_len} leaves no response token of text {i} ({ppos_end} prompt + video tokens)")
                     resp = resp[: self.max_row_len - ppos_end]             # :452-457: the row's tail is cut, the score averages the tokens that remain
                 body = resp[:-1]                                           # the last response token predicts nothing
-                rows = [p0 + plen - 1]
+                rows = [last]
                 if len(body):
-                    s0 = st.add_seq(body, ppos_end + np.arange(len(body)), np.ones(len(body), np.uint8), (p0, plen))
+                    s0 = st.add_seq(body, ppos_end + np.arange(len(body)), np.ones(len(body), np.uint8), (p0, plen), slot=slot)
                     rows += list(range(s0, s0 + len(body)))
                 st.add_pair(rows, resp.astype(np.int32), outs)
         if st.n_pairs:
@@ -354,27 +373,28 @@ class PairScorer(CalibrationMixin):
         """pairs: [P, 2] (video j, text i); score = log P(video j | text i) (mean over clips)."""
         return self.iter_tvg_jobs([(pairs, cpn)])
 
-    def iter_tvg_jobs(self, jobs):
+    def iter_tvg_jobs(self, jobs, slots=None):
         """Several TVG passes -- [(pairs, cpn), ...] -- planned into the SAME engine calls: outputs are concatenated in job order.  A plan does not know which pass
         a sequence belongs to (visibility is per token, a prior's prefix is its own sequence), so a small likelihood pass and its prior fill one call instead of
-        leaving two partly filled ones -- what a rank's share of a sharded evaluation and the calibration sample consist of."""
-        box, base = [_PackState(self, "tvg")], 0
+        leaving two partly filled ones -- what a rank's share of a sharded evaluation and the calibration sample consist of.  slots: a prefix source (_plan_tvg)."""
+        box, base = [_PackState(self, "tvg", slots)], 0
         for pairs, cpn in jobs:
             pairs = np.asarray(pairs, dtype=np.int64)
-            yield from self._plan_tvg(pairs, bool(cpn), box, base)
+            yield from self._plan_tvg(pairs, bool(cpn), box, base, slots)
             base += len(pairs)
         if box[0].n_pairs:
             yield box[0].finish()
 
-    def _plan_tvg(self, pairs: np.ndarray, cpn: bool, box, base: int):
-        """Plans one TVG pass into the pack state box[0] (replaced whenever a call is full and yielded); output slot of pair p = base + p."""
+    def _plan_tvg(self, pairs: np.ndarray, cpn: bool, box, base: int, slots=None):
+        """Plans one TVG pass into the pack state box[0] (replaced whenever a call is full and yielded); output slot of pair p = base + p.  slots: a prefix source
+        (blim_amd/gallery.py: `slot_of` {caption prompt bytes: slot} and `cache.slot_len`) -- a text whose prompt it holds packs no prompt: its merged sequences name
+        the slot and each pair's first row is -(slot + 1).  The priors (cpn) have no cached form."""
         C = self.num_clips
         st = box[0]
         # The continuations of one prefix -- the C - 1 clip tokens of every candidate video of a text (prior: last prompt token + clip tokens) -- are
         # packed into ONE sequence whose segments do not see each other (blim_batch.own_start): the 32-query attention blocks are dense instead of
         # holding 3 - 4 queries each (2,919 -> ~500 blocks per 13,700-token call at the reference's shapes) and the planner adds one sequence per
-        # group instead of one per pair.  SEG_MAX bounds a merged sequence (own-segment tiles below a query's segment are computed and masked).
-        SEG_MAX = 256
+        # group instead of one per pair.  SEG_MAX bounds a merged sequence.
         if cpn:
             # prior depends on (prompt length, last prompt token, first tvg_prefix_length tokens, video) only
             tp = self.m.tvg_prefix_length
@@ -419,31 +439,43 @@ class PairScorer(CalibrationMixin):
                 if not groups or groups[-1][0] != i:
                     groups.append((i, []))
                 groups[-1][1].append(int(idx))
+            per = max(C - 1, 1)
             for i, idxs in groups:
                 pr = self.tvg_split[i]
                 plen = len(pr)
+                slot = -1 if slots is None else slots.slot_of.get(pr.tobytes(), -1)
+                if slot >= 0:
+                    held = slots.cache.slot_len(slot)
+                    if held != plen:
+                        raise RuntimeError(f"text gallery slot {slot} holds {held} positions, the caption prompt of text {i} has {plen}")
                 pos_in, p0 = 0, None
                 while pos_in < len(idxs):
-                    per = max(C - 1, 1)
-                    room = (self.max_tokens - st.n_tok - (plen if p0 is None else 0)) // per
-                    if st.n_tok and room < 1:
-                        yield st.finish(); st = box[0] = _PackState(self, "tvg"); p0 = None
-                        room = (self.max_tokens - plen) // per
+                    own = plen if slot < 0 and p0 is None else 0          # prompt tokens this text still has to pack into the call (a cached text: none)
+                    room = (self.max_tokens - st.n_tok - own) // per
+                    # (num_clips == 1 over a prefix source: a cached text adds no token, so the rows alone fill a call)
+                    if (st.n_tok and room < 1) or (slots is not None and C == 1 and st.n_pairs >= self.max_tokens):
+                        yield st.finish(); st = box[0] = _PackState(self, "tvg", slots); p0 = None
+                        room = (self.max_tokens - (plen if slot < 0 else 0)) // per
                     n = max(1, min(len(idxs) - pos_in, room, SEG_MAX // per))
-                    if p0 is None:                       # the prompt is packed once per engine call; every merged sequence of the text names it
-                        p0 = st.add_seq(pr, np.arange(plen), np.ones(plen, np.uint8), None)
+                    if slot >= 0:
+                        st.used.add(slot)
+                        first, pfx = -(slot + 1), (0, plen)
+                    else:
+                        if p0 is None:                   # the prompt is packed once per engine call; every merged sequence of the text names it
+                            p0 = st.add_seq(pr, np.arange(plen), np.ones(plen, np.uint8), None)
+                        first, pfx = p0 + plen - 1, (p0, plen)
                     chunk = idxs[pos_in:pos_in + n]
                     s0 = None
                     if C > 1:
-                        toks, own = [], []
+                        toks, own_start = [], []
                         for m_, idx in enumerate(chunk):
                             fo = st.add_feat(self.video_feat(int(pairs[idx, 0]), True))
                             toks.append(-(1 + fo + np.arange(C - 1)))
-                            own.append(np.full(C - 1, m_ * (C - 1), np.int32))
-                        s0 = st.add_seq(np.concatenate(toks), np.tile(plen + np.arange(C - 1), n), np.ones(n * (C - 1), np.uint8), (p0, plen),
-                                        own_start=np.concatenate(own))
+                            own_start.append(np.full(C - 1, m_ * (C - 1), np.int32))
+                        s0 = st.add_seq(np.concatenate(toks), np.tile(plen + np.arange(C - 1), n), np.ones(n * (C - 1), np.uint8), pfx,
+                                        own_start=np.concatenate(own_start), slot=slot)
                     for m_, idx in enumerate(chunk):
-                        rows = [p0 + plen - 1]
+                        rows = [first]
                         if C > 1:
                             rows += list(range(s0 + m_ * (C - 1), s0 + (m_ + 1) * (C - 1)))
                         else:
@@ -452,42 +484,60 @@ class PairScorer(CalibrationMixin):
                     pos_in += n
 
     # ---- execution (device) ---------------------------------------------------------------------
-    def run(self, plan: Plan):
-        """One engine call; returns a device f32 tensor [plan.n_pairs]."""
-        self.exec_tokens += plan.n_tokens
-        f8 = getattr(self.engine, "dtype", "") == "f8"
-        if plan.kind == "vtg":
-            mode = self.vtg_mode                                             # None | "full" | "select"
-            bits = getattr(self.engine, "layer_mask", None) if mode == "select" else None
-            self.exec_flops += executed_flops(self.m.dims, plan.n_tokens, plan.n_rows, "vtg", mode, prune=not f8, layer_bits=bits)
-            if getattr(self.engine, "lo6", False):
-                self.exec_flops_lo6 += lo6_pass_flops(self.m.dims, plan.n_tokens, plan.n_rows, "vtg", mode, prune=not f8, layer_bits=bits)
-            comp = mode in VTG_SPLIT_MODES
-            self.engine.set_precise(comp, embeds=comp, mlp=True, layers=mode == "select")
-            try:
-                embeds = self.engine.assemble(plan.src_index, plan.feats)
-                return self.engine.score_vtg(plan.batch, embeds, plan.rows, plan.labels, plan.row_start)
-            finally:
-                self.engine.set_precise(False)
-        self.exec_flops += executed_flops(self.m.dims, plan.n_tokens, plan.n_rows, "tvg", self.tvg_mode if self.split_tvg else None,
-                                          n_vocab=self.n_vocab, prune=not f8)
-        if getattr(self.engine, "lo6", False) and self.split_tvg and getattr(self.engine, "dtype", "") != "bf16":      # (bf16 engines: TVG calls keep the bf16 second pass, Engine.set_precise)
-            self.exec_flops_lo6 += lo6_pass_flops(self.m.dims, plan.n_tokens, plan.n_rows, "tvg", self.tvg_mode, prune=not f8)
-        if self.vocab_cm is None and getattr(self.engine, "_vocab_key", None) != self._vocab_key:
-            self.engine.set_video_vocab(self._vocab_src)                     # another scorer / the literal path registered its own vocabulary since
-        # TVG calls: compensated (3-5 new tokens per pair: cheap); how much of the MLP branch is compensated follows tvg_mode (calibrate_tvg)
-        self.engine.set_precise(self.split_tvg, embeds=self.split_tvg, mlp=self.tvg_mode != "attn", tvg=True)
+    @contextmanager
+    def _call_options(self, kind: str):
+        """The engine options every call of `kind` runs under, for the length of the call.  A prefix cache's fills run under it too (blim_amd/gallery.py): the
+        engine refuses a slot whose fill ran under other options than the call that reads it."""
+        if kind == "vtg":
+            comp = self.vtg_mode in VTG_SPLIT_MODES                          # None | "full" | "select"
+            self.engine.set_precise(comp, embeds=comp, mlp=True, layers=self.vtg_mode == "select")
+        else:
+            if self.vocab_cm is None and getattr(self.engine, "_vocab_key", None) != self._vocab_key:
+                self.engine.set_video_vocab(self._vocab_src)                 # another scorer / the literal path registered its own vocabulary since
+            # TVG calls: compensated (3-5 new tokens per pair: cheap); how much of the MLP branch is compensated follows tvg_mode (calibrate_tvg)
+            self.engine.set_precise(self.split_tvg, embeds=self.split_tvg, mlp=self.tvg_mode != "attn", tvg=True)
         try:
-            embeds = self.engine.assemble(plan.src_index, plan.feats)
-            return self.engine.score_tvg(plan.batch, embeds, plan.rows, self.vocab_cm, plan.labels)
+            yield
         finally:
             self.engine.set_precise(False)
 
-    def score(self, plans, n_requested: int) -> np.ndarray:
+    def _count(self, plan: Plan) -> None:
+        """exec_tokens / exec_flops / exec_flops_lo6 of one engine call."""
+        self.exec_tokens += plan.n_tokens
+        f8 = getattr(self.engine, "dtype", "") == "f8"
+        lo6 = getattr(self.engine, "lo6", False)
+        if plan.kind == "vtg":
+            mode = self.vtg_mode
+            bits = getattr(self.engine, "layer_mask", None) if mode == "select" else None
+            self.exec_flops += executed_flops(self.m.dims, plan.n_tokens, plan.n_rows, "vtg", mode, prune=not f8, layer_bits=bits)
+            if lo6:
+                self.exec_flops_lo6 += lo6_pass_flops(self.m.dims, plan.n_tokens, plan.n_rows, "vtg", mode, prune=not f8, layer_bits=bits)
+            return
+        self.exec_flops += executed_flops(self.m.dims, plan.n_tokens, plan.n_rows, "tvg", self.tvg_mode if self.split_tvg else None,
+                                          n_vocab=self.n_vocab, prune=not f8)
+        if lo6 and self.split_tvg and getattr(self.engine, "dtype", "") != "bf16":      # (bf16 engines: TVG calls keep the bf16 second pass, Engine.set_precise)
+            self.exec_flops_lo6 += lo6_pass_flops(self.m.dims, plan.n_tokens, plan.n_rows, "tvg", self.tvg_mode, prune=not f8)
+
+    def run(self, plan: Plan, cache=None):
+        """One engine call; returns a device f32 tensor [plan.n_pairs].  A plan made over a prefix source (plan.pfx_slot) goes through `cache`, the PrefixCache
+        that holds its slots, and is not counted in exec_*: those count the scorer's own calls."""
+        if plan.pfx_slot is None:
+            self._count(plan)
+            via, slots = self.engine, ()
+        else:
+            via, slots = cache, (plan.pfx_slot, plan.slots_used)
+        with self._call_options(plan.kind):
+            embeds = self.engine.assemble(plan.src_index, plan.feats)
+            if plan.kind == "vtg":
+                return via.score_vtg(plan.batch, *slots, embeds, plan.rows, plan.labels, plan.row_start)
+            return via.score_tvg(plan.batch, *slots, embeds, plan.rows, self.vocab_cm, plan.labels)
+
+    def score(self, plans, n_requested: int, run=None) -> np.ndarray:
         """plans: list or generator of Plan.  Engine calls are asynchronous, so with a generator the host packs plan k+1 while
-        the device runs plan k; the scores are copied back once, at the end."""
+        the device runs plan k; the scores are copied back once, at the end.  run: what executes a plan (default: self.run)."""
+        run = run or self.run
         out = np.full(n_requested, np.nan, dtype=np.float32)
-        done = [(p.out_index, self.run(p)) for p in plans]
+        done = [(p.out_index, run(p)) for p in plans]
         for out_index, r in done:
             sc = r.float().cpu().numpy()
             for k, outs in enumerate(out_index):
@@ -552,12 +602,14 @@ class PairScorer(CalibrationMixin):
 
 
 class _PackState:
-    """Accumulates sequences / rows of one super-batch on the host, then uploads once."""
+    """Accumulates sequences / rows of one super-batch on the host, then uploads once.  slots: the prefix source the call is planned over, if any -- the plan
+    then carries the cache slot of every sequence (-1: in-batch prefix) and the slots the call reads."""
 
-    def __init__(self, scorer: PairScorer, kind: str):
-        self.s, self.kind = scorer, kind
+    def __init__(self, scorer: PairScorer, kind: str, slots=None):
+        self.s, self.kind, self.slots = scorer, kind, slots
         self.tok: List[np.ndarray] = []; self.pos: List[np.ndarray] = []; self.vis: List[np.ndarray] = []
         self.seq_start: List[int] = []; self.seq_len: List[int] = []; self.pfx_start: List[int] = []; self.pfx_len: List[int] = []
+        self.slot: List[int] = []; self.used = set()
         self.own: List[np.ndarray] = []; self.any_own = False             # per token: first own-segment index it attends to (segmented sequences)
         self.feats: List[object] = []; self.feat_key: Dict[int, int] = {}; self.n_feat = 0
         self.rows: List[int] = []; self.labels: List[np.ndarray] = []; self.row_start: List[int] = [0]
@@ -572,7 +624,7 @@ class _PackState:
         self.feats.append(f); self.feat_key[k] = off; self.n_feat += int(f.shape[0])
         return off
 
-    def add_seq(self, toks, pos, vis, prefix, own_start=None) -> int:
+    def add_seq(self, toks, pos, vis, prefix, own_start=None, slot: int = -1) -> int:
         start = self.n_tok
         self.tok.append(np.asarray(toks, np.int64)); self.pos.append(np.asarray(pos, np.int64)); self.vis.append(np.asarray(vis, np.uint8))
         if own_start is None:
@@ -581,6 +633,7 @@ class _PackState:
             self.own.append(np.asarray(own_start, np.int32)); self.any_own = True
         self.seq_start.append(start); self.seq_len.append(len(toks))
         self.pfx_start.append(prefix[0] if prefix else 0); self.pfx_len.append(prefix[1] if prefix else 0)
+        self.slot.append(int(slot))
         self.n_tok += len(toks)
         return start
 
@@ -591,17 +644,27 @@ class _PackState:
         self.out_index.append(np.asarray(outs))
         self.n_pairs += 1
 
-    def finish(self) -> Plan:
+    def upload(self):
+        """-> (PackedBatch, assemble's src_index, feature rows) of the sequences so far, on the device."""
         import torch
         dev = self.s.device
-        src = np.concatenate(self.tok).astype(np.int32)
         batch = PackedBatch(np.concatenate(self.pos), np.concatenate(self.vis), np.array(self.seq_start), np.array(self.seq_len),
                             np.array(self.pfx_start), np.array(self.pfx_len), device=dev, own_start=np.concatenate(self.own) if self.any_own else None)
+        src = torch.from_numpy(np.concatenate(self.tok).astype(np.int32)).to(dev)
         H = self.s.m.dims.hidden_size
         wide = self.s.split_tvg if self.kind == "tvg" else self.s.split_vtg                   # feature rows are [hi | lo]
         feats = torch.cat(self.feats, dim=0) if self.feats else torch.zeros((1, H * (2 if wide else 1)), dtype=self.s.m.dtype, device=dev)
+        return batch, src, feats
+
+    def finish(self) -> Plan:
+        import torch
+        dev = self.s.device
+        if self.slots is not None and self.n_tok == 0:     # every pair reads a cached row only (one-token responses): one dummy token keeps the batch non-empty
+            self.add_seq(np.zeros(1, np.int64), np.zeros(1, np.int64), np.ones(1, np.uint8), None)
+        batch, src, feats = self.upload()
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
-        labels = np.concatenate(self.labels)
-        return Plan(kind=self.kind, batch=batch, src_index=t(src), feats=feats, rows=t(np.array(self.rows)), labels=t(labels),
+        cached = self.slots is not None
+        return Plan(kind=self.kind, batch=batch, src_index=src, feats=feats, rows=t(np.array(self.rows)), labels=t(np.concatenate(self.labels)),
                     row_start=t(np.array(self.row_start)) if self.kind == "vtg" else None, n_pairs=self.n_pairs,
-                    out_index=self.out_index, n_tokens=self.n_tok, n_rows=len(self.rows))
+                    out_index=self.out_index, n_tokens=self.n_tok, n_rows=len(self.rows),
+                    pfx_slot=t(self.slot) if cached else None, slots_used=np.array(sorted(self.used), dtype=np.int32) if cached else None)

@@ -1,6 +1,6 @@
 """CPU: the gallery index's host side (blim_amd/gallery.py, blim_amd/search.py) -- cached plan construction (pfx_slot, negative row references, the
-tokenizer_model_max_length cut, slots under a budget, the (video, pre, post) key), the cache's byte size and the CLI's refusals.  The GPU side is
-tests/test_gallery_gpu.py."""
+tokenizer_model_max_length cut, slots under a budget, the (video, pre, post) key), plans without a slot against the scorer's own, the cache's byte size and the
+CLI's refusals.  The GPU side is tests/test_gallery_gpu.py."""
 import types
 
 import numpy as np
@@ -179,3 +179,55 @@ def test_prior_memo_is_dropped_after_a_weight_or_mode_change():
     s.tvg_mode = "attn"                                                              # a TVG mode change
     g._t2v_prior([0], cand)
     assert calls == [2, 2, 2]
+
+
+def plan_difference(a, b):
+    """None when two plans are the same call, array for array; else the name of the first field that differs (pfx_slot / slots_used apart: only a plan made
+    over a prefix source carries them)."""
+    for k in ("positions", "key_visible", "seq_start", "seq_len", "pfx_start", "pfx_len", "own_start", "blk_seq", "blk_q0"):
+        x, y = getattr(a.batch, k), getattr(b.batch, k)
+        if (x is None) != (y is None) or (x is not None and not torch.equal(x, y)):
+            return "batch." + k
+    for k in ("src_index", "rows", "labels", "row_start", "feats"):
+        x, y = getattr(a, k), getattr(b, k)
+        if (x is None) != (y is None) or (x is not None and not (x.dtype == y.dtype and torch.equal(x, y))):
+            return k
+    if [o.tolist() for o in a.out_index] != [o.tolist() for o in b.out_index]:
+        return "out_index"
+    for k in ("kind", "n_pairs", "n_tokens", "n_rows"):
+        if getattr(a, k) != getattr(b, k):
+            return k
+    return None
+
+
+def _random_texts(n):
+    """Two prompt splits, responses of 1 - 4 tokens."""
+    return [([1, i % 2], [2], list(range(3, 4 + i % 4))) for i in range(n)]
+
+
+@pytest.mark.parametrize("max_tokens", [64, 4096])
+@pytest.mark.parametrize("C", [1, 2, 4])
+def test_plans_without_a_slot_are_the_scorers_own(C, max_tokens):
+    rng = np.random.RandomState(10 * C + max_tokens)
+    s = _fake_scorer(_random_texts(5), n_videos=4, max_tokens=max_tokens)
+    s.num_clips = C
+    pairs = np.stack([rng.randint(0, 4, 40), rng.randint(0, 5, 40)], axis=1)
+    got, want = list(GL.GalleryIndex(s).iter_plans(pairs)), list(s.iter_vtg(pairs))
+    assert len(got) == len(want) and (len(want) > 1) == (max_tokens == 64)
+    assert [plan_difference(a, b) for a, b in zip(got, want)] == [None] * len(want)
+    assert all(p.pfx_slot is None and p.slots_used is None for p in want)
+    assert all(np.all(p.pfx_slot.numpy() == -1) and len(p.slots_used) == 0 for p in got)
+
+
+def test_planning_cached_videos_projects_none():
+    s = _fake_scorer(_random_texts(5), n_videos=4, max_tokens=64)
+    calls = []
+    s.video_feat = lambda j, tvg: calls.append(j) or torch.zeros((NV, H))
+    g = _gallery(s, {k: k for k in range(4 * 2)})                # every (video, split) prefix has a slot
+    rng = np.random.RandomState(2)
+    pairs = np.stack([rng.randint(0, 4, 40), rng.randint(0, 5, 40)], axis=1)
+    plans = list(g.iter_plans(pairs))
+    assert sum(p.n_pairs for p in plans) == 40 and calls == []
+    g = _gallery(s, {k: k for k in range(2, 4 * 2)})             # ... all but video 0's: it alone is projected
+    list(g.iter_plans(pairs))
+    assert calls and set(calls) == {0}

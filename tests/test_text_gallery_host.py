@@ -1,6 +1,6 @@
 """CPU: the text gallery's host side (blim_amd/gallery.py: TextGalleryIndex; blim_amd/search.py --direction v2t) -- cached TVG plan construction (no prompt sequence
 for a cached text, pfx_slot / pfx_len, the negative first row, merged segments, num_clips == 1, SEG_MAX chunks), token counts, slots under a budget, shared slots of
-duplicate prompts, the v2t blend against combine_and_rank and the CLI's refusals.  The GPU side is tests/test_text_gallery_gpu.py."""
+duplicate prompts, plans without a slot against the scorer's own, the v2t blend against combine_and_rank and the CLI's refusals.  The GPU side is tests/test_text_gallery_gpu.py."""
 import types
 
 import numpy as np
@@ -13,6 +13,7 @@ from blim_amd import search as SR
 from blim_amd import synth
 from blim_amd import training_utils as TU
 from blim_amd.pair_scorer import PairScorer
+from test_gallery_host import plan_difference
 
 H = 16
 
@@ -284,3 +285,16 @@ def test_cli_default_blend_per_direction():
     SR.check_args(args)                                                            # c2 = 0 does not act on v2t
     with pytest.raises(SystemExit, match="world size"):
         SR.check_args(args, world=2)
+
+
+@pytest.mark.parametrize("max_tokens", [64, 4096])
+@pytest.mark.parametrize("C", [1, 2, 4])
+def test_plans_without_a_slot_are_the_scorers_own(C, max_tokens):
+    rng = np.random.RandomState(10 * C + max_tokens)
+    s = _fake_scorer([list(range(5, 5 + n)) for n in (4, 7, 5, 9, 6)], n_videos=4, C=C, max_tokens=max_tokens)
+    pairs = np.stack([rng.randint(0, 4, 40), rng.randint(0, 5, 40)], axis=1)
+    got, want = list(GL.TextGalleryIndex(s).iter_plans(pairs)), list(s.iter_tvg(pairs))
+    assert len(got) == len(want) and (len(want) > 1) == (max_tokens == 64 and C > 1)
+    assert [plan_difference(a, b) for a, b in zip(got, want)] == [None] * len(want)
+    assert all(p.pfx_slot is None and p.slots_used is None for p in want)
+    assert all(np.all(p.pfx_slot.numpy() == -1) and len(p.slots_used) == 0 for p in got)
