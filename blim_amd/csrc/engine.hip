@@ -1413,19 +1413,74 @@ static int pc_gather_rows(blim_engine* e, const blim_prefix_cache* pc, const int
     return BLIM_OK;
 }
 
+// An admit call (blim.h: blim_pc_admit): a cached scoring call that also captures the in-batch prefixes it names into slots.  pc_admit_begin checks the admissions --
+// host values only, before anything is launched --, marks their slots empty and has the device build the two maps the capture reads from them (kernels.hpp:
+// launch_admit_map; the admissions travel as kernel arguments): -> *cap [n_tokens] for launch_kv_capture, *row_slot [n_rows] for the hidden-row copy.  Nothing
+// here waits for the device or copies from host memory (the workspace's growth aside, as everywhere): the query path packs its next plan while this one runs.
+static int pc_admit_begin(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const blim_pc_admit* admits, int32_t n_admit, const int32_t* slots_used,
+                          int32_t n_used, int64_t n_rows, hipStream_t s, const int32_t** cap, const int32_t** row_slot) {
+    TRY(check_batch(b));
+    if (e->f8) { blim_set_error("prefix cache admit: fp8 engines are not supported"); return BLIM_ERR_STATE; }
+    const int64_t T = b->n_tokens;
+    std::vector<char> mark(pc->n_slots, 0);
+    for (int k = 0; k < n_used; ++k) if (slots_used[k] >= 0 && slots_used[k] < pc->n_slots) mark[slots_used[k]] = 1;
+    for (int a = 0; a < n_admit; ++a) {
+        const blim_pc_admit& q = admits[a];
+        if (q.slot < 0 || q.slot >= pc->n_slots) { blim_set_error("prefix cache admit: slot %d of admission %d outside 0 .. %d", q.slot, a, pc->n_slots - 1); return BLIM_ERR_ARG; }
+        if (mark[q.slot] == 1) { blim_set_error("prefix cache admit: slot %d is read by this call (slots_used) and admitted in it", q.slot); return BLIM_ERR_ARG; }
+        if (mark[q.slot] == 2) { blim_set_error("prefix cache admit: slot %d admitted twice", q.slot); return BLIM_ERR_ARG; }
+        mark[q.slot] = 2;
+        if (q.seq < 0 || q.seq >= b->n_seqs) { blim_set_error("prefix cache admit: sequence %d of admission %d outside the batch's %d", q.seq, a, b->n_seqs); return BLIM_ERR_ARG; }
+        if (q.len < 1 || q.len > pc->max_len || q.start < 0 || (int64_t)q.start + q.len > T) {
+            blim_set_error("prefix cache admit: len %d (at %d) of admission %d does not fit a slot of %d positions in a batch of %lld tokens", q.len, q.start, a, pc->max_len, (long long)T);
+            return BLIM_ERR_ARG;
+        }
+        if (q.row < 0 || q.row >= n_rows) { blim_set_error("prefix cache admit: row %d of admission %d outside the call's %lld rows", q.row, a, (long long)n_rows); return BLIM_ERR_ARG; }
+    }
+    for (int a = 0; a < n_admit; ++a) pc->len[admits[a].slot] = -1;          // a failed call leaves its slots empty
+    const size_t n_map = (size_t)T + (size_t)n_rows;
+    TRY(ensure(pc->map, n_map * 4));
+    int32_t* map = (int32_t*)pc->map.p;
+    std::vector<int32_t> adm(5 * (size_t)n_admit);
+    for (int a = 0; a < n_admit; ++a) {
+        const blim_pc_admit& q = admits[a];
+        int32_t* d = adm.data() + 5 * (size_t)a;
+        d[0] = q.seq; d[1] = q.slot; d[2] = q.start; d[3] = q.len; d[4] = q.row;
+    }
+    TRY(launch_admit_map(adm.data(), n_admit, map, T, n_rows, pc->max_len, s));      // (the values are kernel arguments: `adm` need not outlive this line)
+    *cap = map; *row_slot = map + T;
+    return BLIM_OK;
+}
+// ... and after the decode: the admitted rows' final-norm hidden states (hsel rows of pf halves of width W) become the slots' hidden rows, hi, then lo (H values
+// each), and the slots record their lengths and the state they were computed under, as a fill's do
+static int pc_admit_finish(blim_engine* e, blim_prefix_cache* pc, const blim_pc_admit* admits, int32_t n_admit, const int32_t* row_slot, int64_t n_rows, int64_t W,
+                           hipStream_t s) {
+    const int H = e->c.hidden_size;
+    const int64_t pf = e->precise ? 2 : 1;
+    TRY(launch_rows_by_index((uint16_t*)pc->hid, pc->hid_w, (const uint16_t*)e->hsel.p, pf * W, row_slot, n_rows, H, pc->n_slots, 0, 0, s));
+    if (e->precise) TRY(launch_rows_by_index((uint16_t*)pc->hid + H, pc->hid_w, (const uint16_t*)e->hsel.p + W, pf * W, row_slot, n_rows, H, pc->n_slots, 0, 0, s));
+    const PcSnap now = pc_snap(e);
+    for (int a = 0; a < n_admit; ++a) { pc->len[admits[a].slot] = admits[a].len; pc->snap[admits[a].slot] = now; }
+    return BLIM_OK;
+}
+
 // ---------------------------------------------------------------------------- fused scoring
 // blim_score_vtg (pc == nullptr), or the same over cached video prefixes: the lease and the gather of the slots' rows around the same three calls
 static int score_vtg_impl(blim_engine* e, blim_prefix_cache* pc, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used, const blim_batch* b,
                           const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows, const int32_t* row_start, int32_t n_pairs,
-                          float* score, void* stream) {
+                          float* score, void* stream, const blim_pc_admit* admits = nullptr, int32_t n_admit = 0) {
     if (pc) TRY(pc_check_read(e, pc, slots_used, n_used));
+    const int32_t* cap = nullptr; const int32_t* row_slot = nullptr;
+    if (n_admit) TRY(pc_admit_begin(e, pc, b, admits, n_admit, slots_used, n_used, n_rows, (hipStream_t)stream, &cap, &row_slot));
     TRY(reserve_rows(e, n_rows));
     const int64_t W = e->c.hidden_size + e->aug;
     {
         PcLease lease{e};
         if (pc) { e->pc_read = pc; e->pc_slot = pfx_slot; }
+        if (n_admit) { e->pc_fill = pc; e->pc_cap_row = cap; }
         TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream, W));   // rows laid out for the adapted lm_head: lm_head_input forms the u columns
     }
+    if (n_admit) TRY(pc_admit_finish(e, pc, admits, n_admit, row_slot, n_rows, W, (hipStream_t)stream));
     if (pc) TRY(pc_gather_rows(e, pc, rows, n_rows, W, (hipStream_t)stream));
     TRY(vtg_logprobs_impl(e, e->hsel.p, e->precise, labels, n_rows, (float*)e->logprob.p, stream, true));
     return blim_segment_mean(e, (const float*)e->logprob.p, row_start, n_pairs, 0, score, stream);
@@ -1441,20 +1496,31 @@ extern "C" int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* pc, cons
     ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && row_start && score && n_rows > 0 && n_pairs > 0);
     return score_vtg_impl(e, pc, pfx_slot, slots_used, n_used, b, embeds, rows, labels, n_rows, row_start, n_pairs, score, stream);
 }
+extern "C" int blim_score_vtg_admit(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                                    const blim_pc_admit* admits, int32_t n_admit, const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows,
+                                    const int32_t* row_start, int32_t n_pairs, float* score, void* stream) {
+    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && (admits || n_admit == 0) && n_admit >= 0 && rows && labels && row_start &&
+              score && n_rows > 0 && n_pairs > 0);
+    return score_vtg_impl(e, pc, pfx_slot, slots_used, n_used, b, embeds, rows, labels, n_rows, row_start, n_pairs, score, stream, admits, n_admit);
+}
 
 // blim_score_tvg (pc == nullptr), or the same over cached caption prompts: a pair's first row (it predicts clip 0) is the prompt's last row -- of the batch, or of a slot
 static int score_tvg_impl(blim_engine* e, blim_prefix_cache* pc, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used, const blim_batch* b,
                           const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab, const int32_t* labels, int32_t n_pairs,
-                          float* score, void* stream) {
+                          float* score, void* stream, const blim_pc_admit* admits = nullptr, int32_t n_admit = 0) {
     if (pc) TRY(pc_check_read(e, pc, slots_used, n_used));
     const int64_t n_rows = (int64_t)n_pairs * e->c.num_clips;
+    const int32_t* cap = nullptr; const int32_t* row_slot = nullptr;
+    if (n_admit) TRY(pc_admit_begin(e, pc, b, admits, n_admit, slots_used, n_used, n_rows, (hipStream_t)stream, &cap, &row_slot));
     TRY(reserve_rows(e, n_rows));
     TRY(ensure(e->vh, (size_t)round_up(n_rows, 256) * e->c.mm_hidden_size * 2 * (e->precise ? 2 : 1)));
     {
         PcLease lease{e};
         if (pc) { e->pc_read = pc; e->pc_slot = pfx_slot; }
+        if (n_admit) { e->pc_fill = pc; e->pc_cap_row = cap; }
         TRY(decode_impl(e, b, embeds, rows, n_rows, e->hsel.p, e->precise, nullptr, stream));
     }
+    if (n_admit) TRY(pc_admit_finish(e, pc, admits, n_admit, row_slot, n_rows, e->c.hidden_size, (hipStream_t)stream));
     if (pc) TRY(pc_gather_rows(e, pc, rows, n_rows, e->c.hidden_size, (hipStream_t)stream));
     TRY(visual_head_impl(e, e->hsel.p, e->precise, n_rows, e->vh.p, stream));
     return tvg_scores_impl(e, e->vh.p, e->precise, vocab_bf16, n_vocab, labels, n_pairs, score, stream);
@@ -1469,6 +1535,13 @@ extern "C" int blim_score_tvg_cached(blim_engine* e, blim_prefix_cache* pc, cons
                                      float* score, void* stream) {
     ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && rows && labels && score && n_pairs > 0);
     return score_tvg_impl(e, pc, pfx_slot, slots_used, n_used, b, embeds, rows, vocab_bf16, n_vocab, labels, n_pairs, score, stream);
+}
+extern "C" int blim_score_tvg_admit(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                                    const blim_pc_admit* admits, int32_t n_admit, const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab,
+                                    const int32_t* labels, int32_t n_pairs, float* score, void* stream) {
+    ARG_CHECK(e && pc && pc->e == e && pfx_slot && (slots_used || n_used == 0) && n_used >= 0 && (admits || n_admit == 0) && n_admit >= 0 && rows && labels && score &&
+              n_pairs > 0);
+    return score_tvg_impl(e, pc, pfx_slot, slots_used, n_used, b, embeds, rows, vocab_bf16, n_vocab, labels, n_pairs, score, stream, admits, n_admit);
 }
 
 // ---------------------------------------------------------------------------- literal forward

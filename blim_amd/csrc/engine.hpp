@@ -62,6 +62,7 @@ struct blim_prefix_cache {
     bf16_t* kv = nullptr;              // [n_slots][num_layers][max_len][kv_w]
     bf16_t* hid = nullptr;             // [n_slots][hid_w]
     DevBuf map;                        // fill: per-token destination rows, per-sequence last rows and slots (uploaded per call)
+                                       // admit call: per-token destination rows | per-scored-row slots (built on the device: launch_admit_map)
     std::vector<int> len;              // filled length per slot (-1: never filled)
     std::vector<PcSnap> snap;
 };

@@ -208,6 +208,43 @@ int launch_kv_capture(const bf16_t* qkv, int64_t ldq, int64_t col, int64_t src_l
     return BLIM_OK;
 }
 
+// The maps of a scoring call that also captures (engine.hip: pc_admit_begin), built on the device so that the host never waits for it.  The call's admissions
+// {seq, slot, start, len, row} travel as KERNEL ARGUMENTS, ADMIT_CHUNK at a time: there is no host buffer whose lifetime a copy could depend on, and no copy.
+// map[t] = slot * max_len + (t - start) for the tokens of an admitted sequence (what kv_capture_kernel reads), map[n_tokens + r] = slot for the scored row r == row
+// (what the hidden-row copy reads), -1 everywhere else.  The first chunk's launch writes every element once, whatever the admissions say; a later chunk's launch
+// (stream-ordered behind it) writes only the elements its own admissions name.
+struct AdmitChunk { int32_t q[ADMIT_CHUNK][5]; };
+__global__ void admit_map_kernel(AdmitChunk adm, int n_admit, int first, int32_t* map, int64_t n_tokens, int64_t n_rows, int max_len) {
+    const int64_t total = n_tokens + n_rows;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        int v = -1;
+        for (int a = 0; a < n_admit; ++a) {
+            if (i < n_tokens) {
+                const int64_t k = i - adm.q[a][2];
+                if (k >= 0 && k < adm.q[a][3]) v = adm.q[a][1] * max_len + (int)k;
+            } else if (i - n_tokens == adm.q[a][4]) {
+                v = adm.q[a][1];
+            }
+        }
+        if (first || v >= 0) map[i] = v;
+    }
+}
+int launch_admit_map(const int32_t* adm_host, int n_admit, int32_t* map, int64_t n_tokens, int64_t n_rows, int max_len, hipStream_t s) {
+    ARG_CHECK(adm_host && map && n_admit > 0 && n_tokens > 0 && n_rows > 0 && max_len > 0);
+    for (int a0 = 0; a0 < n_admit; a0 += ADMIT_CHUNK) {
+        AdmitChunk c;
+        const int n = n_admit - a0 < ADMIT_CHUNK ? n_admit - a0 : ADMIT_CHUNK;
+        for (int a = 0; a < n; ++a)
+            for (int k = 0; k < 5; ++k) c.q[a][k] = adm_host[5 * (size_t)(a0 + a) + k];
+        for (int a = n; a < ADMIT_CHUNK; ++a)
+            for (int k = 0; k < 5; ++k) c.q[a][k] = 0;
+        hipLaunchKernelGGL(admit_map_kernel, dim3(grid_for(n_tokens + n_rows, 256)), dim3(256), 0, s, c, n, a0 == 0 ? 1 : 0, map, n_tokens, n_rows, max_len);
+        LAUNCH_CHECK("admit_map");
+    }
+    return BLIM_OK;
+}
+
 __global__ void rows_by_index_kernel(uint4* dst, int64_t ld_dst8, const uint4* src, int64_t ld_src8, const int32_t* idx, int64_t n_rows, int w8, int64_t n_bound,
                                      int gather, uint32_t fill) {
     const int64_t total = n_rows * w8;

@@ -19,6 +19,11 @@ int launch_gather_rows(void* dst, const void* src, const int32_t* rows, int64_t 
 // src_lo_off > 0 also the lo parts at qkv[t, col + src_lo_off ..] to dst_lo_off further.  16-byte chunks; width, col, ld, offsets multiples of 8 values.
 int launch_kv_capture(const bf16_t* qkv, int64_t ldq, int64_t col, int64_t src_lo_off, int width, const int32_t* dst_row, int64_t n_tokens, bf16_t* cache,
                       int64_t slot_stride, int64_t ld, int64_t dst_lo_off, int max_len, int n_slots, hipStream_t s);
+// The capture maps of a scoring call with admissions (blim.h: blim_pc_admit), built on the device from adm_host [n_admit][5] = {seq, slot, start, len, row} (HOST:
+// the values travel as kernel arguments, ADMIT_CHUNK admissions per launch, so nothing is copied and nothing outlives the call):
+// map[t] = slot * max_len + (t - start) for start <= t < start + len, map[n_tokens + r] = slot for r == row, -1 elsewhere; map (DEVICE) holds n_tokens + n_rows entries.
+#define ADMIT_CHUNK 48
+int launch_admit_map(const int32_t* adm_host, int n_admit, int32_t* map, int64_t n_tokens, int64_t n_rows, int max_len, hipStream_t s);
 // 16-bit row copies by index, `width` values per row (a multiple of 8).  gather = 0: dst[idx[r]] = src[r] for 0 <= idx[r] < n_bound (the cached hidden rows of a fill);
 // gather = 1: for idx[r] < 0, dst[r] = src[-(idx[r] + 1)] when that is < n_bound, else `fill` words (a poisoned score); rows with idx[r] >= 0 are left alone
 int launch_rows_by_index(uint16_t* dst, int64_t ld_dst, const uint16_t* src, int64_t ld_src, const int32_t* idx, int64_t n_rows, int width, int64_t n_bound, int gather,

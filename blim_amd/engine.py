@@ -123,6 +123,8 @@ def load_library(path: str = LIB_PATH):
         "blim_prefix_cache_slot_len": ([vp, i32], C.c_int),
         "blim_score_vtg_cached": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, vp, vp, i64, vp, i32, vp, vp], C.c_int),
         "blim_score_tvg_cached": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp], C.c_int),
+        "blim_score_vtg_admit": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, i32, vp, vp], C.c_int),
+        "blim_score_tvg_admit": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -476,9 +478,10 @@ class Engine:
                                         _ptr(out), _stream()), "blim_tvg_scores")
         return out
 
-    def _score(self, name: str, batch: PackedBatch, embeds, rows, tail, n_pairs: int, cache=None, pfx_slot=None, slots_used=()):
-        """blim_score_<vtg | tvg>, or its _cached form when a PrefixCache is given: the output buffer and the arguments the forms share.  tail: the entry's own
-        arguments between `rows` and `n_pairs`."""
+    def _score(self, name: str, batch: PackedBatch, embeds, rows, tail, n_pairs: int, cache=None, pfx_slot=None, slots_used=(), admits=None):
+        """blim_score_<vtg | tvg>, or its _cached form when a PrefixCache is given, or its _admit form when that call also captures prefixes (admits: host ints
+        [n_admit, 5] = (seq, slot, start, len, row), blim.h: blim_pc_admit): the output buffer and the arguments the forms share.  tail: the entry's own arguments
+        between `rows` and `n_pairs`."""
         import torch
         out = torch.empty(n_pairs, dtype=torch.float32, device=self.device)
         bs = batch.struct(self.max_positions)
@@ -486,6 +489,9 @@ class Engine:
         if cache is not None:
             su = np.ascontiguousarray(slots_used, dtype=np.int32)
             name, head = name + "_cached", (self.h, cache.h, C.byref(bs), _ptr(pfx_slot), su.ctypes.data if len(su) else None, len(su))
+            if admits is not None and len(admits):
+                ad = np.ascontiguousarray(admits, dtype=np.int32).reshape(-1, 5)
+                name, head = name[:-len("_cached")] + "_admit", head + (ad.ctypes.data, len(ad))
         _check(getattr(self.lib, name)(*head, _ptr(embeds), _ptr(rows), *tail, n_pairs, _ptr(out), _stream()), name)
         return out
 
@@ -565,13 +571,15 @@ class PrefixCache:
     def slot_len(self, slot: int) -> int:
         return int(self.lib.blim_prefix_cache_slot_len(self.h, int(slot)))
 
-    def score_vtg(self, batch: PackedBatch, pfx_slot, slots_used, embeds, rows, labels, row_start):
-        """blim_score_vtg_cached: pfx_slot device int32 [n_seqs] (-1: in-batch prefix); slots_used host ints (every slot read); rows[r] < 0: slot -(rows[r] + 1)'s hidden row."""
-        return self.engine.score_vtg(batch, embeds, rows, labels, row_start, cache=self, pfx_slot=pfx_slot, slots_used=slots_used)
+    def score_vtg(self, batch: PackedBatch, pfx_slot, slots_used, embeds, rows, labels, row_start, admits=None):
+        """blim_score_vtg_cached: pfx_slot device int32 [n_seqs] (-1: in-batch prefix); slots_used host ints (every slot read); rows[r] < 0: slot -(rows[r] + 1)'s hidden row.
+        admits (host ints [n_admit, 5] = (seq, slot, start, len, row); non-empty: blim_score_vtg_admit): in-batch prefix sequences the call also captures into slots."""
+        return self.engine.score_vtg(batch, embeds, rows, labels, row_start, cache=self, pfx_slot=pfx_slot, slots_used=slots_used, admits=admits)
 
-    def score_tvg(self, batch: PackedBatch, pfx_slot, slots_used, embeds, rows, vocab_clip_major, labels):
-        """blim_score_tvg_cached: Engine.score_tvg with the slot conventions of score_vtg above (a slot holds a caption prompt; its hidden row predicts clip 0)."""
-        return self.engine.score_tvg(batch, embeds, rows, vocab_clip_major, labels, cache=self, pfx_slot=pfx_slot, slots_used=slots_used)
+    def score_tvg(self, batch: PackedBatch, pfx_slot, slots_used, embeds, rows, vocab_clip_major, labels, admits=None):
+        """blim_score_tvg_cached (non-empty admits: blim_score_tvg_admit): Engine.score_tvg with the slot conventions of score_vtg above (a slot holds a caption prompt;
+        its hidden row predicts clip 0)."""
+        return self.engine.score_tvg(batch, embeds, rows, vocab_clip_major, labels, cache=self, pfx_slot=pfx_slot, slots_used=slots_used, admits=admits)
 
 
 def ce_rows(logits, labels):

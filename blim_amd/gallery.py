@@ -14,10 +14,15 @@ Neither index plans or runs a call of its own.  The planners are PairScorer's (`
 prefix has a slot packs no prefix sequence, every other group is planned as it always is.  The calls, and the fills, run under `PairScorer._call_options`, so a slot
 is read under the options it was filled under.  `_PrefixIndex` holds what the two directions share: slots under a budget, the fill, the refill after a weight or
 mode change.
+
+`fill="lazy"` fills nothing up front: the budget is a capacity, and a prefix that a scoring call had to pack anyway (a miss) is captured into a
+slot by that very call (`blim_score_*_admit`), so the calls after it read it.  Which slot is decided per pass -- one vtg_pairs / tvg_pairs call -- by a
+deterministic policy (`_PrefixIndex._begin_pass`): free slots first, then the least recently used slot whose key this pass does not need, else no admission.
 """
 from __future__ import annotations
 
 import sys
+from dataclasses import asdict, dataclass, field
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -45,6 +50,36 @@ def cache_bytes(dims, n_slots: int, max_len: int, compensated: bool) -> int:
     return int(n_slots) * (dims.num_layers * int(max_len) * 2 * dims.num_kv_heads * dims.head_dim * f + dims.hidden_size * f) * 2
 
 
+@dataclass
+class GalleryStats:
+    """What an index's passes did, counted per prefix group (key) per pass and committed as the pass's calls return: keys found in a slot, keys packed in the batch,
+    of those the ones captured into a slot, the keys that lost their slot to them, and the tokens of every in-batch prefix sequence."""
+    hits: int = 0
+    misses: int = 0
+    admitted: int = 0
+    evicted: int = 0
+    prefix_tokens_packed: int = 0
+
+    def reset(self) -> None:
+        self.hits = self.misses = self.admitted = self.evicted = self.prefix_tokens_packed = 0
+
+    def as_dict(self) -> Dict[str, int]:
+        return asdict(self)
+
+
+@dataclass
+class _Pass:
+    """One vtg_pairs / tvg_pairs call as the index sees it: the keys it needs in the order the planner meets them, and -- lazy fill -- the slot reserved for each
+    miss that is admitted ({key: (slot, the key that loses it or None)}).  Nothing of it is part of the index's state until a call of the pass has returned."""
+    no: int
+    need: List
+    hits: List
+    misses: List
+    reserved: Dict = field(default_factory=dict)
+    offered: set = field(default_factory=set)
+    counted: bool = False
+
+
 def _follow_vtg(s: PairScorer) -> None:
     """As evaluation() does for a caller's scorer: the VTG calls follow what the model has resolved NOW (an unresolved `auto` leaves the scorer's mode)."""
     if hasattr(s.m, "vtg_mode") and s.m.vtg_mode() != "auto":
@@ -60,11 +95,21 @@ def _vtg_state(s: PairScorer):
 class _PrefixIndex:
     """What the two indexes share: one cache slot per prefix key under a memory budget, filled in packed calls and refilled when the weights or the numeric mode
     change.  A subclass names its call kind, its keys (self.keys, in gallery order), a key's prefix (prefix_len, _prefix), compensated(), _mode_state(),
-    _follow_model(), resolve_mode() and iter_plans(); the planners read slot_of and cache."""
+    _follow_model(), resolve_mode(), a pass's keys (_needs) and its plans (_plans); the planners read slot_of and cache (and, on a lazy index, call admit)."""
     kind = ""              # "vtg" | "tvg": the calls whose prefixes the slots hold
     _changed = ""          # the refill's log line opens with it
 
-    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int], priority: Optional[Sequence[int]], log):
+    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int], priority: Optional[Sequence[int]], log, fill: str = "eager"):
+        if fill not in ("eager", "lazy"):
+            raise ValueError(f"fill {fill!r}: 'eager' or 'lazy'")
+        if fill == "lazy" and priority is not None:
+            raise ValueError(f"{type(self).__name__}: priority orders the eager fill; a lazy index follows the queries")
+        self.fill = fill
+        self.n_slots = 0                 # lazy: the capacity (eager: len(slot_of))
+        self.stats = GalleryStats()
+        self._stamp: Dict = {}           # lazy: resident key -> (pass number, position among the pass's keys) of its last use
+        self._pass: Optional[_Pass] = None
+        self._n_pass = 0
         self.s = scorer
         self.m, self.engine = scorer.m, scorer.engine
         if getattr(self.engine, "dtype", "") == "f8":
@@ -114,11 +159,19 @@ class _PrefixIndex:
         t0 = time.perf_counter()
         comp = self.compensated()
         L = self.slot_positions()
-        self.slot_of = slot_plan(self.keys, self.engine.prefix_cache_bytes(1, L, comp), self.budget_bytes, self.priority)
+        per = self.engine.prefix_cache_bytes(1, L, comp)
         self.close()
-        if self.slot_of:
-            self.cache = self.engine.prefix_cache(len(self.slot_of), L, comp)
-            self._fill(sorted(self.slot_of.items(), key=lambda kv: kv[1]))
+        self._drop()
+        if self.fill == "lazy":                      # the budget is a capacity: nothing is filled, the scoring calls admit what they had to pack anyway
+            self.n_slots = len(self.keys) if self.budget_bytes is None else min(len(self.keys), int(self.budget_bytes) // max(int(per), 1))
+            if self.n_slots:
+                self.cache = self.engine.prefix_cache(self.n_slots, L, comp)
+        else:
+            self.slot_of = slot_plan(self.keys, per, self.budget_bytes, self.priority)
+            self.n_slots = len(self.slot_of)
+            if self.slot_of:
+                self.cache = self.engine.prefix_cache(len(self.slot_of), L, comp)
+                self._fill(sorted(self.slot_of.items(), key=lambda kv: kv[1]))
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         self.build_seconds = time.perf_counter() - t0
@@ -149,12 +202,97 @@ class _PrefixIndex:
         if self._state is None:
             self.build()
         elif self._follow_model() or self._mode_state() != self._state:
+            if self.fill == "lazy":                  # the slots are dropped and admitted again on demand; the cache itself stays unless its layout changes
+                self.log(f"{self._changed} changed since the slots were admitted ({self._state} -> {self._mode_state()}): dropping {len(self.slot_of)} slots")
+                if self.cache is None or self.n_slots == 0 or bool(self.cache.compensated) != bool(self.compensated()):
+                    self.build()
+                else:
+                    self._drop()
+                    self._state = self._mode_state()
+                return
             self.log(f"{self._changed} changed since the fill ({self._state} -> {self._mode_state()}): refilling {len(self.slot_of)} slots")
             self.build()
 
+    def _drop(self):
+        """Forgets every slot (and every reservation): the index holds nothing."""
+        self.slot_of, self._stamp, self._pass = {}, {}, None
+
+    # ---- passes (lazy fill: the replacement policy)
+    @property
+    def admit(self):
+        """The planners' hook (PairScorer._pack_vtg / _plan_tvg): present on a lazy index only."""
+        return self._admit if self.fill == "lazy" else None
+
+    def _begin_pass(self, need: List) -> _Pass:
+        """A pass opens: `need` = its keys in the order the planner meets them.  Reservations of plans that were never run are dropped with the pass they belonged
+        to.  Lazy fill, the policy: resident keys the pass needs are pinned; a miss takes a free slot, else the least recently used slot whose key the pass does not
+        need, else it is not admitted -- so no slot is read and overwritten within a pass, and a scan over more keys than slots keeps its resident set.  Nothing the
+        index holds changes here: run() commits."""
+        self._n_pass += 1
+        p = _Pass(self._n_pass, need, [k for k in need if k in self.slot_of], [k for k in need if k not in self.slot_of])
+        if self.fill == "lazy" and self.n_slots:
+            needed = set(need)
+            taken = set(self.slot_of.values())
+            free = [sl for sl in range(self.n_slots) if sl not in taken]
+            victims = sorted((k for k in self.slot_of if k not in needed), key=lambda k: self._stamp.get(k, (0, 0)))
+            for k in p.misses:
+                if free:
+                    p.reserved[k] = (free.pop(0), None)
+                elif victims:
+                    v = victims.pop(0)
+                    p.reserved[k] = (self.slot_of[v], v)
+        self._pass = p
+        return p
+
+    def _admit(self, key):
+        """-> the slot reserved for `key` in the pass being planned (once per pass), or None: the prefix stays in the batch."""
+        p = self._pass
+        if p is None or key not in p.reserved or key in p.offered:
+            return None
+        p.offered.add(key)
+        return p.reserved[key][0]
+
+    def iter_plans(self, pairs):
+        """pairs [P, 2] (video j, text i) -> the engine calls of one pass, planned by PairScorer's planner over this index's slots (the subclass's _plans)."""
+        pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        p = self._begin_pass(self._needs(pairs))
+        for plan in self._plans(pairs):
+            plan.pass_ = p
+            yield plan
+
+    def _commit(self, plan) -> None:
+        """An engine call of the pass returned without error: what it did becomes the index's state -- the pass's hits and misses (once), the slots the call admitted,
+        the keys that lost them, the recency of the keys used."""
+        p = getattr(plan, "pass_", None)
+        if p is None:
+            return
+        st = self.stats
+        if not p.counted:
+            p.counted = True
+            st.hits += len(p.hits); st.misses += len(p.misses)
+            at = {k: n for n, k in enumerate(p.need)}
+            for k in p.hits:
+                if k in self.slot_of:
+                    self._stamp[k] = (p.no, at[k])
+        st.prefix_tokens_packed += int(plan.prefix_tokens)
+        if plan.admits is not None and len(plan.admits):
+            at = {k: n for n, k in enumerate(p.need)}
+            by_slot = {sl: (k, v) for k, (sl, v) in p.reserved.items()}
+            for sl in np.asarray(plan.admits)[:, 1]:
+                k, v = by_slot[int(sl)]
+                if v is not None and self.slot_of.get(v) == int(sl):
+                    del self.slot_of[v]; self._stamp.pop(v, None)
+                    st.evicted += 1
+                self.slot_of[k] = int(sl); self._stamp[k] = (p.no, at[k])
+                st.admitted += 1
+
     # ---- scoring
     def run(self, plan):
-        return self.s.run(plan, self.cache_or_none())
+        if self.fill == "lazy" and getattr(plan, "pass_", None) is not self._pass:
+            raise RuntimeError(f"{type(self).__name__}: this plan belongs to an earlier pass (its slots may have been admitted to other prefixes since): plan again")
+        out = self.s.run(plan, self.cache_or_none())
+        self._commit(plan)
+        return out
 
     def cache_or_none(self):
         if self.cache is None:                       # a budget of zero slots: a one-slot cache that no sequence names keeps the same call path
@@ -178,14 +316,16 @@ class GalleryIndex(_PrefixIndex):
     builder); its prompt splits (vtg_split) and projected video features are reused.  budget_bytes: device memory for the cache (None: every prefix)."""
     kind, _changed = "vtg", "gallery: weights or numeric mode"
 
-    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, priority: Optional[Sequence[int]] = None, log=None):
-        super().__init__(scorer, budget_bytes, priority, log)
+    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, priority: Optional[Sequence[int]] = None, log=None, fill: str = "eager"):
+        super().__init__(scorer, budget_bytes, priority, log, fill)
         # the prompt splits of the texts: (pre, post) pairs, in order of first appearance
         splits: Dict[Tuple[bytes, bytes], Tuple[np.ndarray, np.ndarray]] = {}
         for pre, post, _ in scorer.vtg_split:
             splits.setdefault((pre.tobytes(), post.tobytes()), (pre, post))
         self.splits = splits
         self.keys: List[Tuple[int, bytes, bytes]] = [(j, k[0], k[1]) for j in range(len(scorer.video)) for k in splits]
+        at = {k: n for n, k in enumerate(splits)}
+        self._split_id = np.array([at[(pre.tobytes(), post.tobytes())] for pre, post, _ in scorer.vtg_split], dtype=np.int64)
 
     def prefix_len(self, key) -> int:
         j, pre, post = key
@@ -236,7 +376,16 @@ class GalleryIndex(_PrefixIndex):
         return self.s.vtg_mode
 
     # ---- planning
-    def iter_plans(self, pairs: np.ndarray):
+    def _needs(self, pairs: np.ndarray) -> List:
+        """The (video, pre, post) keys of a pass, in the order _vtg_items forms their groups: by video, then by text."""
+        if not len(pairs):
+            return []
+        order = np.lexsort((pairs[:, 1], pairs[:, 0]))
+        code = (pairs[:, 0] * len(self.splits) + self._split_id[pairs[:, 1]])[order]
+        _, first = np.unique(code, return_index=True)
+        return [self.keys[int(c)] for c in code[np.sort(first)]]
+
+    def _plans(self, pairs: np.ndarray):
         """pairs [P, 2] (video j, text i) -> engine calls, planned by PairScorer._pack_vtg over this index's slots; each plan carries pfx_slot (device) and the
         slots it reads."""
         s = self.s
@@ -315,8 +464,8 @@ class TextGalleryIndex(_PrefixIndex):
     The caption cache is filled on the first TVG use or by build(): a zero-shot blend has no TVG term and never fills it."""
     kind, _changed = "tvg", "text gallery: weights or TVG mode"
 
-    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, video_index: Optional[GalleryIndex] = None, log=None):
-        super().__init__(scorer, budget_bytes, None, log)
+    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, video_index: Optional[GalleryIndex] = None, log=None, fill: str = "eager"):
+        super().__init__(scorer, budget_bytes, None, log, fill)
         if video_index is not None and video_index.s is not scorer:
             raise ValueError("TextGalleryIndex: video_index must be built on the same scorer")
         self.video_index = video_index
@@ -364,7 +513,11 @@ class TextGalleryIndex(_PrefixIndex):
         return self.s.tvg_mode
 
     # ---- planning
-    def iter_plans(self, pairs: np.ndarray):
+    def _needs(self, pairs: np.ndarray) -> List:
+        """The caption prompts of a pass, in the order _plan_tvg meets its texts."""
+        return list(dict.fromkeys(self.s.tvg_split[int(i)].tobytes() for i in np.unique(pairs[:, 1])))
+
+    def _plans(self, pairs: np.ndarray):
         """pairs [P, 2] (video j, text i) -> engine calls, planned by PairScorer._plan_tvg's likelihood branch over this index's slots: the candidates of one text are
         merged sequences of up to SEG_MAX // (C - 1) videos' clip tokens (own_start).  A cached text packs no prompt: its sequences name the slot and each pair's first
         row is -(slot + 1)."""

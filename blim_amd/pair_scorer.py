@@ -43,6 +43,8 @@ class Plan:
     n_rows: int
     pfx_slot: Optional[object] = None            # planned over a prefix source (blim_amd/gallery.py): device int32 per sequence, the cache slot of its prefix (-1: in the batch)
     slots_used: Optional[np.ndarray] = None      # ... host int32: every slot the call reads
+    admits: Optional[np.ndarray] = None          # ... host int32 [n, 5] = (seq, slot, start, len, row): in-batch prefixes the call also captures into slots (a source with `admit`)
+    prefix_tokens: int = 0                       # ... of n_tokens, those of in-batch prefix sequences
 
 
 def _split_prompt_response(ids: np.ndarray, labels: np.ndarray):
@@ -320,7 +322,9 @@ class PairScorer(CalibrationMixin):
 
     def _pack_vtg(self, items, slots=None):
         """Packs groups into super-batches.  slots: a prefix source (blim_amd/gallery.py: `slot_of` {(video, pre, post): slot} and `cache.slot_len`) -- a group whose
-        prefix it holds packs no prefix sequence: its sequences name the slot and each pair's first row is -(slot + 1)."""
+        prefix it holds packs no prefix sequence: its sequences name the slot and each pair's first row is -(slot + 1).  A source with an `admit(key)` hook (a lazy
+        index) is offered every prefix that had to be packed: when it returns a slot, the plan records the admission of that prefix sequence (Plan.admits; its row is
+        the position of the prefix's last token in `rows`).  The group itself keeps the in-batch prefix: a slot is readable from the next call on."""
         st = _PackState(self, "vtg", slots)
         for (j, nv, texts_g, outs_g) in items:
             pre, post, _ = self.vtg_split[texts_g[0]]
@@ -354,6 +358,8 @@ class PairScorer(CalibrationMixin):
                     ptoks = np.concatenate([pre, -(1 + fo + np.arange(n_vid)), post]); ppos = np.arange(len(ptoks))
                 p0 = st.add_seq(ptoks, ppos, np.ones(len(ptoks), np.uint8), None)
                 plen = len(ptoks); last = p0 + plen - 1
+                if j is not None:
+                    st.offer((j, pre.tobytes(), post.tobytes()), p0, plen)
             for i, outs in zip(texts_g, outs_g):
                 resp = self.vtg_split[i][2]
                 if self.max_row_len is not None and ppos_end + len(resp) > self.max_row_len:
@@ -463,6 +469,7 @@ class PairScorer(CalibrationMixin):
                     else:
                         if p0 is None:                   # the prompt is packed once per engine call; every merged sequence of the text names it
                             p0 = st.add_seq(pr, np.arange(plen), np.ones(plen, np.uint8), None)
+                            st.offer(pr.tobytes(), p0, plen)   # (a source with `admit`: the packed prompt may be captured into a slot, as in _pack_vtg)
                         first, pfx = p0 + plen - 1, (p0, plen)
                     chunk = idxs[pos_in:pos_in + n]
                     s0 = None
@@ -526,11 +533,12 @@ class PairScorer(CalibrationMixin):
             via, slots = self.engine, ()
         else:
             via, slots = cache, (plan.pfx_slot, plan.slots_used)
+        more = {} if plan.admits is None else {"admits": plan.admits}        # (plans of a source that admits: the call also captures the prefixes they name)
         with self._call_options(plan.kind):
             embeds = self.engine.assemble(plan.src_index, plan.feats)
             if plan.kind == "vtg":
-                return via.score_vtg(plan.batch, *slots, embeds, plan.rows, plan.labels, plan.row_start)
-            return via.score_tvg(plan.batch, *slots, embeds, plan.rows, self.vocab_cm, plan.labels)
+                return via.score_vtg(plan.batch, *slots, embeds, plan.rows, plan.labels, plan.row_start, **more)
+            return via.score_tvg(plan.batch, *slots, embeds, plan.rows, self.vocab_cm, plan.labels, **more)
 
     def score(self, plans, n_requested: int, run=None) -> np.ndarray:
         """plans: list or generator of Plan.  Engine calls are asynchronous, so with a generator the host packs plan k+1 while
@@ -610,6 +618,9 @@ class _PackState:
         self.tok: List[np.ndarray] = []; self.pos: List[np.ndarray] = []; self.vis: List[np.ndarray] = []
         self.seq_start: List[int] = []; self.seq_len: List[int] = []; self.pfx_start: List[int] = []; self.pfx_len: List[int] = []
         self.slot: List[int] = []; self.used = set()
+        self.admit = getattr(slots, "admit", None)                        # the source's hook, if it admits prefixes inside scoring calls
+        self.admits: List[Tuple[int, int, int, int]] = []                 # (seq, slot, start, len) of the in-batch prefixes this call captures
+        self.n_prefix_tok = 0
         self.own: List[np.ndarray] = []; self.any_own = False             # per token: first own-segment index it attends to (segmented sequences)
         self.feats: List[object] = []; self.feat_key: Dict[int, int] = {}; self.n_feat = 0
         self.rows: List[int] = []; self.labels: List[np.ndarray] = []; self.row_start: List[int] = [0]
@@ -635,7 +646,15 @@ class _PackState:
         self.pfx_start.append(prefix[0] if prefix else 0); self.pfx_len.append(prefix[1] if prefix else 0)
         self.slot.append(int(slot))
         self.n_tok += len(toks)
+        if prefix is None:
+            self.n_prefix_tok += len(toks)
         return start
+
+    def offer(self, key, start: int, plen: int) -> None:
+        """The prefix sequence just packed (the last one added) is offered to a source that admits: a slot back records the admission."""
+        slot = None if self.admit is None else self.admit(key)
+        if slot is not None:
+            self.admits.append((len(self.seq_start) - 1, int(slot), int(start), int(plen)))
 
     def add_pair(self, rows, labels, outs):
         self.rows += rows
@@ -659,12 +678,20 @@ class _PackState:
     def finish(self) -> Plan:
         import torch
         dev = self.s.device
+        n_prefix_tok = self.n_prefix_tok
         if self.slots is not None and self.n_tok == 0:     # every pair reads a cached row only (one-token responses): one dummy token keeps the batch non-empty
             self.add_seq(np.zeros(1, np.int64), np.zeros(1, np.int64), np.ones(1, np.uint8), None)
         batch, src, feats = self.upload()
+        admits = None
+        if self.admits:                                    # the row of an admission: where its prefix's last token stands in `rows` (every pair of the prefix opens with it)
+            at: Dict[int, int] = {}
+            for r, t_ in enumerate(self.rows):
+                at.setdefault(int(t_), r)
+            admits = np.array([(q, sl, st_, ln, at[st_ + ln - 1]) for q, sl, st_, ln in self.admits], dtype=np.int32).reshape(-1, 5)
         t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
         cached = self.slots is not None
         return Plan(kind=self.kind, batch=batch, src_index=src, feats=feats, rows=t(np.array(self.rows)), labels=t(np.concatenate(self.labels)),
                     row_start=t(np.array(self.row_start)) if self.kind == "vtg" else None, n_pairs=self.n_pairs,
                     out_index=self.out_index, n_tokens=self.n_tok, n_rows=len(self.rows),
-                    pfx_slot=t(self.slot) if cached else None, slots_used=np.array(sorted(self.used), dtype=np.int32) if cached else None)
+                    pfx_slot=t(self.slot) if cached else None, slots_used=np.array(sorted(self.used), dtype=np.int32) if cached else None,
+                    admits=admits, prefix_tokens=n_prefix_tok if cached else 0)

@@ -4,7 +4,8 @@ The gallery is the dataset's test videos; their VTG prefixes are computed once (
 are test captions (`--query_ids`) and / or free text (`--query TEXT`, tokenised by the dataset's own prompt builder: needs the real tokenizer).  `--candidates iv2`
 takes each dataset query's top-k of the first-stage t2v row, `--candidates all` scores the whole gallery.  One JSON line per query: the ranked video ids and their
 blended t2v scores (training_utils.combine_and_rank's t2v half: `--cpn --alpha --c`; zero-shot runs blend the query likelihood with the first stage only).
-`--synthetic N [--synthetic_7b]`: a dry run on synth.make_problem, as main.py's.
+`--synthetic N [--synthetic_7b]`: a dry run on synth.make_problem, as main.py's.  `--gallery_fill lazy` computes no prefix up front: the first query runs at once, its
+calls leave their videos' prefixes in the cache, and `--gallery_gb` is the cache's capacity.  The last stderr line reports the hits and misses.
 
 `--direction v2t` is the other half: the gallery is the dataset's test captions and the queries are test videos (`--video_ids`).  The candidate likelihood (VTG) is
 served from the same video cache; a fine-tuned checkpoint's query likelihood (TVG) reads the captions' prompts from a second cache (TextGalleryIndex,
@@ -44,6 +45,9 @@ def get_args_parser():
     p.add_argument("--candidates", default="iv2", choices=["iv2", "all"])
     p.add_argument("--gallery_gb", default=None, type=float, help="device memory for the prefix cache (default: every video)")
     p.add_argument("--text_gallery_gb", default=None, type=float, help="v2t: device memory for the caption-prompt cache (default: every distinct prompt)")
+    p.add_argument("--gallery_fill", default="eager", choices=["eager", "lazy"],
+                   help="eager: every prefix under the budget is computed before the first query; lazy: nothing is, --gallery_gb / --text_gallery_gb are capacities, a "
+                        "query's own calls capture the prefixes they had to pack and the least recently used slots make room")
     p.add_argument("--max_tokens", default=24576, type=int)
     p.add_argument("--shard", default=None, type=int, nargs=2, metavar=("W", "RANK"))
     p.add_argument("--synthetic", default=0, type=int)
@@ -157,11 +161,11 @@ def main(args):
     tvg = RU.padding_ids(tvg_ids, tvg_lab, tvg_msk, tok)
     scorer = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, vocab, vlab, args.num_clips, max_tokens=args.max_tokens)
     budget = None if args.gallery_gb is None else int(args.gallery_gb * 2**30)
-    gal = GalleryIndex(scorer, budget_bytes=budget)
+    gal = GalleryIndex(scorer, budget_bytes=budget, fill=args.gallery_fill)
     if args.direction == "v2t":
         return _main_v2t(args, model, scorer, gal, v2t_iv2, vids, len(tvg_ids), t0)
     gal.build(first_stage=None if t2v_iv2 is None else np.ascontiguousarray(np.asarray(t2v_iv2, dtype=np.float32).T))     # v2t first stage: calibration sample
-    print(f"gallery: {len(video)} videos, {len(gal.slot_of)} cached slots of {gal.cache.bytes // max(len(gal.slot_of), 1) if gal.cache else 0} bytes, "
+    print(f"gallery: {len(video)} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'} of {gal.cache.bytes // max(gal.n_slots, 1) if gal.cache else 0} bytes, "
           f"mode {scorer.vtg_mode or 'none'}, built in {gal.build_seconds:.2f}s (ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
     n_ds = len(vtg_ids) - len(args.query)
     texts = list(args.query_ids) + list(range(n_ds, len(vtg_ids)))
@@ -185,6 +189,7 @@ def main(args):
             out.write(line + "\n")
     if out:
         out.close()
+    print(f"gallery stats: {json.dumps(gal.stats.as_dict())}", file=sys.stderr, flush=True)
     gal.close()
     model.engine.close()
     return 0
@@ -200,11 +205,11 @@ def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) 
     gal.build(first_stage=first)
     finetuned = bool(args.resume)
     tbudget = None if args.text_gallery_gb is None else int(args.text_gallery_gb * 2**30)
-    tg = TextGalleryIndex(scorer, budget_bytes=tbudget, video_index=gal)
+    tg = TextGalleryIndex(scorer, budget_bytes=tbudget, video_index=gal, fill=args.gallery_fill)
     if finetuned:                                     # a zero-shot blend has no TVG term: no caption cache
         tg.build(first_stage=first)
-    print(f"gallery: {n_videos} videos, {len(gal.slot_of)} cached slots, mode {scorer.vtg_mode or 'none'}, built in {gal.build_seconds:.2f}s; "
-          f"{n_texts} texts, {len(tg.slot_of)} caption slots of {tg.per_slot_bytes()} bytes, tvg mode {scorer.tvg_mode}, built in {tg.build_seconds:.2f}s "
+    print(f"gallery: {n_videos} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'}, mode {scorer.vtg_mode or 'none'}, built in {gal.build_seconds:.2f}s; "
+          f"{n_texts} texts, {tg.n_slots} caption slots of {tg.per_slot_bytes()} bytes, tvg mode {scorer.tvg_mode}, built in {tg.build_seconds:.2f}s "
           f"(ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
     bad = [v for v in args.video_ids if not 0 <= v < n_videos]
     if bad:
@@ -226,6 +231,7 @@ def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) 
             out.write(line + "\n")
     if out:
         out.close()
+    print(f"gallery stats: {json.dumps(gal.stats.as_dict())}; text gallery stats: {json.dumps(tg.stats.as_dict())}", file=sys.stderr, flush=True)
     tg.close()
     gal.close()
     model.engine.close()

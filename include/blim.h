@@ -223,7 +223,23 @@ int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* embeds, cons
  *   device arrays.
  * blim_score_tvg_cached: blim_score_tvg with the same conventions (pfx_slot, slots_used, the checks and their messages).  rows[p * num_clips + c] < 0 names the
  *   cached last-row hidden state of slot -(rows + 1): the prompt's last row, which predicts clip 0; it is gathered into the visual head's input after the decode.
- *   Sequences may be segmented (own_start) over a cached prompt: several videos' clip tokens for one text, all naming the text's slot. */
+ *   Sequences may be segmented (own_start) over a cached prompt: several videos' clip tokens for one text, all naming the text's slot.
+ * blim_score_vtg_admit / blim_score_tvg_admit: blim_score_*_cached -- the same scores from the same arguments -- that also CAPTURE in-batch prefixes into slots on the
+ *   way through, so that a prefix a call had to compute anyway (a miss) is a cached one for the calls after it.  admits (HOST, n_admit entries; n_admit 0: the cached
+ *   call) names them: each a pure prefix sequence of `b` -- pfx_len 0, no own_start segments, every key visible -- with its destination slot, its place in the batch
+ *   (start = seq_start[seq], len = seq_len[seq], 1 <= len <= max_len) and row, the index r into rows[] with rows[r] == start + len - 1 (the prefix's last token, whose
+ *   final-norm hidden state predicts the first continuation token: the planners always score that row).  The fill's rule: every layer's K / V of the sequence's rows
+ *   are copied into the slot after the layer's QKV GEMM (the lo parts too, in compensated caches, for the layers whose QKV unit runs compensated), and the final-norm
+ *   hidden state of row rows[row] becomes the slot's hidden row (hi, and lo on a compensated call).  On success every admitted slot records `len` and the engine's
+ *   state, as blim_prefix_cache_fill's do; the admitted slots are marked empty before the work starts, so a failed call leaves them empty.  A later call on the same
+ *   stream may read the slot: stream order is the only synchronisation, and the call itself never waits for the device (the per-token capture map is built by a
+ *   kernel from the admissions, which travel as its arguments: nothing is copied from host memory).  Within the call an admitted prefix is NOT readable: its continuations keep pfx_slot -1.
+ *   Refused before anything is launched (BLIM_ERR_ARG, the message names the problem): a slot outside the cache, a slot admitted twice, a slot that is also in
+ *   slots_used (reading and overwriting one slot in one call is a race), len outside 1 .. max_len or start + len beyond the batch, row outside rows, seq outside the
+ *   batch; and the cached calls' refusals (a compensated call on a plain cache, "attn_tr" 0, an fp8 engine).
+ *   What the library checks is the host array: the device arrays (seq_start, seq_len, pfx_len, own_start, key_visible, rows) are not read back.  An admission whose
+ *   start / len / row are not its sequence's fills the slot with OTHER rows' values -- wrong scores from that slot later, never a write outside the cache. */
+typedef struct blim_pc_admit { int32_t seq, slot, start, len, row; } blim_pc_admit;   /* HOST */
 typedef struct blim_prefix_cache blim_prefix_cache;
 int64_t blim_prefix_cache_bytes(const blim_engine* e, int32_t n_slots, int32_t max_len, int32_t compensated);
 int blim_prefix_cache_create(blim_engine* e, int32_t n_slots, int32_t max_len, int32_t compensated, blim_prefix_cache** out);
@@ -236,6 +252,12 @@ int blim_score_vtg_cached(blim_engine* e, blim_prefix_cache* c, const blim_batch
 int blim_score_tvg_cached(blim_engine* e, blim_prefix_cache* c, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
                           const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab, const int32_t* labels, int32_t n_pairs,
                           float* score, void* stream);
+int blim_score_vtg_admit(blim_engine* e, blim_prefix_cache* c, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                         const blim_pc_admit* admits, int32_t n_admit, const void* embeds, const int32_t* rows, const int32_t* labels, int64_t n_rows,
+                         const int32_t* row_start, int32_t n_pairs, float* score, void* stream);
+int blim_score_tvg_admit(blim_engine* e, blim_prefix_cache* c, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
+                         const blim_pc_admit* admits, int32_t n_admit, const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab,
+                         const int32_t* labels, int32_t n_pairs, float* score, void* stream);
 
 /* ---- Literal model.forward(inputs_embeds=[B,L,H] bf16, attention_mask=[B,L] u8) -> logits f32 [B,L,V] (may be NULL),
  * hidden f32 [B,L,H] (may be NULL).  Replaces VideoChatFlashQwenForCausalLM.forward, modeling_videochat_flash.py:601-629. */

@@ -10,7 +10,15 @@ cached TVG + memoised prior against PairScorer.vtg + .tvg + .vtg(cpn=True)); sin
 and one uncached TVG pass.  Several videos share a text in the Q x top-k set, so its scores are checked within 1e-5 x max(1, |score|) on every repetition; the
 single-query sets (one video per text) are checked bit-equal.
 
-    python tools/gallery_bench.py --direction v2t --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r10_text_gallery.json"""
+    python tools/gallery_bench.py --direction v2t --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r10_text_gallery.json
+
+`--fill lazy` (t2v): the lazy gallery (GalleryIndex(fill="lazy")) on the same protocol -- alternating repetitions in one process, medians.
+(a) time to first result: eager = build() + the first query's top-k, lazy = allocation + the same query, all misses; (b) a pass of all misses with admission
+against PairScorer.vtg on the same pairs (the price of the capture), with the host time of the calls alone; (c) the all-hit pass, lazy against eager; (d) a stream of
+queries, one pass each, under a budget of a quarter of the gallery: hit rate and pairs/s, lazy against the static slot plan -- every query once, the same again,
+and `--stream_draws` draws with a Zipf popularity over the queries.  Scores are checked bit-equal to PairScorer.vtg throughout.
+
+    python tools/gallery_bench.py --fill lazy --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r11_lazy_gallery.json"""
 import argparse
 import json
 import os
@@ -48,6 +56,8 @@ def main():
     ap.add_argument("--max_tokens", type=int, default=24576)
     ap.add_argument("--direction", default="t2v", choices=["t2v", "v2t"])
     ap.add_argument("--tvg_modes", default="attn,full", help="v2t: the TVG calls' modes to measure")
+    ap.add_argument("--fill", default="eager", choices=["eager", "lazy"], help="lazy: the lazy gallery's measurements (t2v)")
+    ap.add_argument("--stream_draws", type=int, default=165, help="--fill lazy: queries of the Zipf stream")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -65,6 +75,8 @@ def main():
     q = np.linspace(0, a.n - 1, a.queries).round().astype(np.int64)
     if a.direction == "v2t":
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if a.fill == "lazy":
+        return main_lazy(a, dims, model, prob, vtg, tvg, video, q, tpc)
     cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
     pairs = np.stack([cand.reshape(-1), np.repeat(q, a.k)], axis=1)
     res = {"n": a.n, "queries": a.queries, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc, "modes": {}}
@@ -100,6 +112,94 @@ def main():
         res["modes"][mode] = r
         print(json.dumps({mode: r}), flush=True)
         gal.close()
+        del sc
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def main_lazy(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
+    pairs = np.stack([cand.reshape(-1), np.repeat(q, a.k)], axis=1)
+    P = len(pairs)
+    med = lambda t: float(np.median(t))
+    res = {"fill": "lazy", "n": a.n, "queries": a.queries, "k": a.k, "reps": a.reps, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc,
+           "pairs": P, "distinct_videos": int(len(np.unique(pairs[:, 0]))), "modes": {}}
+    for mode in a.modes.split(","):
+        model.vtg_precise = None if mode == "none" else mode
+        model.clear_cache()
+        sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, torch.from_numpy(prob.video_vocab),
+                           torch.from_numpy(prob.tvg_video_labels), dims.num_clips, max_tokens=a.max_tokens)
+        sc.set_vtg_mode(model.vtg_mode())
+        ref = sc.vtg(pairs)                                               # warm-up: every feature projected, workspaces sized
+        first = pairs[:a.k]
+        # (a) time to first result, a fresh index each time
+        ttfr = {"eager": [], "lazy": [], "eager_build_s": [], "lazy_build_s": []}
+        for _ in range(a.reps):
+            for fill in ("eager", "lazy"):
+                g = GalleryIndex(sc, fill=fill)
+                dt, got = timed(lambda: (g.build(), g.vtg_pairs(first))[1])
+                assert np.array_equal(got, ref[:a.k]), f"{fill}: first query differs from PairScorer.vtg"
+                ttfr[fill].append(dt); ttfr[fill + "_build_s"].append(g.build_seconds)
+                g.close()
+        # (b) a pass of all misses with admission against PairScorer.vtg; (c) the all-hit pass against an eager index
+        eager = GalleryIndex(sc).build()
+        lazy = GalleryIndex(sc, fill="lazy").build()
+        t_unc, t_miss, t_hit, t_eager, host_miss, host_unc = [], [], [], [], [], []
+        for _ in range(a.reps):
+            lazy._drop()
+            dt, want = timed(lambda: sc.vtg(pairs)); t_unc.append(dt)
+            dt, got = timed(lambda: lazy.vtg_pairs(pairs)); t_miss.append(dt)
+            assert np.array_equal(got, want), "a pass of misses differs from PairScorer.vtg"
+            dt, got = timed(lambda: eager.vtg_pairs(pairs)); t_eager.append(dt)
+            assert np.array_equal(got, want)
+            dt, got = timed(lambda: lazy.vtg_pairs(pairs)); t_hit.append(dt)
+            assert np.array_equal(got, want), "a pass of hits differs from PairScorer.vtg"
+            # the host's time in the engine calls alone (plans made beforehand, the device idle at the start): a call that waited for the device would show here
+            lazy._drop()
+            plans = list(lazy.iter_plans(pairs)); torch.cuda.synchronize()
+            t0 = time.perf_counter(); outs = [lazy.run(p) for p in plans]; host_miss.append(time.perf_counter() - t0); torch.cuda.synchronize()
+            plans = list(sc.iter_vtg(pairs)); torch.cuda.synchronize()
+            t0 = time.perf_counter(); outs = [sc.run(p) for p in plans]; host_unc.append(time.perf_counter() - t0); torch.cuda.synchronize()
+        tok = {"uncached": sum(p.n_tokens for p in sc.iter_vtg(pairs)), "hit": sum(p.n_tokens for p in lazy.iter_plans(pairs)),
+               "eager": sum(p.n_tokens for p in eager.iter_plans(pairs))}
+        lazy.close()
+        # (d) a query stream, one pass per query, under a quarter of the gallery
+        per = eager.per_slot_bytes()
+        eager.close()
+        budget = (a.n // 4) * per
+        rng = np.random.RandomState(0)
+        w = 1.0 / np.arange(1, a.queries + 1); w /= w.sum()
+        streams = {"each_query_once": np.arange(a.queries), "the_same_again": np.arange(a.queries), "zipf": rng.choice(a.queries, size=a.stream_draws, p=w)}
+        stream = {name: {"eager_s": [], "lazy_s": []} for name in streams}
+        for _ in range(a.reps):
+            idx = {"eager": GalleryIndex(sc, budget_bytes=budget).build(), "lazy": GalleryIndex(sc, budget_bytes=budget, fill="lazy").build()}
+            for name, order in streams.items():
+                for fill, g in idx.items():
+                    g.stats.reset()
+                    def run_stream():
+                        return [g.vtg_scores([q[i]], cand[i][None]) for i in order]
+                    dt, outs = timed(run_stream)
+                    for i, o in zip(order, outs):
+                        assert np.array_equal(o[0], ref[i * a.k:(i + 1) * a.k]), f"{fill} stream differs from PairScorer.vtg"
+                    st = g.stats.as_dict()
+                    stream[name][fill + "_s"].append(dt)
+                    stream[name][fill] = dict(st, hit_rate=st["hits"] / max(st["hits"] + st["misses"], 1))
+            for g in idx.values():
+                g.close()
+        for name, order in streams.items():
+            for fill in ("eager", "lazy"):
+                stream[name][fill + "_pairs_per_s"] = len(order) * a.k / med(stream[name][fill + "_s"])
+        r = {"time_to_first_result": dict(ttfr, eager_median_s=med(ttfr["eager"]), lazy_median_s=med(ttfr["lazy"])),
+             "miss_pass": {"uncached_s": t_unc, "lazy_all_misses_s": t_miss, "overhead": med(t_miss) / med(t_unc) - 1.0,
+                           "host_in_calls_lazy_s": host_miss, "host_in_calls_uncached_s": host_unc,
+                           "uncached_pairs_per_s": P / med(t_unc), "lazy_pairs_per_s": P / med(t_miss)},
+             "steady_state": {"eager_s": t_eager, "lazy_all_hits_s": t_hit, "eager_pairs_per_s": P / med(t_eager), "lazy_pairs_per_s": P / med(t_hit), "tokens": tok},
+             "stream": dict(stream, slots=a.n // 4, bytes_per_slot=per), "bit_equal": True}
+        res["modes"][mode] = r
+        print(json.dumps({mode: r}), flush=True)
         del sc
         torch.cuda.empty_cache()
     if a.out:
