@@ -102,7 +102,7 @@ __global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(
     const float c_log2 = p.scale * 1.4426950408889634f;
 
     // staging: 1024 16-B chunks per tile (512 K + 512 V; SPLIT: + 512 V_lo + 512 K_lo = 2048) spread over the workgroup's threads
-    // (MAXC * nthreads >= 1024 / 2048: launch_attention picks MAXC from the group size)
+    // (MAXC * nthreads >= 1024 / 2048: launch_attention picks MAXC from the workgroup's size)
     constexpr int NCHUNK = SPLIT ? 2048 : 1024;
     uint4 st[MAXC];
     uint8_t st_vis = 0;                      // this thread's key-visibility byte of the tile in flight (threads 0 .. 31)
@@ -354,6 +354,14 @@ __global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(
     }
 }
 
+// The kernel's staging invariant, checked beside every launch: MAXC chunks per thread x the workgroup's threads cover a tile's 1,024 chunks (SPLIT: 2,048).
+// A launch short of it leaves LDS rows unwritten -- the result is wrong and nothing faults (G = 5, 6 once ran that way).
+static bool stages_tile(int maxc, const dim3& block, bool split) {
+    if (maxc * (int)block.x >= (split ? 2048 : 1024)) return true;
+    blim_set_error("attention: %d threads x %d staging chunks do not cover a tile's %d", (int)block.x, maxc, split ? 2048 : 1024);
+    return false;
+}
+
 // The cached forms (p.pfx_cache != nullptr): the four forms of launch_attention below with the prefix read from the cache, launched with the same grids and
 // blocks (transposed V reads, 16-bit engines).  A separate function, so that the uncached dispatch stays as it was.
 static int launch_attention_pc(const AttnPcParams& p, int G, hipStream_t stream) {
@@ -361,6 +369,7 @@ static int launch_attention_pc(const AttnPcParams& p, int G, hipStream_t stream)
     static const int g_split = getenv("BLIM_ATTN_HEAD_GROUPS") ? atoi(getenv("BLIM_ATTN_HEAD_GROUPS")) : 2;
 #define ATTN_PC(MC, SP, OL, GRID, BLOCK)                                                                                           \
     do {                                                                                                                       \
+        if (!stages_tile(MC, BLOCK, SP)) return BLIM_ERR_ARG;                                                                  \
         if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, MC, DT_F16, SP, OL, true>), GRID, BLOCK, 0, stream, p);      \
         else hipLaunchKernelGGL((attn_kernel<true, MC, DT_BF16, SP, OL, true>), GRID, BLOCK, 0, stream, p);                   \
     } while (0)
@@ -368,12 +377,14 @@ static int launch_attention_pc(const AttnPcParams& p, int G, hipStream_t stream)
         if (p.out_lo_off) { if (G >= 7) ATTN_PC(5, true, true, grid, block); else ATTN_PC(4, true, true, grid, dim3(512)); }
         else { if (G >= 7) ATTN_PC(5, true, false, grid, block); else ATTN_PC(4, true, false, grid, dim3(512)); }
     } else if (p.out_lo_off != 0) {
-        if (G >= 5 && g_split > 1) ATTN_PC(4, false, true, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        if (G >= 7 && g_split > 1) ATTN_PC(4, false, true, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        else if (G >= 5 && g_split > 1) ATTN_PC(8, false, true, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));     // 192 threads: eight chunks each (launch_attention)
         else if (G >= 4) ATTN_PC(4, false, true, grid, block);
         else if (G >= 2) ATTN_PC(8, false, true, grid, block);
         else ATTN_PC(16, false, true, grid, block);
     } else {
-        if (G >= 5 && g_split > 1) ATTN_PC(4, false, false, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        if (G >= 7 && g_split > 1) ATTN_PC(4, false, false, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        else if (G >= 5 && g_split > 1) ATTN_PC(8, false, false, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));     // 192 threads: eight chunks each (launch_attention)
         else if (G >= 4) ATTN_PC(4, false, false, grid, block);
         else if (G >= 2) ATTN_PC(8, false, false, grid, block);
         else ATTN_PC(16, false, false, grid, block);
@@ -409,6 +420,7 @@ int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream) {
     if (p.v_lo_off != 0) {     // split products; the output as hi + lo (out_lo_off > 0) or hi only (0: the per-layer mask's QKV-compensated, o_proj-plain form)
 #define ATTN_SPLIT(MC, BLOCK)                                                                                                       \
         do {                                                                                                                      \
+            if (!stages_tile(MC, BLOCK, true)) return BLIM_ERR_ARG;                                                               \
             if (p.out_lo_off) {                                                                                                   \
                 if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, MC, DT_F16, true>), grid, BLOCK, 0, stream, p);       \
                 else hipLaunchKernelGGL((attn_kernel<true, MC, DT_BF16, true>), grid, BLOCK, 0, stream, p);                    \
@@ -429,10 +441,12 @@ int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream) {
     if (p.out_lo_off != 0) {   // plain products, output as hi + lo (the per-layer mask's QKV-plain, o_proj-compensated form): the plain kernels' grouping, transposed reads
 #define ATTN_LO(MC, GRID, BLOCK)                                                                                                   \
         do {                                                                                                                     \
+            if (!stages_tile(MC, BLOCK, false)) return BLIM_ERR_ARG;                                                             \
             if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, MC, DT_F16, false, true>), GRID, BLOCK, 0, stream, p);   \
             else hipLaunchKernelGGL((attn_kernel<true, MC, DT_BF16, false, true>), GRID, BLOCK, 0, stream, p);                \
         } while (0)
-        if (G >= 5 && g_split > 1) ATTN_LO(4, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        if (G >= 7 && g_split > 1) ATTN_LO(4, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        else if (G >= 5 && g_split > 1) ATTN_LO(8, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));      // 192 threads: eight chunks each (see below)
         else if (G >= 4) ATTN_LO(4, grid, block);
         else if (G >= 2) ATTN_LO(8, grid, block);
         else ATTN_LO(16, grid, block);
@@ -443,15 +457,24 @@ int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream) {
     }
 #define ATTN_LAUNCH(TR, MC)                                                                             \
     do {                                                                                            \
+        if (!stages_tile(MC, block, false)) return BLIM_ERR_ARG;                                    \
         if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<TR, MC, DT_F16>), grid, block, 0, stream, p); \
         else hipLaunchKernelGGL((attn_kernel<TR, MC, DT_BF16>), grid, block, 0, stream, p);                \
     } while (0)
     if (G >= 5 && g_split > 1 && use_tr_read && !p.out8) {
         // two workgroups of ceil(G / 2) waves per (block, KV head): 1,024 chunks / 256 threads = four per thread
+        // (G = 5, 6: three waves per workgroup = 192 threads, which stage 768 of the 1,024 chunks at four per thread -- rows 16 .. 31 of every V tile were never
+        // written and the result was wrong, tests/test_attention_gpu.py -- so those take eight per thread, the kernels G = 2, 3 run)
         const int hpg = (G + 1) / 2;
         const dim3 grid2(p.n_blocks, p.num_kv_heads * 2), block2(64 * hpg);
-        if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, 4, DT_F16>), grid2, block2, 0, stream, p);
-        else hipLaunchKernelGGL((attn_kernel<true, 4, DT_BF16>), grid2, block2, 0, stream, p);
+        if (!stages_tile(hpg >= 4 ? 4 : 8, block2, false)) return BLIM_ERR_ARG;
+        if (hpg >= 4) {
+            if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, 4, DT_F16>), grid2, block2, 0, stream, p);
+            else hipLaunchKernelGGL((attn_kernel<true, 4, DT_BF16>), grid2, block2, 0, stream, p);
+        } else {
+            if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, 8, DT_F16>), grid2, block2, 0, stream, p);
+            else hipLaunchKernelGGL((attn_kernel<true, 8, DT_BF16>), grid2, block2, 0, stream, p);
+        }
     } else if (G >= 4) { if (use_tr_read) ATTN_LAUNCH(true, 4); else ATTN_LAUNCH(false, 4); }
     else if (G >= 2) { if (use_tr_read) ATTN_LAUNCH(true, 8); else ATTN_LAUNCH(false, 8); }
     else { if (use_tr_read) ATTN_LAUNCH(true, 16); else ATTN_LAUNCH(false, 16); }

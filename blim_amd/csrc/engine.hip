@@ -3,6 +3,7 @@
 // caller's stream.
 #include <math.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -1606,6 +1607,49 @@ extern "C" int blim_gemm_f8(const void* A8, int64_t lda, const float* a_scale, c
                             void* C, int64_t ldc, void* stream) {
     GemmParams p = gp8(A8, lda, a_scale, W8, w_scale, M, N, K, C, ldc);
     return launch_gemm(EPI_BF16, p, (hipStream_t)stream);
+}
+// The decoder's attention as a building block (tests): fills AttnParams / AttnPcParams as decode_impl does and launches.  The argument errors are reported here
+// (the launchers repeat theirs), so that the host-only build of this file sees them too.
+extern "C" int blim_attention(const blim_attention_args* args, void* stream) {
+    ARG_CHECK(args && args->struct_bytes >= (int64_t)offsetof(blim_attention_args, lse_out));
+    blim_attention_args a;
+    memset(&a, 0, sizeof a);
+    memcpy(&a, args, (size_t)std::min<int64_t>(args->struct_bytes, (int64_t)sizeof a));
+    const blim_batch* b = a.batch;
+    ARG_CHECK(b && a.qkv && a.out);
+    ARG_CHECK(b->n_tokens > 0 && b->n_seqs > 0 && b->n_blocks > 0);
+    ARG_CHECK(b->key_visible && b->seq_start && b->seq_len && b->pfx_start && b->pfx_len && b->blk_seq && b->blk_q0);
+    ARG_CHECK(a.dtype16 == BLIM_COMPUTE_BF16 || a.dtype16 == BLIM_COMPUTE_F16);
+    ARG_CHECK(a.num_heads > 0 && a.num_kv_heads > 0 && a.num_heads % a.num_kv_heads == 0);
+    if (a.num_heads / a.num_kv_heads > 8) { blim_set_error("attention: %d query heads per kv head > 8 unsupported", a.num_heads / a.num_kv_heads); return BLIM_ERR_ARG; }
+    ARG_CHECK(a.ldq % 8 == 0 && a.ldo % 4 == 0 && a.v_lo_off >= 0 && a.out_lo_off >= 0 && a.v_lo_off % 8 == 0 && a.out_lo_off % 4 == 0);
+    const int64_t qn = (int64_t)(a.num_heads + 2 * a.num_kv_heads) * 128, hn = (int64_t)a.num_heads * 128, cn = (int64_t)2 * a.num_kv_heads * 128;
+    ARG_CHECK(a.ldq >= qn && a.ldo >= hn);
+    if (a.v_lo_off && (a.v_lo_off < qn || a.v_lo_off + qn > a.ldq)) { blim_set_error("attention: the lo parts at v_lo_off overlap [q | k | v] or leave the row (ldq)"); return BLIM_ERR_ARG; }
+    if (a.out_lo_off && (a.out_lo_off < hn || a.out_lo_off + hn > a.ldo)) { blim_set_error("attention: the lo output at out_lo_off overlaps the output or leaves the row (ldo)"); return BLIM_ERR_ARG; }
+    if ((a.v_lo_off || a.out_lo_off) && !a.use_tr_read) { blim_set_error("attention: the compensated forms read V transposed (use_tr_read = 1)"); return BLIM_ERR_ARG; }
+    if (a.out8) {
+        ARG_CHECK(a.out_mx && a.dtype16 == BLIM_COMPUTE_F16 && a.ldo8 >= (int64_t)a.num_heads * 128 && a.ldo8 % 4 == 0 && a.mx_stride >= ((b->n_tokens + 255) / 256) * 256);
+        if (a.v_lo_off || a.out_lo_off || a.lse_out) { blim_set_error("attention: the fused e4m3 output belongs to the plain form, without lse_out"); return BLIM_ERR_ARG; }
+    }
+    AttnPcParams p;
+    memset(&p, 0, sizeof p);
+    p.dtype = a.dtype16 == BLIM_COMPUTE_F16 ? DT_F16 : DT_BF16;
+    p.qkv = (const bf16_t*)a.qkv; p.ldq = a.ldq; p.num_heads = a.num_heads; p.num_kv_heads = a.num_kv_heads;
+    p.key_visible = b->key_visible; p.seq_start = b->seq_start; p.seq_len = b->seq_len; p.pfx_start = b->pfx_start; p.pfx_len = b->pfx_len;
+    p.blk_seq = b->blk_seq; p.blk_q0 = b->blk_q0; p.own_start = b->own_start; p.n_blocks = b->n_blocks; p.out = (bf16_t*)a.out; p.ldo = a.ldo; p.scale = a.scale;
+    p.v_lo_off = a.v_lo_off; p.out_lo_off = a.out_lo_off;
+    p.out8 = (uint8_t*)a.out8; p.ldo8 = a.ldo8; p.out_mx = (uint8_t*)a.out_mx; p.mx_stride = a.mx_stride; p.lse_out = a.lse_out;
+    if (!a.pfx_cache) return launch_attention(p, a.use_tr_read, (hipStream_t)stream);
+    if (a.out8 || a.lse_out) { blim_set_error("attention: the prefix-cache forms write a 16-bit output and no lse"); return BLIM_ERR_ARG; }
+    if (!a.use_tr_read) { blim_set_error("attention: the prefix-cache forms read V transposed (use_tr_read = 1)"); return BLIM_ERR_ARG; }
+    if (a.v_lo_off != 0 && a.pc_lo_off == 0) { blim_set_error("attention: a compensated call needs a prefix cache that holds lo parts"); return BLIM_ERR_ARG; }
+    ARG_CHECK(a.pfx_slot && a.pc_n_slots > 0 && a.pc_max_len > 0 && a.pc_ld % 8 == 0 && a.pc_lo_off % 8 == 0 && a.pc_slot_stride % 8 == 0 && a.pc_lo_off >= 0);
+    ARG_CHECK(a.pc_ld >= cn && a.pc_slot_stride >= a.pc_max_len * a.pc_ld);
+    if (a.pc_lo_off && (a.pc_lo_off < cn || a.pc_lo_off + cn > a.pc_ld)) { blim_set_error("attention: the cache's lo parts at pc_lo_off overlap [k | v] or leave the row (pc_ld)"); return BLIM_ERR_ARG; }
+    p.pfx_cache = (const bf16_t*)a.pfx_cache; p.pfx_slot = a.pfx_slot; p.pc_slot_stride = a.pc_slot_stride; p.pc_ld = a.pc_ld; p.pc_lo_off = a.pc_lo_off;
+    p.pc_n_slots = a.pc_n_slots; p.pc_max_len = a.pc_max_len;
+    return launch_attention_cached(p, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------- timing / options

@@ -48,6 +48,16 @@ class Batch(C.Structure):
                 ("blk_seq", C.c_void_p), ("blk_q0", C.c_void_p), ("own_start", C.c_void_p)]
 
 
+class AttentionArgs(C.Structure):
+    """blim_attention_args (include/blim.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("batch", C.POINTER(Batch)), ("qkv", C.c_void_p), ("ldq", C.c_int64),
+                ("num_heads", C.c_int32), ("num_kv_heads", C.c_int32), ("dtype16", C.c_int32), ("use_tr_read", C.c_int32),
+                ("v_lo_off", C.c_int64), ("out_lo_off", C.c_int64), ("out", C.c_void_p), ("ldo", C.c_int64), ("scale", C.c_float),
+                ("lse_out", C.c_void_p), ("out8", C.c_void_p), ("ldo8", C.c_int64), ("out_mx", C.c_void_p), ("mx_stride", C.c_int64),
+                ("pfx_cache", C.c_void_p), ("pfx_slot", C.c_void_p), ("pc_slot_stride", C.c_int64), ("pc_ld", C.c_int64), ("pc_lo_off", C.c_int64),
+                ("pc_n_slots", C.c_int32), ("pc_max_len", C.c_int32)]
+
+
 def declared_symbols(header: str = HEADER_PATH) -> Sequence[str]:
     """Names of every function include/blim.h declares."""
     text = open(header).read()
@@ -107,6 +117,7 @@ def load_library(path: str = LIB_PATH):
         "blim_gemm_f16_lo6": ([vp, vp, i32, i32, i32, vp, vp, vp, vp], C.c_int),
         "blim_quant_rows": ([vp, i64, i64, i32, i32, vp, vp, vp], C.c_int),
         "blim_gemm_f8": ([vp, i64, vp, vp, vp, i32, i32, i32, vp, i64, vp], C.c_int),
+        "blim_attention": ([C.POINTER(AttentionArgs), vp], C.c_int),
         "blim_timing_enable": ([vp, i32], C.c_int),
         "blim_timing_num_classes": ([], C.c_int),
         "blim_timing_class_name": ([i32], C.c_char_p),
@@ -653,6 +664,28 @@ def gemm_f16_lo6(a_hilo, w):
     out = torch.empty((M, N), dtype=torch.float32, device=w.device)
     _check(lib.blim_gemm_f16_lo6(_ptr(a_hilo), _ptr(w), M, N, K, _ptr(a6), _ptr(w6), _ptr(out), _stream()), "blim_gemm_f16_lo6")
     return out, a6.view(-1, K // 128, 25600), w6.view(-1, K // 128, 25600)
+
+
+def attention(qkv, batch: PackedBatch, num_heads: int, num_kv_heads: int, out, scale: float = 128 ** -0.5, use_tr_read: int = 1, v_lo_off: int = 0,
+              out_lo_off: int = 0, lse_out=None, out8=None, out_mx=None, mx_stride: int = 0, pfx_cache=None, pfx_slot=None, pc_slot_stride: int = 0,
+              pc_ld: int = 0, pc_lo_off: int = 0, pc_n_slots: int = 0, pc_max_len: int = 0):
+    """The decoder's attention kernel alone (blim_attention): qkv 16-bit [T, ldq] rows [q | k | v (| lo parts at +v_lo_off)], out 16-bit [T, ldo] written in place
+    (hi | lo at +out_lo_off); the row strides are the tensors' widths.  Optional: lse_out f32 [T, num_heads]; out8 uint8 [T, ldo8] + out_mx uint8 (fused e4m3 output);
+    pfx_cache 16-bit + pfx_slot int32 [n_seqs] (the prefix-cache forms).  The fields are blim.h's blim_attention_args."""
+    import torch
+    lib = load_library()
+    assert qkv.dim() == 2 and out.dim() == 2 and qkv.dtype == out.dtype and qkv.dtype in (torch.bfloat16, torch.float16)
+    bs = batch.struct()
+    a = AttentionArgs()
+    a.struct_bytes = C.sizeof(AttentionArgs)
+    a.batch = C.pointer(bs); a.qkv = _ptr(qkv); a.ldq = qkv.shape[1]; a.num_heads = num_heads; a.num_kv_heads = num_kv_heads
+    a.dtype16 = COMPUTE_DTYPES["bf16" if qkv.dtype == torch.bfloat16 else "f16"]; a.use_tr_read = int(use_tr_read)
+    a.v_lo_off = v_lo_off; a.out_lo_off = out_lo_off; a.out = _ptr(out); a.ldo = out.shape[1]; a.scale = scale
+    a.lse_out = _ptr(lse_out); a.out8 = _ptr(out8); a.ldo8 = out8.shape[1] if out8 is not None else 0; a.out_mx = _ptr(out_mx); a.mx_stride = mx_stride
+    a.pfx_cache = _ptr(pfx_cache); a.pfx_slot = _ptr(pfx_slot); a.pc_slot_stride = pc_slot_stride; a.pc_ld = pc_ld; a.pc_lo_off = pc_lo_off
+    a.pc_n_slots = pc_n_slots; a.pc_max_len = pc_max_len
+    _check(lib.blim_attention(C.byref(a), _stream()), "blim_attention")
+    return out
 
 
 def gemm_bf16(a, w):

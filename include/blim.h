@@ -281,6 +281,41 @@ int blim_gemm_f16_lo6(const void* A_hilo, const void* W, int32_t M, int32_t N, i
 int blim_quant_rows(const void* in16, int64_t ld, int64_t n_rows, int32_t K, int32_t dtype16, void* out8, float* scale, void* stream);
 int blim_gemm_f8(const void* A8, int64_t lda, const float* a_scale, const void* W8, const float* w_scale, int32_t M, int32_t N, int32_t K,
                  void* C, int64_t ldc, void* stream);
+/* The decoder's attention kernel alone (tests; additive in ABI v9): every form the engine launches, chosen by the same fields the engine sets (csrc/attention.hpp
+ * states them).  qkv 16-bit [n_tokens, ldq] rows [q heads | k heads | v heads (| their lo parts v_lo_off columns further)], head_dim 128, RoPE already applied;
+ * `batch` as for blim_decode (positions is not read); out 16-bit [n_tokens, ldo] = softmax(scale q.k over the visible keys) v per query head, hi (| lo at
+ * +out_lo_off).  v_lo_off != 0: three-term products over hi + lo operands; out_lo_off != 0: the output leaves as hi + lo; both need use_tr_read = 1.
+ * lse_out (may be NULL): f32 [n_tokens, num_heads], natural log-sum-exp of the scaled visible scores, 1e30 for a row without a visible key.
+ * out8 (may be NULL; fp16 only): the output as e4m3 bytes [n_tokens, ldo8] with one E8M0 byte per (token, head) in out_mx (layout: csrc/gemm.hpp `a_mx`,
+ * mx_stride = bytes per head = 256 * row tiles) INSTEAD of the 16-bit store; `out` must still be a valid pointer.
+ * pfx_cache (may be NULL = the uncached launch): sequence s with 0 <= pfx_slot[s] < pc_n_slots reads its prefix keys from rows of slot pfx_slot[s] -- a slot's
+ * rows start pc_slot_stride values apart, positions pc_ld apart, each [K heads | V heads (| K_lo | V_lo at +pc_lo_off)] -- every cached key visible, pfx_len
+ * clamped to pc_max_len; the cached forms write a 16-bit output only (no out8, no lse_out) and a compensated call needs pc_lo_off != 0.
+ * Rows of no sequence and columns beyond num_heads * 128 (resp. out_lo_off + num_heads * 128) are not written.  struct_bytes = sizeof(blim_attention_args)
+ * as the caller compiled it: fields added later are read as zero from a shorter struct. */
+typedef struct blim_attention_args {
+    int64_t struct_bytes;
+    const blim_batch* batch;
+    const void* qkv;
+    int64_t ldq;
+    int32_t num_heads, num_kv_heads;
+    int32_t dtype16;       /* BLIM_COMPUTE_BF16 / BLIM_COMPUTE_F16 */
+    int32_t use_tr_read;   /* engine option "attn_tr_read" */
+    int64_t v_lo_off, out_lo_off;
+    void* out;
+    int64_t ldo;
+    float scale;           /* 1 / sqrt(128) in the engine */
+    float* lse_out;
+    void* out8;
+    int64_t ldo8;
+    void* out_mx;
+    int64_t mx_stride;
+    const void* pfx_cache;
+    const int32_t* pfx_slot;
+    int64_t pc_slot_stride, pc_ld, pc_lo_off;
+    int32_t pc_n_slots, pc_max_len;
+} blim_attention_args;
+int blim_attention(const blim_attention_args* args, void* stream);
 
 /* ---- per-kernel-class timing (hipEvents on the launch stream).  Classes: see blim_timing_class_name. */
 int blim_timing_enable(blim_engine* e, int32_t on);

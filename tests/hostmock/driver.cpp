@@ -91,8 +91,87 @@ static void score_calls(blim_engine* e, const blim_config& c, int n_seq, int len
     EXPECT(blim_segment_mean(e, f32.data(), row_start.data(), n_seq, 0, scores.data(), nullptr) == 0);
 }
 
+// the engine-less attention entry: one good call of every form, then the argument errors it reports itself
+static void attention_calls() {
+    Batch B(3, 40, true);
+    const int64_t T = B.b.n_tokens;
+    const int nh = 4, nkv = 2, qn = (nh + 2 * nkv) * 128, hn = nh * 128;
+    std::vector<uint16_t> qkv((size_t)T * 2 * qn, 0), out((size_t)T * 2 * hn, 0), cache((size_t)2 * 64 * 4 * nkv * 128, 0);
+    std::vector<uint8_t> out8((size_t)T * hn, 0), mx((size_t)nh * 256, 0);
+    std::vector<float> lse((size_t)T * nh, 0.f);
+    std::vector<int32_t> slot = {-1, 0, 5};
+    blim_attention_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_bytes = sizeof a; a.batch = &B.b; a.qkv = qkv.data(); a.ldq = qn; a.num_heads = nh; a.num_kv_heads = nkv; a.dtype16 = BLIM_COMPUTE_F16; a.use_tr_read = 1;
+    a.out = out.data(); a.ldo = hn; a.scale = 0.0883883f;
+    const blim_attention_args plain = a;
+    EXPECT(blim_attention(&a, nullptr) == 0);
+    a.use_tr_read = 0; a.dtype16 = BLIM_COMPUTE_BF16; a.lse_out = lse.data();
+    EXPECT(blim_attention(&a, nullptr) == 0);
+    a = plain; a.out8 = out8.data(); a.ldo8 = hn; a.out_mx = mx.data(); a.mx_stride = 256;
+    EXPECT(blim_attention(&a, nullptr) == 0);
+    a = plain; a.ldq = 2 * qn; a.v_lo_off = qn; a.ldo = 2 * hn; a.out_lo_off = hn;
+    EXPECT(blim_attention(&a, nullptr) == 0);
+    const blim_attention_args comp = a;
+    a.pfx_cache = cache.data(); a.pfx_slot = slot.data(); a.pc_slot_stride = 64 * 4 * nkv * 128; a.pc_ld = 4 * nkv * 128; a.pc_lo_off = 2 * nkv * 128; a.pc_n_slots = 2; a.pc_max_len = 64;
+    EXPECT(blim_attention(&a, nullptr) == 0);
+    const blim_attention_args cached = a;
+    a.struct_bytes = (int64_t)((const char*)&a.pfx_cache - (const char*)&a);                      // a caller compiled before the cache fields: the uncached launch
+    EXPECT(blim_attention(&a, nullptr) == 0);
+    // ---- refusals
+    EXPECT(blim_attention(nullptr, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.struct_bytes = 8;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.batch = nullptr;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.qkv = nullptr;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.out = nullptr;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    { blim_batch bad = B.b; bad.seq_len = nullptr; a = plain; a.batch = &bad; EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG); }
+    a = plain; a.num_heads = 9; a.num_kv_heads = 1; a.ldq = 11 * 128; a.ldo = 9 * 128;                // G > 8
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "> 8"));
+    a = plain; a.num_heads = 3;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.dtype16 = BLIM_COMPUTE_F8;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.ldq = qn - 8;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = comp; a.use_tr_read = 0;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.out8 = out8.data(); a.ldo8 = hn; a.mx_stride = 256;                                  // out8 without its scale table
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = cached; a.v_lo_off = 0; a.out_lo_off = 0; a.out8 = out8.data(); a.ldo8 = hn; a.out_mx = mx.data(); a.mx_stride = 256;      // out8 together with a cache
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "prefix-cache"));
+    a = cached; a.lse_out = lse.data();
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = cached; a.pc_lo_off = 0;                                                                      // a compensated call, a cache without lo parts
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "lo parts"));
+    a = comp; a.v_lo_off = qn - 8;                                                                    // lo parts that overlap [q | k | v] ...
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "v_lo_off"));
+    a = comp; a.v_lo_off = qn + 8;                                                                    // ... or leave the row
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "v_lo_off"));
+    a = comp; a.out_lo_off = hn - 4;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "out_lo_off"));
+    a = comp; a.out_lo_off = hn + 4;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "out_lo_off"));
+    a = cached; a.pc_lo_off = 2 * nkv * 128 - 8;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "pc_lo_off"));
+    a = cached; a.pc_lo_off = 2 * nkv * 128 + 8;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "pc_lo_off"));
+    a = cached; a.pc_ld = 2 * nkv * 128 - 8; a.v_lo_off = 0; a.pc_lo_off = 0;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = cached; a.pc_slot_stride = 63 * a.pc_ld;                                                      // slots that overlap
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = cached; a.pfx_slot = nullptr;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+    a = cached; a.pc_n_slots = 0;
+    EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
+}
+
 int main() {
     EXPECT(blim_abi_version() == BLIM_ABI_VERSION);
+    attention_calls();
     blim_engine* e = nullptr;
     // ---- creation: bad configurations, no device
     {
