@@ -1652,6 +1652,97 @@ extern "C" int blim_attention(const blim_attention_args* args, void* stream) {
     return launch_attention_cached(p, (hipStream_t)stream);
 }
 
+// The GEMM as a building block (tests): fills GemmParams from the fields the engine and the trainer set and launches.  As for blim_attention the argument errors
+// are reported here (launch_gemm repeats its own), so that the host-only build of this file sees them too.
+extern "C" int blim_gemm(const blim_gemm_args* args, void* stream) {
+    ARG_CHECK(args && args->struct_bytes >= (int64_t)offsetof(blim_gemm_args, bias));
+    blim_gemm_args a;
+    memset(&a, 0, sizeof a);
+    memcpy(&a, args, (size_t)std::min<int64_t>(args->struct_bytes, (int64_t)sizeof a));
+    hipStream_t s = (hipStream_t)stream;
+    ARG_CHECK(a.epi >= BLIM_EPI_BF16 && a.epi <= BLIM_EPI_LSE);
+    ARG_CHECK(a.dtype == BLIM_COMPUTE_BF16 || a.dtype == BLIM_COMPUTE_F16 || a.dtype == BLIM_COMPUTE_F8);
+    ARG_CHECK(a.A && a.W && a.M > 0 && a.N > 0 && a.K > 0 && a.lda > 0);
+    const bool f8 = a.dtype == BLIM_COMPUTE_F8;
+    const int64_t es = f8 ? 1 : 2;
+    ARG_CHECK(a.K * es % 128 == 0 && a.lda * es % 16 == 0);
+    ARG_CHECK(a.w_wrap_k == 0 || (a.K == 2 * a.w_wrap_k && a.w_wrap_k * es % 128 == 0));
+    ARG_CHECK(a.lda >= a.K);
+    const bool out16 = a.epi == BLIM_EPI_BF16 || a.epi == BLIM_EPI_QKV || a.epi == BLIM_EPI_SWIGLU;
+    const int64_t n_out = a.epi == BLIM_EPI_SWIGLU ? a.N / 2 : a.N;
+    const bool fused8 = a.out8 != nullptr;
+    if (fused8) {
+        if (!(a.epi == BLIM_EPI_SWIGLU && f8)) { blim_set_error("gemm: the fused e4m3 output (out8) belongs to the fp8 SwiGLU GEMM"); return BLIM_ERR_ARG; }
+        ARG_CHECK(a.out_mx && a.N % 256 == 0 && a.ldc % 16 == 0 && a.ldc >= n_out && a.lo_off == 0);
+    } else {
+        ARG_CHECK(!a.out_mx);
+        if (a.epi == BLIM_EPI_LSE) ARG_CHECK(a.labels && a.lse_part && a.label_logit);
+        else ARG_CHECK(a.C && a.ldc >= n_out);
+    }
+    if (a.epi != BLIM_EPI_F32 && a.epi != BLIM_EPI_LSE && !fused8) ARG_CHECK(a.ldc % 4 == 0);
+    ARG_CHECK(!f8 || ((a.row_scale || a.a_mx) && a.col_scale));
+    ARG_CHECK((!a.a_mx && !a.out_mx) || (f8 && a.mx_stride >= (int64_t)((a.M + 255) / 256) * 256));
+    ARG_CHECK(!a.a_mx || a.epi == BLIM_EPI_RESID);
+    ARG_CHECK(a.act == 0 || (a.act == 1 && a.epi == BLIM_EPI_BF16));
+    ARG_CHECK(!a.bias || a.epi == BLIM_EPI_BF16 || a.epi == BLIM_EPI_RESID || a.epi == BLIM_EPI_QKV);
+    ARG_CHECK(!a.resid_in || a.epi == BLIM_EPI_RESID);
+    if (a.lo_off) {
+        if (!out16 || f8) { blim_set_error("gemm: split (hi | lo) outputs belong to the 16-bit epilogues of a 16-bit dtype"); return BLIM_ERR_ARG; }
+        if (a.lo_off < n_out || a.lo_off + n_out > a.ldc) { blim_set_error("gemm: the lo half at lo_off overlaps the output or leaves the row (ldc)"); return BLIM_ERR_ARG; }
+        ARG_CHECK(a.lo_off % 4 == 0 && !a.swiglu_act && !a.swiglu_gu);
+    }
+    if (a.epi == BLIM_EPI_QKV) {
+        ARG_CHECK(a.bias && a.rope_rows && a.rope_stride >= a.M && a.N % 128 == 0 && a.rope_cols >= 0 && a.rope_cols % 128 == 0);
+        if (a.rope_cols > a.N) { blim_set_error("gemm: rope_cols %d > N %d", a.rope_cols, a.N); return BLIM_ERR_ARG; }
+    } else ARG_CHECK(a.rope_cols == 0 && !a.rope_rows);
+    if (a.epi == BLIM_EPI_SWIGLU) ARG_CHECK(a.N % 32 == 0);
+    if (a.swiglu_act || a.swiglu_gu) {
+        if (a.epi != BLIM_EPI_BF16 || f8) { blim_set_error("gemm: the trainer's fused SwiGLU forms belong to the plain 16-bit epilogue"); return BLIM_ERR_ARG; }
+        ARG_CHECK(!(a.swiglu_act && a.swiglu_gu));
+        ARG_CHECK(!a.swiglu_gu || (a.N % 16 == 0 && a.swiglu_ld % 8 == 0 && a.swiglu_ld >= 2 * (int64_t)a.N));
+        ARG_CHECK(!a.swiglu_act || (a.N % 32 == 0 && a.swiglu_act_ld % 8 == 0 && a.swiglu_act_ld >= a.N / 2));
+    }
+    if (a.A6 || a.W6 || a.f6_build || a.out6) {
+        if (f8 || !a.A6 || !a.W6) { blim_set_error("gemm: the e2m3 second pass needs a 16-bit dtype and both A6 and W6"); return BLIM_ERR_ARG; }
+        ARG_CHECK(a.w_wrap_k == 0 && (a.epi == BLIM_EPI_RESID || a.epi == BLIM_EPI_QKV || a.epi == BLIM_EPI_SWIGLU || a.epi == BLIM_EPI_LSE));
+        if (a.epi == BLIM_EPI_QKV && a.lo_off == 0) { blim_set_error("gemm: lo6 QKV GEMM: hi | lo outputs only"); return BLIM_ERR_ARG; }
+        if (a.f6_build) {
+            ARG_CHECK(a.K % 128 == 0 && (a.K6 == 0 || a.K6 == a.K) && a.lda >= 2 * (int64_t)a.K);
+            a.K6 = a.K;
+            TRY(launch_f6_tiles((const bf16_t*)a.W, a.K, a.N, a.K, a.dtype, true, (uint8_t*)a.W6, s));
+            TRY(launch_f6_tiles((const bf16_t*)a.A + a.K, a.lda, a.M, a.K, a.dtype, false, (uint8_t*)a.A6, s));
+        }
+        ARG_CHECK(a.K6 > 0 && a.K6 % 128 == 0);
+        ARG_CHECK(!a.out6 || (a.epi == BLIM_EPI_SWIGLU && a.lo_off > 0 && a.N % 256 == 0));
+    }
+    GemmParams p = gp(a.dtype, a.A, a.lda, a.W, a.M, a.N, a.K, fused8 ? a.out8 : a.C, a.ldc);
+    p.row_scale = a.row_scale; p.col_scale = a.col_scale; p.bias = a.bias; p.resid_in = a.resid_in; p.act = a.act; p.scale = a.scale;
+    p.swiglu_gu = (uint16_t*)a.swiglu_gu; p.swiglu_ld = a.swiglu_ld; p.swiglu_act = (uint16_t*)a.swiglu_act; p.swiglu_act_ld = a.swiglu_act_ld;
+    p.rope_cols = a.rope_cols; p.rope_rows = a.rope_rows; p.rope_stride = a.rope_stride;
+    p.labels = a.labels; p.lse_part = (float2*)a.lse_part; p.label_logit = a.label_logit;
+    p.w_wrap_k = a.w_wrap_k; p.lo_off = a.lo_off; p.f16_saturate = a.f16_saturate;
+    p.out_mx = (uint8_t*)a.out_mx; p.a_mx = (const uint8_t*)a.a_mx; p.mx_stride = a.mx_stride;
+    p.A6 = (const uint8_t*)a.A6; p.W6 = (const uint8_t*)a.W6; p.K6 = a.K6; p.out6 = (uint8_t*)a.out6;
+    return launch_gemm((GemmEpi)a.epi, p, s);
+}
+// blim_rope_rows: the engine's two RoPE kernels into caller-owned memory -- rope_table_kernel fills the workspace (cos | sin of every position, as at creation),
+// rope_rows_kernel gathers the rows of `positions` (clamped to [0, max_positions)) into the chunk-major table of gemm.hpp
+extern "C" int64_t blim_rope_rows_bytes(int32_t max_positions) { return max_positions > 0 ? (int64_t)max_positions * 64 * 2 * 4 : -1; }
+extern "C" int blim_rope_rows(const int32_t* positions, int64_t n_tokens, float rope_theta, int32_t max_positions, void* workspace, float* out, int64_t stride, void* stream) {
+    ARG_CHECK(positions && workspace && out && n_tokens > 0 && max_positions > 0 && rope_theta > 0.f);
+    if (stride < n_tokens) { blim_set_error("rope_rows: stride %lld < n_tokens %lld (the chunks would overlap)", (long long)stride, (long long)n_tokens); return BLIM_ERR_ARG; }
+    ARG_CHECK(n_tokens * 32 < (1ll << 31) * 256 && (int64_t)max_positions * 64 < (1ll << 31));
+    hipStream_t s = (hipStream_t)stream;
+    float* cosb = (float*)workspace;
+    float* sinb = cosb + (int64_t)max_positions * 64;
+    const int n = max_positions * 64;
+    hipLaunchKernelGGL(rope_table_kernel, dim3((n + 255) / 256), dim3(256), 0, s, cosb, sinb, max_positions, 64, rope_theta, 128);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rope_rows_kernel, dim3((unsigned)((n_tokens * 32 + 255) / 256)), dim3(256), 0, s, out, positions, cosb, sinb, n_tokens, stride, max_positions);
+    HIP_TRY(hipGetLastError());
+    return BLIM_OK;
+}
+
 // ---------------------------------------------------------------------------- timing / options
 extern "C" int blim_timing_enable(blim_engine* e, int32_t on) {
     ARG_CHECK(e);

@@ -637,7 +637,8 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
         for (int mi = 0; mi < 8; ++mi) {
             const int rl = 128 * wm + 16 * mi + fr;          // row inside the tile
             const int row = row0 + rl;
-            const int lab = (row < p.M) ? p.labels[row] : -1;
+            int lab = (row < p.M) ? p.labels[row] : -1;
+            if (lab >= p.N) lab = -1;                        // a label in the last tile's padding columns [N, 256 ntn) is no column: label_logit stays unwritten
             float v[4][4];
             float mx = -INFINITY;
 #pragma unroll
@@ -785,7 +786,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
             float4 qkv_bias[4];                               // EPI_QKV: this lane's 16 bias values (the same for all eight mi)
             if constexpr (EPI == EPI_QKV) {
 #pragma unroll
-                for (int ni = 0; ni < 4; ++ni) qkv_bias[ni] = *(const float4*)(p.bias + wcol0 + 16 * ni + 4 * tq);
+                for (int ni = 0; ni < 4; ++ni) {               // N % 128 == 0: in the last tile of an N with N % 256 == 128 waves 2 and 3 own no column -- their
+                    const int col = wcol0 + 16 * ni + 4 * tq;  // (never stored) values must not be read from beyond bias[N)
+                    qkv_bias[ni] = col + 3 < p.N ? *(const float4*)(p.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+                }
             }
             float4 bf16_bias[4];                              // EPI_BF16: likewise (zeros without a bias / beyond N)
             if constexpr (EPI == EPI_BF16) {

@@ -58,6 +58,20 @@ class AttentionArgs(C.Structure):
                 ("pc_n_slots", C.c_int32), ("pc_max_len", C.c_int32)]
 
 
+class GemmArgs(C.Structure):
+    """blim_gemm_args (include/blim.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("epi", C.c_int32), ("dtype", C.c_int32), ("A", C.c_void_p), ("lda", C.c_int64), ("W", C.c_void_p),
+                ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32), ("act", C.c_int32), ("C", C.c_void_p), ("ldc", C.c_int64), ("bias", C.c_void_p),
+                ("resid_in", C.c_void_p), ("scale", C.c_float), ("w_wrap_k", C.c_int32), ("lo_off", C.c_int64), ("f16_saturate", C.c_int32),
+                ("rope_cols", C.c_int32), ("rope_rows", C.c_void_p), ("rope_stride", C.c_int64), ("labels", C.c_void_p), ("lse_part", C.c_void_p),
+                ("label_logit", C.c_void_p), ("row_scale", C.c_void_p), ("col_scale", C.c_void_p), ("a_mx", C.c_void_p), ("out8", C.c_void_p),
+                ("out_mx", C.c_void_p), ("mx_stride", C.c_int64), ("A6", C.c_void_p), ("W6", C.c_void_p), ("K6", C.c_int32), ("f6_build", C.c_int32),
+                ("out6", C.c_void_p), ("swiglu_act", C.c_void_p), ("swiglu_act_ld", C.c_int64), ("swiglu_gu", C.c_void_p), ("swiglu_ld", C.c_int64)]
+
+
+EPILOGUES = {"bf16": 0, "f32": 1, "resid": 2, "qkv": 3, "swiglu": 4, "lse": 5}
+
+
 def declared_symbols(header: str = HEADER_PATH) -> Sequence[str]:
     """Names of every function include/blim.h declares."""
     text = open(header).read()
@@ -118,6 +132,9 @@ def load_library(path: str = LIB_PATH):
         "blim_quant_rows": ([vp, i64, i64, i32, i32, vp, vp, vp], C.c_int),
         "blim_gemm_f8": ([vp, i64, vp, vp, vp, i32, i32, i32, vp, i64, vp], C.c_int),
         "blim_attention": ([C.POINTER(AttentionArgs), vp], C.c_int),
+        "blim_gemm": ([C.POINTER(GemmArgs), vp], C.c_int),
+        "blim_rope_rows_bytes": ([i32], C.c_int64),
+        "blim_rope_rows": ([vp, i64, f32, i32, vp, vp, i64, vp], C.c_int),
         "blim_timing_enable": ([vp, i32], C.c_int),
         "blim_timing_num_classes": ([], C.c_int),
         "blim_timing_class_name": ([i32], C.c_char_p),
@@ -685,6 +702,48 @@ def attention(qkv, batch: PackedBatch, num_heads: int, num_kv_heads: int, out, s
     a.pfx_cache = _ptr(pfx_cache); a.pfx_slot = _ptr(pfx_slot); a.pc_slot_stride = pc_slot_stride; a.pc_ld = pc_ld; a.pc_lo_off = pc_lo_off
     a.pc_n_slots = pc_n_slots; a.pc_max_len = pc_max_len
     _check(lib.blim_attention(C.byref(a), _stream()), "blim_attention")
+    return out
+
+
+_GEMM_POINTERS = ("bias", "resid_in", "rope_rows", "labels", "lse_part", "label_logit", "row_scale", "col_scale", "a_mx", "out8", "out_mx", "A6", "W6", "out6",
+                  "swiglu_act", "swiglu_gu")
+_GEMM_INTS = ("act", "w_wrap_k", "lo_off", "rope_cols", "rope_stride", "mx_stride", "K6", "f6_build", "swiglu_act_ld", "swiglu_ld")
+
+
+def gemm(epi: str, dtype: str, a, w, M: int, N: int, K: int, c=None, lda: Optional[int] = None, ldc: Optional[int] = None, scale: float = 1.0,
+         f16_saturate: int = 1, **fields):
+    """The GEMM kernel alone (blim_gemm): epi one of EPILOGUES, dtype "bf16" / "f16" / "f8"; a [M, lda] and w [N, K] device tensors of that format (f8: uint8
+    e4m3 bytes), c the output buffer ([rows, ldc]: its width is the row stride unless ldc is given; None where the epilogue has no C).  Every other field of
+    blim.h's blim_gemm_args by keyword: tensors for the pointers (bias, resid_in, rope_rows, labels, lse_part, label_logit, row_scale, col_scale, a_mx, out8,
+    out_mx, A6, W6, out6, swiglu_act, swiglu_gu), ints for act, w_wrap_k, lo_off, rope_cols, rope_stride, mx_stride, K6, f6_build, swiglu_act_ld, swiglu_ld."""
+    lib = load_library()
+    g = GemmArgs()
+    g.struct_bytes = C.sizeof(GemmArgs)
+    g.epi = EPILOGUES[epi]; g.dtype = COMPUTE_DTYPES[dtype]
+    g.A = _ptr(a); g.lda = a.shape[1] if lda is None else lda; g.W = _ptr(w); g.M = M; g.N = N; g.K = K
+    g.C = _ptr(c); g.ldc = (c.shape[1] if c is not None else 0) if ldc is None else ldc
+    g.scale = scale; g.f16_saturate = int(f16_saturate)
+    for k, v in fields.items():
+        if k in _GEMM_POINTERS:
+            setattr(g, k, _ptr(v))
+        elif k in _GEMM_INTS:
+            setattr(g, k, int(v))
+        else:
+            raise TypeError(f"gemm(): unknown field {k!r}")
+    _check(lib.blim_gemm(C.byref(g), _stream()), "blim_gemm")
+    return c
+
+
+def rope_rows(positions, rope_theta: float, max_positions: int, stride: Optional[int] = None):
+    """blim_rope_rows: positions int32 [T] (device) -> f32 [8, stride, 16], the cos / sin table of the QKV epilogue (csrc/gemm.hpp: rope_rows); rows >= T of
+    every chunk are left as allocated (NaN here)."""
+    import torch
+    lib = load_library()
+    T = positions.numel()
+    stride = T if stride is None else stride
+    ws = torch.empty(lib.blim_rope_rows_bytes(max_positions), dtype=torch.uint8, device=positions.device)
+    out = torch.full((8, stride, 16), float("nan"), dtype=torch.float32, device=positions.device)
+    _check(lib.blim_rope_rows(_ptr(positions), T, rope_theta, max_positions, _ptr(ws), _ptr(out), stride, _stream()), "blim_rope_rows")
     return out
 
 

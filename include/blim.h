@@ -317,6 +317,80 @@ typedef struct blim_attention_args {
 } blim_attention_args;
 int blim_attention(const blim_attention_args* args, void* stream);
 
+/* The GEMM kernel alone (tests; additive in ABI v9): C [M, N] = A [M, K] . W [N, K]^T with every epilogue and operand form the engine and the trainer launch,
+ * chosen by the same fields they set (csrc/gemm.hpp states them; a zero / NULL field is "off").  A: row stride lda, W: row stride K (w_wrap_k when set).
+ * dtype BLIM_COMPUTE_BF16 / _F16: A, W and 16-bit outputs in that format; BLIM_COMPUTE_F8: A, W e4m3 bytes with row_scale [M] (or the E8M0 table a_mx) and
+ * col_scale [N], 16-bit outputs fp16.
+ *   BLIM_EPI_BF16    C 16-bit [M, ldc] = act(acc + bias), act 1 = exact-erf GELU.  Trainer forms: swiglu_act != NULL -- the tile is gate | up (16 / 16 columns
+ *                    interleaved), stored to C, and silu(gate) * up [M, N / 2] goes to swiglu_act (row stride swiglu_act_ld); swiglu_gu != NULL -- the tile is
+ *                    d act and is not stored (C must be valid, it is not written): the saved gate | up rows at swiglu_gu [M, swiglu_ld] become [d gate | d up] in place
+ *   BLIM_EPI_F32     C f32 = acc * scale
+ *   BLIM_EPI_RESID   C f32 = (resid_in ? resid_in : C) + (acc + bias); resid_in has C's row stride
+ *   BLIM_EPI_QKV     C 16-bit = rope(acc + bias) on columns < rope_cols, acc + bias beyond; W rows of q / k heads in the pair-interleaved order of gemm.hpp
+ *                    (qkv_perm_row), the output in natural order; rope_rows: the table blim_rope_rows writes, rope_stride >= M rows per chunk
+ *   BLIM_EPI_SWIGLU  C 16-bit [M, N / 2] = silu(gate) * up, W rows 16 gate / 16 up interleaved.  BLIM_COMPUTE_F8 with out8 != NULL: the output leaves as e4m3
+ *                    bytes at out8 (row stride ldc BYTES, C is not used) with one E8M0 byte per (row, 128 columns) in out_mx (layout: gemm.hpp, mx_stride)
+ *   BLIM_EPI_LSE     lse_part f32 [M, ceil(N / 256), 2] = (max, sum exp(x - max)) per 256-column tile, label_logit [M] = the logit of column labels[m]
+ *                    (not written for a label < 0 or >= N); C is not used
+ * w_wrap_k: A is [hi | lo] along K (K counts both halves), W [N, w_wrap_k] is walked twice.  lo_off != 0 (BF16 / QKV / SWIGLU, 16-bit dtypes): the output leaves
+ * as hi at C and lo = round16(x - hi) at C + lo_off elements; the lo half must lie behind the output and inside the row.  f16_saturate: fp16 stores clamp to
+ * +-65504 instead of overflowing to inf.  A6 / W6 / K6 (16-bit dtypes; RESID / QKV with lo_off / SWIGLU / LSE): a second pass acc += e2m3(lo of A) . e2m3(W)^T
+ * over operand tile images of blim_f6_tiles_bytes(M, K6) / (N, K6) bytes; with f6_build != 0 the entry writes both images first, W6 from W [N, K] and A6 from
+ * the lo part that sits K columns behind A (row stride lda), K6 = K, as blim_gemm_f16_lo6 does.  out6 (SWIGLU with lo_off and A6): the lo half leaves as the
+ * e2m3 tile image of the consuming GEMM (blim_f6_tiles_bytes(M, N / 2) bytes) INSTEAD of the 16-bit store at C + lo_off.
+ * struct_bytes = sizeof(blim_gemm_args) as the caller compiled it: fields added later are read as zero from a shorter struct. */
+#define BLIM_EPI_BF16 0
+#define BLIM_EPI_F32 1
+#define BLIM_EPI_RESID 2
+#define BLIM_EPI_QKV 3
+#define BLIM_EPI_SWIGLU 4
+#define BLIM_EPI_LSE 5
+typedef struct blim_gemm_args {
+    int64_t struct_bytes;
+    int32_t epi;           /* BLIM_EPI_* */
+    int32_t dtype;         /* BLIM_COMPUTE_BF16 / _F16 / _F8 */
+    const void* A;
+    int64_t lda;
+    const void* W;
+    int32_t M, N, K;
+    int32_t act;
+    void* C;
+    int64_t ldc;
+    const float* bias;
+    const float* resid_in;
+    float scale;           /* BLIM_EPI_F32 */
+    int32_t w_wrap_k;
+    int64_t lo_off;
+    int32_t f16_saturate;
+    int32_t rope_cols;
+    const float* rope_rows;
+    int64_t rope_stride;
+    const int32_t* labels;
+    float* lse_part;
+    float* label_logit;
+    const float* row_scale;
+    const float* col_scale;
+    const void* a_mx;
+    void* out8;
+    void* out_mx;
+    int64_t mx_stride;
+    void* A6;
+    void* W6;
+    int32_t K6;
+    int32_t f6_build;
+    void* out6;
+    void* swiglu_act;
+    int64_t swiglu_act_ld;
+    void* swiglu_gu;
+    int64_t swiglu_ld;
+} blim_gemm_args;
+int blim_gemm(const blim_gemm_args* args, void* stream);
+/* cos / sin of every token's position as BLIM_EPI_QKV reads them (csrc/gemm.hpp: rope_rows): out f32 [8 = {cos, sin} x 4 groups of 16 dims][stride rows][16],
+ * row t of every chunk = position min(max(positions[t], 0), max_positions - 1); stride >= n_tokens.  workspace: blim_rope_rows_bytes(max_positions) bytes (the
+ * cos | sin tables of all positions, built by the call as the engine builds its own at creation); out: 128 * stride floats. */
+int64_t blim_rope_rows_bytes(int32_t max_positions);
+int blim_rope_rows(const int32_t* positions, int64_t n_tokens, float rope_theta, int32_t max_positions, void* workspace, float* out, int64_t stride, void* stream);
+
 /* ---- per-kernel-class timing (hipEvents on the launch stream).  Classes: see blim_timing_class_name. */
 int blim_timing_enable(blim_engine* e, int32_t on);
 int blim_timing_num_classes(void);

@@ -169,9 +169,132 @@ static void attention_calls() {
     EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
 }
 
+// the engine-less GEMM entry and blim_rope_rows: one good call of every form, then the argument errors they report themselves
+static void gemm_calls() {
+    const int M = 300, N = 512, K = 128;
+    std::vector<uint16_t> A((size_t)M * 2 * K, 0), W((size_t)N * K, 0), C16((size_t)M * 2 * (N + 8), 0), gu((size_t)M * (2 * N + 8), 0), act((size_t)M * N, 0);
+    std::vector<float> C32((size_t)M * (N + 4), 0.f), bias(N, 0.f), rope((size_t)128 * 512, 0.f), part((size_t)M * 2 * 2, 0.f), ll(M, 0.f), rs(M, 1.f), cs(N, 1.f);
+    std::vector<int32_t> labels(M, 3), pos(M, 5);
+    std::vector<uint8_t> a6((size_t)blim_f6_tiles_bytes(M, K), 0), w6((size_t)blim_f6_tiles_bytes(N, K), 0), o6((size_t)blim_f6_tiles_bytes(M, N / 2), 0);
+    std::vector<uint8_t> c8((size_t)M * N, 0), mx((size_t)8 * 512, 0), ws((size_t)blim_rope_rows_bytes(64), 0);
+    EXPECT(blim_rope_rows_bytes(0) == -1 && blim_rope_rows_bytes(64) == 64 * 64 * 2 * 4);
+    EXPECT(blim_rope_rows(pos.data(), M, 1e6f, 64, ws.data(), rope.data(), 512, nullptr) == 0);
+    EXPECT(blim_rope_rows(pos.data(), M, 1e6f, 64, ws.data(), rope.data(), M - 1, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "stride"));
+    EXPECT(blim_rope_rows(nullptr, M, 1e6f, 64, ws.data(), rope.data(), 512, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_rows(pos.data(), M, 1e6f, 0, ws.data(), rope.data(), 512, nullptr) == BLIM_ERR_ARG);
+    blim_gemm_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_bytes = sizeof a; a.epi = BLIM_EPI_BF16; a.dtype = BLIM_COMPUTE_F16; a.A = A.data(); a.lda = K; a.W = W.data(); a.M = M; a.N = N; a.K = K;
+    a.C = C16.data(); a.ldc = N + 8; a.scale = 1.f; a.f16_saturate = 1;
+    const blim_gemm_args plain = a;
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    a.bias = bias.data(); a.act = 1; a.dtype = BLIM_COMPUTE_BF16;
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    a = plain; a.ldc = 2 * (N + 8); a.lo_off = N + 8; a.lda = 2 * K; a.K = 2 * K; a.w_wrap_k = K;                  // compensated: [hi | lo] in, hi | lo out
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    const blim_gemm_args split = a;
+    a = plain; a.swiglu_act = act.data(); a.swiglu_act_ld = N / 2;
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    a = plain; a.swiglu_gu = gu.data(); a.swiglu_ld = 2 * N + 8;
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    a = plain; a.epi = BLIM_EPI_F32; a.C = C32.data(); a.ldc = N + 3; a.scale = 0.5f;
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    a = plain; a.epi = BLIM_EPI_RESID; a.C = C32.data(); a.ldc = N + 4; a.bias = bias.data(); a.resid_in = C32.data();
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    const blim_gemm_args resid = a;
+    a = plain; a.epi = BLIM_EPI_QKV; a.bias = bias.data(); a.rope_cols = 384; a.rope_rows = rope.data(); a.rope_stride = 512;
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    const blim_gemm_args qkv = a;
+    a = plain; a.epi = BLIM_EPI_SWIGLU;
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    a = plain; a.epi = BLIM_EPI_LSE; a.C = nullptr; a.labels = labels.data(); a.lse_part = part.data(); a.label_logit = ll.data();
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    const blim_gemm_args lse = a;
+    a = plain; a.epi = BLIM_EPI_SWIGLU; a.lda = 2 * K; a.ldc = 2 * (N / 2 + 8); a.lo_off = N / 2 + 8; a.A6 = a6.data(); a.W6 = w6.data(); a.f6_build = 1; a.out6 = o6.data();
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    const blim_gemm_args lo6 = a;
+    a = plain; a.dtype = BLIM_COMPUTE_F8; a.epi = BLIM_EPI_SWIGLU; a.row_scale = rs.data(); a.col_scale = cs.data(); a.C = nullptr; a.out8 = c8.data(); a.ldc = N / 2;
+    a.out_mx = mx.data(); a.mx_stride = 512;
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    const blim_gemm_args f8 = a;
+    a = plain; a.dtype = BLIM_COMPUTE_F8; a.epi = BLIM_EPI_RESID; a.C = C32.data(); a.ldc = N + 4; a.a_mx = mx.data(); a.mx_stride = 512; a.col_scale = cs.data();
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    a = plain; a.struct_bytes = (int64_t)((const char*)&a.bias - (const char*)&a);                                  // the shortest caller: the plain product
+    EXPECT(blim_gemm(&a, nullptr) == 0);
+    // ---- refusals
+    EXPECT(blim_gemm(nullptr, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.struct_bytes = 8;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.epi = 6;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.dtype = 3;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.A = nullptr;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.C = nullptr;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.K = 96;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.ldc = N - 4;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.ldc = N + 2;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.act = 2;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = split; a.lo_off = N - 4;                                                                                     // a lo half that overlaps the output ...
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "lo_off"));
+    a = split; a.lo_off = N + 20;                                                                                    // ... or leaves the row
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "lo_off"));
+    a = resid; a.lo_off = N;                                                                                         // split outputs of an f32 epilogue
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "split"));
+    a = split; a.w_wrap_k = K / 2;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = qkv; a.rope_cols = N + 128;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "rope_cols"));
+    a = qkv; a.bias = nullptr;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = qkv; a.rope_stride = M - 1;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = qkv; a.rope_cols = 320;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.rope_cols = 128;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = lse; a.labels = nullptr;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.epi = BLIM_EPI_F32; a.C = C32.data(); a.bias = bias.data();
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.resid_in = C32.data();
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = lo6; a.W6 = nullptr;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "e2m3"));
+    a = lo6; a.lda = K;                                                                                              // f6_build without a lo part behind A
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = lo6; a.f6_build = 0; a.K6 = 0;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = lo6; a.lo_off = 0; a.ldc = N / 2 + 8;                                                                        // out6 without split outputs
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = qkv; a.lda = 2 * K; a.A6 = a6.data(); a.W6 = w6.data(); a.f6_build = 1;                                      // lo6 QKV with plain outputs
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "hi | lo"));
+    a = f8; a.out_mx = nullptr;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = f8; a.dtype = BLIM_COMPUTE_F16;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "out8"));
+    a = f8; a.mx_stride = 256;                                                                                       // M = 300: two row tiles
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = f8; a.col_scale = nullptr;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.swiglu_act = act.data(); a.swiglu_act_ld = N / 2; a.swiglu_gu = gu.data(); a.swiglu_ld = 2 * N + 8;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.swiglu_gu = gu.data(); a.swiglu_ld = 2 * N - 8;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG);
+    a = plain; a.epi = BLIM_EPI_SWIGLU; a.swiglu_act = act.data(); a.swiglu_act_ld = N / 2;
+    EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "trainer"));
+}
+
 int main() {
     EXPECT(blim_abi_version() == BLIM_ABI_VERSION);
     attention_calls();
+    gemm_calls();
     blim_engine* e = nullptr;
     // ---- creation: bad configurations, no device
     {
