@@ -591,3 +591,47 @@ extern "C" int blim_train_debug_read(blim_trainer* t, const char* which, void* d
     HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
     return BLIM_OK;
 }
+
+// ---------------------------------------------------------------------------- the attention backward and the RoPE backward as building blocks (tests)
+// As for blim_attention the argument errors are reported here (the launcher repeats some), so that the host-only build of this file sees them too.
+static int64_t attn_bwd_d_bytes(int64_t n_tokens, int32_t num_heads) { return (n_tokens * num_heads * 4 + 15) / 16 * 16; }      // P16 / dS16 are accessed as uint4
+extern "C" int64_t blim_attention_bwd_workspace_bytes(int64_t n_tokens, int32_t n_seqs, int32_t num_heads, int32_t max_len) {
+    if (n_tokens <= 0 || n_tokens > (1ll << 40) || n_seqs <= 0 || num_heads <= 0 || max_len <= 0 || max_len > (1 << 20)) return -1;
+    if ((int64_t)n_seqs * num_heads > 65535) return -1;                                      // the grid's z range; keeps the products below inside int64
+    const int64_t Lm = attn_bwd_lm(max_len);
+    return attn_bwd_d_bytes(n_tokens, num_heads) + 2 * ((int64_t)n_seqs * num_heads * Lm * Lm * 2);      // D (rounded up to 16 bytes) | P16 | dS16
+}
+extern "C" int blim_attention_bwd(const blim_attention_bwd_args* args, void* stream) {
+    ARG_CHECK(args && args->struct_bytes >= (int64_t)sizeof(blim_attention_bwd_args));
+    const blim_attention_bwd_args& a = *args;
+    ARG_CHECK(a.qkv && a.dout && a.o16 && a.lse && a.key_visible && a.seq_start && a.seq_len && a.workspace && a.dqkv);
+    ARG_CHECK(a.dtype16 == BLIM_COMPUTE_BF16 || a.dtype16 == BLIM_COMPUTE_F16);
+    ARG_CHECK(a.num_heads > 0 && a.num_kv_heads > 0 && a.num_heads % a.num_kv_heads == 0);
+    ARG_CHECK(a.n_tokens > 0 && a.n_seqs > 0 && a.max_len > 0);
+    ARG_CHECK(a.ldq % 8 == 0 && a.ldo % 8 == 0 && a.ldo16 % 2 == 0);
+    const int64_t qn = (int64_t)(a.num_heads + 2 * a.num_kv_heads) * 128, hn = (int64_t)a.num_heads * 128;
+    if (a.ldq < qn || a.ldo < hn || a.ldo16 < hn) { blim_set_error("attention backward: a row stride is shorter than its heads (ldq %lld, ldo %lld, ldo16 %lld)", (long long)a.ldq, (long long)a.ldo, (long long)a.ldo16); return BLIM_ERR_ARG; }
+    if ((int64_t)a.n_seqs * a.num_heads > 65535) { blim_set_error("attention backward: %d sequences x %d heads exceed the grid's z range; split the batch", a.n_seqs, a.num_heads); return BLIM_ERR_ARG; }
+    const int64_t need = blim_attention_bwd_workspace_bytes(a.n_tokens, a.n_seqs, a.num_heads, a.max_len);
+    if (((uintptr_t)a.workspace & 15) != 0) { blim_set_error("attention backward: workspace is not 16-byte aligned"); return BLIM_ERR_ARG; }
+    if (need < 0 || a.workspace_bytes < need) { blim_set_error("attention backward: workspace of %lld bytes, %lld needed", (long long)a.workspace_bytes, (long long)need); return BLIM_ERR_ARG; }
+    const int64_t Lm = attn_bwd_lm(a.max_len);
+    const int64_t mats = (int64_t)a.n_seqs * a.num_heads * Lm * Lm;
+    AttnBwdParams p;
+    memset(&p, 0, sizeof(p));
+    p.dtype = a.dtype16 == BLIM_COMPUTE_F16 ? DT_F16 : DT_BF16;
+    p.qkv = (const uint16_t*)a.qkv; p.ldq = a.ldq; p.dout = (const uint16_t*)a.dout; p.ldo = a.ldo; p.o16 = (const uint16_t*)a.o16; p.ldo16 = a.ldo16; p.lse = a.lse;
+    p.num_heads = a.num_heads; p.num_kv_heads = a.num_kv_heads; p.key_visible = a.key_visible; p.seq_start = a.seq_start; p.seq_len = a.seq_len;
+    p.n_seqs = a.n_seqs; p.max_len = a.max_len; p.scale = a.scale;
+    p.D = (float*)a.workspace; p.P16 = (uint16_t*)((char*)a.workspace + attn_bwd_d_bytes(a.n_tokens, a.num_heads)); p.dS16 = p.P16 + mats; p.dqkv = a.dqkv;
+    return launch_attention_bwd(p, a.n_tokens, (hipStream_t)stream);
+}
+extern "C" int blim_rope_bwd(void* out16, const float* dqkv, int64_t n_tokens, int32_t qkv_n, int32_t rope_cols, const int32_t* positions, const float* cos, const float* sin,
+                             int32_t n_pos, int32_t dtype16, void* stream) {
+    ARG_CHECK(out16 && dqkv && positions && cos && sin && n_tokens > 0 && n_pos > 0);
+    ARG_CHECK(dtype16 == BLIM_COMPUTE_BF16 || dtype16 == BLIM_COMPUTE_F16);
+    ARG_CHECK(qkv_n > 0 && qkv_n % 128 == 0 && rope_cols >= 0 && rope_cols % 128 == 0);
+    if (rope_cols > qkv_n) { blim_set_error("rope backward: rope_cols %d > qkv_n %d", rope_cols, qkv_n); return BLIM_ERR_ARG; }
+    ARG_CHECK(n_tokens * (qkv_n / 2) < (1ll << 31) * 256);
+    return launch_rope_bwd((uint16_t*)out16, dqkv, n_tokens, qkv_n, rope_cols, positions, cos, sin, n_pos, dtype16 == BLIM_COMPUTE_F16 ? DT_F16 : DT_BF16, (hipStream_t)stream);
+}

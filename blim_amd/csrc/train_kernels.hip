@@ -701,20 +701,22 @@ int64_t attn_bwd_lm(int max_len) { return (max_len + 63) / 64 * 64; }
 enum { AB_S = 0, AB_DP = 1, AB_DQ = 2, AB_DV = 3, AB_DK = 4 };
 #define AB_LD 40    // LDS row stride (16-bit elements) of a [64][32] operand tile: 80 B keeps 16-B alignment and spreads banks
 
+// S, dP (A = Q / dO rows, B = K / V rows, both k-contiguous over the head dim) and dQ = dS K (A = dS rows, B = K with the token as contraction index).
+// dV and dK are attn_tn_kernel's.
 template <int DT, int MODE>
 __global__ __launch_bounds__(256) void attn_bgemm_kernel(AttnBwdParams p, int Lm) {
+    static_assert(MODE == AB_S || MODE == AB_DP || MODE == AB_DQ, "dV / dK: attn_tn_kernel");
     __shared__ __attribute__((aligned(16))) uint16_t As[64 * AB_LD];
     __shared__ __attribute__((aligned(16))) uint16_t Bs[64 * AB_LD];
     const int nh = p.num_heads, nkv = p.num_kv_heads, grp = nh / nkv;
-    const int HB = (MODE == AB_DV || MODE == AB_DK) ? nkv : nh;
-    const int s = blockIdx.z / HB, hb = blockIdx.z % HB;
+    const int s = blockIdx.z / nh, hb = blockIdx.z % nh;
     const int L = p.seq_len[s];
     const int64_t t0 = p.seq_start[s];
     const int m0 = blockIdx.y * 64, n0 = blockIdx.x * 64;
     if (m0 >= L) return;
-    if ((MODE == AB_S || MODE == AB_DP) && n0 > m0 + 63) {
-        // above the diagonal: never read, except the tile that shares a 128-column block with a diagonal tile (attn_tn_kernel reads
-        // 128-wide column blocks of P / dS): that one is written as zeros
+    if (MODE != AB_DQ && n0 > m0 + 63) {
+        // above the diagonal (this includes every tile of columns beyond the row's length): never read, except the tile that shares a
+        // 128-column block with a diagonal tile (attn_tn_kernel reads 128-wide column blocks of P / dS): that one is written as zeros
         if (n0 < (m0 / 128 + 1) * 128) {
             uint16_t* dst = (MODE == AB_S ? p.P16 : p.dS16) + ((int64_t)s * p.num_heads + hb) * (int64_t)Lm * Lm;
             for (int i = threadIdx.x; i < 64 * 8; i += 256) {
@@ -724,76 +726,48 @@ __global__ __launch_bounds__(256) void attn_bgemm_kernel(AttnBwdParams p, int Lm
         }
         return;
     }
-    if ((MODE == AB_S || MODE == AB_DP) && n0 >= L) {      // columns beyond the row's length: zeros (same readers)
-        uint16_t* dst = (MODE == AB_S ? p.P16 : p.dS16) + ((int64_t)s * p.num_heads + hb) * (int64_t)Lm * Lm;
-        for (int i = threadIdx.x; i < 64 * 8; i += 256) {
-            const int r = m0 + (i >> 3), c = n0 + 8 * (i & 7);
-            if (r < L) *(uint4*)(dst + (int64_t)r * Lm + c) = make_uint4(0, 0, 0, 0);
-        }
-        return;
-    }
-    const int kvh = HB == nh ? hb / grp : hb;
+    const int kvh = hb / grp;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, wm = w >> 1, wn = w & 1;
     f32x16 acc;
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    const int64_t mat = ((int64_t)s * nh) * (int64_t)Lm * Lm;      // + h * Lm * Lm
-    const int n_hh = (MODE == AB_DV || MODE == AB_DK) ? grp : 1;
-    for (int hh = 0; hh < n_hh; ++hh) {
-        const int h = (MODE == AB_DV || MODE == AB_DK) ? kvh * grp + hh : hb;
-        const uint16_t* PS = (MODE == AB_DV ? p.P16 : p.dS16) + mat + (int64_t)h * Lm * Lm;
-        int k_begin = 0, k_end = 128;
-        if (MODE == AB_DQ) { k_begin = 0; k_end = min((L + 31) / 32 * 32, m0 + 64); }
-        if (MODE == AB_DV || MODE == AB_DK) { k_begin = m0; k_end = (L + 31) / 32 * 32; }
-        for (int k0 = k_begin; k0 < k_end; k0 += 32) {
-            __syncthreads();
-            // ---- A tile: As[m][k]
-            if (MODE == AB_S || MODE == AB_DP || MODE == AB_DQ) {     // k-contiguous source
-                const int row = tid >> 2, kc = (tid & 3) * 8;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                const int i = m0 + row;
-                if (i < L) {
-                    if (MODE == AB_S) v = *(const uint4*)(p.qkv + (t0 + i) * p.ldq + hb * 128 + k0 + kc);
-                    else if (MODE == AB_DP) v = *(const uint4*)(p.dout + (t0 + i) * p.ldo + hb * 128 + k0 + kc);
-                    else v = *(const uint4*)(PS + (int64_t)i * Lm + k0 + kc);
-                }
-                *(uint4*)(As + row * AB_LD + kc) = v;
-            } else {                                                  // m-contiguous source: A(m = j, k = i) = P/dS[i][j]
-                const int k = tid >> 3, mc = (tid & 7) * 8;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                const int i = k0 + k;
-                if (i < L) v = *(const uint4*)(PS + (int64_t)i * Lm + m0 + mc);
-                const uint16_t* e = (const uint16_t*)&v;
-#pragma unroll
-                for (int q = 0; q < 8; ++q) As[(mc + q) * AB_LD + k] = e[q];
+    const int64_t mat = ((int64_t)s * nh + hb) * (int64_t)Lm * Lm;
+    const int k_end = MODE == AB_DQ ? min((L + 31) / 32 * 32, m0 + 64) : 128;
+    for (int k0 = 0; k0 < k_end; k0 += 32) {
+        __syncthreads();
+        {   // ---- A tile: As[m][k], k-contiguous source
+            const int row = tid >> 2, kc = (tid & 3) * 8;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            const int i = m0 + row;
+            if (i < L) {
+                if (MODE == AB_S) v = *(const uint4*)(p.qkv + (t0 + i) * p.ldq + hb * 128 + k0 + kc);
+                else if (MODE == AB_DP) v = *(const uint4*)(p.dout + (t0 + i) * p.ldo + hb * 128 + k0 + kc);
+                else v = *(const uint4*)(p.dS16 + mat + (int64_t)i * Lm + k0 + kc);
             }
-            // ---- B tile: Bs[n][k]
-            if (MODE == AB_S || MODE == AB_DP) {                      // B(n = j, k = d): k-contiguous rows of K / V
-                const int row = tid >> 2, kc = (tid & 3) * 8;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                const int j = n0 + row;
-                if (j < L) v = *(const uint4*)(p.qkv + (t0 + j) * p.ldq + (MODE == AB_S ? nh + kvh : nh + nkv + kvh) * 128 + k0 + kc);
-                *(uint4*)(Bs + row * AB_LD + kc) = v;
-            } else {                                                  // B(n = d, k = token): n-contiguous rows
-                const int k = tid >> 3, nc = (tid & 7) * 8;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                const int tok = k0 + k;
-                if (tok < L) {
-                    if (MODE == AB_DQ) v = *(const uint4*)(p.qkv + (t0 + tok) * p.ldq + (nh + kvh) * 128 + n0 + nc);
-                    else if (MODE == AB_DV) v = *(const uint4*)(p.dout + (t0 + tok) * p.ldo + h * 128 + n0 + nc);
-                    else v = *(const uint4*)(p.qkv + (t0 + tok) * p.ldq + h * 128 + n0 + nc);
-                }
-                const uint16_t* e = (const uint16_t*)&v;
+            *(uint4*)(As + row * AB_LD + kc) = v;
+        }
+        // ---- B tile: Bs[n][k]
+        if (MODE == AB_S || MODE == AB_DP) {                      // B(n = j, k = d): k-contiguous rows of K / V
+            const int row = tid >> 2, kc = (tid & 3) * 8;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            const int j = n0 + row;
+            if (j < L) v = *(const uint4*)(p.qkv + (t0 + j) * p.ldq + (MODE == AB_S ? nh + kvh : nh + nkv + kvh) * 128 + k0 + kc);
+            *(uint4*)(Bs + row * AB_LD + kc) = v;
+        } else {                                                  // dQ: B(n = d, k = token): n-contiguous rows of K
+            const int k = tid >> 3, nc = (tid & 7) * 8;
+            uint4 v = make_uint4(0, 0, 0, 0);
+            const int tok = k0 + k;
+            if (tok < L) v = *(const uint4*)(p.qkv + (t0 + tok) * p.ldq + (nh + kvh) * 128 + n0 + nc);
+            const uint16_t* e = (const uint16_t*)&v;
 #pragma unroll
-                for (int q = 0; q < 8; ++q) Bs[(nc + q) * AB_LD + k] = e[q];
-            }
-            __syncthreads();
+            for (int q = 0; q < 8; ++q) Bs[(nc + q) * AB_LD + k] = e[q];
+        }
+        __syncthreads();
 #pragma unroll
-            for (int kk = 0; kk < 2; ++kk) {
-                const bf16x8 a = *(const bf16x8*)(As + (32 * wm + (lane & 31)) * AB_LD + 16 * kk + 8 * (lane >> 5));
-                const bf16x8 b = *(const bf16x8*)(Bs + (32 * wn + (lane & 31)) * AB_LD + 16 * kk + 8 * (lane >> 5));
-                acc = mfma32<DT>(a, b, acc);
-            }
+        for (int kk = 0; kk < 2; ++kk) {
+            const bf16x8 a = *(const bf16x8*)(As + (32 * wm + (lane & 31)) * AB_LD + 16 * kk + 8 * (lane >> 5));
+            const bf16x8 b = *(const bf16x8*)(Bs + (32 * wn + (lane & 31)) * AB_LD + 16 * kk + 8 * (lane >> 5));
+            acc = mfma32<DT>(a, b, acc);
         }
     }
     // ---- store: acc[4g + j] <-> m = 32 wm + 8 g + 4 (lane >> 5) + j, n = 32 wn + (lane & 31)
@@ -808,14 +782,12 @@ __global__ __launch_bounds__(256) void attn_bgemm_kernel(AttnBwdParams p, int Lm
             if (MODE == AB_S) {            // P = exp(scale * q.k - lse) on the visible keys j <= i (the forward's softmax, re-materialised)
                 const bool vis = n <= m && n < L && p.key_visible[t0 + n];
                 const float pv = vis ? __expf(v * p.scale - p.lse[(t0 + m) * nh + hb]) : 0.f;
-                p.P16[mat + (int64_t)hb * Lm * Lm + (int64_t)m * Lm + n] = to16<DT>(pv);
+                p.P16[mat + (int64_t)m * Lm + n] = to16<DT>(pv);
             } else if (MODE == AB_DP) {    // dS = scale * P o (dP - D),  D = rowsum(dO o O) = rowsum(P o dP)
-                const int64_t at = mat + (int64_t)hb * Lm * Lm + (int64_t)m * Lm + n;
+                const int64_t at = mat + (int64_t)m * Lm + n;
                 const float pv = from16<DT>(p.P16[at]);
                 p.dS16[at] = to16<DT>(p.scale * pv * (v - p.D[(t0 + m) * nh + hb]));
-            } else if (MODE == AB_DQ) p.dqkv[(t0 + m) * p.ldq + hb * 128 + n] = v;
-            else if (MODE == AB_DK) p.dqkv[(t0 + m) * p.ldq + (nh + kvh) * 128 + n] = v;
-            else p.dqkv[(t0 + m) * p.ldq + (nh + nkv + kvh) * 128 + n] = v;
+            } else p.dqkv[(t0 + m) * p.ldq + hb * 128 + n] = v;
         }
 }
 

@@ -58,6 +58,14 @@ class AttentionArgs(C.Structure):
                 ("pc_n_slots", C.c_int32), ("pc_max_len", C.c_int32)]
 
 
+class AttentionBwdArgs(C.Structure):
+    """blim_attention_bwd_args (include/blim.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("qkv", C.c_void_p), ("ldq", C.c_int64), ("dout", C.c_void_p), ("ldo", C.c_int64), ("o16", C.c_void_p),
+                ("ldo16", C.c_int64), ("lse", C.c_void_p), ("num_heads", C.c_int32), ("num_kv_heads", C.c_int32), ("dtype16", C.c_int32),
+                ("key_visible", C.c_void_p), ("seq_start", C.c_void_p), ("seq_len", C.c_void_p), ("n_seqs", C.c_int32), ("max_len", C.c_int32),
+                ("scale", C.c_float), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("dqkv", C.c_void_p), ("n_tokens", C.c_int64)]
+
+
 class GemmArgs(C.Structure):
     """blim_gemm_args (include/blim.h)."""
     _fields_ = [("struct_bytes", C.c_int64), ("epi", C.c_int32), ("dtype", C.c_int32), ("A", C.c_void_p), ("lda", C.c_int64), ("W", C.c_void_p),
@@ -132,6 +140,9 @@ def load_library(path: str = LIB_PATH):
         "blim_quant_rows": ([vp, i64, i64, i32, i32, vp, vp, vp], C.c_int),
         "blim_gemm_f8": ([vp, i64, vp, vp, vp, i32, i32, i32, vp, i64, vp], C.c_int),
         "blim_attention": ([C.POINTER(AttentionArgs), vp], C.c_int),
+        "blim_attention_bwd_workspace_bytes": ([i64, i32, i32, i32], C.c_int64),
+        "blim_attention_bwd": ([C.POINTER(AttentionBwdArgs), vp], C.c_int),
+        "blim_rope_bwd": ([vp, vp, i64, i32, i32, vp, vp, vp, i32, i32, vp], C.c_int),
         "blim_gemm": ([C.POINTER(GemmArgs), vp], C.c_int),
         "blim_rope_rows_bytes": ([i32], C.c_int64),
         "blim_rope_rows": ([vp, i64, f32, i32, vp, vp, i64, vp], C.c_int),
@@ -703,6 +714,40 @@ def attention(qkv, batch: PackedBatch, num_heads: int, num_kv_heads: int, out, s
     a.pc_n_slots = pc_n_slots; a.pc_max_len = pc_max_len
     _check(lib.blim_attention(C.byref(a), _stream()), "blim_attention")
     return out
+
+
+def attention_bwd_workspace_bytes(n_tokens: int, n_seqs: int, num_heads: int, max_len: int) -> int:
+    return int(load_library().blim_attention_bwd_workspace_bytes(n_tokens, n_seqs, num_heads, max_len))
+
+
+def attention_bwd(qkv, dout, o16, lse, batch: PackedBatch, num_heads: int, num_kv_heads: int, max_len: int, dqkv, workspace, scale: float = 128 ** -0.5):
+    """The trainer's attention backward alone (blim_attention_bwd): qkv / dout / o16 16-bit [T, ld*] (the row strides are the tensors' widths), lse f32
+    [T, num_heads]; batch gives key_visible, seq_start, seq_len (no prefixes); dqkv f32 [T, ldq] is written in place on the sequences' rows; workspace: a uint8
+    tensor of attention_bwd_workspace_bytes(T, n_seqs, num_heads, max_len) bytes or more.  The fields are blim.h's blim_attention_bwd_args."""
+    import torch
+    lib = load_library()
+    assert qkv.dim() == 2 and dout.dim() == 2 and o16.dim() == 2 and dqkv.shape == qkv.shape and dqkv.dtype == torch.float32 and lse.dtype == torch.float32
+    assert qkv.dtype == dout.dtype == o16.dtype and qkv.dtype in (torch.bfloat16, torch.float16) and workspace.dtype == torch.uint8
+    a = AttentionBwdArgs()
+    a.struct_bytes = C.sizeof(AttentionBwdArgs)
+    a.qkv = _ptr(qkv); a.ldq = qkv.shape[1]; a.dout = _ptr(dout); a.ldo = dout.shape[1]; a.o16 = _ptr(o16); a.ldo16 = o16.shape[1]; a.lse = _ptr(lse)
+    a.num_heads = num_heads; a.num_kv_heads = num_kv_heads; a.dtype16 = COMPUTE_DTYPES["bf16" if qkv.dtype == torch.bfloat16 else "f16"]
+    a.key_visible = _ptr(batch.key_visible); a.seq_start = _ptr(batch.seq_start); a.seq_len = _ptr(batch.seq_len); a.n_seqs = batch.n_seqs; a.max_len = max_len
+    a.scale = scale; a.workspace = _ptr(workspace); a.workspace_bytes = workspace.numel(); a.dqkv = _ptr(dqkv); a.n_tokens = qkv.shape[0]
+    _check(lib.blim_attention_bwd(C.byref(a), _stream()), "blim_attention_bwd")
+    return dqkv
+
+
+def rope_bwd(dqkv, rope_cols: int, positions, cos, sin, out16):
+    """blim_rope_bwd: dqkv f32 [T, qkv_n] -> out16 16-bit [T, qkv_n] (written in place), the inverse rotation on the columns < rope_cols; positions int32 [T],
+    cos / sin f32 [n_pos, 64], all on the device."""
+    import torch
+    lib = load_library()
+    assert dqkv.dim() == 2 and dqkv.dtype == torch.float32 and out16.dtype in (torch.bfloat16, torch.float16) and out16.numel() >= dqkv.numel()
+    assert cos.shape == sin.shape and cos.shape[1] == 64 and cos.dtype == sin.dtype == torch.float32 and positions.dtype == torch.int32
+    _check(lib.blim_rope_bwd(_ptr(out16), _ptr(dqkv), dqkv.shape[0], dqkv.shape[1], rope_cols, _ptr(positions), _ptr(cos), _ptr(sin), cos.shape[0],
+                             COMPUTE_DTYPES["bf16" if out16.dtype == torch.bfloat16 else "f16"], _stream()), "blim_rope_bwd")
+    return out16
 
 
 _GEMM_POINTERS = ("bias", "resid_in", "rope_rows", "labels", "lse_part", "label_logit", "row_scale", "col_scale", "a_mx", "out8", "out_mx", "A6", "W6", "out6",

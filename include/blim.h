@@ -317,6 +317,44 @@ typedef struct blim_attention_args {
 } blim_attention_args;
 int blim_attention(const blim_attention_args* args, void* stream);
 
+/* The trainer's attention backward alone (tests; additive in ABI v9): the kernels of csrc/train_kernels.hip over materialised scores, chosen by the fields the
+ * trainer sets (csrc/train.hpp: AttnBwdParams).  Sequences have no shared prefix: token i of sequence s is row seq_start[s] + i, query i sees the keys j <= i with
+ * key_visible != 0.  qkv 16-bit [n_tokens, ldq] rows [q heads | k heads | v heads], head_dim 128, RoPE applied; dout 16-bit [n_tokens, ldo] = d(attention
+ * output), q-head major; o16 16-bit [n_tokens, ldo16] = the forward's output; lse f32 [n_tokens, num_heads] = the forward's lse_out.  key_visible, seq_start,
+ * seq_len: device arrays as in blim_batch; max_len >= the longest seq_len (device data: the library cannot check it).  dqkv f32 [n_tokens, ldq] receives the
+ * gradient w.r.t. the post-RoPE q | k | v on the rows of the sequences, columns < (num_heads + 2 num_kv_heads) * 128; nothing else is written.
+ * workspace: blim_attention_bwd_workspace_bytes(...) bytes, caller-owned, 16-byte aligned, contents on entry irrelevant -- D f32 [n_tokens, num_heads] rounded up to
+ * 16 bytes, then P16 and dS16, 16-bit [n_seqs][num_heads][Lm][Lm] each, Lm = round_up(max_len, 64); -1 for arguments out of range (n_seqs * num_heads > 65535
+ * among them).  struct_bytes = sizeof(blim_attention_bwd_args). */
+typedef struct blim_attention_bwd_args {
+    int64_t struct_bytes;
+    const void* qkv;
+    int64_t ldq;
+    const void* dout;
+    int64_t ldo;
+    const void* o16;
+    int64_t ldo16;
+    const float* lse;
+    int32_t num_heads, num_kv_heads;
+    int32_t dtype16;       /* BLIM_COMPUTE_BF16 / BLIM_COMPUTE_F16 */
+    const uint8_t* key_visible;
+    const int32_t* seq_start;
+    const int32_t* seq_len;
+    int32_t n_seqs, max_len;
+    float scale;           /* 1 / sqrt(128) in the trainer */
+    void* workspace;
+    int64_t workspace_bytes;
+    float* dqkv;
+    int64_t n_tokens;
+} blim_attention_bwd_args;
+int64_t blim_attention_bwd_workspace_bytes(int64_t n_tokens, int32_t n_seqs, int32_t num_heads, int32_t max_len);
+int blim_attention_bwd(const blim_attention_bwd_args* args, void* stream);
+/* The RoPE backward that follows it (tests): out16 16-bit [n_tokens, qkv_n] = the inverse rotation of dqkv f32 [n_tokens, qkv_n] on the columns < rope_cols
+ * (pairs d, d + 64 of every 128-wide head), the plain 16-bit rounding beyond.  cos / sin: device arrays f32 [n_pos, 64]; the row of token t is
+ * min(max(positions[t], 0), n_pos - 1).  qkv_n and rope_cols are multiples of 128, rope_cols <= qkv_n. */
+int blim_rope_bwd(void* out16, const float* dqkv, int64_t n_tokens, int32_t qkv_n, int32_t rope_cols, const int32_t* positions, const float* cos, const float* sin,
+                  int32_t n_pos, int32_t dtype16, void* stream);
+
 /* The GEMM kernel alone (tests; additive in ABI v9): C [M, N] = A [M, K] . W [N, K]^T with every epilogue and operand form the engine and the trainer launch,
  * chosen by the same fields they set (csrc/gemm.hpp states them; a zero / NULL field is "off").  A: row stride lda, W: row stride K (w_wrap_k when set).
  * dtype BLIM_COMPUTE_BF16 / _F16: A, W and 16-bit outputs in that format; BLIM_COMPUTE_F8: A, W e4m3 bytes with row_scale [M] (or the E8M0 table a_mx) and

@@ -169,6 +169,93 @@ static void attention_calls() {
     EXPECT(blim_attention(&a, nullptr) == BLIM_ERR_ARG);
 }
 
+// the engine-less attention backward and RoPE backward: the good call, then every refusal of both entries
+static void attention_bwd_calls() {
+    const int T = 150, nh = 4, nkv = 2, qn = (nh + 2 * nkv) * 128, hn = nh * 128, n_seqs = 2, max_len = 70;
+    std::vector<uint16_t> qkv((size_t)T * (qn + 8), 0), dout((size_t)T * (hn + 8), 0), o16((size_t)T * (hn + 2), 0), out16((size_t)T * qn, 0);
+    std::vector<float> lse((size_t)T * nh, 0.f), dqkv((size_t)T * (qn + 8), 0.f), cs((size_t)32 * 64, 1.f), sn((size_t)32 * 64, 0.f);
+    std::vector<uint8_t> vis(T, 1);
+    std::vector<int32_t> start = {3, 80}, len = {70, 33}, pos(T, 5);
+    const int64_t need = blim_attention_bwd_workspace_bytes(T, n_seqs, nh, max_len);
+    EXPECT(need == (int64_t)T * nh * 4 + 2 * ((int64_t)n_seqs * nh * 128 * 128 * 2) && blim_attention_bwd_workspace_bytes(271, 3, 7, 193) % 16 == 0);
+    EXPECT(blim_attention_bwd_workspace_bytes(271, 3, 7, 193) == 7600 + 2 * ((int64_t)3 * 7 * 256 * 256 * 2));              // D of 7588 bytes rounded up to 16
+    EXPECT(blim_attention_bwd_workspace_bytes(T, 16384, nh, max_len) == -1 && blim_attention_bwd_workspace_bytes(T, 1 << 30, 1 << 30, 1 << 20) == -1);
+    EXPECT(blim_attention_bwd_workspace_bytes(0, n_seqs, nh, max_len) == -1 && blim_attention_bwd_workspace_bytes(T, 0, nh, max_len) == -1);
+    EXPECT(blim_attention_bwd_workspace_bytes(T, n_seqs, 0, max_len) == -1 && blim_attention_bwd_workspace_bytes(T, n_seqs, nh, 0) == -1);
+    std::vector<uint8_t> ws_mem((size_t)need + 16, 0xFF);
+    uint8_t* const ws = ws_mem.data() + (16 - ((uintptr_t)ws_mem.data() & 15)) % 16;
+    blim_attention_bwd_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_bytes = sizeof a; a.qkv = qkv.data(); a.ldq = qn + 8; a.dout = dout.data(); a.ldo = hn + 8; a.o16 = o16.data(); a.ldo16 = hn + 2; a.lse = lse.data();
+    a.num_heads = nh; a.num_kv_heads = nkv; a.dtype16 = BLIM_COMPUTE_F16; a.key_visible = vis.data(); a.seq_start = start.data(); a.seq_len = len.data();
+    a.n_seqs = n_seqs; a.max_len = max_len; a.scale = 0.0883883f; a.workspace = ws; a.workspace_bytes = need; a.dqkv = dqkv.data(); a.n_tokens = T;
+    const blim_attention_bwd_args good = a;
+    EXPECT(blim_attention_bwd(&a, nullptr) == 0);
+    a.dtype16 = BLIM_COMPUTE_BF16;
+    EXPECT(blim_attention_bwd(&a, nullptr) == 0);
+    // ---- refusals
+    EXPECT(blim_attention_bwd(nullptr, nullptr) == BLIM_ERR_ARG);
+    a = good; a.struct_bytes = 8;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.qkv = nullptr;          EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.dout = nullptr;         EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.o16 = nullptr;          EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.lse = nullptr;          EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.key_visible = nullptr;  EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.seq_start = nullptr;    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.seq_len = nullptr;      EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.workspace = nullptr;    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.dqkv = nullptr;         EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.dtype16 = BLIM_COMPUTE_F8;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.num_heads = 3;                                                                        // num_heads % num_kv_heads
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.num_kv_heads = 0;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.ldq = qn + 4;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.ldo = hn + 4;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.ldo16 = hn + 1;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.ldq = qn - 8;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "row stride"));
+    a = good; a.ldo = hn - 8;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "row stride"));
+    a = good; a.ldo16 = hn - 2;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "row stride"));
+    a = good; a.max_len = 0;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.n_seqs = 0;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.n_tokens = 0;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.n_seqs = 16384;                                                                       // 16384 x 4 heads > 65535: the grid's z range
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "z range"));
+    a = good; a.workspace = ws + 4; a.workspace_bytes = need - 4;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "aligned"));
+    a = good; a.workspace_bytes = need - 2;
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+    a = good; a.max_len = 129;                                                                        // Lm 128 -> 192: the same workspace is too small now
+    EXPECT(blim_attention_bwd(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+    // ---- blim_rope_bwd
+    const int rc = (nh + nkv) * 128;
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, rc, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_F16, nullptr) == 0);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, 0, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_BF16, nullptr) == 0);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, qn, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_BF16, nullptr) == 0);
+    EXPECT(blim_rope_bwd(nullptr, dqkv.data(), T, qn, rc, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), nullptr, T, qn, rc, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, rc, nullptr, cs.data(), sn.data(), 32, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, rc, pos.data(), nullptr, sn.data(), 32, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, rc, pos.data(), cs.data(), nullptr, 32, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), 0, qn, rc, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, rc, pos.data(), cs.data(), sn.data(), 0, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, rc, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_F8, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn + 64, rc, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, rc + 64, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rope_bwd(out16.data(), dqkv.data(), T, qn, qn + 128, pos.data(), cs.data(), sn.data(), 32, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "rope_cols"));
+}
+
 // the engine-less GEMM entry and blim_rope_rows: one good call of every form, then the argument errors they report themselves
 static void gemm_calls() {
     const int M = 300, N = 512, K = 128;
@@ -294,6 +381,7 @@ static void gemm_calls() {
 int main() {
     EXPECT(blim_abi_version() == BLIM_ABI_VERSION);
     attention_calls();
+    attention_bwd_calls();
     gemm_calls();
     blim_engine* e = nullptr;
     // ---- creation: bad configurations, no device
