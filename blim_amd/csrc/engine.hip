@@ -1465,6 +1465,95 @@ static int pc_admit_finish(blim_engine* e, blim_prefix_cache* pc, const blim_pc_
     return BLIM_OK;
 }
 
+// Slot export / import (blim.h: blim_prefix_cache_export / _import).  pc_moves_check is what the two share: every check that needs host values only, before anything
+// is launched -> the moves as launch_slot_pack takes them.  `tickets` given: an import (the ticket's magic, geometry and length are checked too).
+static int64_t pc_record_bytes(const blim_prefix_cache* pc, int64_t len) {
+    return round_up(((int64_t)pc->e->c.num_layers * len * pc->kv_w + pc->hid_w) * 2, 256);
+}
+extern "C" int64_t blim_prefix_cache_record_bytes(const blim_prefix_cache* pc, int32_t len) {
+    if (!pc || len < 1 || len > pc->max_len) return -1;
+    return pc_record_bytes(pc, len);
+}
+static int pc_moves_check(const char* what, blim_engine* e, blim_prefix_cache* pc, const blim_pc_move* moves, int32_t n, const void* staging, int64_t staging_bytes,
+                          const blim_pc_ticket* tickets, std::vector<int64_t>* mv) {
+    if (n < 1) { blim_set_error("prefix cache %s: n = %d moves (at least 1)", what, n); return BLIM_ERR_ARG; }
+    if (e->f8) { blim_set_error("prefix cache %s: fp8 engines are not supported", what); return BLIM_ERR_STATE; }
+    if (((uintptr_t)staging & 15) != 0 || staging_bytes < 0) { blim_set_error("prefix cache %s: staging must be 16-byte aligned", what); return BLIM_ERR_ARG; }
+    std::vector<char> seen(pc->n_slots, 0);
+    std::vector<std::pair<int64_t, int>> span((size_t)n);          // (offset, move), sorted below: neighbours must not overlap
+    for (int i = 0; i < n; ++i) {
+        const blim_pc_move& m = moves[i];
+        if (m.slot < 0 || m.slot >= pc->n_slots) { blim_set_error("prefix cache %s: slot %d of move %d outside 0 .. %d", what, m.slot, i, pc->n_slots - 1); return BLIM_ERR_ARG; }
+        if (seen[m.slot]) { blim_set_error("prefix cache %s: slot %d named twice (move %d)", what, m.slot, i); return BLIM_ERR_ARG; }
+        seen[m.slot] = 1;
+        if (m.offset < 0 || m.offset % 256) { blim_set_error("prefix cache %s: offset %lld of move %d is not a multiple of 256", what, (long long)m.offset, i); return BLIM_ERR_ARG; }
+        if (tickets) {
+            const blim_pc_ticket& t = tickets[i];
+            if (t.magic != BLIM_PC_TICKET_MAGIC) { blim_set_error("prefix cache %s: the ticket of move %d was not written by an export", what, i); return BLIM_ERR_ARG; }
+            if (t.num_layers != e->c.num_layers || t.kv_w != pc->kv_w || t.hid_w != pc->hid_w || t.n_bits < 0 || t.n_bits > BLIM_PC_TICKET_LAYERS) {
+                blim_set_error("prefix cache %s: the ticket of move %d has another geometry (%d layers, widths %d | %d; this cache: %d, %d | %d)", what, i, t.num_layers, t.kv_w,
+                               t.hid_w, e->c.num_layers, pc->kv_w, pc->hid_w);
+                return BLIM_ERR_ARG;
+            }
+            if (m.len < 1 || m.len > pc->max_len || m.len != t.len) {
+                blim_set_error("prefix cache %s: len %d of move %d (its ticket: %d) does not fit a slot of %d positions", what, m.len, i, t.len, pc->max_len);
+                return BLIM_ERR_ARG;
+            }
+        } else {
+            if (pc->len[m.slot] < 0) { blim_set_error("prefix cache %s: slot %d of move %d was never filled", what, m.slot, i); return BLIM_ERR_STATE; }
+            if (m.len != pc->len[m.slot]) { blim_set_error("prefix cache %s: len %d of move %d is not slot %d's filled length %d", what, m.len, i, m.slot, pc->len[m.slot]); return BLIM_ERR_ARG; }
+            if (pc->snap[m.slot].bits.size() > BLIM_PC_TICKET_LAYERS) { blim_set_error("prefix cache %s: a ticket holds the bits of %d layers at most", what, BLIM_PC_TICKET_LAYERS); return BLIM_ERR_STATE; }
+        }
+        if (m.offset > staging_bytes || pc_record_bytes(pc, m.len) > staging_bytes - m.offset) {
+            blim_set_error("prefix cache %s: the record of move %d (%lld bytes at %lld) does not fit the staging buffer's %lld bytes", what, i, (long long)pc_record_bytes(pc, m.len),
+                           (long long)m.offset, (long long)staging_bytes);
+            return BLIM_ERR_ARG;
+        }
+        span[i] = {m.offset, i};
+    }
+    std::sort(span.begin(), span.end());
+    for (int k = 1; k < n; ++k) {
+        const int a = span[k - 1].second, b = span[k].second;
+        if (span[k - 1].first + pc_record_bytes(pc, moves[a].len) > span[k].first) { blim_set_error("prefix cache %s: the records of moves %d and %d overlap", what, a, b); return BLIM_ERR_ARG; }
+    }
+    mv->resize(3 * (size_t)n);
+    for (int i = 0; i < n; ++i) { (*mv)[3 * (size_t)i] = moves[i].slot; (*mv)[3 * (size_t)i + 1] = moves[i].len; (*mv)[3 * (size_t)i + 2] = moves[i].offset; }
+    return BLIM_OK;
+}
+extern "C" int blim_prefix_cache_export(blim_engine* e, blim_prefix_cache* pc, const blim_pc_move* moves, int32_t n, void* staging, int64_t staging_bytes,
+                                        blim_pc_ticket* tickets_out, void* stream) {
+    ARG_CHECK(e && pc && pc->e == e && moves && staging && tickets_out);
+    std::vector<int64_t> mv;
+    TRY(pc_moves_check("export", e, pc, moves, n, staging, staging_bytes, nullptr, &mv));
+    TRY(launch_slot_pack(mv.data(), n, 1, (uint16_t*)pc->kv, (uint16_t*)pc->hid, (uint8_t*)staging, e->c.num_layers, pc->max_len, pc->kv_w, pc->hid_w, (hipStream_t)stream));
+    for (int i = 0; i < n; ++i) {                  // the tickets: host values the cache already holds
+        const PcSnap& sn = pc->snap[moves[i].slot];
+        blim_pc_ticket& t = tickets_out[i];
+        memset(&t, 0, sizeof t);
+        t.magic = BLIM_PC_TICKET_MAGIC; t.len = moves[i].len; t.num_layers = e->c.num_layers; t.kv_w = pc->kv_w; t.hid_w = pc->hid_w;
+        t.precise = sn.precise; t.embeds = sn.embeds; t.mlp = sn.mlp; t.layers = sn.layers; t.lo6 = sn.lo6; t.mqz = sn.mqz; t.epoch = sn.epoch;
+        t.n_bits = (int32_t)sn.bits.size();
+        if (t.n_bits) memcpy(t.bits, sn.bits.data(), sn.bits.size());
+    }
+    return BLIM_OK;
+}
+extern "C" int blim_prefix_cache_import(blim_engine* e, blim_prefix_cache* pc, const blim_pc_move* moves, int32_t n, const void* staging, int64_t staging_bytes,
+                                        const blim_pc_ticket* tickets, void* stream) {
+    ARG_CHECK(e && pc && pc->e == e && moves && staging && tickets);
+    std::vector<int64_t> mv;
+    TRY(pc_moves_check("import", e, pc, moves, n, staging, staging_bytes, tickets, &mv));
+    for (int i = 0; i < n; ++i) pc->len[moves[i].slot] = -1;          // a failed import leaves its slots empty
+    TRY(launch_slot_pack(mv.data(), n, 0, (uint16_t*)pc->kv, (uint16_t*)pc->hid, (uint8_t*)staging, e->c.num_layers, pc->max_len, pc->kv_w, pc->hid_w, (hipStream_t)stream));
+    for (int i = 0; i < n; ++i) {                  // the ticket's state, not the engine's: pc_check_read stays the one place that refuses a stale slot
+        const blim_pc_ticket& t = tickets[i];
+        PcSnap sn;
+        sn.epoch = t.epoch; sn.precise = t.precise; sn.embeds = t.embeds; sn.mlp = t.mlp; sn.layers = t.layers; sn.lo6 = t.lo6; sn.mqz = t.mqz;
+        sn.bits.assign(t.bits, t.bits + t.n_bits);
+        pc->len[moves[i].slot] = t.len; pc->snap[moves[i].slot] = sn;
+    }
+    return BLIM_OK;
+}
+
 // ---------------------------------------------------------------------------- fused scoring
 // blim_score_vtg (pc == nullptr), or the same over cached video prefixes: the lease and the gather of the slots' rows around the same three calls
 static int score_vtg_impl(blim_engine* e, blim_prefix_cache* pc, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used, const blim_batch* b,

@@ -271,6 +271,52 @@ int launch_rows_by_index(uint16_t* dst, int64_t ld_dst, const uint16_t* src, int
     return BLIM_OK;
 }
 
+// Slot export / import (kernels.hpp: launch_slot_pack).  blockIdx.y is the move; the blocks of a row walk the record's 16-byte chunks in a grid-stride loop: chunk j of
+// the K / V part is (layer, r) with r = pos * kv_w8 + c, contiguous in the record and at layer * max_len * kv_w8 + r in the slot; the hidden row follows.  All
+// indices are 64-bit.  Plain loads and stores: no LDS, no scratch.
+struct SlotMoveChunk { int64_t q[ADMIT_CHUNK][3]; };       // {slot, len, record offset in 16-byte chunks}
+__global__ void slot_pack_kernel(SlotMoveChunk mv, int to_record, uint4* kv, uint4* hid, uint4* rec, int64_t num_layers, int64_t max_len, int64_t kv_w8, int64_t hid_w8) {
+    const int64_t slot = mv.q[blockIdx.y][0], len = mv.q[blockIdx.y][1];
+    uint4* r = rec + mv.q[blockIdx.y][2];
+    uint4* k = kv + slot * num_layers * max_len * kv_w8;
+    uint4* h = hid + slot * hid_w8;
+    const int64_t per_layer = len * kv_w8;
+    const int64_t n_kv = num_layers * per_layer;
+    const int64_t total = n_kv + hid_w8;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < total; j += stride) {
+        uint4* c;
+        if (j < n_kv) {
+            const int64_t layer = j / per_layer;
+            c = k + layer * max_len * kv_w8 + (j - layer * per_layer);
+        } else {
+            c = h + (j - n_kv);
+        }
+        if (to_record) r[j] = *c; else *c = r[j];
+    }
+}
+int launch_slot_pack(const int64_t* mv_host, int n_moves, int to_record, uint16_t* kv, uint16_t* hid, uint8_t* rec, int num_layers, int max_len, int kv_w, int hid_w,
+                     hipStream_t s) {
+    ARG_CHECK(mv_host && n_moves > 0 && kv && hid && rec && num_layers > 0 && max_len > 0 && kv_w > 0 && hid_w > 0 && kv_w % 8 == 0 && hid_w % 8 == 0);
+    ARG_CHECK(((uintptr_t)rec & 15) == 0 && ((uintptr_t)kv & 15) == 0 && ((uintptr_t)hid & 15) == 0);
+    for (int m0 = 0; m0 < n_moves; m0 += ADMIT_CHUNK) {
+        SlotMoveChunk c;
+        const int n = n_moves - m0 < ADMIT_CHUNK ? n_moves - m0 : ADMIT_CHUNK;
+        int64_t most = 0;
+        for (int m = 0; m < ADMIT_CHUNK; ++m) {
+            const int64_t* q = mv_host + 3 * (size_t)(m0 + (m < n ? m : 0));
+            ARG_CHECK(q[0] >= 0 && q[1] >= 1 && q[1] <= max_len && q[2] >= 0 && q[2] % 16 == 0);
+            c.q[m][0] = q[0]; c.q[m][1] = q[1]; c.q[m][2] = q[2] / 16;
+            const int64_t chunks = (int64_t)num_layers * q[1] * (kv_w / 8) + hid_w / 8;
+            if (m < n && chunks > most) most = chunks;
+        }
+        hipLaunchKernelGGL(slot_pack_kernel, dim3(grid_for(most, 256, 2048), n), dim3(256), 0, s, c, to_record, (uint4*)kv, (uint4*)hid, (uint4*)rec, (int64_t)num_layers,
+                           (int64_t)max_len, (int64_t)(kv_w / 8), (int64_t)(hid_w / 8));
+        LAUNCH_CHECK(to_record ? "slot_pack" : "slot_unpack");
+    }
+    return BLIM_OK;
+}
+
 // ---------------------------------------------------------------------------- RMSNorm (K3/K9)
 // One wave per row; the row (H f32) is read once in float4 pieces and kept in registers when H <= 64*4*16.
 template <int MAXV, int DT>

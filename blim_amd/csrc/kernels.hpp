@@ -24,6 +24,13 @@ int launch_kv_capture(const bf16_t* qkv, int64_t ldq, int64_t col, int64_t src_l
 // map[t] = slot * max_len + (t - start) for start <= t < start + len, map[n_tokens + r] = slot for r == row, -1 elsewhere; map (DEVICE) holds n_tokens + n_rows entries.
 #define ADMIT_CHUNK 48
 int launch_admit_map(const int32_t* adm_host, int n_admit, int32_t* map, int64_t n_tokens, int64_t n_rows, int max_len, hipStream_t s);
+// Slot export / import (blim.h: blim_prefix_cache_export / _import): a slot's filled positions and its hidden row, packed as one record [layer][pos < len][kv_w] |
+// [hid_w] 16-bit values at rec + offset, or unpacked from it (to_record = 0).  mv_host [n_moves][3] = {slot, len, record offset in bytes} (HOST: the values travel
+// as kernel arguments, ADMIT_CHUNK moves per launch, as launch_admit_map's do).  Byte copies in 16-byte chunks: kv_w, hid_w multiples of 8 values, rec and the offsets
+// multiples of 16 bytes.  A launch writes the named records' bytes (export) or the named slots' positions < len and hidden rows (import), nothing else; the caller has
+// checked slot < n_slots, 1 <= len <= max_len and the records' place in the staging buffer.
+int launch_slot_pack(const int64_t* mv_host, int n_moves, int to_record, uint16_t* kv, uint16_t* hid, uint8_t* rec, int num_layers, int max_len, int kv_w, int hid_w,
+                     hipStream_t s);
 // 16-bit row copies by index, `width` values per row (a multiple of 8).  gather = 0: dst[idx[r]] = src[r] for 0 <= idx[r] < n_bound (the cached hidden rows of a fill);
 // gather = 1: for idx[r] < 0, dst[r] = src[-(idx[r] + 1)] when that is < n_bound, else `fill` words (a poisoned score); rows with idx[r] >= 0 are left alone
 int launch_rows_by_index(uint16_t* dst, int64_t ld_dst, const uint16_t* src, int64_t ld_src, const int32_t* idx, int64_t n_rows, int width, int64_t n_bound, int gather,

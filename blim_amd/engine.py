@@ -10,7 +10,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 import re
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -164,6 +164,9 @@ def load_library(path: str = LIB_PATH):
         "blim_score_tvg_cached": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp], C.c_int),
         "blim_score_vtg_admit": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, i32, vp, vp, vp, i64, vp, i32, vp, vp], C.c_int),
         "blim_score_tvg_admit": ([vp, vp, C.POINTER(Batch), vp, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, vp], C.c_int),
+        "blim_prefix_cache_record_bytes": ([vp, i32], C.c_int64),
+        "blim_prefix_cache_export": ([vp, vp, vp, i32, vp, i64, vp, vp], C.c_int),
+        "blim_prefix_cache_import": ([vp, vp, vp, i32, vp, i64, vp, vp], C.c_int),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -578,6 +581,29 @@ class Engine:
         return {self.lib.blim_timing_class_name(i).decode(): {"ms": ms[i], "calls": int(calls[i]), "flops": fl[i]} for i in range(n)}
 
 
+PC_TICKET_LAYERS = 256
+
+
+class PcMove(C.Structure):
+    """blim.h: blim_pc_move."""
+    _fields_ = [("slot", C.c_int32), ("len", C.c_int32), ("offset", C.c_int64)]
+
+
+class PcTicket(C.Structure):
+    """blim.h: blim_pc_ticket -- what an exported slot needs to come back: its length, the state it was computed under, the record's geometry."""
+    _fields_ = [("magic", C.c_uint32), ("len", C.c_int32), ("num_layers", C.c_int32), ("kv_w", C.c_int32), ("hid_w", C.c_int32),
+                ("precise", C.c_int32), ("embeds", C.c_int32), ("mlp", C.c_int32), ("layers", C.c_int32), ("lo6", C.c_int32), ("mqz", C.c_int32), ("n_bits", C.c_int32),
+                ("epoch", C.c_uint64), ("bits", C.c_uint8 * PC_TICKET_LAYERS)]
+
+
+def _pc_moves(moves):
+    """[(slot, len, offset)] -> a blim_pc_move array."""
+    arr = (PcMove * max(len(moves), 1))()
+    for k, (slot, ln, off) in enumerate(moves):
+        arr[k].slot, arr[k].len, arr[k].offset = int(slot), int(ln), int(off)
+    return arr
+
+
 class PrefixCache:
     """Device-resident K / V + last-row hidden state of prefixes (blim.h: blim_prefix_cache_*), one slot per prefix: VTG video prefixes or TVG caption prompts."""
 
@@ -609,6 +635,33 @@ class PrefixCache:
 
     def slot_len(self, slot: int) -> int:
         return int(self.lib.blim_prefix_cache_slot_len(self.h, int(slot)))
+
+    # ---- slot export / import (blim.h: blim_prefix_cache_export / _import; blim_amd/gallery.py: HostTier)
+    def record_bytes(self, length: int) -> int:
+        """Bytes of the packed record of a slot with `length` filled positions (a multiple of 256; -1: length outside 1 .. max_len)."""
+        return int(self.lib.blim_prefix_cache_record_bytes(self.h, int(length)))
+
+    def export_slots(self, moves, staging) -> List["PcTicket"]:
+        """moves [(slot, len, offset)]: each slot's packed record is written at `offset` bytes into staging (device uint8) -> one ticket per move, for import_slots.
+        Stream-ordered; never waits for the device."""
+        mv, tk = _pc_moves(moves), (PcTicket * max(len(moves), 1))()
+        _check(self.lib.blim_prefix_cache_export(self.engine.h, self.h, mv, len(moves), _ptr(staging), staging.numel() * staging.element_size(), tk, _stream()),
+               "blim_prefix_cache_export")
+        out = []
+        for k in range(len(moves)):
+            t = PcTicket()
+            C.memmove(C.byref(t), C.byref(tk[k]), C.sizeof(PcTicket))
+            out.append(t)
+        return out
+
+    def import_slots(self, moves, staging, tickets):
+        """The reverse: the records at the moves' offsets in staging become the moves' slots, under the state their tickets recorded."""
+        assert len(tickets) == len(moves)
+        mv, tk = _pc_moves(moves), (PcTicket * max(len(moves), 1))()
+        for k, t in enumerate(tickets):
+            C.memmove(C.byref(tk[k]), C.byref(t), C.sizeof(PcTicket))
+        _check(self.lib.blim_prefix_cache_import(self.engine.h, self.h, mv, len(moves), _ptr(staging), staging.numel() * staging.element_size(), tk, _stream()),
+               "blim_prefix_cache_import")
 
     def score_vtg(self, batch: PackedBatch, pfx_slot, slots_used, embeds, rows, labels, row_start, admits=None):
         """blim_score_vtg_cached: pfx_slot device int32 [n_seqs] (-1: in-batch prefix); slots_used host ints (every slot read); rows[r] < 0: slot -(rows[r] + 1)'s hidden row.

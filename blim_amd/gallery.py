@@ -17,7 +17,8 @@ mode change.
 
 `fill="lazy"` fills nothing up front: the budget is a capacity, and a prefix that a scoring call had to pack anyway (a miss) is captured into a
 slot by that very call (`blim_score_*_admit`), so the calls after it read it.  Which slot is decided per pass -- one vtg_pairs / tvg_pairs call -- by a
-deterministic policy (`_PrefixIndex._begin_pass`): free slots first, then the least recently used slot whose key this pass does not need, else no admission.
+deterministic policy (`_PrefixIndex._begin_pass`): free slots first, then the least recently used slot whose key this pass does not need, else no admission.  `host_budget_bytes` (lazy fill) puts a `HostTier` under the cache: a key that loses its slot is kept as a packed record
+in pinned host memory, and a key that has a record gets a slot back by a copy (blim.h: blim_prefix_cache_export / _import) instead of a decode.
 """
 from __future__ import annotations
 
@@ -68,6 +69,140 @@ class GalleryStats:
 
 
 @dataclass
+class HostStats:
+    """What a host tier did: slots restored from a record, slots spilled into one, records given up (to make room, or because the weights or the mode changed),
+    and the bytes copied each way."""
+    restored: int = 0
+    spilled: int = 0
+    dropped: int = 0
+    bytes_to_host: int = 0
+    bytes_from_host: int = 0
+
+    def as_dict(self) -> Dict[str, int]:
+        return asdict(self)
+
+
+def _pinned_bytes(n: int):
+    import torch
+    return torch.empty(int(n), dtype=torch.uint8, pin_memory=True)
+
+
+def _device_bytes(n: int, device):
+    import torch
+    return torch.empty(int(n), dtype=torch.uint8, device=device)
+
+
+def _device_sync():
+    import torch
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+
+
+class HostTier:
+    """The lazy index's second tier: slots that lose their place in the prefix cache are kept as packed records (blim.h:
+    blim_prefix_cache_export) in pinned host memory, and a key with a record gets its slot back by a copy (blim_prefix_cache_import) instead of a decode.
+
+    arena: pinned uint8, host_budget_bytes cut into fixed records of record_bytes(positions) -- a slot of any filled length fits one; only the bytes of the slot's own
+    record are copied.  staging: device uint8 of stage_records records, what the two entry points write and read; a transfer of more slots goes in chunks.  Every copy
+    is copy_(non_blocking=True) on the current stream -- the one the scoring calls run on -- so that the reuse of a record, of the staging buffer and the calls that read
+    a restored slot are ordered by that stream alone, and the host never reads the arena.  One ticket per record.  The tier is inclusive: a record stays valid after
+    its key was restored, and a slot that has one is not exported again."""
+
+    def __init__(self, cache, positions: int, host_budget_bytes: int, stage_records: int = 16, arena=None, staging=None, sync=None):
+        self.record_bytes = int(cache.record_bytes(int(positions)))
+        if self.record_bytes <= 0:
+            raise ValueError(f"HostTier: the cache has no record of {positions} positions")
+        self.n_records = max(int(host_budget_bytes), 0) // self.record_bytes
+        self.stage_records = max(1, min(int(stage_records), max(self.n_records, 1)))
+        self.stats = HostStats()
+        self.rec_of: Dict = {}           # key -> its record
+        self.key_of: Dict[int, object] = {}
+        self.len_of: Dict[int, int] = {}
+        self.tickets: Dict[int, object] = {}
+        self._stamp: Dict = {}           # key -> its last use, as the index stamps it
+        self._sync = sync if sync is not None else _device_sync
+        self.arena = self.staging = None
+        if self.n_records:
+            self.arena = arena if arena is not None else _pinned_bytes(self.n_records * self.record_bytes)
+            if not self.arena.is_pinned():
+                raise ValueError("HostTier: the arena must be pinned host memory (a pageable copy would make every transfer wait for the device)")
+            if self.arena.numel() < self.n_records * self.record_bytes:
+                raise ValueError(f"HostTier: the arena holds {self.arena.numel()} bytes, {self.n_records} records need {self.n_records * self.record_bytes}")
+            self.staging = staging if staging is not None else _device_bytes(self.stage_records * self.record_bytes, cache.engine.device)
+
+    def has(self, key) -> bool:
+        return key in self.rec_of
+
+    def touch(self, key, stamp) -> None:
+        if key in self.rec_of:
+            self._stamp[key] = stamp
+
+    def plan_spills(self, victims: Sequence, protected) -> List[Tuple]:
+        """-> [(victim, record, the key that gives the record up or None)] for the victims that get a record, in their order: a free record, else the least recently
+        used record whose key is not in `protected`; a victim that finds neither is lost, as without a tier.  Nothing changes here."""
+        free = [r for r in range(self.n_records) if r not in self.key_of]
+        lru = sorted((k for k in self.rec_of if k not in protected), key=lambda k: self._stamp.get(k, (0, 0)))
+        out = []
+        for v in victims:
+            if free:
+                out.append((v, free.pop(0), None))
+            elif lru:
+                d = lru.pop(0)
+                out.append((v, self.rec_of[d], d))
+        return out
+
+    def _chunks(self, items):
+        for a in range(0, len(items), self.stage_records):
+            yield items[a:a + self.stage_records]
+
+    def spill(self, cache, items: Sequence[Tuple]) -> None:
+        """items [(key, slot, record, dropped key or None, stamp)]: the slots' records go to the arena.  A chunk is committed when its export has returned."""
+        rb = self.record_bytes
+        for part in self._chunks(list(items)):
+            moves = [(slot, cache.slot_len(slot), n * rb) for n, (_, slot, _, _, _) in enumerate(part)]
+            tickets = cache.export_slots(moves, self.staging)
+            for (key, slot, rec, dropped, stamp), (_, ln, off), t in zip(part, moves, tickets):
+                nb = cache.record_bytes(ln)
+                self.arena[rec * rb:rec * rb + nb].copy_(self.staging[off:off + nb], non_blocking=True)
+                if dropped is not None and self.rec_of.get(dropped) == rec:
+                    del self.rec_of[dropped]; self._stamp.pop(dropped, None)
+                    self.stats.dropped += 1
+                self.rec_of[key], self.key_of[rec], self.len_of[rec], self.tickets[rec], self._stamp[key] = rec, key, ln, t, stamp
+                self.stats.spilled += 1; self.stats.bytes_to_host += nb
+
+    def restore(self, cache, items: Sequence[Tuple], committed=None) -> None:
+        """items [(key, slot, stamp)]: the keys' records become the slots.  committed(key, slot, stamp) is called per key once its chunk's import has returned; a
+        failed import raises and commits nothing of its chunk."""
+        rb = self.record_bytes
+        for part in self._chunks(list(items)):
+            moves, tickets = [], []
+            for n, (key, slot, _) in enumerate(part):
+                rec = self.rec_of[key]
+                ln = self.len_of[rec]
+                nb = cache.record_bytes(ln)
+                self.staging[n * rb:n * rb + nb].copy_(self.arena[rec * rb:rec * rb + nb], non_blocking=True)
+                moves.append((slot, ln, n * rb)); tickets.append(self.tickets[rec])
+            cache.import_slots(moves, self.staging, tickets)
+            for (key, slot, stamp), (_, ln, _) in zip(part, moves):
+                self._stamp[key] = stamp
+                self.stats.restored += 1; self.stats.bytes_from_host += cache.record_bytes(ln)
+                if committed is not None:
+                    committed(key, slot, stamp)
+
+    def forget_all(self) -> None:
+        """A weight, adapter or mode change: no record is valid any more (the engine would refuse their slots as stale)."""
+        self.stats.dropped += len(self.rec_of)
+        self.rec_of, self.key_of, self.len_of, self.tickets, self._stamp = {}, {}, {}, {}, {}
+
+    def close(self) -> None:
+        """Copies into and out of the arena may still be in flight: the device is waited for before the memory goes."""
+        if self.arena is not None:
+            self._sync()
+        self.arena = self.staging = None
+        self.rec_of, self.key_of, self.len_of, self.tickets, self._stamp = {}, {}, {}, {}, {}
+
+
+@dataclass
 class _Pass:
     """One vtg_pairs / tvg_pairs call as the index sees it: the keys it needs in the order the planner meets them, and -- lazy fill -- the slot reserved for each
     miss that is admitted ({key: (slot, the key that loses it or None)}).  Nothing of it is part of the index's state until a call of the pass has returned."""
@@ -99,9 +234,14 @@ class _PrefixIndex:
     kind = ""              # "vtg" | "tvg": the calls whose prefixes the slots hold
     _changed = ""          # the refill's log line opens with it
 
-    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int], priority: Optional[Sequence[int]], log, fill: str = "eager"):
+    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int], priority: Optional[Sequence[int]], log, fill: str = "eager",
+                 host_budget_bytes: Optional[int] = None):
         if fill not in ("eager", "lazy"):
             raise ValueError(f"fill {fill!r}: 'eager' or 'lazy'")
+        if host_budget_bytes is not None and fill != "lazy":
+            raise ValueError(f"{type(self).__name__}: host_budget_bytes keeps the slots a lazy index evicts; an eager index ({fill!r}) evicts none: use fill='lazy'")
+        self.host_budget_bytes = host_budget_bytes
+        self.host: Optional[HostTier] = None         # lazy fill with host_budget_bytes: built with the cache
         if fill == "lazy" and priority is not None:
             raise ValueError(f"{type(self).__name__}: priority orders the eager fill; a lazy index follows the queries")
         self.fill = fill
@@ -166,6 +306,8 @@ class _PrefixIndex:
             self.n_slots = len(self.keys) if self.budget_bytes is None else min(len(self.keys), int(self.budget_bytes) // max(int(per), 1))
             if self.n_slots:
                 self.cache = self.engine.prefix_cache(self.n_slots, L, comp)
+                if self.host_budget_bytes is not None:
+                    self.host = HostTier(self.cache, L, self.host_budget_bytes)
         else:
             self.slot_of = slot_plan(self.keys, per, self.budget_bytes, self.priority)
             self.n_slots = len(self.slot_of)
@@ -216,6 +358,8 @@ class _PrefixIndex:
     def _drop(self):
         """Forgets every slot (and every reservation): the index holds nothing."""
         self.slot_of, self._stamp, self._pass = {}, {}, None
+        if self.host is not None:
+            self.host.forget_all()
 
     # ---- passes (lazy fill: the replacement policy)
     @property
@@ -227,20 +371,52 @@ class _PrefixIndex:
         """A pass opens: `need` = its keys in the order the planner meets them.  Reservations of plans that were never run are dropped with the pass they belonged
         to.  Lazy fill, the policy: resident keys the pass needs are pinned; a miss takes a free slot, else the least recently used slot whose key the pass does not
         need, else it is not admitted -- so no slot is read and overwritten within a pass, and a scan over more keys than slots keeps its resident set.  Nothing the
-        index holds changes here: run() commits."""
+        index holds changes here: run() commits.
+
+        With a host tier the same rule hands out the slots, and a key that gets one and has a record is RESTORED instead of admitted: the
+        tier's transfers run here, before the pass is planned (the planner reads slot_of and the cache's lengths) -- every export, then every import -- and a restore is
+        part of the index's state as soon as its import has returned.  The keys that lose their slots are exported unless they have a record already; those of
+        admissions stay resident until the admitting call commits."""
         self._n_pass += 1
-        p = _Pass(self._n_pass, need, [k for k in need if k in self.slot_of], [k for k in need if k not in self.slot_of])
+        no = self._n_pass
+        reserved: Dict = {}
         if self.fill == "lazy" and self.n_slots:
             needed = set(need)
+            at = {k: n for n, k in enumerate(need)}
             taken = set(self.slot_of.values())
             free = [sl for sl in range(self.n_slots) if sl not in taken]
             victims = sorted((k for k in self.slot_of if k not in needed), key=lambda k: self._stamp.get(k, (0, 0)))
-            for k in p.misses:
+            host = self.host if self.host is not None and self.host.n_records else None
+            restores, losers = [], []
+            for k in need:
+                if k in self.slot_of:
+                    continue
                 if free:
-                    p.reserved[k] = (free.pop(0), None)
+                    sl, v = free.pop(0), None
                 elif victims:
                     v = victims.pop(0)
-                    p.reserved[k] = (self.slot_of[v], v)
+                    sl = self.slot_of[v]
+                else:
+                    break
+                if host is not None and host.has(k):
+                    restores.append((k, sl, v))
+                else:
+                    reserved[k] = (sl, v)
+                if v is not None:
+                    losers.append(v)
+            if host is not None and (restores or losers):
+                spills = host.plan_spills([v for v in losers if not host.has(v)], needed | set(losers))
+                host.spill(self.cache, [(v, self.slot_of[v], rec, dropped, self._stamp.get(v, (0, 0))) for v, rec, dropped in spills])
+                loser_of = {sl: v for _, sl, v in restores}
+
+                def committed(k, sl, stamp):
+                    v = loser_of[sl]
+                    if v is not None and self.slot_of.get(v) == sl:
+                        del self.slot_of[v]; self._stamp.pop(v, None)
+                        self.stats.evicted += 1
+                    self.slot_of[k] = sl; self._stamp[k] = stamp
+                host.restore(self.cache, [(k, sl, (no, at[k])) for k, sl, _ in restores], committed)
+        p = _Pass(no, need, [k for k in need if k in self.slot_of], [k for k in need if k not in self.slot_of], reserved)
         self._pass = p
         return p
 
@@ -274,6 +450,8 @@ class _PrefixIndex:
             for k in p.hits:
                 if k in self.slot_of:
                     self._stamp[k] = (p.no, at[k])
+                    if self.host is not None:
+                        self.host.touch(k, (p.no, at[k]))
         st.prefix_tokens_packed += int(plan.prefix_tokens)
         if plan.admits is not None and len(plan.admits):
             at = {k: n for n, k in enumerate(p.need)}
@@ -305,6 +483,8 @@ class _PrefixIndex:
         return self.s.score(self.iter_plans(pairs), len(pairs), self.run)
 
     def close(self):
+        if self.host is not None:                    # first: its copies read and write the cache's staging partner on the stream; it waits for the device
+            self.host.close(); self.host = None
         if self.cache is not None:
             self.cache.close(); self.cache = None
 
@@ -316,8 +496,9 @@ class GalleryIndex(_PrefixIndex):
     builder); its prompt splits (vtg_split) and projected video features are reused.  budget_bytes: device memory for the cache (None: every prefix)."""
     kind, _changed = "vtg", "gallery: weights or numeric mode"
 
-    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, priority: Optional[Sequence[int]] = None, log=None, fill: str = "eager"):
-        super().__init__(scorer, budget_bytes, priority, log, fill)
+    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, priority: Optional[Sequence[int]] = None, log=None, fill: str = "eager",
+                 host_budget_bytes: Optional[int] = None):
+        super().__init__(scorer, budget_bytes, priority, log, fill, host_budget_bytes)
         # the prompt splits of the texts: (pre, post) pairs, in order of first appearance
         splits: Dict[Tuple[bytes, bytes], Tuple[np.ndarray, np.ndarray]] = {}
         for pre, post, _ in scorer.vtg_split:
@@ -464,8 +645,9 @@ class TextGalleryIndex(_PrefixIndex):
     The caption cache is filled on the first TVG use or by build(): a zero-shot blend has no TVG term and never fills it."""
     kind, _changed = "tvg", "text gallery: weights or TVG mode"
 
-    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, video_index: Optional[GalleryIndex] = None, log=None, fill: str = "eager"):
-        super().__init__(scorer, budget_bytes, None, log, fill)
+    def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, video_index: Optional[GalleryIndex] = None, log=None, fill: str = "eager",
+                 host_budget_bytes: Optional[int] = None):
+        super().__init__(scorer, budget_bytes, None, log, fill, host_budget_bytes)
         if video_index is not None and video_index.s is not scorer:
             raise ValueError("TextGalleryIndex: video_index must be built on the same scorer")
         self.video_index = video_index

@@ -5,7 +5,9 @@ are test captions (`--query_ids`) and / or free text (`--query TEXT`, tokenised 
 takes each dataset query's top-k of the first-stage t2v row, `--candidates all` scores the whole gallery.  One JSON line per query: the ranked video ids and their
 blended t2v scores (training_utils.combine_and_rank's t2v half: `--cpn --alpha --c`; zero-shot runs blend the query likelihood with the first stage only).
 `--synthetic N [--synthetic_7b]`: a dry run on synth.make_problem, as main.py's.  `--gallery_fill lazy` computes no prefix up front: the first query runs at once, its
-calls leave their videos' prefixes in the cache, and `--gallery_gb` is the cache's capacity.  The last stderr line reports the hits and misses.
+calls leave their videos' prefixes in the cache, and `--gallery_gb` is the cache's capacity.  The `gallery stats:` stderr line reports the hits
+and misses.  `--gallery_host_gb` / `--text_gallery_host_gb` (lazy fill) keep the evicted slots in pinned host memory; one more stderr line
+reports what that tier did.
 
 `--direction v2t` is the other half: the gallery is the dataset's test captions and the queries are test videos (`--video_ids`).  The candidate likelihood (VTG) is
 served from the same video cache; a fine-tuned checkpoint's query likelihood (TVG) reads the captions' prompts from a second cache (TextGalleryIndex,
@@ -48,6 +50,9 @@ def get_args_parser():
     p.add_argument("--gallery_fill", default="eager", choices=["eager", "lazy"],
                    help="eager: every prefix under the budget is computed before the first query; lazy: nothing is, --gallery_gb / --text_gallery_gb are capacities, a "
                         "query's own calls capture the prefixes they had to pack and the least recently used slots make room")
+    p.add_argument("--gallery_host_gb", default=None, type=float,
+                   help="--gallery_fill lazy: pinned host memory that keeps the video slots the cache evicts; a video with a record there is copied back instead of decoded again")
+    p.add_argument("--text_gallery_host_gb", default=None, type=float, help="v2t, --gallery_fill lazy: the same for the caption-prompt cache")
     p.add_argument("--max_tokens", default=24576, type=int)
     p.add_argument("--shard", default=None, type=int, nargs=2, metavar=("W", "RANK"))
     p.add_argument("--synthetic", default=0, type=int)
@@ -64,6 +69,11 @@ def check_args(args, world: int = 1) -> None:
         raise SystemExit("search: --shard is not supported (a gallery is not sharded over ranks)")
     if world > 1:
         raise SystemExit(f"search: world size {world} > 1 is not supported (run one process)")
+    for flag in ("gallery_host_gb", "text_gallery_host_gb"):
+        if getattr(args, flag, None) is not None and args.gallery_fill != "lazy":
+            raise SystemExit(f"search: --{flag} needs --gallery_fill lazy (the host tier keeps the slots a lazy cache evicts; an eager cache is filled once and evicts none)")
+        if getattr(args, flag, None) is not None and getattr(args, flag) < 0:
+            raise SystemExit(f"search: --{flag} must not be negative")
     v2t = getattr(args, "direction", "t2v") == "v2t"
     if args.c is None:                        # the likelihood of the direction alone: t2v c0 = c2 = 1; v2t c1 = 0, c3 = 1
         args.c = [1.0, 0.0, 1.0, 1.0] if v2t else [1.0, 0.0, 1.0, 0.0]
@@ -161,7 +171,8 @@ def main(args):
     tvg = RU.padding_ids(tvg_ids, tvg_lab, tvg_msk, tok)
     scorer = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, vocab, vlab, args.num_clips, max_tokens=args.max_tokens)
     budget = None if args.gallery_gb is None else int(args.gallery_gb * 2**30)
-    gal = GalleryIndex(scorer, budget_bytes=budget, fill=args.gallery_fill)
+    host = None if args.gallery_host_gb is None else int(args.gallery_host_gb * 2**30)
+    gal = GalleryIndex(scorer, budget_bytes=budget, fill=args.gallery_fill, host_budget_bytes=host)
     if args.direction == "v2t":
         return _main_v2t(args, model, scorer, gal, v2t_iv2, vids, len(tvg_ids), t0)
     gal.build(first_stage=None if t2v_iv2 is None else np.ascontiguousarray(np.asarray(t2v_iv2, dtype=np.float32).T))     # v2t first stage: calibration sample
@@ -190,6 +201,8 @@ def main(args):
     if out:
         out.close()
     print(f"gallery stats: {json.dumps(gal.stats.as_dict())}", file=sys.stderr, flush=True)
+    if gal.host is not None:
+        print(f"gallery host tier: {json.dumps(dict(gal.host.stats.as_dict(), records=gal.host.n_records, record_bytes=gal.host.record_bytes))}", file=sys.stderr, flush=True)
     gal.close()
     model.engine.close()
     return 0
@@ -205,7 +218,8 @@ def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) 
     gal.build(first_stage=first)
     finetuned = bool(args.resume)
     tbudget = None if args.text_gallery_gb is None else int(args.text_gallery_gb * 2**30)
-    tg = TextGalleryIndex(scorer, budget_bytes=tbudget, video_index=gal, fill=args.gallery_fill)
+    thost = None if args.text_gallery_host_gb is None else int(args.text_gallery_host_gb * 2**30)
+    tg = TextGalleryIndex(scorer, budget_bytes=tbudget, video_index=gal, fill=args.gallery_fill, host_budget_bytes=thost)
     if finetuned:                                     # a zero-shot blend has no TVG term: no caption cache
         tg.build(first_stage=first)
     print(f"gallery: {n_videos} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'}, mode {scorer.vtg_mode or 'none'}, built in {gal.build_seconds:.2f}s; "
@@ -232,6 +246,9 @@ def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) 
     if out:
         out.close()
     print(f"gallery stats: {json.dumps(gal.stats.as_dict())}; text gallery stats: {json.dumps(tg.stats.as_dict())}", file=sys.stderr, flush=True)
+    tiers = [(name, ix.host) for name, ix in (("gallery", gal), ("text gallery", tg)) if ix.host is not None]
+    if tiers:
+        print("; ".join(f"{name} host tier: {json.dumps(dict(h.stats.as_dict(), records=h.n_records, record_bytes=h.record_bytes))}" for name, h in tiers), file=sys.stderr, flush=True)
     tg.close()
     gal.close()
     model.engine.close()

@@ -259,6 +259,41 @@ int blim_score_tvg_admit(blim_engine* e, blim_prefix_cache* c, const blim_batch*
                          const blim_pc_admit* admits, int32_t n_admit, const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab,
                          const int32_t* labels, int32_t n_pairs, float* score, void* stream);
 
+/* ---- Slot export / import (additive in ABI v9; blim_amd/gallery.py: HostTier): a slot leaves the prefix cache as a PACKED RECORD and comes back from one, so that
+ * a slot can be produced without running the model.  The record of a slot with `len` filled positions: [num_layers][pos < len][kv_w] 16-bit values, then the slot's
+ * hidden row of [hid_w] values -- kv_w = 256 * num_kv_heads * (1 + compensated), hid_w = hidden_size * (1 + compensated), the cache's own widths, so a compensated
+ * cache's lo parts travel too (those of layers that ran plain as they are: the kernels copy bytes and interpret nothing).  The layout does not depend on the cache's
+ * max_len: a record moves between caches of one engine that differ in max_len and slot count.
+ * blim_prefix_cache_record_bytes: (num_layers * len * kv_w + hid_w) * 2 rounded up to 256; -1 on bad arguments (len outside 1 .. max_len).
+ * blim_prefix_cache_export: packs the slots moves[i].slot into `staging` (DEVICE, 16-byte aligned, staging_bytes long) at moves[i].offset, and writes one ticket per
+ *   move (HOST, caller-owned) from host values: the slot's length, the state it was computed under, and the record's geometry.  Only the records' own bytes are
+ *   written: their padding and the staging bytes between them are not.
+ * blim_prefix_cache_import: the reverse; tickets[i] belongs to moves[i].  The slots are marked empty before the work starts; on success each records `len` and the
+ *   TICKET's state (not the engine's present one): a record exported before a weight or option change imports, and the next scoring call that names its slot is
+ *   refused as stale, as for any slot.  Only positions < len and the hidden rows of the named slots are written.
+ * Both: the moves travel as kernel arguments (48 per launch), no host buffer outlives the call, the call never waits for the device, and stream order is the only
+ *   synchronisation -- a later call on the same stream may read an imported slot, or overwrite an exported one.  The transfer between `staging` and host memory is
+ *   the caller's.  Refused before anything is launched, the message naming the move: n < 1, a slot outside the cache or named twice, an offset that is not a
+ *   multiple of 256, a record outside staging_bytes or overlapping another (BLIM_ERR_ARG); export of an empty slot (BLIM_ERR_STATE) or with len other than the slot's
+ *   filled length (BLIM_ERR_ARG); import of a ticket without the magic or with another geometry, len outside 1 .. max_len or other than the ticket's
+ *   (BLIM_ERR_ARG); an fp8 engine (BLIM_ERR_STATE).  A ticket is meaningful to the engine that wrote it, while it lives (the weights epoch is the engine's counter). */
+#define BLIM_PC_TICKET_MAGIC 0x544B4350u      /* "PCKT" */
+#define BLIM_PC_TICKET_LAYERS 256
+typedef struct blim_pc_move { int32_t slot; int32_t len; int64_t offset; } blim_pc_move;   /* HOST; offset: bytes into the staging buffer, multiple of 256 */
+typedef struct blim_pc_ticket {               /* HOST, plain data */
+    uint32_t magic;
+    int32_t len;
+    int32_t num_layers, kv_w, hid_w;          /* the record's geometry */
+    int32_t precise, embeds, mlp, layers, lo6, mqz, n_bits;     /* the slot's recorded state ... */
+    uint64_t epoch;
+    uint8_t bits[BLIM_PC_TICKET_LAYERS];      /* ... and its n_bits per-layer bits (option "precise_layer_bits") */
+} blim_pc_ticket;
+int64_t blim_prefix_cache_record_bytes(const blim_prefix_cache* c, int32_t len);
+int blim_prefix_cache_export(blim_engine* e, blim_prefix_cache* c, const blim_pc_move* moves, int32_t n, void* staging, int64_t staging_bytes,
+                             blim_pc_ticket* tickets_out, void* stream);
+int blim_prefix_cache_import(blim_engine* e, blim_prefix_cache* c, const blim_pc_move* moves, int32_t n, const void* staging, int64_t staging_bytes,
+                             const blim_pc_ticket* tickets, void* stream);
+
 /* ---- Literal model.forward(inputs_embeds=[B,L,H] bf16, attention_mask=[B,L] u8) -> logits f32 [B,L,V] (may be NULL),
  * hidden f32 [B,L,H] (may be NULL).  Replaces VideoChatFlashQwenForCausalLM.forward, modeling_videochat_flash.py:601-629. */
 int blim_forward(blim_engine* e, const void* embeds, const uint8_t* mask, int32_t B, int32_t L, float* logits, float* hidden, void* stream);

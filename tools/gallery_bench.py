@@ -18,7 +18,14 @@ against PairScorer.vtg on the same pairs (the price of the capture), with the ho
 queries, one pass each, under a budget of a quarter of the gallery: hit rate and pairs/s, lazy against the static slot plan -- every query once, the same again,
 and `--stream_draws` draws with a Zipf popularity over the queries.  Scores are checked bit-equal to PairScorer.vtg throughout.
 
-    python tools/gallery_bench.py --fill lazy --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r11_lazy_gallery.json"""
+    python tools/gallery_bench.py --fill lazy --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r11_lazy_gallery.json
+
+`--host_gb G` (t2v): the lazy gallery's host tier (GalleryIndex(fill="lazy", host_budget_bytes=G GB)).  (a) the transfers alone, 16 slots at a
+time: the export and import kernels (slot <-> device staging) and the whole spill and restore (with the copy to and from pinned host memory), ms per record and GB/s;
+(b) the query streams of `--fill lazy` (d) under a quarter of the gallery, a lazy index without a tier against one with it, alternated in one process: hit rate,
+pairs/s, time per query, and what the tier moved.  Scores are checked bit-equal to PairScorer.vtg throughout.
+
+    python tools/gallery_bench.py --host_gb 10 --n 1000 --queries 55 --k 16 --reps 3 --synthetic_7b --out profiles/r15_host_tier.json"""
 import argparse
 import json
 import os
@@ -58,6 +65,7 @@ def main():
     ap.add_argument("--tvg_modes", default="attn,full", help="v2t: the TVG calls' modes to measure")
     ap.add_argument("--fill", default="eager", choices=["eager", "lazy"], help="lazy: the lazy gallery's measurements (t2v)")
     ap.add_argument("--stream_draws", type=int, default=165, help="--fill lazy: queries of the Zipf stream")
+    ap.add_argument("--host_gb", type=float, default=None, help="the host tier's measurements (t2v): pinned host memory of the tier, GB")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -75,6 +83,8 @@ def main():
     q = np.linspace(0, a.n - 1, a.queries).round().astype(np.int64)
     if a.direction == "v2t":
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if a.host_gb is not None:
+        return main_host(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.fill == "lazy":
         return main_lazy(a, dims, model, prob, vtg, tvg, video, q, tpc)
     cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
@@ -198,6 +208,85 @@ def main_lazy(a, dims, model, prob, vtg, tvg, video, q, tpc):
                            "uncached_pairs_per_s": P / med(t_unc), "lazy_pairs_per_s": P / med(t_miss)},
              "steady_state": {"eager_s": t_eager, "lazy_all_hits_s": t_hit, "eager_pairs_per_s": P / med(t_eager), "lazy_pairs_per_s": P / med(t_hit), "tokens": tok},
              "stream": dict(stream, slots=a.n // 4, bytes_per_slot=per), "bit_equal": True}
+        res["modes"][mode] = r
+        print(json.dumps({mode: r}), flush=True)
+        del sc
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def main_host(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
+    pairs = np.stack([cand.reshape(-1), np.repeat(q, a.k)], axis=1)
+    med = lambda t: float(np.median(t))
+    host_bytes = int(a.host_gb * 2**30)
+    res = {"host_gb": a.host_gb, "n": a.n, "queries": a.queries, "k": a.k, "reps": a.reps, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc,
+           "pairs": len(pairs), "distinct_videos": int(len(np.unique(pairs[:, 0]))), "modes": {}}
+    for mode in a.modes.split(","):
+        model.vtg_precise = None if mode == "none" else mode
+        model.clear_cache()
+        sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, torch.from_numpy(prob.video_vocab),
+                           torch.from_numpy(prob.tvg_video_labels), dims.num_clips, max_tokens=a.max_tokens)
+        sc.set_vtg_mode(model.vtg_mode())
+        ref = sc.vtg(pairs)                                               # warm-up: every feature projected, workspaces sized
+        per = GalleryIndex(sc, fill="lazy").per_slot_bytes()
+        budget = (a.n // 4) * per
+        # (a) the transfers alone: the first query's k slots, admitted by its own call, out and back in
+        g = GalleryIndex(sc, budget_bytes=budget, fill="lazy", host_budget_bytes=host_bytes).build()
+        assert np.array_equal(g.vtg_pairs(pairs[:a.k]), ref[:a.k])
+        keys = list(g.slot_of)[:g.host.stage_records]
+        ln = g.cache.slot_len(g.slot_of[keys[0]])
+        nb = g.cache.record_bytes(ln)
+        moves = [(g.slot_of[k], ln, n * g.host.record_bytes) for n, k in enumerate(keys)]
+        items_out = [(k, g.slot_of[k], n, None, (0, n)) for n, k in enumerate(keys)]
+        items_in = [(k, g.slot_of[k], (0, n)) for n, k in enumerate(keys)]
+        tr = {"pack_s": [], "spill_s": [], "unpack_s": [], "restore_s": []}
+        for _ in range(a.reps + 1):                                       # (the first round warms the copies up and is dropped)
+            dt, tickets = timed(lambda: g.cache.export_slots(moves, g.host.staging)); tr["pack_s"].append(dt)
+            dt, _ = timed(lambda: g.cache.import_slots(moves, g.host.staging, tickets)); tr["unpack_s"].append(dt)
+            dt, _ = timed(lambda: g.host.spill(g.cache, items_out)); tr["spill_s"].append(dt)
+            dt, _ = timed(lambda: g.host.restore(g.cache, items_in)); tr["restore_s"].append(dt)
+        assert np.array_equal(g.vtg_pairs(pairs[:a.k]), ref[:a.k]), "scores differ after the slots went out and came back"
+        transfers = {"records": len(keys), "record_bytes": nb, "slot_positions": ln}
+        for name, t in tr.items():
+            m = med(t[1:])
+            transfers[name] = t[1:]
+            transfers[name[:-2] + "_ms_per_record"] = 1e3 * m / len(keys)
+            transfers[name[:-2] + "_GB_per_s"] = len(keys) * nb / m / 1e9
+        n_records, pinned = g.host.n_records, g.host.n_records * g.host.record_bytes
+        g.close()
+        # (b) the query streams under a quarter of the gallery: lazy without a tier against lazy with it
+        rng = np.random.RandomState(0)
+        w = 1.0 / np.arange(1, a.queries + 1); w /= w.sum()
+        streams = {"each_query_once": np.arange(a.queries), "the_same_again": np.arange(a.queries), "zipf": rng.choice(a.queries, size=a.stream_draws, p=w)}
+        stream = {name: {"lazy_s": [], "tier_s": []} for name in streams}
+        for _ in range(a.reps):
+            idx = {"lazy": GalleryIndex(sc, budget_bytes=budget, fill="lazy").build(),
+                   "tier": GalleryIndex(sc, budget_bytes=budget, fill="lazy", host_budget_bytes=host_bytes).build()}
+            for name, order in streams.items():
+                for form, g in idx.items():
+                    g.stats.reset()
+                    h0 = g.host.stats.as_dict() if g.host is not None else None
+                    def run_stream():
+                        return [g.vtg_scores([q[i]], cand[i][None]) for i in order]
+                    dt, outs = timed(run_stream)
+                    for i, o in zip(order, outs):
+                        assert np.array_equal(o[0], ref[i * a.k:(i + 1) * a.k]), f"{form} stream differs from PairScorer.vtg"
+                    st = g.stats.as_dict()
+                    stream[name][form + "_s"].append(dt)
+                    stream[name][form] = dict(st, hit_rate=st["hits"] / max(st["hits"] + st["misses"], 1))
+                    if h0 is not None:
+                        stream[name]["host"] = {k: v - h0[k] for k, v in g.host.stats.as_dict().items()}
+            for g in idx.values():
+                g.close()
+        for name, order in streams.items():
+            for form in ("lazy", "tier"):
+                stream[name][form + "_pairs_per_s"] = len(order) * a.k / med(stream[name][form + "_s"])
+                stream[name][form + "_ms_per_query"] = 1e3 * med(stream[name][form + "_s"]) / len(order)
+        r = {"transfers": transfers, "stream": dict(stream, slots=a.n // 4, bytes_per_slot=per, host_records=n_records, pinned_bytes=pinned), "bit_equal": True}
         res["modes"][mode] = r
         print(json.dumps({mode: r}), flush=True)
         del sc
