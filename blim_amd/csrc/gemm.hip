@@ -1126,8 +1126,144 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
     }  // persistent tile loop
 }
 
+// ---- narrow-tile residual GEMM (GemmParams::narrow).  EPI_RESID on plain 16-bit operands in 64 x 64 tiles, one tile per workgroup of four
+// waves (2 M x 2 N, each 32 x 32 of C as 2 x 2 fragments), not persistent: a call of a few hundred rows against N = 3584 (o_proj, down of a small scoring call) is
+// 28 tiles of 256 x 256 -- 28 of the chip's 256 CUs -- and 448 of these.  Everything that decides a VALUE is the 256 x 256 kernel's: K-steps of 128 bytes staged by
+// LDS-DMA as the same 1-KiB block images (8 rows x 128 B, chunk c of row r at slot c ^ ((r >> 1) & 7)), the same fragment reads (lane (fr, fc): chunks fc and
+// fc + 4 of row fr), mfma16<DT> with the W fragment first, and per accumulator fragment ks = 0 then ks = 1 of every K-step in ascending order, across the ring's
+// wrap and across w_wrap_k -- so every C element sees the same chain of MFMAs and the epilogue's o + (v + rb) gives the same bits.  No split of K, no atomics.
+// LDS: a ring of NRING K-steps (A 8 KiB + W 8 KiB each); step kt + NRING - 1 is requested right behind the barrier that ends step kt - 1 (whose slot it takes),
+// each wave waits for its own four requests of step kt with a counted vmcnt, and one barrier per step publishes them.  64 KiB: two workgroups per CU.
+#define NBM 64
+#define NBN 64
+#define NRING 4
+#define N_A_BYTES (NBM * 128)
+#define N_STEP_BYTES ((NBM + NBN) * 128)
+#define N_THREADS 256
+template <int DT>
+__global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[NRING * N_STEP_BYTES];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    // tile order: XCD-contiguous chunks (blocks b, b + 8, ... share an XCD), inside a chunk bands of group_m M-tiles walked M first -- the tiles an XCD runs at
+    // one time share a few W panels (W is the large operand of these calls: each panel reaches one XCD's L2 only)
+    const int ntm = (p.M + NBM - 1) / NBM, ntn = (p.N + NBN - 1) / NBN;
+    const int nwg = ntm * ntn;
+    const int bid = blockIdx.x, xcd = bid & 7, cq = nwg >> 3, cr = nwg & 7;
+    const int pid = (xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq) + (bid >> 3);
+    const int width = p.group_m * ntn;
+    const int first_m = (pid / width) * p.group_m;
+    const int gsz = min(ntm - first_m, p.group_m);
+    const int tm = first_m + (pid % width) % gsz;
+    const int tn = (pid % width) / gsz;
+    const int row0 = tm * NBM, col0 = tn * NBN;
+
+    // LDS-DMA sources: wave w stages blocks w and w + 4 (8 rows each) of both operands; lane -> row sr of the block, source chunk sc for its slot lane & 7
+    const int sr = lane >> 3;
+    const int sc = (lane & 7) ^ (4 * (wave & 1) + (sr >> 1));
+    const int64_t w_ld = p.w_wrap_k > 0 ? p.w_wrap_k : p.K;           // W row stride (elements)
+    uint32_t offA[2], offW[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int b = wave + 4 * i;
+        offA[i] = (uint32_t)((int64_t)min(row0 + 8 * b + sr, p.M - 1) * p.lda * 2 + 16 * sc);
+        offW[i] = (uint32_t)((int64_t)min(col0 + 8 * b + sr, p.N - 1) * w_ld * 2 + 16 * sc);
+    }
+    const char* baseA = (const char*)p.A;
+    const char* baseW = (const char*)p.W;
+    const int nk = p.K / 64;                                           // K-steps of 128 bytes
+    const int wrap = p.w_wrap_k > 0 ? p.w_wrap_k / 64 : 0x7fffffff;    // A = [hi | lo]: W's K-step index wraps
+    auto stage = [&](int slot, int kt) __attribute__((always_inline)) {
+        const char* ga = baseA + (int64_t)kt * 128;
+        const char* gw = baseW + (int64_t)(kt >= wrap ? kt - wrap : kt) * 128;
+        char* d = smem + slot * N_STEP_BYTES + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            uint32_t oa = offA[i], ow = offW[i];
+            asm volatile("" : "+v"(oa), "+v"(ow));                     // 32-bit lane offsets at the point of use: the saddr + voffset form
+            glds16(ga + oa, d + i * 4096);
+            glds16(gw + ow, d + N_A_BYTES + i * 4096);
+        }
+    };
+    // fragment reads: as in gemm_kernel
+    const int fr = lane & 15, fc = lane >> 4;
+    const int fg = (fr >> 1) & 7;
+    const int frag_off = (fr >> 3) * 1024 + (fr & 7) * 128 + 16 * ((fc ^ (fg & 3)) + 4 * (fg >> 2));
+    const int a_off = (2 * wm) * 2048 + frag_off;                      // + mi * 2048; second read: ^ 64
+    const int b_off = N_A_BYTES + (2 * wn) * 2048 + frag_off;          // + ni * 2048
+
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+    for (int s = 0; s < NRING - 1; ++s)
+        if (s < nk) stage(s, s);
+    int slot = 0;
+    for (int kt = 0; kt < nk; ++kt) {
+        // my four requests of step kt have landed: those of the (at most NRING - 2) later steps requested so far may stay in flight
+        if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // my LDS reads of step kt - 1 have returned (WAR on the slot refilled below)
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (kt + NRING - 1 < nk) stage((slot + NRING - 1) & (NRING - 1), kt + NRING - 1);
+        const char* ba[2] = {smem + slot * N_STEP_BYTES + a_off, smem + ((slot * N_STEP_BYTES + a_off) ^ 64)};
+        const char* bb[2] = {smem + slot * N_STEP_BYTES + b_off, smem + ((slot * N_STEP_BYTES + b_off) ^ 64)};
+        bf16x8 fa[2][2], fb[2][2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) fb[ks][ni] = *(const bf16x8*)(bb[ks] + ni * 2048);
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) fa[ks][mi] = *(const bf16x8*)(ba[ks] + mi * 2048);
+        }
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma16<DT>(fb[ks][ni], fa[ks][mi], acc[mi][ni]);
+        slot = (slot + 1) & (NRING - 1);
+    }
+    static_assert(NRING == 4, "the counted waits above are written for three steps in flight");
+
+    // ---- epilogue: C = (resid_in ? resid_in : C) + (acc + bias), straight from the accumulators (lane: row lane & 15 and four consecutive columns of each fragment:
+    // 64-byte row segments; the tile is 16 KiB).  The two forms and their associations are gemm_kernel's: float4 where col + 3 < N, element by element beyond.
+    const int tq = lane >> 4, rsub = lane & 15;
+    const float* rsrc = p.resid_in ? p.resid_in : (const float*)p.C;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+        const int row = row0 + 32 * wm + 16 * mi + rsub;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int col = col0 + 32 * wn + 16 * ni + 4 * tq;
+            if (row >= p.M || col >= p.N) continue;
+            const f32x4 v = acc[mi][ni];
+            float* out = (float*)p.C + (int64_t)row * p.ldc + col;
+            const float* in = rsrc + (int64_t)row * p.ldc + col;
+            if ((col + 3 < p.N) && ((p.ldc & 3) == 0)) {
+                const float4 rb = p.bias ? *(const float4*)(p.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 o = *(const float4*)in;
+                *(float4*)out = make_float4(o.x + (v[0] + rb.x), o.y + (v[1] + rb.y), o.z + (v[2] + rb.z), o.w + (v[3] + rb.w));
+            } else {
+                const float x[4] = {v[0], v[1], v[2], v[3]};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (col + j < p.N) out[j] = in[j] + x[j] + (p.bias ? p.bias[col + j] : 0.f);
+            }
+        }
+    }
+}
+
 #include <stdlib.h>
 #include <algorithm>
+#include <atomic>
 static int g_gemm_persistent = getenv("BLIM_GEMM_PERSISTENT") ? atoi(getenv("BLIM_GEMM_PERSISTENT")) : 1;
 static int g_gemm_tile_map = getenv("BLIM_GEMM_TILE_MAP") ? atoi(getenv("BLIM_GEMM_TILE_MAP")) : -1;   // -1: by shape
 static int g_gemm_group_m = getenv("BLIM_GEMM_GROUP_M") ? atoi(getenv("BLIM_GEMM_GROUP_M")) : GROUP_M;   // M-tiles per band of the tile order
@@ -1196,6 +1332,29 @@ static int launch_t(const GemmParams& p, hipStream_t stream) {
 
 static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream);
 
+// ---- GemmParams::narrow.  The narrow kernel is instantiated for EPI_RESID on plain fp16 / bf16 operands (w_wrap_k and lda > K included); every other form --
+// the e2m3 second pass (A6 / W6), fp8 (a_mx included), any other epilogue, the timing aids -- keeps the 256 x 256 kernel whatever `narrow` says.
+static std::atomic<int64_t> g_narrow_launches{0};
+extern "C" int64_t blim_gemm_narrow_launches(void) { return g_narrow_launches.load(); }
+extern "C" int32_t blim_gemm_narrow_threshold(void) { return GEMM_NARROW_TILES; }
+static bool narrow_eligible(GemmEpi epi, const GemmParams& p) {
+    return epi == EPI_RESID && (p.dtype == DT_F16 || p.dtype == DT_BF16) && !p.A6 && !p.W6 && !p.a_mx && !p.swiglu_act && !p.debug_stamps && !p.debug_skip_epilogue;
+}
+static bool narrow_chosen(GemmEpi epi, const GemmParams& p) {
+    if (p.narrow == 0 || !narrow_eligible(epi, p)) return false;
+    if (p.narrow == 2) return true;
+    return (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) < GEMM_NARROW_TILES;      // auto: gemm.hpp
+}
+static int launch_narrow(const GemmParams& p, hipStream_t stream) {
+    const dim3 grid((unsigned)(((p.M + NBM - 1) / NBM) * ((p.N + NBN - 1) / NBN)));
+    if (p.dtype == DT_F16) hipLaunchKernelGGL((gemm_narrow_kernel<DT_F16>), grid, dim3(N_THREADS), 0, stream, p);
+    else hipLaunchKernelGGL((gemm_narrow_kernel<DT_BF16>), grid, dim3(N_THREADS), 0, stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { blim_set_error("narrow gemm launch failed: %s", hipGetErrorString(e)); return BLIM_ERR_HIP; }
+    g_narrow_launches.fetch_add(1);
+    return BLIM_OK;
+}
+
 // The kernel addresses its operands with 32-bit byte offsets from the (scalar) base pointers.  An A operand of 4 GiB or more
 // (e.g. the [T, I] SwiGLU output beyond 113 k tokens at 7B) is processed as consecutive row chunks, each a whole number of
 // 256-row tiles: rows are independent in every epilogue, so the chunks are ordinary launches on shifted bases.
@@ -1261,6 +1420,7 @@ static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream) {
     ARG_CHECK(!p.out6 || (epi == EPI_SWIGLU && p.A6 && p.lo_off > 0 && p.N % 256 == 0));
     ARG_CHECK(p.w_wrap_k == 0 || (p.K == 2 * p.w_wrap_k && (int64_t)p.w_wrap_k * es % 128 == 0));   // A = [hi | lo]: W is walked twice
     ARG_CHECK(p.lo_off == 0 || epi == EPI_BF16 || epi == EPI_QKV || epi == EPI_SWIGLU);
+    if (p.narrow < 0 || p.narrow > 2) { blim_set_error("gemm: narrow = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = the narrow kernel wherever it is eligible)", p.narrow); return BLIM_ERR_ARG; }
     ARG_CHECK((int64_t)p.M * p.lda * es < (1ll << 32) && (int64_t)p.N * (p.w_wrap_k > 0 ? p.w_wrap_k : p.K) * es < (1ll << 32));  // 32-bit operand offsets
     switch (epi) {
         case EPI_BF16:
@@ -1269,7 +1429,10 @@ static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream) {
             ARG_CHECK(!p.swiglu_act || (p.N % 32 == 0 && p.swiglu_act_ld % 8 == 0 && p.swiglu_act_ld >= p.N / 2 && !p.swiglu_gu));
             return launch_t<EPI_BF16>(p, stream);
         case EPI_F32: ARG_CHECK(p.C && p.bias == nullptr); return launch_t<EPI_F32>(p, stream);
-        case EPI_RESID: ARG_CHECK(p.C && p.ldc % 4 == 0); return launch_t<EPI_RESID>(p, stream);
+        case EPI_RESID:
+            ARG_CHECK(p.C && p.ldc % 4 == 0);
+            if (narrow_chosen(epi, p)) return launch_narrow(p, stream);
+            return launch_t<EPI_RESID>(p, stream);
         case EPI_QKV:
             ARG_CHECK(p.C && p.bias && p.rope_rows && p.rope_stride >= p.M && p.N % 128 == 0 && p.rope_cols % 128 == 0 && p.ldc % 4 == 0);
             return launch_t<EPI_QKV>(p, stream);

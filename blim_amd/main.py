@@ -86,6 +86,10 @@ def get_args_parser():
                         "opt-in, 0.69x the plain rate with about one fp16 rounding's accuracy).  16bit: a second walk in the engine's own format (bf16 engines: the default and the "
                         "parity mode, 0.5x the plain rate at 1 - 3e-6).  auto (bf16 engines): measured on the loaded checkpoint like --vtg_precise auto -- the e2m3 form is kept "
                         "when its scores stay inside the bar of the 16-bit form's on the evaluation's own calibration pairs")
+    p.add_argument("--narrow_gemm", default="off", choices=["off", "auto"],
+                   help="auto: the decoder layers' o_proj and down projections of SMALL calls (fewer 256 x 256 tiles than the library's measured threshold) run on the "
+                        "narrow-tile residual GEMM, which spreads them over the whole chip; the scores are the same bit for bit (engine option \"narrow_gemm\" = 1).  "
+                        "Refused with --dtype f8")
     p.add_argument("--calibration_store", default=None, type=str, metavar="DIR",
                    help="keep what --vtg_precise auto | select, --tvg_precise auto and --second_pass auto measure in DIR, one JSON record per weights fingerprint "
                         "(blim_weights_fingerprint: weights, adapters, visual head, config) + numeric options + library build.  A later run on the same key checks the "
@@ -150,6 +154,8 @@ def main(args):
         raise SystemExit("--lr is required for training (main.py:41: absolute learning rate)")
     if not args.eval and args.dtype == "f8":
         raise SystemExit("training needs a 16-bit engine (--dtype f16 | bf16)")
+    if args.narrow_gemm == "auto" and args.dtype == "f8":
+        raise SystemExit("--narrow_gemm auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM takes fp16 / bf16 operands")
     t0 = time.time()
     train_loader = None
     if args.synthetic > 0:
@@ -208,6 +214,10 @@ def main(args):
         model.tvg_precise = args.tvg_precise
     if args.vtg_precise is not None and model.engine.can_precise:
         model.vtg_precise = None if args.vtg_precise == "none" else args.vtg_precise        # "auto": resolved by evaluation() on the loaded weights
+    if args.narrow_gemm == "auto":
+        if model.engine.dtype == "f8":
+            raise SystemExit("--narrow_gemm auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM takes fp16 / bf16 operands")
+        model.engine.set_option("narrow_gemm", 1)
     if model.engine.dtype == "f8":
         finetuned_file = bool(args.resume) and os.path.isfile(args.resume)
         mask = args.f8_mask if args.f8_mask is not None else (12 if finetuned_file else 31)

@@ -456,8 +456,17 @@ typedef struct blim_gemm_args {
     int64_t swiglu_act_ld;
     void* swiglu_gu;
     int64_t swiglu_ld;
+    int32_t tile;          /* 0 = 256 x 256 tiles, 1 = auto, 2 = the narrow kernel (see below) */
 } blim_gemm_args;
 int blim_gemm(const blim_gemm_args* args, void* stream);
+/* tile (added at the end of the struct; the ABI version is unchanged -- a shorter struct reads as 0): BLIM_EPI_RESID on fp16 / bf16 operands without A6 / W6 also exists
+ * in 64 x 64 tiles, one per 4-wave workgroup, with the same walk over K -- every C element sees the same chain of MFMAs in the same order, so the result is the 256 x 256
+ * kernel's bit for bit -- for calls whose 256 x 256 grid leaves most of the chip idle (a few hundred rows against N = 3584: 28 workgroups).  2 = that kernel; any other
+ * epilogue, BLIM_COMPUTE_F8, A6 / W6 and a_mx are refused with the field named.  1 = auto: that kernel when the form is eligible and
+ * ceil(M / 256) * ceil(N / 256) < blim_gemm_narrow_threshold(), the 256 x 256 kernel otherwise (an ineligible form is not an error).  Other values: BLIM_ERR_ARG.
+ * blim_gemm_narrow_launches(): launches of the narrow kernel by this process so far (host-side counter; tests read it to see which kernel ran). */
+int64_t blim_gemm_narrow_launches(void);
+int32_t blim_gemm_narrow_threshold(void);
 /* cos / sin of every token's position as BLIM_EPI_QKV reads them (csrc/gemm.hpp: rope_rows): out f32 [8 = {cos, sin} x 4 groups of 16 dims][stride rows][16],
  * row t of every chunk = position min(max(positions[t], 0), max_positions - 1); stride >= n_tokens.  workspace: blim_rope_rows_bytes(max_positions) bytes (the
  * cos | sin tables of all positions, built by the call as the engine builds its own at creation); out: 128 * stride floats. */
@@ -503,6 +512,10 @@ int blim_debug_gemm_stamps(void* device_buf);
  *   is BLIM_ERR_NOMEM with the matrix named); activations: the lo parts a producer wrote are re-written as operand tiles (one HBM-bound pass per GEMM input).  A
  *   fully compensated call costs 1.49x a plain one instead of 2x and stays within 4e-5 of the fp32 reference where the fp16 second pass reads 4e-6 (28 layers of
  *   the 7B configuration); on weights with a trained checkpoint's massive activations the two differ by <= 1.6e-4 over 16,000 scores (rms 9e-6);
+ * "narrow_gemm" (0 / 1 / 2, default 0; other values BLIM_ERR_ARG): blim_gemm's `tile` for the decoder layers' o_proj and down launches -- the plain and the w_wrap_k
+ *   forms, adapters apart and the last layer's pruned rows included; 1 = auto, 2 = wherever the form is eligible.  Launches of an ineligible form (fp8 engines, the e2m3
+ *   second pass of "precise_lo6") keep the 256 x 256 kernel.  The option changes NO value (the narrow kernel's results are the 256 x 256 kernel's bit for bit), only which
+ *   kernel computes it: it is no part of a prefix cache's snapshot of the numeric options, of the calibration store's key or of the weights fingerprint;
  * "masked_query_zero" (0/1, default 0; 16-bit engines; PARITY-UNPINNED): query positions the key mask hides (blim_batch.key_visible == 0) write a ZERO attention output
  *   instead of attending to their visible keys.  The default is the semantics parity is pinned to -- the reference's eager / SDPA attention classes
  *   (modeling_qwen2_flash.py:288-310, 701-709), where a masked query row is computed like any other.  Its flash-attention-2 class drops such positions before the

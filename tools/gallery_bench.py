@@ -25,7 +25,14 @@ time: the export and import kernels (slot <-> device staging) and the whole spil
 (b) the query streams of `--fill lazy` (d) under a quarter of the gallery, a lazy index without a tier against one with it, alternated in one process: hit rate,
 pairs/s, time per query, and what the tier moved.  Scores are checked bit-equal to PairScorer.vtg throughout.
 
-    python tools/gallery_bench.py --host_gb 10 --n 1000 --queries 55 --k 16 --reps 3 --synthetic_7b --out profiles/r15_host_tier.json"""
+    python tools/gallery_bench.py --host_gb 10 --n 1000 --queries 55 --k 16 --reps 3 --synthetic_7b --out profiles/r15_host_tier.json
+
+`--narrow_gemm` (t2v): engine option "narrow_gemm"  off (0) against auto (1), alternated `--reps` times in one process on ONE eager index: the
+single-query latency table above (k = 16 and k = N, per mode), a stream of the Q queries one cached pass of k pairs each, and the engine's timing classes of one cached
+k = 16 query under each value.  Option 0 launches the kernels the library launched before the option existed.  Scores are checked bit-equal between the two values
+on every repetition.
+
+    python tools/gallery_bench.py --narrow_gemm --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r16_narrow_gemm_gallery.json"""
 import argparse
 import json
 import os
@@ -66,6 +73,7 @@ def main():
     ap.add_argument("--fill", default="eager", choices=["eager", "lazy"], help="lazy: the lazy gallery's measurements (t2v)")
     ap.add_argument("--stream_draws", type=int, default=165, help="--fill lazy: queries of the Zipf stream")
     ap.add_argument("--host_gb", type=float, default=None, help="the host tier's measurements (t2v): pinned host memory of the tier, GB")
+    ap.add_argument("--narrow_gemm", action="store_true", help="engine option narrow_gemm 0 against 1 (t2v, eager index): single-query latency, query stream, timing classes")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -83,6 +91,8 @@ def main():
     q = np.linspace(0, a.n - 1, a.queries).round().astype(np.int64)
     if a.direction == "v2t":
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if a.narrow_gemm:
+        return main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.host_gb is not None:
         return main_host(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.fill == "lazy":
@@ -119,6 +129,73 @@ def main():
         r = {"build_s": t_build, "slots": len(gal.slot_of), "bytes_per_slot": gal.cache.bytes // len(gal.slot_of), "tokens_uncached": tok_unc,
              "tokens_cached": tok_cac, "uncached_s": t_unc, "cached_s": t_cac, "uncached_pairs_per_s": P / float(np.median(t_unc)),
              "cached_pairs_per_s": P / float(np.median(t_cac)), "speedup": float(np.median(t_unc) / np.median(t_cac)), "latency": lat, "bit_equal": True}
+        res["modes"][mode] = r
+        print(json.dumps({mode: r}), flush=True)
+        gal.close()
+        del sc
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    """Option "narrow_gemm" 0 against 1 on one eager index (see the module text)."""
+    from blim_amd import engine as eng
+    e = model.engine
+    res = {"n": a.n, "queries": a.queries, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc, "reps": a.reps,
+           "threshold_tiles": eng.gemm_narrow_threshold(), "modes": {}}
+    med = lambda x: float(np.median(x))
+    spread = lambda x: float((max(x) - min(x)) / np.median(x))
+    for mode in a.modes.split(","):
+        model.vtg_precise = None if mode == "none" else mode
+        model.clear_cache()
+        sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, torch.from_numpy(prob.video_vocab),
+                           torch.from_numpy(prob.tvg_video_labels), dims.num_clips, max_tokens=a.max_tokens)
+        sc.set_vtg_mode(model.vtg_mode())
+        sc.vtg(np.stack([np.arange(8), np.full(8, q[0])], axis=1))
+        gal = GalleryIndex(sc)
+        gal.build()
+        r = {"latency": {}}
+        for kk in (a.k, a.n):
+            c1 = np.argsort(-prob.t2v_sims[q[0]], kind="stable")[:kk][None]
+            ts, launches, ref = {0: [], 1: []}, {}, None
+            for v in (0, 1):                                               # warm-up of both kernels' paths
+                e.set_option("narrow_gemm", v); gal.vtg_scores([q[0]], c1)
+            for _ in range(a.reps):
+                for v in (0, 1):
+                    e.set_option("narrow_gemm", v)
+                    n0 = eng.gemm_narrow_launches()
+                    dt, got = timed(lambda: gal.vtg_scores([q[0]], c1))
+                    ts[v].append(dt); launches[v] = eng.gemm_narrow_launches() - n0
+                    ref = got if ref is None else ref
+                    assert np.array_equal(np.asarray(ref), np.asarray(got)), "scores differ between narrow_gemm 0 and 1"
+            r["latency"][f"k{kk}"] = {"off_ms": 1e3 * med(ts[0]), "auto_ms": 1e3 * med(ts[1]), "off_spread": spread(ts[0]), "auto_spread": spread(ts[1]),
+                                      "off_all_ms": [1e3 * t for t in ts[0]], "auto_all_ms": [1e3 * t for t in ts[1]], "narrow_launches": launches}
+        cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
+        ts = {0: [], 1: []}
+
+        def stream():
+            return [np.asarray(gal.vtg_scores([int(t)], cand[i][None])) for i, t in enumerate(q)]
+        ref = None
+        for _ in range(a.reps):
+            for v in (0, 1):
+                e.set_option("narrow_gemm", v)
+                dt, got = timed(stream); ts[v].append(dt)
+                ref = got if ref is None else ref
+                assert all(np.array_equal(x, y) for x, y in zip(ref, got)), "stream scores differ between narrow_gemm 0 and 1"
+        r["stream"] = {"queries": len(q), "k": a.k, "off_s": med(ts[0]), "auto_s": med(ts[1]), "off_spread": spread(ts[0]), "auto_spread": spread(ts[1]),
+                       "off_ms_per_query": 1e3 * med(ts[0]) / len(q), "auto_ms_per_query": 1e3 * med(ts[1]) / len(q)}
+        c1 = np.argsort(-prob.t2v_sims[q[0]], kind="stable")[:a.k][None]
+        r["classes"] = {}
+        for v in (0, 1):
+            e.set_option("narrow_gemm", v)
+            e.timing_enable(True); e.timing_report()
+            gal.vtg_scores([q[0]], c1)
+            r["classes"]["auto" if v else "off"] = {k: x for k, x in e.timing_report().items() if x["calls"]}
+            e.timing_enable(False)
+        e.set_option("narrow_gemm", 0)
         res["modes"][mode] = r
         print(json.dumps({mode: r}), flush=True)
         gal.close()

@@ -1,0 +1,70 @@
+"""blim_gemm alone, the residual epilogue in fp16: time per launch of the 256 x 256 kernel (tile = 0) and of the narrow-tile kernel (tile = 2, csrc/gemm.hip:
+gemm_narrow_kernel) at M in {32 .. 4096} x (N, K) in {(3584, 3584), (3584, 18944)} -- o_proj and down of the 7B decoder.  HIP events around `--inner` back-to-back
+launches, the two tiles alternated `--reps` times in one process, medians and spreads; the results of the two tiles are compared bit for bit at every shape.  The auto
+rule's constant (gemm.hpp: GEMM_NARROW_TILES) is read off this table: the largest count of 256 x 256 tiles below which the narrow kernel is never the slower one.
+
+    python tools/narrow_gemm_sweep.py --out profiles/r16_narrow_gemm_sweep.json"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from blim_amd import engine as eng  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--ms", default="32,64,128,256,512,1024,2048,4096")
+    ap.add_argument("--shapes", default="3584x3584,3584x18944", help="N x K")
+    ap.add_argument("--dtype", default="f16", choices=["f16", "bf16"])
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--inner", type=int, default=10)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    tdt = torch.float16 if a.dtype == "f16" else torch.bfloat16
+    g = torch.Generator(device="cuda").manual_seed(1)
+    rows = []
+    for shape in a.shapes.split(","):
+        N, K = (int(x) for x in shape.split("x"))
+        w = (torch.randn((N, K), device="cuda", generator=g) * 0.02).to(tdt)
+        for M in (int(x) for x in a.ms.split(",")):
+            x = torch.randn((M, K), device="cuda", generator=g).to(tdt)
+            base = torch.randn((M, N), device="cuda", generator=g)
+            out = {}
+            for tile in (0, 2):                                                       # the same bits, and a warm-up of both kernels
+                c = base.clone()
+                n0 = eng.gemm_narrow_launches()
+                eng.gemm("resid", a.dtype, x, w, M, N, K, c, tile=tile)
+                torch.cuda.synchronize()
+                assert eng.gemm_narrow_launches() - n0 == (1 if tile == 2 else 0)
+                out[tile] = c
+            assert torch.equal(out[0].view(torch.int32), out[2].view(torch.int32)), (M, N, K, "the two tiles' results differ")
+            c = base.clone()
+            ts = {0: [], 2: []}
+            for _ in range(a.reps):
+                for tile in (0, 2):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(a.inner):
+                        eng.gemm("resid", a.dtype, x, w, M, N, K, c, tile=tile)
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ts[tile].append(e0.elapsed_time(e1) * 1e3 / a.inner)
+            med = {t: float(np.median(v)) for t, v in ts.items()}
+            r = {"M": M, "N": N, "K": K, "tiles_256": -(-M // 256) * -(-N // 256), "tiles_narrow": -(-M // 64) * -(-N // 64), "wide_us": med[0], "narrow_us": med[2],
+                 "wide_spread": float((max(ts[0]) - min(ts[0])) / med[0]), "narrow_spread": float((max(ts[2]) - min(ts[2])) / med[2]), "narrow_over_wide": med[2] / med[0],
+                 "wide_tflops": 2.0 * M * N * K / med[0] * 1e-6, "narrow_tflops": 2.0 * M * N * K / med[2] * 1e-6}
+            rows.append(r)
+            print(json.dumps(r), flush=True)
+    res = {"dtype": a.dtype, "reps": a.reps, "inner": a.inner, "threshold_tiles_in_library": eng.gemm_narrow_threshold(), "rows": rows}
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
