@@ -635,3 +635,169 @@ extern "C" int blim_rope_bwd(void* out16, const float* dqkv, int64_t n_tokens, i
     ARG_CHECK(n_tokens * (qkv_n / 2) < (1ll << 31) * 256);
     return launch_rope_bwd((uint16_t*)out16, dqkv, n_tokens, qkv_n, rope_cols, positions, cos, sin, n_pos, dtype16 == BLIM_COMPUTE_F16 ? DT_F16 : DT_BF16, (hipStream_t)stream);
 }
+
+// ---------------------------------------------------------------------------- the remaining kernels of train_kernels.hip as building blocks (tests)
+// Each entry runs the launchers the trainer runs, in the trainer's order, over caller memory; the argument errors are reported here (the launchers repeat some),
+// so that the host-only build of this file sees them too.
+#define TK_MAX_DIM (1 << 24)                  // N, K, V: keeps N * r and the launchers' other int products inside int
+#define TK_MAX_ROWS (65535ll * 1024)          // T: lora_wgrad_kernel's time splits are the grid's y range
+static bool tk_aligned(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
+static int tk_dtype(int32_t dtype16) { return dtype16 == BLIM_COMPUTE_F16 ? DT_F16 : DT_BF16; }
+static int64_t tk_up16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
+static int tk_workspace(const char* what, const void* ws, int64_t have, int64_t need) {
+    if (!ws) { blim_set_error("%s: workspace is NULL", what); return BLIM_ERR_ARG; }
+    if (!tk_aligned(ws, 16)) { blim_set_error("%s: workspace is not 16-byte aligned", what); return BLIM_ERR_ARG; }
+    if (need < 0 || have < need) { blim_set_error("%s: workspace of %lld bytes, %lld needed", what, (long long)have, (long long)need); return BLIM_ERR_ARG; }
+    return BLIM_OK;
+}
+
+extern "C" int64_t blim_lora_down_workspace_bytes(int32_t n_adapters, int32_t K) {
+    if (n_adapters < 1 || n_adapters > 3 || K <= 0 || K > TK_MAX_DIM || K % 16 != 0) return -1;
+    return (int64_t)n_adapters * 16 * K * 2;
+}
+extern "C" int blim_lora_down(const blim_lora_down_args* args, void* stream) {
+    ARG_CHECK(args && args->struct_bytes >= (int64_t)sizeof(blim_lora_down_args));
+    const blim_lora_down_args& a = *args;
+    hipStream_t s = (hipStream_t)stream;
+    ARG_CHECK(a.dtype16 == BLIM_COMPUTE_BF16 || a.dtype16 == BLIM_COMPUTE_F16);
+    ARG_CHECK(a.n_adapters >= 1 && a.n_adapters <= 3 && a.r >= 1 && a.r <= 16);
+    ARG_CHECK(a.T > 0 && a.T <= TK_MAX_ROWS && a.K > 0 && a.K <= TK_MAX_DIM && a.K % 16 == 0 && a.ldx % 8 == 0);
+    ARG_CHECK(a.x16 && tk_aligned(a.x16, 16));
+    for (int j = 0; j < a.n_adapters; ++j) ARG_CHECK(a.A[j] != nullptr);
+    ARG_CHECK(a.drop_p >= 0.f && a.drop_p < 1.f);
+    if (a.ldx < (int64_t)a.K + a.n_adapters * a.r) { blim_set_error("lora down: row stride %lld is shorter than K + n_adapters * r = %d", (long long)a.ldx, a.K + a.n_adapters * a.r); return BLIM_ERR_ARG; }
+    TRY(tk_workspace("lora down", a.workspace, a.workspace_bytes, blim_lora_down_workspace_bytes(a.n_adapters, a.K)));
+    const int dt = tk_dtype(a.dtype16);
+    HIP_TRY(hipMemsetAsync(a.workspace, 0, (size_t)a.n_adapters * 16 * a.K * 2, s));                  // rows r..15 of every A16 are the MFMA tile's zero padding
+    LoraDownArgs la; la.n = a.n_adapters; la.A16[0] = la.A16[1] = la.A16[2] = nullptr;
+    for (int j = 0; j < a.n_adapters; ++j) {
+        uint16_t* A16 = (uint16_t*)a.workspace + (int64_t)j * 16 * a.K;
+        TRY(launch_lora_a16(A16, a.A[j], a.K, a.r, dt, s));
+        la.A16[j] = A16;
+    }
+    return launch_lora_down((uint16_t*)a.x16, a.ldx, a.T, a.K, la, a.r, a.scale, a.drop_p, a.seed, a.site, dt, s);
+}
+
+static int64_t lora_grads_scratch(int32_t flags, int64_t T, int32_t N, int32_t K, int32_t r) {
+    size_t b = 0;
+    if (flags & BLIM_LORA_DB) b = std::max(b, lora_wgrad_scratch_bytes(T, N, r));
+    if (flags & BLIM_LORA_DA) b = std::max(b, lora_wgrad_scratch_bytes(T, K, r));
+    if (flags & BLIM_LORA_DU) b = std::max(b, lora_du_scratch_bytes(T, (int)round_up(N, 16), r));
+    return tk_up16((int64_t)b);
+}
+extern "C" int64_t blim_lora_grads_workspace_bytes(int32_t flags, int64_t T, int32_t N, int32_t K, int32_t r) {
+    if (flags <= 0 || flags > 7 || T <= 0 || T > TK_MAX_ROWS || r < 1 || r > 16) return -1;
+    if ((flags & (BLIM_LORA_DB | BLIM_LORA_DU)) && (N <= 0 || N > TK_MAX_DIM)) return -1;
+    if ((flags & BLIM_LORA_DA) && (K <= 0 || K > TK_MAX_DIM || K % 8 != 0)) return -1;
+    return lora_grads_scratch(flags, T, N, K, r) + ((flags & BLIM_LORA_DU) ? 16 * round_up(N, 16) * 2 : 0);
+}
+extern "C" int blim_lora_grads(const blim_lora_grads_args* args, void* stream) {
+    ARG_CHECK(args && args->struct_bytes >= (int64_t)sizeof(blim_lora_grads_args));
+    const blim_lora_grads_args& a = *args;
+    hipStream_t s = (hipStream_t)stream;
+    const bool dB = a.flags & BLIM_LORA_DB, dU = a.flags & BLIM_LORA_DU, dA = a.flags & BLIM_LORA_DA;
+    ARG_CHECK(a.flags > 0 && a.flags <= 7);
+    ARG_CHECK(a.dtype16 == BLIM_COMPUTE_BF16 || a.dtype16 == BLIM_COMPUTE_F16);
+    ARG_CHECK(a.r >= 1 && a.r <= 16 && a.T > 0 && a.T <= TK_MAX_ROWS);
+    const int64_t Np = round_up(a.N, 16);
+    if (dB || dU) {
+        ARG_CHECK(a.N > 0 && a.N <= TK_MAX_DIM && a.dy16 && tk_aligned(a.dy16, 16) && a.ldy % 8 == 0);
+        if (a.ldy < (dU ? Np : round_up(a.N, 8))) { blim_set_error("lora grads: dy row stride %lld is shorter than N rounded up to %d", (long long)a.ldy, dU ? 16 : 8); return BLIM_ERR_ARG; }
+    }
+    if (dB) ARG_CHECK(a.dB && a.u16 && a.ldu >= a.r);
+    if (dU) ARG_CHECK(a.B && a.du);
+    if (dA) {
+        ARG_CHECK(a.dA && a.du && a.x16 && tk_aligned(a.x16, 16) && a.K > 0 && a.K <= TK_MAX_DIM && a.K % 8 == 0 && a.ldx % 8 == 0 && a.drop_p >= 0.f && a.drop_p < 1.f);
+        if (a.ldx < a.K) { blim_set_error("lora grads: x row stride %lld is shorter than K = %d", (long long)a.ldx, a.K); return BLIM_ERR_ARG; }
+    }
+    TRY(tk_workspace("lora grads", a.workspace, a.workspace_bytes, blim_lora_grads_workspace_bytes(a.flags, a.T, a.N, a.K, a.r)));
+    const int dt = tk_dtype(a.dtype16);
+    float* scr = (float*)a.workspace;
+    if (dB) TRY(launch_lora_dB(a.dB, (const uint16_t*)a.dy16, a.ldy, (const uint16_t*)a.u16, a.ldu, a.T, a.N, a.r, dt, scr, s));
+    if (dU) {
+        uint16_t* Bt16 = (uint16_t*)((char*)a.workspace + lora_grads_scratch(a.flags, a.T, a.N, a.K, a.r));
+        HIP_TRY(hipMemsetAsync(Bt16, 0, (size_t)16 * Np * 2, s));                                     // rows r.. and columns N.. stay zero
+        TRY(launch_lora_bt(Bt16, Np, a.B, a.N, a.r, dt, s));
+        TRY(launch_lora_du(a.du, (const uint16_t*)a.dy16, a.ldy, Bt16, Np, a.T, (int)Np, a.r, a.scale, dt, scr, s));
+    }
+    if (dA) TRY(launch_lora_dA(a.dA, a.du, (const uint16_t*)a.x16, a.ldx, a.T, a.K, a.r, a.drop_p, a.seed, a.site, dt, scr, s));
+    return BLIM_OK;
+}
+
+static int tk_dx_args(LoraDxArgs* la, int32_t n, const float* const* du, const float* const* A) {
+    la->n = n;
+    for (int j = 0; j < 3; ++j) { la->du[j] = j < n ? du[j] : nullptr; la->A[j] = j < n ? A[j] : nullptr; }
+    for (int j = 0; j < n; ++j) ARG_CHECK(du[j] != nullptr && A[j] != nullptr && tk_aligned(A[j], 16));
+    return BLIM_OK;
+}
+extern "C" int blim_lora_dx(const blim_lora_dx_args* args, void* stream) {
+    ARG_CHECK(args && args->struct_bytes >= (int64_t)sizeof(blim_lora_dx_args));
+    const blim_lora_dx_args& a = *args;
+    ARG_CHECK(a.dtype16 == BLIM_COMPUTE_BF16 || a.dtype16 == BLIM_COMPUTE_F16);
+    ARG_CHECK(a.n_adapters >= 1 && a.n_adapters <= 3 && a.r >= 1 && a.r <= 16);
+    ARG_CHECK(a.T > 0 && a.T <= TK_MAX_ROWS && a.K > 0 && a.K <= TK_MAX_DIM && a.K % 4 == 0 && a.ldd % 4 == 0 && a.dx && tk_aligned(a.dx, 16));
+    ARG_CHECK(a.drop_p >= 0.f && a.drop_p < 1.f);
+    if (a.ldd < a.K) { blim_set_error("lora dx: dx row stride %lld is shorter than K = %d", (long long)a.ldd, a.K); return BLIM_ERR_ARG; }
+    if (a.out16) {
+        ARG_CHECK(a.ldo % 4 == 0 && tk_aligned(a.out16, 8));
+        if (a.ldo < a.K) { blim_set_error("lora dx: out16 row stride %lld is shorter than K = %d", (long long)a.ldo, a.K); return BLIM_ERR_ARG; }
+    }
+    LoraDxArgs la;
+    TRY(tk_dx_args(&la, a.n_adapters, a.du, a.A));
+    return launch_lora_dx(a.dx, a.ldd, la, a.T, a.K, a.r, a.drop_p, a.seed, a.site, (hipStream_t)stream, (uint16_t*)a.out16, a.ldo, tk_dtype(a.dtype16));
+}
+
+extern "C" int blim_rmsnorm_bwd(const blim_rmsnorm_bwd_args* args, void* stream) {
+    ARG_CHECK(args && args->struct_bytes >= (int64_t)sizeof(blim_rmsnorm_bwd_args));
+    const blim_rmsnorm_bwd_args& a = *args;
+    ARG_CHECK(a.dtype16 == BLIM_COMPUTE_BF16 || a.dtype16 == BLIM_COMPUTE_F16);
+    ARG_CHECK(a.dx && a.dy && a.x && a.w && tk_aligned(a.dx, 16) && tk_aligned(a.dy, 16) && tk_aligned(a.x, 16) && tk_aligned(a.w, 16));
+    ARG_CHECK(a.n_rows > 0 && a.n_rows <= 0x7fffffffll && a.H > 0 && a.H % 4 == 0 && a.n_adapters >= 0 && a.n_adapters <= 3);
+    if (a.H > 8192) { blim_set_error("rmsnorm backward: H = %d > 8192", a.H); return BLIM_ERR_ARG; }
+    if (a.out16 && a.rows) { blim_set_error("rmsnorm backward: out16 with rows (the 16-bit copy has no gather form)"); return BLIM_ERR_ARG; }
+    if (a.n_adapters > 0 && a.rows) { blim_set_error("rmsnorm backward: adapters with rows (the fused form has no gather)"); return BLIM_ERR_ARG; }
+    if (a.n_adapters > 0 && a.H > 4096) { blim_set_error("rmsnorm backward: adapters with H = %d > 4096 (run blim_lora_dx first)", a.H); return BLIM_ERR_ARG; }
+    if (a.out16) ARG_CHECK(tk_aligned(a.out16, 8));
+    const int dt = tk_dtype(a.dtype16);
+    if (a.n_adapters == 0) return launch_rmsnorm_bwd(a.dx, a.dy, a.x, a.rows, a.n_rows, a.H, a.w, a.eps, a.accumulate, (uint16_t*)a.out16, dt, (hipStream_t)stream);
+    ARG_CHECK(a.r >= 1 && a.r <= 16 && a.drop_p >= 0.f && a.drop_p < 1.f);
+    LoraDxArgs la;
+    TRY(tk_dx_args(&la, a.n_adapters, a.du, a.A));
+    return launch_rmsnorm_bwd(a.dx, a.dy, a.x, nullptr, a.n_rows, a.H, a.w, a.eps, a.accumulate, (uint16_t*)a.out16, dt, (hipStream_t)stream, &la, a.r, a.drop_p, a.seed, a.site);
+}
+
+extern "C" int64_t blim_ce_workspace_bytes(int64_t n_rows) { return n_rows <= 0 || n_rows > 0x7fffffffll ? -1 : tk_up16(n_rows * 4); }
+extern "C" int blim_ce_fwd_bwd(const float* logits, int64_t ldl, int32_t V, const int32_t* labels, int32_t label_div, int64_t n_rows, float coef, void* dl16, float* dl32,
+                               int64_t ldd, float* loss, int32_t dtype16, void* workspace, int64_t workspace_bytes, void* stream) {
+    ARG_CHECK(logits && labels && loss && n_rows > 0 && n_rows <= 0x7fffffffll && V > 0 && V <= TK_MAX_DIM && label_div >= 1);
+    ARG_CHECK(dtype16 == BLIM_COMPUTE_BF16 || dtype16 == BLIM_COMPUTE_F16);
+    if ((dl16 != nullptr) == (dl32 != nullptr)) { blim_set_error("cross-entropy: exactly one of dl16 and dl32"); return BLIM_ERR_ARG; }
+    if (ldl < V || ldd < V || ldd > 0x7fffffffll) { blim_set_error("cross-entropy: a row stride is shorter than V = %d (ldl %lld, ldd %lld)", V, (long long)ldl, (long long)ldd); return BLIM_ERR_ARG; }
+    TRY(tk_workspace("cross-entropy", workspace, workspace_bytes, blim_ce_workspace_bytes(n_rows)));
+    return launch_ce_fwd_bwd(logits, ldl, V, labels, label_div, n_rows, coef, (uint16_t*)dl16, dl32, ldd, loss, tk_dtype(dtype16), (float*)workspace, (hipStream_t)stream);
+}
+
+extern "C" int blim_gelu(int32_t backward, void* out16, int64_t ldo, const void* pre16, const float* dh, int64_t rows, int32_t H, int32_t dtype16, void* stream) {
+    ARG_CHECK(out16 && pre16 && rows > 0 && H > 0 && H <= TK_MAX_DIM && rows <= TK_MAX_ROWS);
+    ARG_CHECK(dtype16 == BLIM_COMPUTE_BF16 || dtype16 == BLIM_COMPUTE_F16);
+    if (backward) {
+        ARG_CHECK(dh != nullptr);
+        if (ldo != H) { blim_set_error("gelu backward: ldo %lld != H = %d (the gradient rows are contiguous)", (long long)ldo, H); return BLIM_ERR_ARG; }
+        return launch_gelu_bwd((uint16_t*)out16, dh, (const uint16_t*)pre16, rows, H, tk_dtype(dtype16), (hipStream_t)stream);
+    }
+    if (ldo < H) { blim_set_error("gelu: ldo %lld is shorter than H = %d", (long long)ldo, H); return BLIM_ERR_ARG; }
+    return launch_gelu_fwd((uint16_t*)out16, ldo, (const uint16_t*)pre16, rows, H, tk_dtype(dtype16), (hipStream_t)stream);
+}
+
+extern "C" int blim_adamw_raw(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                              float inv_scale, int32_t step, void* stream) {
+    ARG_CHECK(p && g && exp_avg && exp_avg_sq && step >= 1 && n > 0 && n <= (1ll << 38));
+    const float c1 = 1.0f - powf(beta1, (float)step), c2 = 1.0f - powf(beta2, (float)step);       // as blim_train_adamw
+    return launch_adamw(p, g, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, inv_scale, c1, c2, (hipStream_t)stream);
+}
+extern "C" int64_t blim_grad_stats_workspace_bytes(int64_t n) { return n <= 0 || n > (1ll << 40) ? -1 : 1024 * 4; }
+extern "C" int blim_grad_stats_raw(const float* g, int64_t n, float inv_scale, float* stats, void* workspace, int64_t workspace_bytes, void* stream) {
+    ARG_CHECK(g && stats && n > 0 && n <= (1ll << 40));
+    TRY(tk_workspace("grad stats", workspace, workspace_bytes, blim_grad_stats_workspace_bytes(n)));
+    return launch_grad_stats(g, n, inv_scale, stats, (float*)workspace, (hipStream_t)stream);
+}

@@ -66,6 +66,40 @@ class AttentionBwdArgs(C.Structure):
                 ("scale", C.c_float), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("dqkv", C.c_void_p), ("n_tokens", C.c_int64)]
 
 
+class LoraDownArgs(C.Structure):
+    """blim_lora_down_args (include/blim.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("x16", C.c_void_p), ("ldx", C.c_int64), ("T", C.c_int64), ("K", C.c_int32), ("n_adapters", C.c_int32),
+                ("r", C.c_int32), ("dtype16", C.c_int32), ("A", C.c_void_p * 3), ("scale", C.c_float), ("drop_p", C.c_float), ("seed", C.c_uint64),
+                ("site", C.c_uint32), ("reserved", C.c_int32), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
+class LoraGradsArgs(C.Structure):
+    """blim_lora_grads_args (include/blim.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("flags", C.c_int32), ("dtype16", C.c_int32), ("T", C.c_int64), ("N", C.c_int32), ("K", C.c_int32),
+                ("r", C.c_int32), ("reserved", C.c_int32), ("dy16", C.c_void_p), ("ldy", C.c_int64), ("u16", C.c_void_p), ("ldu", C.c_int64),
+                ("x16", C.c_void_p), ("ldx", C.c_int64), ("B", C.c_void_p), ("scale", C.c_float), ("drop_p", C.c_float), ("seed", C.c_uint64),
+                ("site", C.c_uint32), ("reserved2", C.c_int32), ("dB", C.c_void_p), ("du", C.c_void_p), ("dA", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64)]
+
+
+class LoraDxArgs(C.Structure):
+    """blim_lora_dx_args (include/blim.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("dx", C.c_void_p), ("ldd", C.c_int64), ("T", C.c_int64), ("K", C.c_int32), ("n_adapters", C.c_int32),
+                ("r", C.c_int32), ("dtype16", C.c_int32), ("du", C.c_void_p * 3), ("A", C.c_void_p * 3), ("drop_p", C.c_float), ("site", C.c_uint32),
+                ("seed", C.c_uint64), ("out16", C.c_void_p), ("ldo", C.c_int64)]
+
+
+class RmsnormBwdArgs(C.Structure):
+    """blim_rmsnorm_bwd_args (include/blim.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("dx", C.c_void_p), ("dy", C.c_void_p), ("x", C.c_void_p), ("rows", C.c_void_p), ("n_rows", C.c_int64),
+                ("H", C.c_int32), ("accumulate", C.c_int32), ("w", C.c_void_p), ("eps", C.c_float), ("dtype16", C.c_int32), ("out16", C.c_void_p),
+                ("n_adapters", C.c_int32), ("r", C.c_int32), ("du", C.c_void_p * 3), ("A", C.c_void_p * 3), ("drop_p", C.c_float), ("site", C.c_uint32),
+                ("seed", C.c_uint64)]
+
+
+LORA_DB, LORA_DU, LORA_DA = 1, 2, 4
+
+
 class GemmArgs(C.Structure):
     """blim_gemm_args (include/blim.h)."""
     _fields_ = [("struct_bytes", C.c_int64), ("epi", C.c_int32), ("dtype", C.c_int32), ("A", C.c_void_p), ("lda", C.c_int64), ("W", C.c_void_p),
@@ -143,6 +177,18 @@ def load_library(path: str = LIB_PATH):
         "blim_attention_bwd_workspace_bytes": ([i64, i32, i32, i32], C.c_int64),
         "blim_attention_bwd": ([C.POINTER(AttentionBwdArgs), vp], C.c_int),
         "blim_rope_bwd": ([vp, vp, i64, i32, i32, vp, vp, vp, i32, i32, vp], C.c_int),
+        "blim_lora_down_workspace_bytes": ([i32, i32], C.c_int64),
+        "blim_lora_down": ([C.POINTER(LoraDownArgs), vp], C.c_int),
+        "blim_lora_grads_workspace_bytes": ([i32, i64, i32, i32, i32], C.c_int64),
+        "blim_lora_grads": ([C.POINTER(LoraGradsArgs), vp], C.c_int),
+        "blim_lora_dx": ([C.POINTER(LoraDxArgs), vp], C.c_int),
+        "blim_rmsnorm_bwd": ([C.POINTER(RmsnormBwdArgs), vp], C.c_int),
+        "blim_ce_workspace_bytes": ([i64], C.c_int64),
+        "blim_ce_fwd_bwd": ([vp, i64, i32, vp, i32, i64, f32, vp, vp, i64, vp, i32, vp, i64, vp], C.c_int),
+        "blim_gelu": ([i32, vp, i64, vp, vp, i64, i32, i32, vp], C.c_int),
+        "blim_adamw_raw": ([vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, i32, vp], C.c_int),
+        "blim_grad_stats_workspace_bytes": ([i64], C.c_int64),
+        "blim_grad_stats_raw": ([vp, i64, f32, vp, vp, i64, vp], C.c_int),
         "blim_gemm": ([C.POINTER(GemmArgs), vp], C.c_int),
         "blim_gemm_narrow_launches": ([], C.c_int64),
         "blim_gemm_narrow_threshold": ([], C.c_int32),
@@ -803,6 +849,103 @@ def rope_bwd(dqkv, rope_cols: int, positions, cos, sin, out16):
     _check(lib.blim_rope_bwd(_ptr(out16), _ptr(dqkv), dqkv.shape[0], dqkv.shape[1], rope_cols, _ptr(positions), _ptr(cos), _ptr(sin), cos.shape[0],
                              COMPUTE_DTYPES["bf16" if out16.dtype == torch.bfloat16 else "f16"], _stream()), "blim_rope_bwd")
     return out16
+
+
+# ---- the trainer's remaining kernels alone (include/blim.h: blim_lora_down .. blim_grad_stats_raw).  Tensors are device tensors written in place; `workspace` is a
+# uint8 tensor of the entry's *_workspace_bytes(...) or more; `dtype` is "f16" / "bf16".  Row strides are explicit: the tests pad their rows.
+def _dt16(t) -> int:
+    import torch
+    assert t.dtype in (torch.bfloat16, torch.float16)
+    return COMPUTE_DTYPES["bf16" if t.dtype == torch.bfloat16 else "f16"]
+
+
+def _ptr3(ts):
+    arr = (C.c_void_p * 3)()
+    for i, t in enumerate(ts):
+        arr[i] = _ptr(t)
+    return arr
+
+
+def lora_down_workspace_bytes(n_adapters: int, K: int) -> int:
+    return int(load_library().blim_lora_down_workspace_bytes(n_adapters, K))
+
+
+def lora_down(x16, T: int, K: int, A: Sequence, r: int, scale: float, drop_p: float, seed: int, site: int, workspace, ldx: Optional[int] = None):
+    """blim_lora_down: x16 16-bit [rows >= T, ldx], A a list of 1..3 f32 [r, K] tensors; columns K .. K + len(A) * r of rows < T are written."""
+    a = LoraDownArgs()
+    a.struct_bytes = C.sizeof(LoraDownArgs)
+    a.x16 = _ptr(x16); a.ldx = x16.shape[1] if ldx is None else ldx; a.T = T; a.K = K; a.n_adapters = len(A); a.r = r; a.dtype16 = _dt16(x16)
+    a.A = _ptr3(A); a.scale = scale; a.drop_p = drop_p; a.seed = seed; a.site = site
+    a.workspace = _ptr(workspace); a.workspace_bytes = workspace.numel()
+    _check(load_library().blim_lora_down(C.byref(a), _stream()), "blim_lora_down")
+    return x16
+
+
+def lora_grads_workspace_bytes(flags: int, T: int, N: int, K: int, r: int) -> int:
+    return int(load_library().blim_lora_grads_workspace_bytes(flags, T, N, K, r))
+
+
+def lora_grads(flags: int, T: int, r: int, workspace, dtype: str, N: int = 0, K: int = 0, dy16=None, ldy: int = 0, u16=None, ldu: int = 0, x16=None, ldx: int = 0,
+               B=None, scale: float = 1.0, drop_p: float = 0.0, seed: int = 0, site: int = 0, dB=None, du=None, dA=None, u16_offset: int = 0):
+    """blim_lora_grads: flags = LORA_DB | LORA_DU | LORA_DA.  u16_offset: u16 starts that many 16-bit elements into the tensor (the u~ columns of an augmented row)."""
+    a = LoraGradsArgs()
+    a.struct_bytes = C.sizeof(LoraGradsArgs)
+    a.flags = flags; a.dtype16 = COMPUTE_DTYPES[dtype]; a.T = T; a.N = N; a.K = K; a.r = r
+    a.dy16 = _ptr(dy16); a.ldy = ldy; a.u16 = None if u16 is None else _ptr(u16) + 2 * u16_offset; a.ldu = ldu; a.x16 = _ptr(x16); a.ldx = ldx; a.B = _ptr(B)
+    a.scale = scale; a.drop_p = drop_p; a.seed = seed; a.site = site; a.dB = _ptr(dB); a.du = _ptr(du); a.dA = _ptr(dA)
+    a.workspace = _ptr(workspace); a.workspace_bytes = workspace.numel()
+    _check(load_library().blim_lora_grads(C.byref(a), _stream()), "blim_lora_grads")
+
+
+def lora_dx(dx, T: int, K: int, du: Sequence, A: Sequence, r: int, drop_p: float, seed: int, site: int, out16=None, dtype: str = "f16"):
+    """blim_lora_dx: dx f32 [rows >= T, ldd] (+)= the adapters' input gradient; with out16 ([rows, ldo] 16-bit) dx is only read."""
+    a = LoraDxArgs()
+    a.struct_bytes = C.sizeof(LoraDxArgs)
+    a.dx = _ptr(dx); a.ldd = dx.shape[1]; a.T = T; a.K = K; a.n_adapters = len(A); a.r = r
+    a.dtype16 = COMPUTE_DTYPES[dtype] if out16 is None else _dt16(out16)
+    a.du = _ptr3(du); a.A = _ptr3(A); a.drop_p = drop_p; a.site = site; a.seed = seed; a.out16 = _ptr(out16); a.ldo = out16.shape[1] if out16 is not None else 0
+    _check(load_library().blim_lora_dx(C.byref(a), _stream()), "blim_lora_dx")
+
+
+def rmsnorm_bwd(dx, dy, x, w, eps: float, n_rows: int, H: int, rows=None, accumulate: int = 0, out16=None, dtype: str = "f16", du: Sequence = (), A: Sequence = (),
+                r: int = 0, drop_p: float = 0.0, seed: int = 0, site: int = 0):
+    """blim_rmsnorm_bwd: dx, x f32 [*, H], dy f32 [n_rows, H]; rows int32 [n_rows] (gather); out16 16-bit [*, H]; du / A: the fused adapters."""
+    a = RmsnormBwdArgs()
+    a.struct_bytes = C.sizeof(RmsnormBwdArgs)
+    a.dx = _ptr(dx); a.dy = _ptr(dy); a.x = _ptr(x); a.rows = _ptr(rows); a.n_rows = n_rows; a.H = H; a.accumulate = accumulate; a.w = _ptr(w); a.eps = eps
+    a.dtype16 = COMPUTE_DTYPES[dtype] if out16 is None else _dt16(out16)
+    a.out16 = _ptr(out16); a.n_adapters = len(A); a.r = r; a.du = _ptr3(du); a.A = _ptr3(A); a.drop_p = drop_p; a.site = site; a.seed = seed
+    _check(load_library().blim_rmsnorm_bwd(C.byref(a), _stream()), "blim_rmsnorm_bwd")
+
+
+def ce_workspace_bytes(n_rows: int) -> int:
+    return int(load_library().blim_ce_workspace_bytes(n_rows))
+
+
+def ce_fwd_bwd(logits, V: int, labels, label_div: int, n_rows: int, coef: float, loss, workspace, dl16=None, dl32=None, dtype: str = "f16"):
+    """blim_ce_fwd_bwd: logits f32 [n_rows, ldl], labels int32, loss f32 [1] (incremented), dl16 16-bit or dl32 f32 [n_rows, ldd]."""
+    out = dl16 if dl16 is not None else dl32
+    _check(load_library().blim_ce_fwd_bwd(_ptr(logits), logits.shape[1], V, _ptr(labels), label_div, n_rows, coef, _ptr(dl16), _ptr(dl32),
+                                          out.shape[1] if out is not None else 0, _ptr(loss), COMPUTE_DTYPES[dtype] if dl16 is None else _dt16(dl16),
+                                          _ptr(workspace), workspace.numel(), _stream()), "blim_ce_fwd_bwd")
+
+
+def gelu(pre16, out16, rows: int, H: int, dh=None):
+    """blim_gelu: forward (dh None) out16 [rows, ldo] = gelu(pre16 [rows, H]); backward out16 [rows, H] = 16-bit(dh * gelu'(pre16))."""
+    _check(load_library().blim_gelu(0 if dh is None else 1, _ptr(out16), out16.shape[1], _ptr(pre16), _ptr(dh), rows, H, _dt16(pre16), _stream()), "blim_gelu")
+
+
+def adamw_raw(p, g, exp_avg, exp_avg_sq, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, inv_scale: float, step: int):
+    _check(load_library().blim_adamw_raw(_ptr(p), _ptr(g), _ptr(exp_avg), _ptr(exp_avg_sq), p.numel(), lr, beta1, beta2, eps, weight_decay, inv_scale, step, _stream()),
+           "blim_adamw_raw")
+
+
+def grad_stats_workspace_bytes(n: int) -> int:
+    return int(load_library().blim_grad_stats_workspace_bytes(n))
+
+
+def grad_stats_raw(g, inv_scale: float, stats, workspace):
+    _check(load_library().blim_grad_stats_raw(_ptr(g), g.numel(), inv_scale, _ptr(stats), _ptr(workspace), workspace.numel(), _stream()), "blim_grad_stats_raw")
 
 
 _GEMM_POINTERS = ("bias", "resid_in", "rope_rows", "labels", "lse_part", "label_logit", "row_scale", "col_scale", "a_mx", "out8", "out_mx", "A6", "W6", "out6",

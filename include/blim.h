@@ -390,6 +390,129 @@ int blim_attention_bwd(const blim_attention_bwd_args* args, void* stream);
 int blim_rope_bwd(void* out16, const float* dqkv, int64_t n_tokens, int32_t qkv_n, int32_t rope_cols, const int32_t* positions, const float* cos, const float* sin,
                   int32_t n_pos, int32_t dtype16, void* stream);
 
+/* ---- The trainer's remaining kernels alone (tests; additive in ABI v9): the LoRA products, the RMSNorm backward, cross-entropy, GELU, AdamW and the gradient
+ * statistics of csrc/train_kernels.hip, each behind the launcher the trainer calls (csrc/train.hpp states the operations), over raw device pointers: no engine, no
+ * trainer.  Every entry checks its host-visible arguments before any launch (BLIM_ERR_ARG + blim_last_error()); scratch is ONE caller-owned workspace per entry,
+ * 16-byte aligned, contents on entry irrelevant, sized by the entry's ..._workspace_bytes(...) (-1 for arguments out of range).  dtype16 = BLIM_COMPUTE_BF16 / _F16,
+ * r = the adapter rank, 1..16.  The bases that the kernels read or write as vectors must be 16-byte aligned and are checked: x16, dy16, dx, dy, x, w and
+ * every A of the dx / RMSNorm entries (out16: 8 bytes); the others (u16, du, B, dB, dA, the GELU and optimizer arrays) are accessed element by element.  struct_bytes = sizeof(the struct). */
+
+/* u~ = scale * drop(x) A^T of 1..3 adapters reading the same rows: x16 16-bit [T, ldx], columns [0, K) are read, columns K + seg * r + j (seg < n_adapters, j < r)
+ * receive 16-bit(scale * sum_k drop_seg(x)[t, k] * 16-bit(A_seg[j, k])); nothing else is written.  A[seg]: f32 [r, K].  Adapter seg uses dropout site `site + seg`;
+ * the mask of element (t, k) is drop_mult4's at index t * K + k.  K % 16 == 0, ldx % 8 == 0, ldx >= K + n_adapters * r.
+ * workspace: n_adapters 16-bit [16, K] copies of A (rows r.. zeroed by the entry). */
+typedef struct blim_lora_down_args {
+    int64_t struct_bytes;
+    void* x16;
+    int64_t ldx, T;
+    int32_t K, n_adapters, r, dtype16;
+    const float* A[3];
+    float scale, drop_p;
+    uint64_t seed;
+    uint32_t site;
+    int32_t reserved;
+    void* workspace;
+    int64_t workspace_bytes;
+} blim_lora_down_args;
+int64_t blim_lora_down_workspace_bytes(int32_t n_adapters, int32_t K);
+int blim_lora_down(const blim_lora_down_args* args, void* stream);
+
+/* The three gradients of one adapter y += scale * B A drop(x), any subset (flags), in the trainer's order dB, du, dA:
+ *   BLIM_LORA_DB  dB f32 [N, r] += sum_t dy16[t, n] * u16[t, j]            dy16 16-bit [T, ldy] (ldy % 8 == 0, ldy >= round_up(N, 8); columns [N, ldy) are not
+ *                                                                          read into the result), u16 16-bit rows of stride ldu (the u~ columns of an augmented row)
+ *   BLIM_LORA_DU  du f32 [T, r]  = scale * sum_n dy16[t, n] * 16-bit(B[n, j])   B f32 [N, r]; OVERWRITTEN.  The contraction runs over round_up(N, 16) columns:
+ *                                                                          ldy >= round_up(N, 16) and dy16 columns [N, round_up(N, 16)) MUST BE ZERO
+ *   BLIM_LORA_DA  dA f32 [r, K] += sum_t du[t, j] * drop(x16)[t, k]        x16 16-bit [T, ldx] (K % 8 == 0, ldx % 8 == 0, ldx >= K), du f32 [T, r] (this call's
+ *                                                                          when BLIM_LORA_DU is set, else the caller's), entering as hi + lo 16-bit parts
+ * workspace: the split reductions' partial sums (the largest of the selected products'), then Bt16 16-bit [16, round_up(N, 16)] for du. */
+#define BLIM_LORA_DB 1
+#define BLIM_LORA_DU 2
+#define BLIM_LORA_DA 4
+typedef struct blim_lora_grads_args {
+    int64_t struct_bytes;
+    int32_t flags, dtype16;
+    int64_t T;
+    int32_t N, K, r, reserved;
+    const void* dy16;
+    int64_t ldy;
+    const void* u16;
+    int64_t ldu;
+    const void* x16;
+    int64_t ldx;
+    const float* B;
+    float scale, drop_p;
+    uint64_t seed;
+    uint32_t site;
+    int32_t reserved2;
+    float* dB;
+    float* du;
+    float* dA;
+    void* workspace;
+    int64_t workspace_bytes;
+} blim_lora_grads_args;
+int64_t blim_lora_grads_workspace_bytes(int32_t flags, int64_t T, int32_t N, int32_t K, int32_t r);
+int blim_lora_grads(const blim_lora_grads_args* args, void* stream);
+
+/* The adapters' input gradient: dx f32 [T, ldd] columns [0, K) += sum_seg keep_seg(t, k) / (1 - p) * sum_j du[seg][t, j] * A[seg][j, k] (du f32 [T, r], A f32 [r, K]).
+ * out16 != NULL: dx is only READ and the sum leaves as 16-bit rows [T, ldo] instead.  K % 4 == 0, ldd % 4 == 0, ldo % 4 == 0, both >= K.  No workspace. */
+typedef struct blim_lora_dx_args {
+    int64_t struct_bytes;
+    float* dx;
+    int64_t ldd, T;
+    int32_t K, n_adapters, r, dtype16;
+    const float* du[3];
+    const float* A[3];
+    float drop_p;
+    uint32_t site;
+    uint64_t seed;
+    void* out16;
+    int64_t ldo;
+} blim_lora_dx_args;
+int blim_lora_dx(const blim_lora_dx_args* args, void* stream);
+
+/* d/dx of y = w * x * rsqrt(mean(x^2) + eps) applied to dy f32 [n_rows, H]: row i of dy belongs to row (rows ? rows[i] : i) of x and dx (f32, row stride H);
+ * accumulate != 0 adds to dx.  out16 (rows == NULL): the 16-bit copy of the updated dx rows.  n_adapters > 0 (rows == NULL, H <= 4096): dy is taken as
+ * dy + blim_lora_dx's term (du, A, r, drop_p, seed, site as there, K = H), formed on the fly.  H % 4 == 0, H <= 8192.  Refused by name: out16 with rows,
+ * adapters with rows, adapters with H > 4096, H > 8192.  No workspace. */
+typedef struct blim_rmsnorm_bwd_args {
+    int64_t struct_bytes;
+    float* dx;
+    const float* dy;
+    const float* x;
+    const int32_t* rows;
+    int64_t n_rows;
+    int32_t H, accumulate;
+    const float* w;
+    float eps;
+    int32_t dtype16;
+    void* out16;
+    int32_t n_adapters, r;
+    const float* du[3];
+    const float* A[3];
+    float drop_p;
+    uint32_t site;
+    uint64_t seed;
+} blim_rmsnorm_bwd_args;
+int blim_rmsnorm_bwd(const blim_rmsnorm_bwd_args* args, void* stream);
+
+/* Cross-entropy over rows of f32 logits [n_rows, ldl] (columns [V, ldl) are not read): the label of row i is labels[i / label_div]; *loss += sum_i -log_softmax(
+ * logits[i])[label]; d = coef * (softmax - onehot) leaves as 16-bit (dl16) or f32 (dl32) rows [n_rows, ldd] -- exactly one of the two -- with columns [V, ldd)
+ * written as 0.  A label < 0 or >= V: loss 0 and an all-zero gradient row.  workspace: n_rows floats (the per-row losses, summed in a fixed order). */
+int64_t blim_ce_workspace_bytes(int64_t n_rows);
+int blim_ce_fwd_bwd(const float* logits, int64_t ldl, int32_t V, const int32_t* labels, int32_t label_div, int64_t n_rows, float coef, void* dl16, float* dl32,
+                    int64_t ldd, float* loss, int32_t dtype16, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Exact-erf GELU on 16-bit pre-activations pre16 [rows, H] (contiguous).  backward == 0: out16 [rows, ldo] = gelu(pre16), ldo >= H, dh not read.
+ * backward != 0: out16 [rows, H] = 16-bit(dh * gelu'(pre16)), dh f32 [rows, H], ldo == H. */
+int blim_gelu(int32_t backward, void* out16, int64_t ldo, const void* pre16, const float* dh, int64_t rows, int32_t H, int32_t dtype16, void* stream);
+
+/* blim_train_adamw's kernel on caller arrays of n floats (step >= 1 gives the bias corrections), and blim_train_grad_stats's: stats[0] += sum (g * inv_scale)^2,
+ * stats[1] = 1 if any g * inv_scale is inf / NaN (otherwise untouched).  workspace of the latter: 1024 floats. */
+int blim_adamw_raw(float* p, const float* g, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                   float inv_scale, int32_t step, void* stream);
+int64_t blim_grad_stats_workspace_bytes(int64_t n);
+int blim_grad_stats_raw(const float* g, int64_t n, float inv_scale, float* stats, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The GEMM kernel alone (tests; additive in ABI v9): C [M, N] = A [M, K] . W [N, K]^T with every epilogue and operand form the engine and the trainer launch,
  * chosen by the same fields they set (csrc/gemm.hpp states them; a zero / NULL field is "off").  A: row stride lda, W: row stride K (w_wrap_k when set).
  * dtype BLIM_COMPUTE_BF16 / _F16: A, W and 16-bit outputs in that format; BLIM_COMPUTE_F8: A, W e4m3 bytes with row_scale [M] (or the E8M0 table a_mx) and

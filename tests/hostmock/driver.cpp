@@ -378,11 +378,205 @@ static void gemm_calls() {
     EXPECT(blim_gemm(&a, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "trainer"));
 }
 
+// the engine-less entries of the trainer's small kernels: one good call each, then every refusal and the workspace-size arithmetic
+static uint8_t* aligned16(std::vector<uint8_t>& mem) { return mem.data() + (16 - ((uintptr_t)mem.data() & 15)) % 16; }
+static void train_kernel_calls() {
+    const int T = 70, K = 48, N = 100, r = 8, H = 128;
+    std::vector<uint16_t> x16((size_t)T * (K + 64), 0), dy16((size_t)T * 120, 0), o16((size_t)T * 2 * H, 0);
+    std::vector<float> A((size_t)16 * H, 0.f), B((size_t)N * 16, 0.f), dB((size_t)N * 16, 0.f), du((size_t)T * 16, 0.f), dA((size_t)16 * K, 0.f), f32a((size_t)T * H, 0.f),
+        f32b((size_t)T * H, 0.f), f32c((size_t)T * H, 0.f), w(H, 1.f), stats(2, 0.f), loss(1, 0.f);
+    std::vector<int32_t> rows = {3, 1, 0}, labels(T, 2);
+    std::vector<uint8_t> ws_mem(1 << 20, 0xFF);
+    uint8_t* const ws = aligned16(ws_mem);
+    // ---- blim_lora_down
+    EXPECT(blim_lora_down_workspace_bytes(3, K) == 3 * 16 * K * 2 && blim_lora_down_workspace_bytes(1, 1024) == 32768);
+    EXPECT(blim_lora_down_workspace_bytes(0, K) == -1 && blim_lora_down_workspace_bytes(4, K) == -1 && blim_lora_down_workspace_bytes(1, K + 8) == -1 && blim_lora_down_workspace_bytes(1, 0) == -1);
+    blim_lora_down_args d;
+    memset(&d, 0, sizeof d);
+    d.struct_bytes = sizeof d; d.x16 = x16.data(); d.ldx = K + 64; d.T = T; d.K = K; d.n_adapters = 3; d.r = r; d.dtype16 = BLIM_COMPUTE_F16;
+    d.A[0] = d.A[1] = d.A[2] = A.data(); d.scale = 2.f; d.drop_p = 0.1f; d.seed = 5; d.site = 8; d.workspace = ws; d.workspace_bytes = blim_lora_down_workspace_bytes(3, K);
+    const blim_lora_down_args dgood = d;
+    EXPECT(blim_lora_down(&d, nullptr) == 0);
+    d.dtype16 = BLIM_COMPUTE_BF16; d.n_adapters = 1; d.r = 16; d.drop_p = 0.f;
+    EXPECT(blim_lora_down(&d, nullptr) == 0);
+    EXPECT(blim_lora_down(nullptr, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.struct_bytes = 8;      EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.x16 = nullptr;         EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.A[2] = nullptr;        EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.dtype16 = BLIM_COMPUTE_F8; EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.r = 0;                 EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.r = 17;                EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.n_adapters = 4;        EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.T = 0;                 EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.K = 40;                EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.ldx = K + 60;          EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.ldx = K + 16;          EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "row stride"));
+    d = dgood; d.drop_p = 1.f;          EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.x16 = x16.data() + 1;  EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG);
+    d = dgood; d.workspace = nullptr;   EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+    d = dgood; d.workspace = ws + 4;    EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "aligned"));
+    d = dgood; d.workspace_bytes -= 2;  EXPECT(blim_lora_down(&d, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+    // ---- blim_lora_grads
+    const int all = BLIM_LORA_DB | BLIM_LORA_DU | BLIM_LORA_DA;
+    EXPECT(blim_lora_grads_workspace_bytes(BLIM_LORA_DB, 2049, 264, 0, 16) == 3 * 264 * 16 * 4);                  // three time splits of 1,024 rows
+    EXPECT(blim_lora_grads_workspace_bytes(BLIM_LORA_DA, 1024, 0, 136, 4) == 136 * 4 * 4 && blim_lora_grads_workspace_bytes(BLIM_LORA_DA, 1025, 0, 136, 4) == 2 * 136 * 4 * 4);
+    EXPECT(blim_lora_grads_workspace_bytes(BLIM_LORA_DU, 33, 16, 0, 4) == 33 * 4 * 4 + 16 * 16 * 2);               // one slice [T, r], rounded up to 16 bytes, then Bt16 [16, 16]
+    EXPECT(blim_lora_grads_workspace_bytes(BLIM_LORA_DU, 33, 9, 0, 4) == blim_lora_grads_workspace_bytes(BLIM_LORA_DU, 33, 16, 0, 4));      // N rounds up to 16
+    EXPECT(blim_lora_grads_workspace_bytes(all, T, N, K, r) % 16 == 0 && blim_lora_grads_workspace_bytes(all, T, N, K, r) >= blim_lora_grads_workspace_bytes(BLIM_LORA_DU, T, N, K, r));
+    EXPECT(blim_lora_grads_workspace_bytes(0, T, N, K, r) == -1 && blim_lora_grads_workspace_bytes(8, T, N, K, r) == -1 && blim_lora_grads_workspace_bytes(all, 0, N, K, r) == -1);
+    EXPECT(blim_lora_grads_workspace_bytes(all, T, 0, K, r) == -1 && blim_lora_grads_workspace_bytes(all, T, N, 4, r) == -1 && blim_lora_grads_workspace_bytes(all, T, N, K, 17) == -1);
+    EXPECT(blim_lora_grads_workspace_bytes(BLIM_LORA_DA, T, 0, K, r) > 0 && blim_lora_grads_workspace_bytes(BLIM_LORA_DB, T, N, 0, r) > 0);      // the unused width is not looked at
+    blim_lora_grads_args g;
+    memset(&g, 0, sizeof g);
+    g.struct_bytes = sizeof g; g.flags = all; g.dtype16 = BLIM_COMPUTE_F16; g.T = T; g.N = N; g.K = K; g.r = r; g.dy16 = dy16.data(); g.ldy = 120; g.u16 = x16.data() + K; g.ldu = K + 64;
+    g.x16 = x16.data(); g.ldx = K + 64; g.B = B.data(); g.scale = 2.f; g.drop_p = 0.1f; g.seed = 5; g.site = 8; g.dB = dB.data(); g.du = du.data(); g.dA = dA.data();
+    g.workspace = ws; g.workspace_bytes = blim_lora_grads_workspace_bytes(all, T, N, K, r);
+    const blim_lora_grads_args ggood = g;
+    EXPECT(blim_lora_grads(&g, nullptr) == 0);
+    for (int flags = 1; flags <= 7; ++flags) { g = ggood; g.flags = flags; g.dtype16 = flags & 1 ? BLIM_COMPUTE_BF16 : BLIM_COMPUTE_F16; EXPECT(blim_lora_grads(&g, nullptr) == 0); }
+    g = ggood; g.flags = BLIM_LORA_DB; g.ldy = 104; g.B = nullptr; g.x16 = nullptr; g.du = nullptr; g.dA = nullptr; g.K = 0;      // dB alone: N rounded up to 8 is enough, the rest unused
+    EXPECT(blim_lora_grads(&g, nullptr) == 0);
+    EXPECT(blim_lora_grads(nullptr, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.struct_bytes = 8;      EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.flags = 0;             EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.flags = 8;             EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.dtype16 = BLIM_COMPUTE_F8; EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.r = 17;                EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.T = 0;                 EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.N = 0;                 EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.dy16 = nullptr;        EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.ldy = 116;             EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.ldy = 104;             EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "rounded up to 16"));      // du contracts over round_up(N, 16)
+    g = ggood; g.flags = BLIM_LORA_DB; g.ldy = 96; EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "rounded up to 8"));
+    g = ggood; g.u16 = nullptr;         EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.ldu = r - 1;           EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.dB = nullptr;          EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.B = nullptr;           EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.du = nullptr;          EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.dA = nullptr;          EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.x16 = nullptr;         EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.K = 44;                EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.ldx = K + 4;           EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.ldx = K - 8;           EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "row stride"));
+    g = ggood; g.drop_p = -0.1f;        EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG);
+    g = ggood; g.workspace = nullptr;   EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+    g = ggood; g.workspace = ws + 8;    EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "aligned"));
+    g = ggood; g.workspace_bytes -= 2;  EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+    g = ggood; g.T = 2049;              EXPECT(blim_lora_grads(&g, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));      // three time splits: the same workspace is too small now
+    // ---- blim_lora_dx
+    blim_lora_dx_args x;
+    memset(&x, 0, sizeof x);
+    x.struct_bytes = sizeof x; x.dx = f32a.data(); x.ldd = H; x.T = T; x.K = H - 4; x.n_adapters = 3; x.r = r; x.dtype16 = BLIM_COMPUTE_F16;
+    x.du[0] = x.du[1] = x.du[2] = du.data(); x.A[0] = x.A[1] = x.A[2] = A.data(); x.drop_p = 0.1f; x.site = 8; x.seed = 5;
+    const blim_lora_dx_args xgood = x;
+    EXPECT(blim_lora_dx(&x, nullptr) == 0);
+    x.out16 = o16.data(); x.ldo = H; x.dtype16 = BLIM_COMPUTE_BF16; x.n_adapters = 1;
+    EXPECT(blim_lora_dx(&x, nullptr) == 0);
+    const blim_lora_dx_args x16good = x;
+    EXPECT(blim_lora_dx(nullptr, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.struct_bytes = 8;      EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.dx = nullptr;          EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.dx = f32a.data() + 1;  EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.du[1] = nullptr;       EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.A[2] = nullptr;        EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.n_adapters = 0;        EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.r = 17;                EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.T = 0;                 EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.K = H - 2;             EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.ldd = H + 2;           EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.ldd = H - 8;           EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "row stride"));
+    x = xgood; x.dtype16 = BLIM_COMPUTE_F8; EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = xgood; x.drop_p = 1.5f;         EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = x16good; x.ldo = H - 2;         EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG);
+    x = x16good; x.ldo = H - 8;         EXPECT(blim_lora_dx(&x, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "row stride"));
+    // ---- blim_rmsnorm_bwd
+    blim_rmsnorm_bwd_args n;
+    memset(&n, 0, sizeof n);
+    n.struct_bytes = sizeof n; n.dx = f32a.data(); n.dy = f32b.data(); n.x = f32c.data(); n.n_rows = 5; n.H = H; n.w = w.data(); n.eps = 1e-6f; n.dtype16 = BLIM_COMPUTE_F16;
+    const blim_rmsnorm_bwd_args ngood = n;
+    EXPECT(blim_rmsnorm_bwd(&n, nullptr) == 0);
+    n.rows = rows.data(); n.n_rows = 3; n.accumulate = 1;
+    EXPECT(blim_rmsnorm_bwd(&n, nullptr) == 0);
+    n = ngood; n.out16 = o16.data(); n.dtype16 = BLIM_COMPUTE_BF16;
+    EXPECT(blim_rmsnorm_bwd(&n, nullptr) == 0);
+    n.n_adapters = 3; n.r = r; n.du[0] = n.du[1] = n.du[2] = du.data(); n.A[0] = n.A[1] = n.A[2] = A.data(); n.drop_p = 0.1f; n.accumulate = 1;
+    EXPECT(blim_rmsnorm_bwd(&n, nullptr) == 0);
+    const blim_rmsnorm_bwd_args nfused = n;
+    EXPECT(blim_rmsnorm_bwd(nullptr, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.struct_bytes = 8;      EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.dx = nullptr;          EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.dy = nullptr;          EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.x = nullptr;           EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.w = nullptr;           EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.dy = f32b.data() + 1;  EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.n_rows = 0;            EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.H = H + 2;             EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.dtype16 = BLIM_COMPUTE_F8; EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.n_adapters = 4;        EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = ngood; n.H = 8196;              EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "> 8192"));
+    n = ngood; n.rows = rows.data(); n.n_rows = 3; n.out16 = o16.data(); EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "out16 with rows"));
+    n = nfused; n.out16 = nullptr; n.rows = rows.data(); n.n_rows = 3;   EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "adapters with rows"));
+    n = nfused; n.H = 4100;             EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "> 4096"));
+    n = nfused; n.r = 0;                EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = nfused; n.r = 17;               EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = nfused; n.du[2] = nullptr;      EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = nfused; n.A[0] = nullptr;       EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    n = nfused; n.drop_p = 1.f;         EXPECT(blim_rmsnorm_bwd(&n, nullptr) == BLIM_ERR_ARG);
+    // ---- blim_ce_fwd_bwd
+    const int V = 61;
+    EXPECT(blim_ce_workspace_bytes(16) == 64 && blim_ce_workspace_bytes(5) == 32 && blim_ce_workspace_bytes(0) == -1 && blim_ce_workspace_bytes(1ll << 31) == -1);
+    const int64_t cneed = blim_ce_workspace_bytes(T);
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == 0);
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 4, T, 0.5f, nullptr, f32b.data(), V, loss.data(), BLIM_COMPUTE_BF16, ws, cneed, nullptr) == 0);
+    EXPECT(blim_ce_fwd_bwd(nullptr, 64, V, labels.data(), 1, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, nullptr, 1, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, T, 0.5f, o16.data(), nullptr, 64, nullptr, BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 0, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, 0, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, 0, labels.data(), 1, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F8, ws, cneed, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, T, 0.5f, nullptr, nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "exactly one"));
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, T, 0.5f, o16.data(), f32b.data(), 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "exactly one"));
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), V - 1, V, labels.data(), 1, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "row stride"));
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, T, 0.5f, o16.data(), nullptr, V - 1, loss.data(), BLIM_COMPUTE_F16, ws, cneed, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "row stride"));
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, nullptr, cneed, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws + 4, cneed, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "aligned"));
+    EXPECT(blim_ce_fwd_bwd(f32a.data(), 64, V, labels.data(), 1, T, 0.5f, o16.data(), nullptr, 64, loss.data(), BLIM_COMPUTE_F16, ws, cneed - 16, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+    // ---- blim_gelu
+    EXPECT(blim_gelu(0, o16.data(), H + 8, x16.data(), nullptr, 20, H, BLIM_COMPUTE_F16, nullptr) == 0);
+    EXPECT(blim_gelu(1, o16.data(), H, x16.data(), f32a.data(), 20, H, BLIM_COMPUTE_BF16, nullptr) == 0);
+    EXPECT(blim_gelu(0, nullptr, H, x16.data(), nullptr, 20, H, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_gelu(0, o16.data(), H, nullptr, nullptr, 20, H, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_gelu(0, o16.data(), H, x16.data(), nullptr, 0, H, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_gelu(0, o16.data(), H, x16.data(), nullptr, 20, 0, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_gelu(0, o16.data(), H, x16.data(), nullptr, 20, H, BLIM_COMPUTE_F8, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_gelu(0, o16.data(), H - 1, x16.data(), nullptr, 20, H, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "shorter"));
+    EXPECT(blim_gelu(1, o16.data(), H, x16.data(), nullptr, 20, H, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_gelu(1, o16.data(), H + 8, x16.data(), f32a.data(), 20, H, BLIM_COMPUTE_F16, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "contiguous"));
+    // ---- blim_adamw_raw, blim_grad_stats_raw
+    EXPECT(blim_adamw_raw(f32a.data(), f32b.data(), f32c.data(), du.data(), 257, 1e-3f, 0.9f, 0.95f, 1e-8f, 0.05f, 1.f, 1, nullptr) == 0);
+    EXPECT(blim_adamw_raw(nullptr, f32b.data(), f32c.data(), du.data(), 257, 1e-3f, 0.9f, 0.95f, 1e-8f, 0.05f, 1.f, 1, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_adamw_raw(f32a.data(), nullptr, f32c.data(), du.data(), 257, 1e-3f, 0.9f, 0.95f, 1e-8f, 0.05f, 1.f, 1, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_adamw_raw(f32a.data(), f32b.data(), nullptr, du.data(), 257, 1e-3f, 0.9f, 0.95f, 1e-8f, 0.05f, 1.f, 1, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_adamw_raw(f32a.data(), f32b.data(), f32c.data(), nullptr, 257, 1e-3f, 0.9f, 0.95f, 1e-8f, 0.05f, 1.f, 1, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_adamw_raw(f32a.data(), f32b.data(), f32c.data(), du.data(), 0, 1e-3f, 0.9f, 0.95f, 1e-8f, 0.05f, 1.f, 1, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_adamw_raw(f32a.data(), f32b.data(), f32c.data(), du.data(), 257, 1e-3f, 0.9f, 0.95f, 1e-8f, 0.05f, 1.f, 0, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_grad_stats_workspace_bytes(1) == 4096 && blim_grad_stats_workspace_bytes(256 * 1024 + 5) == 4096 && blim_grad_stats_workspace_bytes(0) == -1);
+    EXPECT(blim_grad_stats_raw(f32a.data(), 257, 1.f, stats.data(), ws, 4096, nullptr) == 0);
+    EXPECT(blim_grad_stats_raw(nullptr, 257, 1.f, stats.data(), ws, 4096, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_grad_stats_raw(f32a.data(), 257, 1.f, nullptr, ws, 4096, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_grad_stats_raw(f32a.data(), 0, 1.f, stats.data(), ws, 4096, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_grad_stats_raw(f32a.data(), 257, 1.f, stats.data(), nullptr, 4096, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+    EXPECT(blim_grad_stats_raw(f32a.data(), 257, 1.f, stats.data(), ws + 4, 4096, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "aligned"));
+    EXPECT(blim_grad_stats_raw(f32a.data(), 257, 1.f, stats.data(), ws, 4092, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
+}
+
 int main() {
     EXPECT(blim_abi_version() == BLIM_ABI_VERSION);
     attention_calls();
     attention_bwd_calls();
     gemm_calls();
+    train_kernel_calls();
     blim_engine* e = nullptr;
     // ---- creation: bad configurations, no device
     {
