@@ -972,7 +972,7 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
               GemmParams p = gp3(e, attn_live, Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, n_live, H, rl, H, 0, pf, cO, false); p.ldc = H; p.lo_off = 0;
               if (lo6 && cO) { p = gp(c.compute_dtype, attn_live, 2 * Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, n_live, H, (int)Hq, rl, H);
                          TRY(attach_lo6(p, attn_live, 2 * Hq, n_live, (int)Hq, G ? e->AD[li].wo_aug6 : l.wo6)); }
-              p.narrow = e->narrow_gemm; TRY(launch_gemm(EPI_RESID, p, s)); }
+              p.narrow = e->narrow_gemm; p.narrow_lo6 = e->narrow_lo6; TRY(launch_gemm(EPI_RESID, p, s)); }
             { SpanGuard g(e, s, TC_NORM, 0);
               TRY(launch_rmsnorm(rl, H, nullptr, n_live, H, l.norm2, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pfm * H, (cG && !n2_tiles) ? xn + H : nullptr, true, n2_tiles ? (uint8_t*)e->a6.p : nullptr)); }
             // SwiGLU output [n_live, pfm * I]: `act` holds attn_live only until o_proj above has run (stream order), so it is free again here
@@ -983,7 +983,7 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
             { SpanGuard g(e, s, TC_GEMM_DOWN, 2.0 * tl * H * I * (cD ? 2 : 1));
               GemmParams p = gp3(e, act, I, l.wd, n_live, H, rl, H, 0, pfm, cD, false); p.ldc = H; p.lo_off = 0;
               if (lo6 && cD) { p = gp(c.compute_dtype, act, 2 * (int64_t)I, l.wd, n_live, H, I, rl, H); if (fuse6) { p.A6 = (const uint8_t*)e->a6b.p; p.W6 = l.wd6; p.K6 = (int)I; } else TRY(attach_lo6(p, act, 2 * (int64_t)I, n_live, I, l.wd6)); }
-              p.narrow = e->narrow_gemm; TRY(launch_gemm(EPI_RESID, p, s)); }
+              p.narrow = e->narrow_gemm; p.narrow_lo6 = e->narrow_lo6; TRY(launch_gemm(EPI_RESID, p, s)); }
             *final_resid = rl; *final_is_live = true;
             break;
         }
@@ -1001,7 +1001,7 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
 #ifdef ENGINE_ABLATE_NORMFOLD
             if (!e->precise && !G && !o8 && e->lse_part.p) { p.swiglu_act = (uint16_t*)xn; p.swiglu_act_ld = H; p.col_scale = l.norm2; p.lse_part = (float2*)e->lse_part.p; }
 #endif
-            p.narrow = e->narrow_gemm;                                   // option "narrow_gemm": an ineligible form (fp8, the e2m3 second pass) keeps the 256 x 256 kernel
+            p.narrow = e->narrow_gemm; p.narrow_lo6 = e->narrow_lo6;      // options "narrow_gemm" (the plain and w_wrap_k forms) and "narrow_lo6" (the e2m3 second pass); fp8 keeps the 256 x 256 kernel
             TRY(launch_gemm(EPI_RESID, p, s));
         }
         {
@@ -1038,7 +1038,7 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
 #ifdef ENGINE_ABLATE_NORMFOLD
             if (!e->precise && !G && !d8 && e->lse_part.p && li + 1 < c.num_layers) { p.swiglu_act = (uint16_t*)xn; p.swiglu_act_ld = H; p.col_scale = e->L[li + 1].norm1; p.lse_part = (float2*)e->lse_part.p; }
 #endif
-            p.narrow = e->narrow_gemm;                                   // option "narrow_gemm": an ineligible form (fp8, the e2m3 second pass) keeps the 256 x 256 kernel
+            p.narrow = e->narrow_gemm; p.narrow_lo6 = e->narrow_lo6;      // options "narrow_gemm" (the plain and w_wrap_k forms) and "narrow_lo6" (the e2m3 second pass); fp8 keeps the 256 x 256 kernel
             TRY(launch_gemm(EPI_RESID, p, s));
         }
     }
@@ -1765,6 +1765,14 @@ extern "C" int blim_gemm(const blim_gemm_args* args, void* stream) {
         if (a.A6 || a.W6) { blim_set_error("gemm: tile = 2 (the narrow kernel) has no e2m3 second pass (A6 / W6)"); return BLIM_ERR_ARG; }
         if (a.a_mx) { blim_set_error("gemm: tile = 2 (the narrow kernel) takes no block-scaled A operand (a_mx)"); return BLIM_ERR_ARG; }
     }
+    // tile_lo6: the same three values for the form `tile` refuses, the residual epilogue with the e2m3 second pass (A6 / W6); 2 is refused, with the field named, for every other form
+    if (a.tile_lo6 < 0 || a.tile_lo6 > 2) { blim_set_error("gemm: tile_lo6 = %d (0 = 256 x 256, 1 = auto, 2 = narrow)", (int)a.tile_lo6); return BLIM_ERR_ARG; }
+    if (a.tile_lo6 == 2) {
+        if (a.epi != BLIM_EPI_RESID) { blim_set_error("gemm: tile_lo6 = 2 (the narrow e2m3 kernel) has the residual epilogue only (epi = %d)", (int)a.epi); return BLIM_ERR_ARG; }
+        if (f8) { blim_set_error("gemm: tile_lo6 = 2 (the narrow e2m3 kernel) takes fp16 / bf16 operands (dtype = f8)"); return BLIM_ERR_ARG; }
+        if (!a.A6 || !a.W6) { blim_set_error("gemm: tile_lo6 = 2 (the narrow e2m3 kernel) needs the e2m3 second pass (A6 / W6)"); return BLIM_ERR_ARG; }
+        if (a.w_wrap_k) { blim_set_error("gemm: tile_lo6 = 2 (the narrow e2m3 kernel) takes no wrapped W (w_wrap_k = %d): that form is `tile`'s", (int)a.w_wrap_k); return BLIM_ERR_ARG; }
+    }
     ARG_CHECK(a.K * es % 128 == 0 && a.lda * es % 16 == 0);
     ARG_CHECK(a.w_wrap_k == 0 || (a.K == 2 * a.w_wrap_k && a.w_wrap_k * es % 128 == 0));
     ARG_CHECK(a.lda >= a.K);
@@ -1816,7 +1824,7 @@ extern "C" int blim_gemm(const blim_gemm_args* args, void* stream) {
         ARG_CHECK(!a.out6 || (a.epi == BLIM_EPI_SWIGLU && a.lo_off > 0 && a.N % 256 == 0));
     }
     GemmParams p = gp(a.dtype, a.A, a.lda, a.W, a.M, a.N, a.K, fused8 ? a.out8 : a.C, a.ldc);
-    p.narrow = a.tile;
+    p.narrow = a.tile; p.narrow_lo6 = a.tile_lo6;
     p.row_scale = a.row_scale; p.col_scale = a.col_scale; p.bias = a.bias; p.resid_in = a.resid_in; p.act = a.act; p.scale = a.scale;
     p.swiglu_gu = (uint16_t*)a.swiglu_gu; p.swiglu_ld = a.swiglu_ld; p.swiglu_act = (uint16_t*)a.swiglu_act; p.swiglu_act_ld = a.swiglu_act_ld;
     p.rope_cols = a.rope_cols; p.rope_rows = a.rope_rows; p.rope_stride = a.rope_stride;
@@ -1900,6 +1908,10 @@ extern "C" int blim_set_option(blim_engine* e, const char* key, int32_t value) {
             blim_set_error("option 'precise_lo6': hidden and intermediate sizes must be multiples of 128, at most 20480"); return BLIM_ERR_ARG; }
         if (value && e->aug && e->aug % 128) { blim_set_error("option 'precise_lo6': adapters were loaded with a %d-column K extension; set the option before loading adapters", e->aug); return BLIM_ERR_STATE; }
         e->lo6 = value != 0; return BLIM_OK;
+    }
+    if (!strcmp(key, "narrow_lo6")) {
+        if (value < 0 || value > 2) { blim_set_error("option 'narrow_lo6': 0 (off), 1 (auto) or 2 (wherever eligible), got %d", (int)value); return BLIM_ERR_ARG; }
+        e->narrow_lo6 = value; return BLIM_OK;
     }
     if (!strcmp(key, "narrow_gemm")) {
         if (value < 0 || value > 2) { blim_set_error("option 'narrow_gemm': 0 (off), 1 (auto) or 2 (wherever eligible), got %d", (int)value); return BLIM_ERR_ARG; }

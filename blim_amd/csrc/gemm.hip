@@ -1140,6 +1140,48 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
 #define N_A_BYTES (NBM * 128)
 #define N_STEP_BYTES ((NBM + NBN) * 128)
 #define N_THREADS 256
+// The narrow kernels' epilogue: C = (resid_in ? resid_in : C) + (acc + bias), straight from the accumulators of one wave's 32 x 32 of C (first row wrow0, first
+// column wcol0; lane: row lane & 15 and four consecutive columns of each fragment: 64-byte row segments; the tile is 16 KiB).  The two forms and their associations
+// are gemm_kernel's: float4 where col + 3 < N, element by element beyond.
+__device__ __forceinline__ void narrow_resid_epilogue(const GemmParams& p, const f32x4 (&acc)[2][2], int wrow0, int wcol0, int lane) {
+    const int tq = lane >> 4, rsub = lane & 15;
+    const float* rsrc = p.resid_in ? p.resid_in : (const float*)p.C;
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) {
+        const int row = wrow0 + 16 * mi + rsub;
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const int col = wcol0 + 16 * ni + 4 * tq;
+            if (row >= p.M || col >= p.N) continue;
+            const f32x4 v = acc[mi][ni];
+            float* out = (float*)p.C + (int64_t)row * p.ldc + col;
+            const float* in = rsrc + (int64_t)row * p.ldc + col;
+            if ((col + 3 < p.N) && ((p.ldc & 3) == 0)) {
+                const float4 rb = p.bias ? *(const float4*)(p.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const float4 o = *(const float4*)in;
+                *(float4*)out = make_float4(o.x + (v[0] + rb.x), o.y + (v[1] + rb.y), o.z + (v[2] + rb.z), o.w + (v[3] + rb.w));
+            } else {
+                const float x[4] = {v[0], v[1], v[2], v[3]};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    if (col + j < p.N) out[j] = in[j] + x[j] + (p.bias ? p.bias[col + j] : 0.f);
+            }
+        }
+    }
+}
+// ... and their tile order: XCD-contiguous chunks (blocks b, b + 8, ... share an XCD), inside a chunk bands of group_m M-tiles walked M first -- the tiles an XCD
+// runs at one time share a few W panels (W is the large operand of these calls: each panel reaches one XCD's L2 only)
+__device__ __forceinline__ void narrow_tile(const GemmParams& p, int bid, int& tm, int& tn) {
+    const int ntm = (p.M + NBM - 1) / NBM, ntn = (p.N + NBN - 1) / NBN;
+    const int nwg = ntm * ntn;
+    const int xcd = bid & 7, cq = nwg >> 3, cr = nwg & 7;
+    const int pid = (xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq) + (bid >> 3);
+    const int width = p.group_m * ntn;
+    const int first_m = (pid / width) * p.group_m;
+    const int gsz = min(ntm - first_m, p.group_m);
+    tm = first_m + (pid % width) % gsz;
+    tn = (pid % width) / gsz;
+}
 template <int DT>
 __global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[NRING * N_STEP_BYTES];
@@ -1147,17 +1189,8 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
-    // tile order: XCD-contiguous chunks (blocks b, b + 8, ... share an XCD), inside a chunk bands of group_m M-tiles walked M first -- the tiles an XCD runs at
-    // one time share a few W panels (W is the large operand of these calls: each panel reaches one XCD's L2 only)
-    const int ntm = (p.M + NBM - 1) / NBM, ntn = (p.N + NBN - 1) / NBN;
-    const int nwg = ntm * ntn;
-    const int bid = blockIdx.x, xcd = bid & 7, cq = nwg >> 3, cr = nwg & 7;
-    const int pid = (xcd < cr ? xcd * (cq + 1) : cr * (cq + 1) + (xcd - cr) * cq) + (bid >> 3);
-    const int width = p.group_m * ntn;
-    const int first_m = (pid / width) * p.group_m;
-    const int gsz = min(ntm - first_m, p.group_m);
-    const int tm = first_m + (pid % width) % gsz;
-    const int tn = (pid % width) / gsz;
+    int tm, tn;
+    narrow_tile(p, blockIdx.x, tm, tn);
     const int row0 = tm * NBM, col0 = tn * NBN;
 
     // LDS-DMA sources: wave w stages blocks w and w + 4 (8 rows each) of both operands; lane -> row sr of the block, source chunk sc for its slot lane & 7
@@ -1233,32 +1266,161 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams
     }
     static_assert(NRING == 4, "the counted waits above are written for three steps in flight");
 
-    // ---- epilogue: C = (resid_in ? resid_in : C) + (acc + bias), straight from the accumulators (lane: row lane & 15 and four consecutive columns of each fragment:
-    // 64-byte row segments; the tile is 16 KiB).  The two forms and their associations are gemm_kernel's: float4 where col + 3 < N, element by element beyond.
-    const int tq = lane >> 4, rsub = lane & 15;
-    const float* rsrc = p.resid_in ? p.resid_in : (const float*)p.C;
+    narrow_resid_epilogue(p, acc, row0 + 32 * wm, col0 + 32 * wn, lane);
+}
+
+// ---- narrow-tile residual GEMM with the e2m3 second pass (GemmParams::narrow_lo6): gemm_narrow_kernel's tiles, order and 16-bit K walk
+// over the hi operand (lda > K, w_wrap_k = 0), then, in the SAME accumulators, one block-scaled e2m3 MFMA per 128-value K-step and accumulator fragment over the
+// A operand's lo part -- the chain gemm_kernel<EPI_RESID, DT, false, true> gives every C element (its phase 1, then its phase 2 in ascending K, W fragment first,
+// then the same epilogue), so the bits are that kernel's.  The second pass reads the SAME tile images (gemm.hpp, at A6): the 64-row quarter q of a 256-row tile is
+// the four consecutive fragment groups 4 q .. 4 q + 3 of every block -- 6 KiB contiguous -- its A-side scales are the 4-byte word + 4 (q & 1) of every lane's 8-byte
+// entry in the 512-byte half (q >> 1), the W-side scales of the 64-column group qn the 256 bytes at qn * 256.
+// ONE ring for both passes: step t of the nk + nk6 steps lives in slot t & 3 (16 KiB; a second-pass step fills 12 KiB + 1 KiB of scales of it), is requested
+// right behind the barrier that ends step t - 4, and costs every wave FOUR LDS-DMA requests in either pass (second pass: three KiB-blocks of e2m3 and a 256-byte
+// piece of the scales as 16-byte pieces of the first 16 lanes -- see dma6 on why not 4-byte ones; the fourth wave stages a spare copy of the W scales so that the
+// counted vmcnt waits are the same for all waves and across the hand-over).  The first second-pass steps are therefore in flight under the last 16-bit steps.
+#define N6_Q_BYTES 6144                      // a 64-row quarter of one operand's e2m3 block: four fragment groups of 1536 B
+#define N6_SC_OFF (2 * N6_Q_BYTES)           // the step's scales inside its slot: A half (512 B) | W group (256 B) | spare (256 B)
+template <int DT>
+__global__ __launch_bounds__(N_THREADS) void gemm_narrow_lo6_kernel(const GemmParams p) {
+    __shared__ __attribute__((aligned(16))) char smem[NRING * N_STEP_BYTES];
+    static_assert(N6_SC_OFF + 1024 <= N_STEP_BYTES, "a second-pass step fits a ring slot");
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    int tm, tn;
+    narrow_tile(p, blockIdx.x, tm, tn);
+    const int row0 = tm * NBM, col0 = tn * NBN;
+
+    // ---- first pass: gemm_narrow_kernel's sources and fragment reads
+    const int sr = lane >> 3;
+    const int sc = (lane & 7) ^ (4 * (wave & 1) + (sr >> 1));
+    uint32_t offA[2], offW[2];
 #pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-        const int row = row0 + 32 * wm + 16 * mi + rsub;
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-            const int col = col0 + 32 * wn + 16 * ni + 4 * tq;
-            if (row >= p.M || col >= p.N) continue;
-            const f32x4 v = acc[mi][ni];
-            float* out = (float*)p.C + (int64_t)row * p.ldc + col;
-            const float* in = rsrc + (int64_t)row * p.ldc + col;
-            if ((col + 3 < p.N) && ((p.ldc & 3) == 0)) {
-                const float4 rb = p.bias ? *(const float4*)(p.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-                const float4 o = *(const float4*)in;
-                *(float4*)out = make_float4(o.x + (v[0] + rb.x), o.y + (v[1] + rb.y), o.z + (v[2] + rb.z), o.w + (v[3] + rb.w));
-            } else {
-                const float x[4] = {v[0], v[1], v[2], v[3]};
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (col + j < p.N) out[j] = in[j] + x[j] + (p.bias ? p.bias[col + j] : 0.f);
-            }
-        }
+    for (int i = 0; i < 2; ++i) {
+        const int b = wave + 4 * i;
+        offA[i] = (uint32_t)((int64_t)min(row0 + 8 * b + sr, p.M - 1) * p.lda * 2 + 16 * sc);
+        offW[i] = (uint32_t)((int64_t)min(col0 + 8 * b + sr, p.N - 1) * p.K * 2 + 16 * sc);
     }
+    const char* baseA = (const char*)p.A;
+    const char* baseW = (const char*)p.W;
+    const int nk = p.K / 64;                                           // K-steps of 128 bytes
+    const int nk6 = p.K6 / 128;                                        // ... of 128 e2m3 values
+    const int nt = nk + nk6;
+    auto stage = [&](int slot, int kt) __attribute__((always_inline)) {
+        const char* ga = baseA + (int64_t)kt * 128;
+        const char* gw = baseW + (int64_t)kt * 128;
+        char* d = smem + slot * N_STEP_BYTES + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            uint32_t oa = offA[i], ow = offW[i];
+            asm volatile("" : "+v"(oa), "+v"(ow));
+            glds16(ga + oa, d + i * 4096);
+            glds16(gw + ow, d + N_A_BYTES + i * 4096);
+        }
+    };
+    const int fr = lane & 15, fc = lane >> 4;
+    const int fg = (fr >> 1) & 7;
+    const int frag_off = (fr >> 3) * 1024 + (fr & 7) * 128 + 16 * ((fc ^ (fg & 3)) + 4 * (fg >> 2));
+    const int a_off = (2 * wm) * 2048 + frag_off;
+    const int b_off = N_A_BYTES + (2 * wn) * 2048 + frag_off;
+
+    // ---- second pass: lane-linear copies out of the tile images.  A step's slot: [0, 6 KiB) the A quarter, [6, 12 KiB) the W quarter, then the scales.  Wave w
+    // copies KiB-blocks w, w + 4, w + 8 of those twelve and scale piece w (0, 1: the halves of the A half; 2: the W group; 3: the W group again, never read)
+    const int q = tm & 3, qn = tn & 3;
+    const char* g6A = (const char*)p.A6 + (int64_t)(tm >> 2) * nk6 * F6_TILE_BYTES;
+    const char* g6W = (const char*)p.W6 + (int64_t)(tn >> 2) * nk6 * F6_TILE_BYTES;
+    const char* qA = g6A + q * N6_Q_BYTES;
+    const char* qW = g6W + qn * N6_Q_BYTES;
+    const char* src6[4] = {qA + wave * 1024, wave < 2 ? qA + (wave + 4) * 1024 : qW + (wave - 2) * 1024, qW + (wave + 2) * 1024,
+                           wave < 2 ? g6A + 24576 + (q >> 1) * 512 + wave * 256 : g6W + 24576 + qn * 256};
+    auto stage6 = [&](int slot, int kd) __attribute__((always_inline)) {
+        const int64_t ko = (int64_t)kd * F6_TILE_BYTES;
+        char* d = smem + slot * N_STEP_BYTES;
+        uint32_t o16 = (uint32_t)lane * 16u;
+        asm volatile("" : "+v"(o16));
+#pragma unroll
+        for (int i = 0; i < 3; ++i) glds16(src6[i] + ko + o16, d + (wave + 4 * i) * 1024);
+        if (lane < 16) glds16(src6[3] + ko + o16, d + N6_SC_OFF + wave * 256);
+    };
+    typedef int i32x8 __attribute__((ext_vector_type(8)));
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    typedef int i32x2 __attribute__((ext_vector_type(2)));
+    typedef int i32x1 __attribute__((ext_vector_type(1)));
+    // one 16-row fragment: ds_read_b128 + ds_read_b64, as in gemm_kernel (rd6)
+    auto rd6 = [&](const char* fb) __attribute__((always_inline)) {
+        const i32x4 l = *(const i32x4*)(fb + lane * 16);
+        const i32x2 h = *(const i32x2*)(fb + 1024 + lane * 8);
+        return (i32x8){l[0], l[1], l[2], l[3], h[0], h[1], 0, 0};
+    };
+    const int a6_off = (2 * wm) * 1536, b6_off = N6_Q_BYTES + (2 * wn) * 1536;              // + mi / ni * 1536
+    const int sa_off = N6_SC_OFF + lane * 8 + 4 * (q & 1), sw_off = N6_SC_OFF + 512 + lane * 4;
+    const int sa_sh = 16 * wm, sw_sh = 16 * wn;                                              // this wave's two fragments: bytes 2 wm + mi / 2 wn + ni of the word
+
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    auto request = [&](int slot, int t) __attribute__((always_inline)) {
+        if (t < nk) stage(slot, t); else stage6(slot, t - nk);
+    };
+#pragma unroll
+    for (int s = 0; s < NRING - 1; ++s)
+        if (s < nt) request(s, s);
+    int slot = 0;
+    // the head of step t in either pass: my four requests of step t have landed (those of the at most NRING - 2 later steps requested so far may stay in flight),
+    // my LDS reads of step t - 1 have returned (WAR on the slot refilled below), one barrier, then the request of step t + NRING - 1
+    auto head = [&](int t) __attribute__((always_inline)) {
+        if (t + 2 < nt) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (t + NRING - 1 < nt) request((slot + NRING - 1) & (NRING - 1), t + NRING - 1);
+    };
+    for (int kt = 0; kt < nk; ++kt) {
+        head(kt);
+        const char* ba[2] = {smem + slot * N_STEP_BYTES + a_off, smem + ((slot * N_STEP_BYTES + a_off) ^ 64)};
+        const char* bb[2] = {smem + slot * N_STEP_BYTES + b_off, smem + ((slot * N_STEP_BYTES + b_off) ^ 64)};
+        bf16x8 fa[2][2], fb[2][2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) fb[ks][ni] = *(const bf16x8*)(bb[ks] + ni * 2048);
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) fa[ks][mi] = *(const bf16x8*)(ba[ks] + mi * 2048);
+        }
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma16<DT>(fb[ks][ni], fa[ks][mi], acc[mi][ni]);
+        slot = (slot + 1) & (NRING - 1);
+    }
+    for (int k6 = 0; k6 < nk6; ++k6) {
+        head(nk + k6);
+        const char* sb = smem + slot * N_STEP_BYTES;
+        // (scales read through ext-vector types like the fragments: see gemm_kernel's rd6_sw)
+        const uint32_t scw = (uint32_t)(*(const i32x1*)(sb + sw_off))[0] >> sw_sh;
+        const uint32_t sca = (uint32_t)(*(const i32x1*)(sb + sa_off))[0] >> sa_sh;
+        i32x8 fa8[2], fb8[2];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) fb8[ni] = rd6(sb + b6_off + ni * 1536);
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) fa8[mi] = rd6(sb + a6_off + mi * 1536);
+#define N6_MMA(MI, NI) acc[MI][NI] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb8[NI], fa8[MI], acc[MI][NI], 2, 2, NI, (int)scw, MI, (int)sca);   // cbsz = blgp = 2: e2m3
+        N6_MMA(0, 0) N6_MMA(0, 1) N6_MMA(1, 0) N6_MMA(1, 1)
+#undef N6_MMA
+        slot = (slot + 1) & (NRING - 1);
+    }
+    static_assert(NRING == 4, "the counted waits above are written for three steps in flight");
+
+    narrow_resid_epilogue(p, acc, row0 + 32 * wm, col0 + 32 * wn, lane);
 }
 
 #include <stdlib.h>
@@ -1333,7 +1495,7 @@ static int launch_t(const GemmParams& p, hipStream_t stream) {
 static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream);
 
 // ---- GemmParams::narrow.  The narrow kernel is instantiated for EPI_RESID on plain fp16 / bf16 operands (w_wrap_k and lda > K included); every other form --
-// the e2m3 second pass (A6 / W6), fp8 (a_mx included), any other epilogue, the timing aids -- keeps the 256 x 256 kernel whatever `narrow` says.
+// the e2m3 second pass (A6 / W6: GemmParams::narrow_lo6 below), fp8 (a_mx included), any other epilogue, the timing aids -- keeps the 256 x 256 kernel whatever `narrow` says.
 static std::atomic<int64_t> g_narrow_launches{0};
 extern "C" int64_t blim_gemm_narrow_launches(void) { return g_narrow_launches.load(); }
 extern "C" int32_t blim_gemm_narrow_threshold(void) { return GEMM_NARROW_TILES; }
@@ -1344,6 +1506,28 @@ static bool narrow_chosen(GemmEpi epi, const GemmParams& p) {
     if (p.narrow == 0 || !narrow_eligible(epi, p)) return false;
     if (p.narrow == 2) return true;
     return (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) < GEMM_NARROW_TILES;      // auto: gemm.hpp
+}
+// ---- GemmParams::narrow_lo6: the same choice for the form `narrow` leaves out, EPI_RESID with the e2m3 second pass (A6 / W6, w_wrap_k = 0), with a kernel, a
+// counter and a threshold of its own -- `narrow` and blim_gemm_narrow_launches() keep their meaning.
+static std::atomic<int64_t> g_narrow_lo6_launches{0};
+extern "C" int64_t blim_gemm_narrow_lo6_launches(void) { return g_narrow_lo6_launches.load(); }
+extern "C" int32_t blim_gemm_narrow_lo6_threshold(void) { return GEMM_NARROW_LO6_TILES; }
+static bool narrow_lo6_eligible(GemmEpi epi, const GemmParams& p) {
+    return epi == EPI_RESID && (p.dtype == DT_F16 || p.dtype == DT_BF16) && p.A6 && p.W6 && p.w_wrap_k == 0 && !p.a_mx && !p.swiglu_act && !p.debug_stamps && !p.debug_skip_epilogue;
+}
+static bool narrow_lo6_chosen(GemmEpi epi, const GemmParams& p) {
+    if (p.narrow_lo6 == 0 || !narrow_lo6_eligible(epi, p)) return false;
+    if (p.narrow_lo6 == 2) return true;
+    return (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) < GEMM_NARROW_LO6_TILES;  // auto: gemm.hpp
+}
+static int launch_narrow_lo6(const GemmParams& p, hipStream_t stream) {
+    const dim3 grid((unsigned)(((p.M + NBM - 1) / NBM) * ((p.N + NBN - 1) / NBN)));
+    if (p.dtype == DT_F16) hipLaunchKernelGGL((gemm_narrow_lo6_kernel<DT_F16>), grid, dim3(N_THREADS), 0, stream, p);
+    else hipLaunchKernelGGL((gemm_narrow_lo6_kernel<DT_BF16>), grid, dim3(N_THREADS), 0, stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { blim_set_error("narrow lo6 gemm launch failed: %s", hipGetErrorString(e)); return BLIM_ERR_HIP; }
+    g_narrow_lo6_launches.fetch_add(1);
+    return BLIM_OK;
 }
 static int launch_narrow(const GemmParams& p, hipStream_t stream) {
     const dim3 grid((unsigned)(((p.M + NBM - 1) / NBM) * ((p.N + NBN - 1) / NBN)));
@@ -1421,6 +1605,7 @@ static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream) {
     ARG_CHECK(p.w_wrap_k == 0 || (p.K == 2 * p.w_wrap_k && (int64_t)p.w_wrap_k * es % 128 == 0));   // A = [hi | lo]: W is walked twice
     ARG_CHECK(p.lo_off == 0 || epi == EPI_BF16 || epi == EPI_QKV || epi == EPI_SWIGLU);
     if (p.narrow < 0 || p.narrow > 2) { blim_set_error("gemm: narrow = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = the narrow kernel wherever it is eligible)", p.narrow); return BLIM_ERR_ARG; }
+    if (p.narrow_lo6 < 0 || p.narrow_lo6 > 2) { blim_set_error("gemm: narrow_lo6 = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = the narrow e2m3 kernel wherever it is eligible)", p.narrow_lo6); return BLIM_ERR_ARG; }
     ARG_CHECK((int64_t)p.M * p.lda * es < (1ll << 32) && (int64_t)p.N * (p.w_wrap_k > 0 ? p.w_wrap_k : p.K) * es < (1ll << 32));  // 32-bit operand offsets
     switch (epi) {
         case EPI_BF16:
@@ -1432,6 +1617,7 @@ static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream) {
         case EPI_RESID:
             ARG_CHECK(p.C && p.ldc % 4 == 0);
             if (narrow_chosen(epi, p)) return launch_narrow(p, stream);
+            if (narrow_lo6_chosen(epi, p)) return launch_narrow_lo6(p, stream);
             return launch_t<EPI_RESID>(p, stream);
         case EPI_QKV:
             ARG_CHECK(p.C && p.bias && p.rope_rows && p.rope_stride >= p.M && p.N % 128 == 0 && p.rope_cols % 128 == 0 && p.ldc % 4 == 0);

@@ -81,7 +81,9 @@ struct GemmParams {
     unsigned long long* debug_stamps;  // timing aid: [n_workgroups][8] s_memrealtime at {entry, main loop start, main loop end, exit, C staged in LDS, stores issued}
     int narrow;              // EPI_RESID on plain 16-bit operands (gemm.hip: gemm_narrow_kernel, 64 x 64 tiles, the same bits): 0 = the 256 x 256 kernel, 2 = the narrow kernel
                              // whenever the form is eligible, 1 = auto: eligible and fewer than GEMM_NARROW_TILES tiles of 256 x 256 (the measured crossover).  An ineligible form takes the
-                             // 256 x 256 kernel under any value.  LAST field: the existing kernels' argument offsets do not move
+                             // 256 x 256 kernel under any value.  Appended behind every older field: the existing kernels' argument offsets do not move
+    int narrow_lo6;          // EPI_RESID with the e2m3 second pass (A6 / W6, w_wrap_k = 0; gemm.hip: gemm_narrow_lo6_kernel, 64 x 64 tiles, the same bits): 0 / 2 / 1 as `narrow`, the
+                             // auto rule with a constant of its own (GEMM_NARROW_LO6_TILES).  An ineligible form takes the 256 x 256 kernel under any value.  LAST field
 };
 // auto rule of GemmParams::narrow: the narrow kernel runs when ceil(M / 256) * ceil(N / 256) < GEMM_NARROW_TILES.  Measured (profiles/r16_narrow_gemm.md, blim_gemm alone, fp16,
 // N = 3584, K = 3584 | 18944, narrow time over 256 x 256 time): 14 tiles (M <= 256) 0.30 - 0.34, 28 tiles (M = 512) 0.39 - 0.42, 56 tiles (M = 1024) 0.73 - 0.75, 112 tiles
@@ -89,6 +91,10 @@ struct GemmParams {
 // MEASURED point at which the narrow kernel wins, so auto takes it up to there and nowhere beyond (the starting rule, half the chip's 256 CUs = 128, would have been the
 // slower choice at 112 tiles)
 #define GEMM_NARROW_TILES 57
+// auto rule of GemmParams::narrow_lo6, by the same rule from a sweep of its own (profiles/r18_narrow_lo6.md, blim_gemm alone, fp16, the e2m3 second pass over K6 = K,
+// N = 3584, K = 3584 | 18944, narrow time over 256 x 256 time): 14 tiles 0.36 - 0.37, 28 tiles 0.43 - 0.44, 56 tiles 0.80 - 0.88, 112 tiles 1.39 - 1.60, 224 tiles
+// 2.05 - 2.50 -- the same crossover as the plain form's, with a little less to spare at 56 tiles (the second pass is a third of the narrow kernel's K-steps).  56 tiles is the last MEASURED point at which the narrow kernel wins
+#define GEMM_NARROW_LO6_TILES 57
 void gemm_set_debug_stamps(unsigned long long* buf);
 
 // 256x256 tiles x 128 bytes of K per step (64 16-bit / 128 fp8 elements), 512 threads.  K % 64 == 0 (fp8: % 128), lda % 8 == 0 (fp8: % 16).  Rows/cols beyond M/N are clamped on

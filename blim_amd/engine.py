@@ -108,7 +108,8 @@ class GemmArgs(C.Structure):
                 ("rope_cols", C.c_int32), ("rope_rows", C.c_void_p), ("rope_stride", C.c_int64), ("labels", C.c_void_p), ("lse_part", C.c_void_p),
                 ("label_logit", C.c_void_p), ("row_scale", C.c_void_p), ("col_scale", C.c_void_p), ("a_mx", C.c_void_p), ("out8", C.c_void_p),
                 ("out_mx", C.c_void_p), ("mx_stride", C.c_int64), ("A6", C.c_void_p), ("W6", C.c_void_p), ("K6", C.c_int32), ("f6_build", C.c_int32),
-                ("out6", C.c_void_p), ("swiglu_act", C.c_void_p), ("swiglu_act_ld", C.c_int64), ("swiglu_gu", C.c_void_p), ("swiglu_ld", C.c_int64), ("tile", C.c_int32)]
+                ("out6", C.c_void_p), ("swiglu_act", C.c_void_p), ("swiglu_act_ld", C.c_int64), ("swiglu_gu", C.c_void_p), ("swiglu_ld", C.c_int64), ("tile", C.c_int32),
+                ("tile_lo6", C.c_int32)]
 
 
 EPILOGUES = {"bf16": 0, "f32": 1, "resid": 2, "qkv": 3, "swiglu": 4, "lse": 5}
@@ -192,6 +193,8 @@ def load_library(path: str = LIB_PATH):
         "blim_gemm": ([C.POINTER(GemmArgs), vp], C.c_int),
         "blim_gemm_narrow_launches": ([], C.c_int64),
         "blim_gemm_narrow_threshold": ([], C.c_int32),
+        "blim_gemm_narrow_lo6_launches": ([], C.c_int64),
+        "blim_gemm_narrow_lo6_threshold": ([], C.c_int32),
         "blim_rope_rows_bytes": ([i32], C.c_int64),
         "blim_rope_rows": ([vp, i64, f32, i32, vp, vp, i64, vp], C.c_int),
         "blim_timing_enable": ([vp, i32], C.c_int),
@@ -950,7 +953,7 @@ def grad_stats_raw(g, inv_scale: float, stats, workspace):
 
 _GEMM_POINTERS = ("bias", "resid_in", "rope_rows", "labels", "lse_part", "label_logit", "row_scale", "col_scale", "a_mx", "out8", "out_mx", "A6", "W6", "out6",
                   "swiglu_act", "swiglu_gu")
-_GEMM_INTS = ("act", "w_wrap_k", "lo_off", "rope_cols", "rope_stride", "mx_stride", "K6", "f6_build", "swiglu_act_ld", "swiglu_ld", "tile")
+_GEMM_INTS = ("act", "w_wrap_k", "lo_off", "rope_cols", "rope_stride", "mx_stride", "K6", "f6_build", "swiglu_act_ld", "swiglu_ld", "tile", "tile_lo6")
 
 
 def gemm(epi: str, dtype: str, a, w, M: int, N: int, K: int, c=None, lda: Optional[int] = None, ldc: Optional[int] = None, scale: float = 1.0,
@@ -959,7 +962,8 @@ def gemm(epi: str, dtype: str, a, w, M: int, N: int, K: int, c=None, lda: Option
     e4m3 bytes), c the output buffer ([rows, ldc]: its width is the row stride unless ldc is given; None where the epilogue has no C).  Every other field of
     blim.h's blim_gemm_args by keyword: tensors for the pointers (bias, resid_in, rope_rows, labels, lse_part, label_logit, row_scale, col_scale, a_mx, out8,
     out_mx, A6, W6, out6, swiglu_act, swiglu_gu), ints for act, w_wrap_k, lo_off, rope_cols, rope_stride, mx_stride, K6, f6_build, swiglu_act_ld, swiglu_ld,
-    tile (0 = 256 x 256 tiles, 1 = auto, 2 = the narrow residual kernel: the same bits; gemm_narrow_launches() tells which kernel ran)."""
+    tile (0 = 256 x 256 tiles, 1 = auto, 2 = the narrow residual kernel: the same bits; gemm_narrow_launches() tells which kernel ran), tile_lo6 (the same three
+    values for the residual epilogue with A6 / W6: 2 = the narrow kernel with the e2m3 second pass; gemm_narrow_lo6_launches())."""
     lib = load_library()
     g = GemmArgs()
     g.struct_bytes = C.sizeof(GemmArgs)
@@ -986,6 +990,17 @@ def gemm_narrow_launches() -> int:
 def gemm_narrow_threshold() -> int:
     """The auto rule's constant: tile = 1 / option "narrow_gemm" = 1 take the narrow kernel below this many 256 x 256 tiles (blim_gemm_narrow_threshold)."""
     return int(load_library().blim_gemm_narrow_threshold())
+
+
+def gemm_narrow_lo6_launches() -> int:
+    """Launches of the narrow residual GEMM kernel with the e2m3 second pass by this process so far (blim_gemm_narrow_lo6_launches): a counter of its own,
+    gemm_narrow_launches() does not move on them."""
+    return int(load_library().blim_gemm_narrow_lo6_launches())
+
+
+def gemm_narrow_lo6_threshold() -> int:
+    """The auto rule's constant: tile_lo6 = 1 / option "narrow_lo6" = 1 take that kernel below this many 256 x 256 tiles (blim_gemm_narrow_lo6_threshold)."""
+    return int(load_library().blim_gemm_narrow_lo6_threshold())
 
 
 def rope_rows(positions, rope_theta: float, max_positions: int, stride: Optional[int] = None):

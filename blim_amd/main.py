@@ -90,6 +90,10 @@ def get_args_parser():
                    help="auto: the decoder layers' o_proj and down projections of SMALL calls (fewer 256 x 256 tiles than the library's measured threshold) run on the "
                         "narrow-tile residual GEMM, which spreads them over the whole chip; the scores are the same bit for bit (engine option \"narrow_gemm\" = 1).  "
                         "Refused with --dtype f8")
+    p.add_argument("--narrow_lo6", default="off", choices=["off", "auto"],
+                   help="auto: the same for the compensated o_proj and down launches that carry the e2m3 second pass (fp16 engines; bf16 under --second_pass e2m3), with a "
+                        "measured threshold of its own (engine option \"narrow_lo6\" = 1); the scores are the same bit for bit.  Does nothing where the compensated calls "
+                        "walk K twice in 16 bits: those launches are --narrow_gemm's.  Refused with --dtype f8")
     p.add_argument("--calibration_store", default=None, type=str, metavar="DIR",
                    help="keep what --vtg_precise auto | select, --tvg_precise auto and --second_pass auto measure in DIR, one JSON record per weights fingerprint "
                         "(blim_weights_fingerprint: weights, adapters, visual head, config) + numeric options + library build.  A later run on the same key checks the "
@@ -156,6 +160,8 @@ def main(args):
         raise SystemExit("training needs a 16-bit engine (--dtype f16 | bf16)")
     if args.narrow_gemm == "auto" and args.dtype == "f8":
         raise SystemExit("--narrow_gemm auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM takes fp16 / bf16 operands")
+    if args.narrow_lo6 == "auto" and args.dtype == "f8":
+        raise SystemExit("--narrow_lo6 auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM with the e2m3 second pass takes fp16 / bf16 operands")
     t0 = time.time()
     train_loader = None
     if args.synthetic > 0:
@@ -218,6 +224,10 @@ def main(args):
         if model.engine.dtype == "f8":
             raise SystemExit("--narrow_gemm auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM takes fp16 / bf16 operands")
         model.engine.set_option("narrow_gemm", 1)
+    if args.narrow_lo6 == "auto":
+        if model.engine.dtype == "f8":
+            raise SystemExit("--narrow_lo6 auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM with the e2m3 second pass takes fp16 / bf16 operands")
+        model.engine.set_option("narrow_lo6", 1)
     if model.engine.dtype == "f8":
         finetuned_file = bool(args.resume) and os.path.isfile(args.resume)
         mask = args.f8_mask if args.f8_mask is not None else (12 if finetuned_file else 31)

@@ -580,6 +580,7 @@ typedef struct blim_gemm_args {
     void* swiglu_gu;
     int64_t swiglu_ld;
     int32_t tile;          /* 0 = 256 x 256 tiles, 1 = auto, 2 = the narrow kernel (see below) */
+    int32_t tile_lo6;      /* the same for BLIM_EPI_RESID with A6 / W6: 0 = 256 x 256 tiles, 1 = auto, 2 = the narrow e2m3 kernel (see below) */
 } blim_gemm_args;
 int blim_gemm(const blim_gemm_args* args, void* stream);
 /* tile (added at the end of the struct; the ABI version is unchanged -- a shorter struct reads as 0): BLIM_EPI_RESID on fp16 / bf16 operands without A6 / W6 also exists
@@ -590,6 +591,15 @@ int blim_gemm(const blim_gemm_args* args, void* stream);
  * blim_gemm_narrow_launches(): launches of the narrow kernel by this process so far (host-side counter; tests read it to see which kernel ran). */
 int64_t blim_gemm_narrow_launches(void);
 int32_t blim_gemm_narrow_threshold(void);
+/* tile_lo6 (added behind `tile`, same rule: a shorter struct reads as 0): the form `tile` refuses -- BLIM_EPI_RESID on fp16 / bf16 operands WITH the e2m3 second
+ * pass (A6 / W6, w_wrap_k = 0) -- exists in 64 x 64 tiles as well.  The kernel walks the hi operand as the narrow kernel does and continues, in the same
+ * accumulators, with one block-scaled e2m3 MFMA per 128-value K-step over the same A6 / W6 tile images: every C element sees the 256 x 256 kernel's chain, so the
+ * bits are equal.  2 = that kernel; a call without A6 / W6, any other epilogue, BLIM_COMPUTE_F8 and w_wrap_k are refused with the field named.  1 = auto: that
+ * kernel when the form is eligible and ceil(M / 256) * ceil(N / 256) < blim_gemm_narrow_lo6_threshold(), the 256 x 256 kernel otherwise (an ineligible form is not
+ * an error).  Other values: BLIM_ERR_ARG.  `tile` keeps every behaviour it has (tile = 2 with A6 is still refused): the two fields choose for disjoint forms.
+ * blim_gemm_narrow_lo6_launches(): launches of THAT kernel by this process so far -- a counter of its own; blim_gemm_narrow_launches() does not move on them. */
+int64_t blim_gemm_narrow_lo6_launches(void);
+int32_t blim_gemm_narrow_lo6_threshold(void);
 /* cos / sin of every token's position as BLIM_EPI_QKV reads them (csrc/gemm.hpp: rope_rows): out f32 [8 = {cos, sin} x 4 groups of 16 dims][stride rows][16],
  * row t of every chunk = position min(max(positions[t], 0), max_positions - 1); stride >= n_tokens.  workspace: blim_rope_rows_bytes(max_positions) bytes (the
  * cos | sin tables of all positions, built by the call as the engine builds its own at creation); out: 128 * stride floats. */
@@ -639,6 +649,10 @@ int blim_debug_gemm_stamps(void* device_buf);
  *   forms, adapters apart and the last layer's pruned rows included; 1 = auto, 2 = wherever the form is eligible.  Launches of an ineligible form (fp8 engines, the e2m3
  *   second pass of "precise_lo6") keep the 256 x 256 kernel.  The option changes NO value (the narrow kernel's results are the 256 x 256 kernel's bit for bit), only which
  *   kernel computes it: it is no part of a prefix cache's snapshot of the numeric options, of the calibration store's key or of the weights fingerprint;
+ * "narrow_lo6" (0 / 1 / 2, default 0; other values BLIM_ERR_ARG): blim_gemm's `tile_lo6` for the same launches where they carry the e2m3 second pass of "precise_lo6"
+ *   (the compensated o_proj and down of fp16 engines, of bf16 engines under "precise_lo6" = 1); 1 = auto, 2 = wherever the form is eligible.  Every other launch is
+ *   untouched: the plain and w_wrap_k forms stay "narrow_gemm"'s, fp8 engines keep the 256 x 256 kernel.  Like "narrow_gemm" it changes NO value and is no part of a
+ *   prefix cache's snapshot, of the calibration store's key or of the weights fingerprint;
  * "masked_query_zero" (0/1, default 0; 16-bit engines; PARITY-UNPINNED): query positions the key mask hides (blim_batch.key_visible == 0) write a ZERO attention output
  *   instead of attending to their visible keys.  The default is the semantics parity is pinned to -- the reference's eager / SDPA attention classes
  *   (modeling_qwen2_flash.py:288-310, 701-709), where a masked query row is computed like any other.  Its flash-attention-2 class drops such positions before the

@@ -32,7 +32,14 @@ single-query latency table above (k = 16 and k = N, per mode), a stream of the Q
 k = 16 query under each value.  Option 0 launches the kernels the library launched before the option existed.  Scores are checked bit-equal between the two values
 on every repetition.
 
-    python tools/gallery_bench.py --narrow_gemm --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r16_narrow_gemm_gallery.json"""
+    python tools/gallery_bench.py --narrow_gemm --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r16_narrow_gemm_gallery.json
+
+`--narrow_lo6`: the same measurements for engine option "narrow_lo6" (the compensated o_proj and down launches that carry the e2m3 second
+pass), in the compensated modes: t2v under `--modes full,select` (select: layers 0 - 3 compensated in every unit, the others plain), and with `--direction v2t` the
+cached TVG leg of one k = 16 query under `--tvg_modes attn,full`.
+
+    python tools/gallery_bench.py --narrow_lo6 --modes full,select --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r18_narrow_lo6_gallery.json
+    python tools/gallery_bench.py --narrow_lo6 --direction v2t --n 1000 --k 16 --synthetic_7b --out profiles/r18_narrow_lo6_v2t.json"""
 import argparse
 import json
 import os
@@ -74,6 +81,7 @@ def main():
     ap.add_argument("--stream_draws", type=int, default=165, help="--fill lazy: queries of the Zipf stream")
     ap.add_argument("--host_gb", type=float, default=None, help="the host tier's measurements (t2v): pinned host memory of the tier, GB")
     ap.add_argument("--narrow_gemm", action="store_true", help="engine option narrow_gemm 0 against 1 (t2v, eager index): single-query latency, query stream, timing classes")
+    ap.add_argument("--narrow_lo6", action="store_true", help="engine option narrow_lo6 0 against 1 in the compensated modes (t2v: --modes full,select; v2t: the TVG leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -89,10 +97,12 @@ def main():
     tvg = RU.padding_ids(Tt(prob.tvg_ids), Tt(prob.tvg_labels), Tt(prob.tvg_masks), tok)
     video = [torch.from_numpy(v) for v in prob.video]
     q = np.linspace(0, a.n - 1, a.queries).round().astype(np.int64)
+    if a.narrow_lo6 and a.direction == "v2t":
+        return main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.direction == "v2t":
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
-    if a.narrow_gemm:
-        return main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if a.narrow_gemm or a.narrow_lo6:
+        return main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_lo6" if a.narrow_lo6 else "narrow_gemm")
     if a.host_gb is not None:
         return main_host(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.fill == "lazy":
@@ -140,16 +150,22 @@ def main():
     model.engine.close()
 
 
-def main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc):
-    """Option "narrow_gemm" 0 against 1 on one eager index (see the module text)."""
+def main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_gemm"):
+    """Option "narrow_gemm" (or "narrow_lo6") 0 against 1 on one eager index (see the module text)."""
     from blim_amd import engine as eng
     e = model.engine
+    launches_of, threshold = ((eng.gemm_narrow_lo6_launches, eng.gemm_narrow_lo6_threshold) if option == "narrow_lo6" else
+                              (eng.gemm_narrow_launches, eng.gemm_narrow_threshold))
     res = {"n": a.n, "queries": a.queries, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc, "reps": a.reps,
-           "threshold_tiles": eng.gemm_narrow_threshold(), "modes": {}}
+           "threshold_tiles": threshold(), "modes": {}}
+    if option != "narrow_gemm":
+        res["option"] = option
     med = lambda x: float(np.median(x))
     spread = lambda x: float((max(x) - min(x)) / np.median(x))
     for mode in a.modes.split(","):
         model.vtg_precise = None if mode == "none" else mode
+        if mode == "select":                                               # a fixed mask instead of a calibration: the first four layers compensated in every unit
+            model.resolve_vtg("select", np.array([15 if li < 4 else 0 for li in range(dims.num_layers)], dtype=np.uint8))
         model.clear_cache()
         sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, torch.from_numpy(prob.video_vocab),
                            torch.from_numpy(prob.tvg_video_labels), dims.num_clips, max_tokens=a.max_tokens)
@@ -162,15 +178,15 @@ def main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc):
             c1 = np.argsort(-prob.t2v_sims[q[0]], kind="stable")[:kk][None]
             ts, launches, ref = {0: [], 1: []}, {}, None
             for v in (0, 1):                                               # warm-up of both kernels' paths
-                e.set_option("narrow_gemm", v); gal.vtg_scores([q[0]], c1)
+                e.set_option(option, v); gal.vtg_scores([q[0]], c1)
             for _ in range(a.reps):
                 for v in (0, 1):
-                    e.set_option("narrow_gemm", v)
-                    n0 = eng.gemm_narrow_launches()
+                    e.set_option(option, v)
+                    n0 = launches_of()
                     dt, got = timed(lambda: gal.vtg_scores([q[0]], c1))
-                    ts[v].append(dt); launches[v] = eng.gemm_narrow_launches() - n0
+                    ts[v].append(dt); launches[v] = launches_of() - n0
                     ref = got if ref is None else ref
-                    assert np.array_equal(np.asarray(ref), np.asarray(got)), "scores differ between narrow_gemm 0 and 1"
+                    assert np.array_equal(np.asarray(ref), np.asarray(got)), "scores differ between the option's values 0 and 1"
             r["latency"][f"k{kk}"] = {"off_ms": 1e3 * med(ts[0]), "auto_ms": 1e3 * med(ts[1]), "off_spread": spread(ts[0]), "auto_spread": spread(ts[1]),
                                       "off_all_ms": [1e3 * t for t in ts[0]], "auto_all_ms": [1e3 * t for t in ts[1]], "narrow_launches": launches}
         cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
@@ -181,24 +197,78 @@ def main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc):
         ref = None
         for _ in range(a.reps):
             for v in (0, 1):
-                e.set_option("narrow_gemm", v)
+                e.set_option(option, v)
                 dt, got = timed(stream); ts[v].append(dt)
                 ref = got if ref is None else ref
-                assert all(np.array_equal(x, y) for x, y in zip(ref, got)), "stream scores differ between narrow_gemm 0 and 1"
+                assert all(np.array_equal(x, y) for x, y in zip(ref, got)), "stream scores differ between the option's values 0 and 1"
         r["stream"] = {"queries": len(q), "k": a.k, "off_s": med(ts[0]), "auto_s": med(ts[1]), "off_spread": spread(ts[0]), "auto_spread": spread(ts[1]),
                        "off_ms_per_query": 1e3 * med(ts[0]) / len(q), "auto_ms_per_query": 1e3 * med(ts[1]) / len(q)}
         c1 = np.argsort(-prob.t2v_sims[q[0]], kind="stable")[:a.k][None]
         r["classes"] = {}
         for v in (0, 1):
-            e.set_option("narrow_gemm", v)
+            e.set_option(option, v)
             e.timing_enable(True); e.timing_report()
             gal.vtg_scores([q[0]], c1)
             r["classes"]["auto" if v else "off"] = {k: x for k, x in e.timing_report().items() if x["calls"]}
             e.timing_enable(False)
-        e.set_option("narrow_gemm", 0)
+        e.set_option(option, 0)
         res["modes"][mode] = r
         print(json.dumps({mode: r}), flush=True)
         gal.close()
+        del sc
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    """Option "narrow_lo6" 0 against 1 on the cached TVG leg of one v2t query of k candidates, per TVG mode (see the module text)."""
+    from blim_amd import engine as eng
+    e = model.engine
+    med = lambda x: float(np.median(x))
+    spread = lambda x: float((max(x) - min(x)) / np.median(x))
+    res = {"direction": "v2t", "option": "narrow_lo6", "n": a.n, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc,
+           "reps": a.reps, "threshold_tiles": eng.gemm_narrow_lo6_threshold(), "tvg_modes": {}}
+    model.vtg_precise = None
+    c1 = np.argsort(-prob.v2t_sims[q[0]], kind="stable")[:a.k]
+    p1 = np.stack([np.full(a.k, q[0]), c1], axis=1)
+    for mode in a.tvg_modes.split(","):
+        model.tvg_precise = mode
+        model.clear_cache()
+        sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, torch.from_numpy(prob.video_vocab),
+                           torch.from_numpy(prob.tvg_video_labels), dims.num_clips, max_tokens=a.max_tokens)
+        sc.set_vtg_mode(model.vtg_mode()); sc.set_tvg_mode(model.tvg_mode())
+        sc.tvg(p1[:8])
+        gal = GalleryIndex(sc)
+        gal.build()
+        tg = TextGalleryIndex(sc, video_index=gal)
+        tg.build()
+        ts, launches, ref = {0: [], 1: []}, {}, None
+        for v in (0, 1):
+            e.set_option("narrow_lo6", v); tg.tvg_pairs(p1)
+        for _ in range(a.reps):
+            for v in (0, 1):
+                e.set_option("narrow_lo6", v)
+                n0 = eng.gemm_narrow_lo6_launches()
+                dt, got = timed(lambda: tg.tvg_pairs(p1))
+                ts[v].append(dt); launches[v] = eng.gemm_narrow_lo6_launches() - n0
+                ref = got if ref is None else ref
+                assert np.array_equal(ref, got), "TVG scores differ between narrow_lo6 0 and 1"
+        r = {"off_ms": 1e3 * med(ts[0]), "auto_ms": 1e3 * med(ts[1]), "off_spread": spread(ts[0]), "auto_spread": spread(ts[1]),
+             "off_all_ms": [1e3 * t for t in ts[0]], "auto_all_ms": [1e3 * t for t in ts[1]], "narrow_launches": launches,
+             "tokens_cached": sum(p.n_tokens for p in tg.iter_plans(p1)), "classes": {}}
+        for v in (0, 1):
+            e.set_option("narrow_lo6", v)
+            e.timing_enable(True); e.timing_report()
+            tg.tvg_pairs(p1)
+            r["classes"]["auto" if v else "off"] = {k: x for k, x in e.timing_report().items() if x["calls"]}
+            e.timing_enable(False)
+        e.set_option("narrow_lo6", 0)
+        res["tvg_modes"][mode] = r
+        print(json.dumps({mode: r}), flush=True)
+        tg.close(); gal.close()
         del sc
         torch.cuda.empty_cache()
     if a.out:

@@ -3,7 +3,12 @@ gemm_narrow_kernel) at M in {32 .. 4096} x (N, K) in {(3584, 3584), (3584, 18944
 launches, the two tiles alternated `--reps` times in one process, medians and spreads; the results of the two tiles are compared bit for bit at every shape.  The auto
 rule's constant (gemm.hpp: GEMM_NARROW_TILES) is read off this table: the largest count of 256 x 256 tiles below which the narrow kernel is never the slower one.
 
-    python tools/narrow_gemm_sweep.py --out profiles/r16_narrow_gemm_sweep.json"""
+    python tools/narrow_gemm_sweep.py --out profiles/r16_narrow_gemm_sweep.json
+
+--lo6: the compensated form instead -- A = [hi | lo] rows (lda = 2 K), the e2m3 second pass over K6 = K on images built once per shape (f6_build), the 256 x 256
+kernel (tile_lo6 = 0) against gemm_narrow_lo6_kernel (tile_lo6 = 2); that table sets GEMM_NARROW_LO6_TILES.
+
+    python tools/narrow_gemm_sweep.py --lo6 --ms 256,512,1024,2048,4096 --out profiles/r18_narrow_lo6_sweep.json"""
 import argparse
 import json
 import os
@@ -24,7 +29,11 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--inner", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lo6", action="store_true", help="the compensated form: the e2m3 second pass, tile_lo6 instead of tile")
     a = ap.parse_args()
+    field = "tile_lo6" if a.lo6 else "tile"
+    launches = eng.gemm_narrow_lo6_launches if a.lo6 else eng.gemm_narrow_launches
+    lib = eng.load_library()
     tdt = torch.float16 if a.dtype == "f16" else torch.bfloat16
     g = torch.Generator(device="cuda").manual_seed(1)
     rows = []
@@ -34,13 +43,21 @@ def main():
         for M in (int(x) for x in a.ms.split(",")):
             x = torch.randn((M, K), device="cuda", generator=g).to(tdt)
             base = torch.randn((M, N), device="cuda", generator=g)
+            kw = {}
+            if a.lo6:                                                                 # [hi | lo] rows with true lo parts (2^-11 of the values in fp16); the images are built below
+                x32 = torch.randn((M, K), device="cuda", generator=g)
+                hi = x32.to(tdt)
+                x = torch.cat([hi, (x32 - hi.float()).to(tdt)], dim=1).contiguous()
+                kw = dict(lda=2 * K, K6=K, A6=torch.empty(lib.blim_f6_tiles_bytes(M, K), dtype=torch.uint8, device="cuda"),
+                          W6=torch.empty(lib.blim_f6_tiles_bytes(N, K), dtype=torch.uint8, device="cuda"))
+                eng.gemm("resid", a.dtype, x, w, M, N, K, base.clone(), f6_build=1, **{**kw, "K6": 0})
             out = {}
             for tile in (0, 2):                                                       # the same bits, and a warm-up of both kernels
                 c = base.clone()
-                n0 = eng.gemm_narrow_launches()
-                eng.gemm("resid", a.dtype, x, w, M, N, K, c, tile=tile)
+                n0 = launches()
+                eng.gemm("resid", a.dtype, x, w, M, N, K, c, **{field: tile}, **kw)
                 torch.cuda.synchronize()
-                assert eng.gemm_narrow_launches() - n0 == (1 if tile == 2 else 0)
+                assert launches() - n0 == (1 if tile == 2 else 0)
                 out[tile] = c
             assert torch.equal(out[0].view(torch.int32), out[2].view(torch.int32)), (M, N, K, "the two tiles' results differ")
             c = base.clone()
@@ -50,7 +67,7 @@ def main():
                     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     e0.record()
                     for _ in range(a.inner):
-                        eng.gemm("resid", a.dtype, x, w, M, N, K, c, tile=tile)
+                        eng.gemm("resid", a.dtype, x, w, M, N, K, c, **{field: tile}, **kw)
                     e1.record()
                     torch.cuda.synchronize()
                     ts[tile].append(e0.elapsed_time(e1) * 1e3 / a.inner)
@@ -61,6 +78,8 @@ def main():
             rows.append(r)
             print(json.dumps(r), flush=True)
     res = {"dtype": a.dtype, "reps": a.reps, "inner": a.inner, "threshold_tiles_in_library": eng.gemm_narrow_threshold(), "rows": rows}
+    if a.lo6:
+        res.update(form="lo6", threshold_tiles_in_library=eng.gemm_narrow_lo6_threshold())
     if a.out:
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
         json.dump(res, open(a.out, "w"), indent=1)
