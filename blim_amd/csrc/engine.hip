@@ -924,6 +924,7 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
                 if (n1_tiles) attach_lo6_ready(p, (int)Hq, l.wqkv6); else TRY(attach_lo6(p, xn, 2 * Hq, T, (int)Hq, G ? e->AD[li].wqkv_aug6 : l.wqkv6));
             }
             p.bias = l.bqkv; p.rope_cols = (c.num_heads + c.num_kv_heads) * 128; p.rope_rows = rope_rows; p.rope_stride = round_up(T, 256);
+            p.narrow_qkv = e->narrow_qkv;                                 // option "narrow_qkv": every 16-bit form of this launch is eligible; fp8 keeps the 256 x 256 kernel
             TRY(launch_gemm(EPI_QKV, p, s));
         }
         if (e->pc_fill) {      // gallery fill: this layer's K / V heads of the prefix rows (+ their lo parts where the attention reads them) into the cache slots
@@ -1773,6 +1774,14 @@ extern "C" int blim_gemm(const blim_gemm_args* args, void* stream) {
         if (!a.A6 || !a.W6) { blim_set_error("gemm: tile_lo6 = 2 (the narrow e2m3 kernel) needs the e2m3 second pass (A6 / W6)"); return BLIM_ERR_ARG; }
         if (a.w_wrap_k) { blim_set_error("gemm: tile_lo6 = 2 (the narrow e2m3 kernel) takes no wrapped W (w_wrap_k = %d): that form is `tile`'s", (int)a.w_wrap_k); return BLIM_ERR_ARG; }
     }
+    // tile_qkv: the same three values for BLIM_EPI_QKV on fp16 / bf16 operands (plain or hi | lo outputs, the w_wrap_k walk, the e2m3 second pass behind hi | lo outputs);
+    // 2 is refused, with the field named, for every other form
+    if (a.tile_qkv < 0 || a.tile_qkv > 2) { blim_set_error("gemm: tile_qkv = %d (0 = 256 x 256, 1 = auto, 2 = narrow)", (int)a.tile_qkv); return BLIM_ERR_ARG; }
+    if (a.tile_qkv == 2) {
+        if (a.epi != BLIM_EPI_QKV) { blim_set_error("gemm: tile_qkv = 2 (the narrow QKV kernel) has the QKV epilogue only (epi = %d)", (int)a.epi); return BLIM_ERR_ARG; }
+        if (f8) { blim_set_error("gemm: tile_qkv = 2 (the narrow QKV kernel) takes fp16 / bf16 operands (dtype = f8)"); return BLIM_ERR_ARG; }
+        if (a.A6 && a.lo_off == 0) { blim_set_error("gemm: tile_qkv = 2 (the narrow QKV kernel) has the e2m3 second pass (A6) behind hi | lo outputs only (lo_off = 0)"); return BLIM_ERR_ARG; }
+    }
     ARG_CHECK(a.K * es % 128 == 0 && a.lda * es % 16 == 0);
     ARG_CHECK(a.w_wrap_k == 0 || (a.K == 2 * a.w_wrap_k && a.w_wrap_k * es % 128 == 0));
     ARG_CHECK(a.lda >= a.K);
@@ -1824,7 +1833,7 @@ extern "C" int blim_gemm(const blim_gemm_args* args, void* stream) {
         ARG_CHECK(!a.out6 || (a.epi == BLIM_EPI_SWIGLU && a.lo_off > 0 && a.N % 256 == 0));
     }
     GemmParams p = gp(a.dtype, a.A, a.lda, a.W, a.M, a.N, a.K, fused8 ? a.out8 : a.C, a.ldc);
-    p.narrow = a.tile; p.narrow_lo6 = a.tile_lo6;
+    p.narrow = a.tile; p.narrow_lo6 = a.tile_lo6; p.narrow_qkv = a.tile_qkv;
     p.row_scale = a.row_scale; p.col_scale = a.col_scale; p.bias = a.bias; p.resid_in = a.resid_in; p.act = a.act; p.scale = a.scale;
     p.swiglu_gu = (uint16_t*)a.swiglu_gu; p.swiglu_ld = a.swiglu_ld; p.swiglu_act = (uint16_t*)a.swiglu_act; p.swiglu_act_ld = a.swiglu_act_ld;
     p.rope_cols = a.rope_cols; p.rope_rows = a.rope_rows; p.rope_stride = a.rope_stride;
@@ -1912,6 +1921,10 @@ extern "C" int blim_set_option(blim_engine* e, const char* key, int32_t value) {
     if (!strcmp(key, "narrow_lo6")) {
         if (value < 0 || value > 2) { blim_set_error("option 'narrow_lo6': 0 (off), 1 (auto) or 2 (wherever eligible), got %d", (int)value); return BLIM_ERR_ARG; }
         e->narrow_lo6 = value; return BLIM_OK;
+    }
+    if (!strcmp(key, "narrow_qkv")) {
+        if (value < 0 || value > 2) { blim_set_error("option 'narrow_qkv': 0 (off), 1 (auto) or 2 (wherever eligible), got %d", (int)value); return BLIM_ERR_ARG; }
+        e->narrow_qkv = value; return BLIM_OK;
     }
     if (!strcmp(key, "narrow_gemm")) {
         if (value < 0 || value > 2) { blim_set_error("option 'narrow_gemm': 0 (off), 1 (auto) or 2 (wherever eligible), got %d", (int)value); return BLIM_ERR_ARG; }

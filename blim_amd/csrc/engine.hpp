@@ -90,6 +90,7 @@ struct blim_engine {
     bool prune_last = true;               // option "prune_last"
     int narrow_gemm = 0;                  // option "narrow_gemm": GemmParams::narrow of run_layers' o_proj and down launches (0 / 1 auto / 2).  Changes no value
     int narrow_lo6 = 0;                   // option "narrow_lo6": GemmParams::narrow_lo6 of the same launches (their e2m3 second-pass form).  Changes no value
+    int narrow_qkv = 0;                   // option "narrow_qkv": GemmParams::narrow_qkv of run_layers' QKV launch (0 / 1 auto / 2).  Changes no value
     DevBuf x8, a8, act8, hsel8, rscale;   // fp8 mode: quantised GEMM inputs and their per-row scales
     DevBuf attn_mx;                       // fp8 mode: E8M0 scale per (token, head), written by the attention kernel (attention.hpp: out_mx)
     DevBuf act_mx;                        // fp8 mode: E8M0 scale per (token, 128 SwiGLU outputs), written by the gate|up epilogue (gemm.hpp: out_mx)

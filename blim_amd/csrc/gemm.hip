@@ -1182,6 +1182,8 @@ __device__ __forceinline__ void narrow_tile(const GemmParams& p, int bid, int& t
     tm = first_m + (pid % width) % gsz;
     tn = (pid % width) / gsz;
 }
+// (This K walk -- stage, the fragment offsets, the counted waits -- is restated in gemm_narrow_lo6_kernel and, for both passes, in gemm_nqkv_kernel below: a change to
+// the ring or to the waits goes to all three.)
 template <int DT>
 __global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[NRING * N_STEP_BYTES];
@@ -1281,6 +1283,7 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams
 // counted vmcnt waits are the same for all waves and across the hand-over).  The first second-pass steps are therefore in flight under the last 16-bit steps.
 #define N6_Q_BYTES 6144                      // a 64-row quarter of one operand's e2m3 block: four fragment groups of 1536 B
 #define N6_SC_OFF (2 * N6_Q_BYTES)           // the step's scales inside its slot: A half (512 B) | W group (256 B) | spare (256 B)
+// (Both passes -- stage, stage6, head, the fragment and scale offsets -- are restated in gemm_nqkv_kernel below: a change to the ring or to the waits goes there too.)
 template <int DT>
 __global__ __launch_bounds__(N_THREADS) void gemm_narrow_lo6_kernel(const GemmParams p) {
     __shared__ __attribute__((aligned(16))) char smem[NRING * N_STEP_BYTES];
@@ -1423,6 +1426,237 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_lo6_kernel(const GemmPa
     narrow_resid_epilogue(p, acc, row0 + 32 * wm, col0 + 32 * wn, lane);
 }
 
+// ---- narrow-tile QKV GEMM (GemmParams::narrow_qkv): EPI_QKV on fp16 / bf16 operands in the narrow kernels' 64 x 64 tiles and tile order.  A small
+// scoring call's QKV projection (N = 4608) is 18 tiles of 256 x 256 per 256 rows -- 36 workgroups at k = 16, 18 on the v2t TVG leg -- and 16 times as many of these.
+// Main loop: gemm_narrow_kernel's 16-bit K walk (w_wrap_k and lda > K included) and, with LO6, gemm_narrow_lo6_kernel's e2m3 steps behind it in the same accumulators and
+// the same four-slot ring, restated here so that those two kernels keep their code.  Epilogue: gemm_kernel<EPI_QKV>'s per element -- x = acc + bias[col]; a wave's 32
+// stored columns are ONE 32-row group g of a head (fragment 0: natural dim d = 16 g + .., fragment 1: its RoPE partner d + 64), rotated with the cos / sin of chunks g and
+// 4 + g of the rope_rows table at row min(row, M - 1) by the same expression text, or (V heads) plain in stored order; rounded through pack2<ODT> inside the same fp16
+// saturation window; SPLIT: hi at C, lo = r16(x - f32(hi)) at C + lo_off.  Every stored element is the 256 x 256 kernel's bit for bit.
+// What no value depends on: bias and the wave's cos / sin rows are requested in FRONT of the K walk (24 registers; older than every LDS-DMA, so the counted vmcnt waits
+// cover them) and the tile goes to memory straight from the accumulators, 8 bytes per lane: a tile's natural columns are two 32-column runs per head anyway.
+template <int DT, bool SPLIT, bool LO6>
+__global__ __launch_bounds__(N_THREADS) void gemm_nqkv_kernel(const GemmParams p) {
+    static_assert(!(LO6 && !SPLIT), "the e2m3 second pass has hi | lo outputs only");
+    __shared__ __attribute__((aligned(16))) char smem[NRING * N_STEP_BYTES];
+    static_assert(N6_SC_OFF + 1024 <= N_STEP_BYTES, "a second-pass step fits a ring slot");
+    constexpr int ODT = out16<DT>::value;
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave >> 1, wn = wave & 1;
+    int tm, tn;
+    narrow_tile(p, blockIdx.x, tm, tn);
+    const int row0 = tm * NBM, col0 = tn * NBN;
+    if constexpr (ODT == DT_F16) { if (p.f16_saturate) f16_saturate_off(); }          // the MFMAs must see NaN / inf operands as such (common.hpp)
+
+    // ---- epilogue inputs, requested first
+    const int wrow0 = row0 + 32 * wm, wcol0 = col0 + 32 * wn;
+    const int tq = lane >> 4, rsub = lane & 15;
+    const bool rotated = wcol0 < p.rope_cols;                                          // wave-uniform (rope_cols % 128 == 0)
+    float4 qkv_bias[2];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+        const int col = wcol0 + 16 * ni + 4 * tq;
+        qkv_bias[ni] = col + 3 < p.N ? *(const float4*)(p.bias + col) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    const int g = (wcol0 & 127) >> 5;                                                  // this wave's 32-row group inside its head
+    float4 cs[2], sn[2];                                                               // [mi]
+#pragma unroll
+    for (int mi = 0; mi < 2; ++mi) cs[mi] = sn[mi] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (rotated) {
+        const int64_t cstride = p.rope_stride * 16;                                    // floats per chunk (gemm.hpp: rope_rows)
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+            const int row = min(wrow0 + 16 * mi + rsub, p.M - 1);
+            const float* base = p.rope_rows + (int64_t)row * 16 + 4 * tq;
+            cs[mi] = *(const float4*)(base + g * cstride);
+            sn[mi] = *(const float4*)(base + (4 + g) * cstride);
+        }
+    }
+
+    // ---- first pass: gemm_narrow_kernel's sources and fragment reads
+    const int sr = lane >> 3;
+    const int sc = (lane & 7) ^ (4 * (wave & 1) + (sr >> 1));
+    const int64_t w_ld = p.w_wrap_k > 0 ? p.w_wrap_k : p.K;           // W row stride (elements)
+    uint32_t offA[2], offW[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int b = wave + 4 * i;
+        offA[i] = (uint32_t)((int64_t)min(row0 + 8 * b + sr, p.M - 1) * p.lda * 2 + 16 * sc);
+        offW[i] = (uint32_t)((int64_t)min(col0 + 8 * b + sr, p.N - 1) * w_ld * 2 + 16 * sc);
+    }
+    const char* baseA = (const char*)p.A;
+    const char* baseW = (const char*)p.W;
+    const int nk = p.K / 64;                                           // K-steps of 128 bytes
+    const int nk6 = LO6 ? p.K6 / 128 : 0;                              // ... of 128 e2m3 values
+    const int nt = nk + nk6;
+    const int wrap = p.w_wrap_k > 0 ? p.w_wrap_k / 64 : 0x7fffffff;    // A = [hi | lo]: W's K-step index wraps
+    auto stage = [&](int slot, int kt) __attribute__((always_inline)) {
+        const char* ga = baseA + (int64_t)kt * 128;
+        const char* gw = baseW + (int64_t)(kt >= wrap ? kt - wrap : kt) * 128;
+        char* d = smem + slot * N_STEP_BYTES + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            uint32_t oa = offA[i], ow = offW[i];
+            asm volatile("" : "+v"(oa), "+v"(ow));
+            glds16(ga + oa, d + i * 4096);
+            glds16(gw + ow, d + N_A_BYTES + i * 4096);
+        }
+    };
+    const int fr = lane & 15, fc = lane >> 4;
+    const int fg = (fr >> 1) & 7;
+    const int frag_off = (fr >> 3) * 1024 + (fr & 7) * 128 + 16 * ((fc ^ (fg & 3)) + 4 * (fg >> 2));
+    const int a_off = (2 * wm) * 2048 + frag_off;
+    const int b_off = N_A_BYTES + (2 * wn) * 2048 + frag_off;
+
+    // ---- second pass (LO6): gemm_narrow_lo6_kernel's copies out of the tile images
+    const int q = tm & 3, qn = tn & 3;
+    const char* src6[4] = {nullptr, nullptr, nullptr, nullptr};
+    if constexpr (LO6) {
+        const char* g6A = (const char*)p.A6 + (int64_t)(tm >> 2) * nk6 * F6_TILE_BYTES;
+        const char* g6W = (const char*)p.W6 + (int64_t)(tn >> 2) * nk6 * F6_TILE_BYTES;
+        const char* qA = g6A + q * N6_Q_BYTES;
+        const char* qW = g6W + qn * N6_Q_BYTES;
+        src6[0] = qA + wave * 1024;
+        src6[1] = wave < 2 ? qA + (wave + 4) * 1024 : qW + (wave - 2) * 1024;
+        src6[2] = qW + (wave + 2) * 1024;
+        src6[3] = wave < 2 ? g6A + 24576 + (q >> 1) * 512 + wave * 256 : g6W + 24576 + qn * 256;
+    }
+    auto stage6 = [&](int slot, int kd) __attribute__((always_inline)) {
+        const int64_t ko = (int64_t)kd * F6_TILE_BYTES;
+        char* d = smem + slot * N_STEP_BYTES;
+        uint32_t o16 = (uint32_t)lane * 16u;
+        asm volatile("" : "+v"(o16));
+#pragma unroll
+        for (int i = 0; i < 3; ++i) glds16(src6[i] + ko + o16, d + (wave + 4 * i) * 1024);
+        if (lane < 16) glds16(src6[3] + ko + o16, d + N6_SC_OFF + wave * 256);
+    };
+    typedef int i32x8 __attribute__((ext_vector_type(8)));
+    typedef int i32x4 __attribute__((ext_vector_type(4)));
+    typedef int i32x2 __attribute__((ext_vector_type(2)));
+    typedef int i32x1 __attribute__((ext_vector_type(1)));
+    auto rd6 = [&](const char* fb) __attribute__((always_inline)) {
+        const i32x4 l = *(const i32x4*)(fb + lane * 16);
+        const i32x2 h = *(const i32x2*)(fb + 1024 + lane * 8);
+        return (i32x8){l[0], l[1], l[2], l[3], h[0], h[1], 0, 0};
+    };
+    const int a6_off = (2 * wm) * 1536, b6_off = N6_Q_BYTES + (2 * wn) * 1536;
+    const int sa_off = N6_SC_OFF + lane * 8 + 4 * (q & 1), sw_off = N6_SC_OFF + 512 + lane * 4;
+    const int sa_sh = 16 * wm, sw_sh = 16 * wn;
+
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+
+    auto request = [&](int slot, int t) __attribute__((always_inline)) {
+        if constexpr (LO6) { if (t < nk) stage(slot, t); else stage6(slot, t - nk); }
+        else stage(slot, t);
+    };
+#pragma unroll
+    for (int s = 0; s < NRING - 1; ++s)
+        if (s < nt) request(s, s);
+    int slot = 0;
+    // the head of step t in either pass, as in gemm_narrow_lo6_kernel
+    auto head = [&](int t) __attribute__((always_inline)) {
+        if (t + 2 < nt) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+        else if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (t + NRING - 1 < nt) request((slot + NRING - 1) & (NRING - 1), t + NRING - 1);
+    };
+    for (int kt = 0; kt < nk; ++kt) {
+        head(kt);
+        const char* ba[2] = {smem + slot * N_STEP_BYTES + a_off, smem + ((slot * N_STEP_BYTES + a_off) ^ 64)};
+        const char* bb[2] = {smem + slot * N_STEP_BYTES + b_off, smem + ((slot * N_STEP_BYTES + b_off) ^ 64)};
+        bf16x8 fa[2][2], fb[2][2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) fb[ks][ni] = *(const bf16x8*)(bb[ks] + ni * 2048);
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) fa[ks][mi] = *(const bf16x8*)(ba[ks] + mi * 2048);
+        }
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma16<DT>(fb[ks][ni], fa[ks][mi], acc[mi][ni]);
+        slot = (slot + 1) & (NRING - 1);
+    }
+    if constexpr (LO6) {
+        for (int k6 = 0; k6 < nk6; ++k6) {
+            head(nk + k6);
+            const char* sb = smem + slot * N_STEP_BYTES;
+            const uint32_t scw = (uint32_t)(*(const i32x1*)(sb + sw_off))[0] >> sw_sh;
+            const uint32_t sca = (uint32_t)(*(const i32x1*)(sb + sa_off))[0] >> sa_sh;
+            i32x8 fa8[2], fb8[2];
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) fb8[ni] = rd6(sb + b6_off + ni * 1536);
+#pragma unroll
+            for (int mi = 0; mi < 2; ++mi) fa8[mi] = rd6(sb + a6_off + mi * 1536);
+#define N6_MMA(MI, NI) acc[MI][NI] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb8[NI], fa8[MI], acc[MI][NI], 2, 2, NI, (int)scw, MI, (int)sca);   // cbsz = blgp = 2: e2m3
+            N6_MMA(0, 0) N6_MMA(0, 1) N6_MMA(1, 0) N6_MMA(1, 1)
+#undef N6_MMA
+            slot = (slot + 1) & (NRING - 1);
+        }
+    }
+    static_assert(NRING == 4, "the counted waits above are written for three steps in flight");
+
+    // ---- epilogue
+    if constexpr (ODT == DT_F16) { if (p.f16_saturate) f16_saturate_on(); }          // fp16 stores saturate instead of overflowing to inf
+    auto ST = [&](int row, int col, float a_, float b_, float c_, float d_) __attribute__((always_inline)) {
+        const uint2 hi_ = make_uint2(pack2<ODT>(a_, b_), pack2<ODT>(c_, d_));
+        uint2 lo_ = make_uint2(0u, 0u);
+        if constexpr (SPLIT) {
+            const uint16_t* h16_ = (const uint16_t*)&hi_;
+            lo_ = make_uint2(pack2<ODT>(a_ - from16<ODT>(h16_[0]), b_ - from16<ODT>(h16_[1])), pack2<ODT>(c_ - from16<ODT>(h16_[2]), d_ - from16<ODT>(h16_[3])));
+        }
+        if (row >= p.M || col + 3 >= p.N) return;                                    // (N % 128 == 0: a tile's columns are all inside or all outside)
+        bf16_t* out = (bf16_t*)p.C + (int64_t)row * p.ldc + col;
+        *(uint2*)out = hi_;                                                          // 8-byte stores: ldc % 4 == 0 (launch_one), lo_off % 4 == 0 (narrow_qkv_eligible)
+        if constexpr (SPLIT) *(uint2*)(out + p.lo_off) = lo_;
+    };
+    if (rotated) {
+        const int ncol = (wcol0 & ~127) + 16 * g + 4 * tq;                            // natural column of fragment 0's first element; fragment 1: + 64
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+            const int row = wrow0 + 16 * mi + rsub;
+            const float4 c = cs[mi], sv = sn[mi];
+            const float c4[4] = {c.x, c.y, c.z, c.w}, s4[4] = {sv.x, sv.y, sv.z, sv.w};
+            const float4 b0 = qkv_bias[0], b1 = qkv_bias[1];
+            const float bl[4] = {b0.x, b0.y, b0.z, b0.w}, bh[4] = {b1.x, b1.y, b1.z, b1.w};
+            float lo[4], hi[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float x1 = acc[mi][0][j] + bl[j];
+                const float x2 = acc[mi][1][j] + bh[j];
+                // lo = x1 c - x2 s, hi = x2 c + x1 s as the 256 x 256 kernels COMPILE them: of each expression's two contracted forms hipcc takes there the one below
+                // (read from their v_pk_mul_f32 / v_pk_fma_f32 sequences; the same text contracts hi the other way round here, one ulp apart)
+                lo[j] = __builtin_fmaf(x1, c4[j], -__fmul_rn(x2, s4[j]));
+                hi[j] = __builtin_fmaf(x2, c4[j], __fmul_rn(x1, s4[j]));
+            }
+            ST(row, ncol, lo[0], lo[1], lo[2], lo[3]);
+            ST(row, ncol + 64, hi[0], hi[1], hi[2], hi[3]);
+        }
+    } else {
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+            const int row = wrow0 + 16 * mi + rsub;
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                const float4 bv = qkv_bias[ni];
+                ST(row, wcol0 + 16 * ni + 4 * tq, acc[mi][ni][0] + bv.x, acc[mi][ni][1] + bv.y, acc[mi][ni][2] + bv.z, acc[mi][ni][3] + bv.w);
+            }
+        }
+    }
+}
+
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
@@ -1529,6 +1763,34 @@ static int launch_narrow_lo6(const GemmParams& p, hipStream_t stream) {
     g_narrow_lo6_launches.fetch_add(1);
     return BLIM_OK;
 }
+// ---- GemmParams::narrow_qkv: the same choice for EPI_QKV on fp16 / bf16 operands -- plain or hi | lo outputs over the plain or the w_wrap_k walk, hi | lo outputs
+// behind the e2m3 second pass -- with a kernel family, a counter and a threshold of its own.  A6 without lo_off is no form of either kernel; fp8 and the timing aids
+// keep the 256 x 256 kernel.
+static std::atomic<int64_t> g_narrow_qkv_launches{0};
+extern "C" int64_t blim_gemm_narrow_qkv_launches(void) { return g_narrow_qkv_launches.load(); }
+extern "C" int32_t blim_gemm_narrow_qkv_threshold(void) { return GEMM_NARROW_QKV_TILES; }
+static bool narrow_qkv_eligible(GemmEpi epi, const GemmParams& p) {
+    return epi == EPI_QKV && (p.dtype == DT_F16 || p.dtype == DT_BF16) && !(p.A6 && p.lo_off == 0) && p.lo_off % 4 == 0 && !p.a_mx && !p.debug_stamps && !p.debug_skip_epilogue;   // (lo_off % 4: the kernel's 8-byte stores of the lo half; blim_gemm and the engine pass no other)
+}
+static bool narrow_qkv_chosen(GemmEpi epi, const GemmParams& p) {
+    if (p.narrow_qkv == 0 || !narrow_qkv_eligible(epi, p)) return false;
+    if (p.narrow_qkv == 2) return true;
+    return (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) < GEMM_NARROW_QKV_TILES;  // auto: gemm.hpp
+}
+template <int DT>
+static int launch_narrow_qkv_t(const GemmParams& p, hipStream_t stream) {
+    const dim3 grid((unsigned)(((p.M + NBM - 1) / NBM) * ((p.N + NBN - 1) / NBN)));
+    if (p.A6) hipLaunchKernelGGL((gemm_nqkv_kernel<DT, true, true>), grid, dim3(N_THREADS), 0, stream, p);
+    else if (p.lo_off != 0) hipLaunchKernelGGL((gemm_nqkv_kernel<DT, true, false>), grid, dim3(N_THREADS), 0, stream, p);
+    else hipLaunchKernelGGL((gemm_nqkv_kernel<DT, false, false>), grid, dim3(N_THREADS), 0, stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { blim_set_error("narrow qkv gemm launch failed: %s", hipGetErrorString(e)); return BLIM_ERR_HIP; }
+    g_narrow_qkv_launches.fetch_add(1);
+    return BLIM_OK;
+}
+static int launch_narrow_qkv(const GemmParams& p, hipStream_t stream) {
+    return p.dtype == DT_F16 ? launch_narrow_qkv_t<DT_F16>(p, stream) : launch_narrow_qkv_t<DT_BF16>(p, stream);
+}
 static int launch_narrow(const GemmParams& p, hipStream_t stream) {
     const dim3 grid((unsigned)(((p.M + NBM - 1) / NBM) * ((p.N + NBN - 1) / NBN)));
     if (p.dtype == DT_F16) hipLaunchKernelGGL((gemm_narrow_kernel<DT_F16>), grid, dim3(N_THREADS), 0, stream, p);
@@ -1606,6 +1868,7 @@ static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream) {
     ARG_CHECK(p.lo_off == 0 || epi == EPI_BF16 || epi == EPI_QKV || epi == EPI_SWIGLU);
     if (p.narrow < 0 || p.narrow > 2) { blim_set_error("gemm: narrow = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = the narrow kernel wherever it is eligible)", p.narrow); return BLIM_ERR_ARG; }
     if (p.narrow_lo6 < 0 || p.narrow_lo6 > 2) { blim_set_error("gemm: narrow_lo6 = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = the narrow e2m3 kernel wherever it is eligible)", p.narrow_lo6); return BLIM_ERR_ARG; }
+    if (p.narrow_qkv < 0 || p.narrow_qkv > 2) { blim_set_error("gemm: narrow_qkv = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = the narrow QKV kernel wherever it is eligible)", p.narrow_qkv); return BLIM_ERR_ARG; }
     ARG_CHECK((int64_t)p.M * p.lda * es < (1ll << 32) && (int64_t)p.N * (p.w_wrap_k > 0 ? p.w_wrap_k : p.K) * es < (1ll << 32));  // 32-bit operand offsets
     switch (epi) {
         case EPI_BF16:
@@ -1621,6 +1884,7 @@ static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream) {
             return launch_t<EPI_RESID>(p, stream);
         case EPI_QKV:
             ARG_CHECK(p.C && p.bias && p.rope_rows && p.rope_stride >= p.M && p.N % 128 == 0 && p.rope_cols % 128 == 0 && p.ldc % 4 == 0);
+            if (narrow_qkv_chosen(epi, p)) return launch_narrow_qkv(p, stream);
             return launch_t<EPI_QKV>(p, stream);
         case EPI_SWIGLU: ARG_CHECK(p.C && p.N % 32 == 0 && p.ldc % 4 == 0); return launch_t<EPI_SWIGLU>(p, stream);
         case EPI_LSE: ARG_CHECK(p.labels && p.lse_part && p.label_logit); return launch_t<EPI_LSE>(p, stream);

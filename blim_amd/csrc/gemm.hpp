@@ -83,7 +83,10 @@ struct GemmParams {
                              // whenever the form is eligible, 1 = auto: eligible and fewer than GEMM_NARROW_TILES tiles of 256 x 256 (the measured crossover).  An ineligible form takes the
                              // 256 x 256 kernel under any value.  Appended behind every older field: the existing kernels' argument offsets do not move
     int narrow_lo6;          // EPI_RESID with the e2m3 second pass (A6 / W6, w_wrap_k = 0; gemm.hip: gemm_narrow_lo6_kernel, 64 x 64 tiles, the same bits): 0 / 2 / 1 as `narrow`, the
-                             // auto rule with a constant of its own (GEMM_NARROW_LO6_TILES).  An ineligible form takes the 256 x 256 kernel under any value.  LAST field
+                             // auto rule with a constant of its own (GEMM_NARROW_LO6_TILES).  An ineligible form takes the 256 x 256 kernel under any value
+    int narrow_qkv;          // EPI_QKV on fp16 / bf16 operands (gemm.hip: gemm_nqkv_kernel, 64 x 64 tiles, the same bits): plain or hi | lo outputs over the plain or the w_wrap_k
+                             // walk, hi | lo outputs behind the e2m3 second pass.  0 / 2 / 1 as `narrow`, the auto rule with GEMM_NARROW_QKV_TILES.  An ineligible form (fp8,
+                             // A6 without lo_off, the timing aids) takes the 256 x 256 kernel under any value.  LAST field
 };
 // auto rule of GemmParams::narrow: the narrow kernel runs when ceil(M / 256) * ceil(N / 256) < GEMM_NARROW_TILES.  Measured (profiles/r16_narrow_gemm.md, blim_gemm alone, fp16,
 // N = 3584, K = 3584 | 18944, narrow time over 256 x 256 time): 14 tiles (M <= 256) 0.30 - 0.34, 28 tiles (M = 512) 0.39 - 0.42, 56 tiles (M = 1024) 0.73 - 0.75, 112 tiles
@@ -95,6 +98,11 @@ struct GemmParams {
 // N = 3584, K = 3584 | 18944, narrow time over 256 x 256 time): 14 tiles 0.36 - 0.37, 28 tiles 0.43 - 0.44, 56 tiles 0.80 - 0.88, 112 tiles 1.39 - 1.60, 224 tiles
 // 2.05 - 2.50 -- the same crossover as the plain form's, with a little less to spare at 56 tiles (the second pass is a third of the narrow kernel's K-steps).  56 tiles is the last MEASURED point at which the narrow kernel wins
 #define GEMM_NARROW_LO6_TILES 57
+// auto rule of GemmParams::narrow_qkv, by the same rule from a sweep of its own (profiles/r19_narrow_qkv.md, blim_gemm alone, fp16, N = 4608, K = 3584, the plain form | hi | lo
+// outputs over the w_wrap_k walk | hi | lo outputs behind the e2m3 pass, narrow time over 256 x 256 time): 18 tiles (M = 256) 0.37 | 0.37 | 0.40, 36 tiles (M = 512)
+// 0.66 | 0.65 | 0.70, 54 tiles (M = 768) 0.72 | 0.73 | 0.76, 72 tiles (M = 1024) 0.97 | 0.99 | 1.04, 108 tiles 1.26 - 1.38, 144 tiles 1.51 - 1.63.  The constant is the minimum
+// over the three forms: 54 tiles is the last MEASURED point at which the narrow kernel wins in all of them (at 72 the e2m3 form loses and the wrap form's margin is inside the spread)
+#define GEMM_NARROW_QKV_TILES 55
 void gemm_set_debug_stamps(unsigned long long* buf);
 
 // 256x256 tiles x 128 bytes of K per step (64 16-bit / 128 fp8 elements), 512 threads.  K % 64 == 0 (fp8: % 128), lda % 8 == 0 (fp8: % 16).  Rows/cols beyond M/N are clamped on

@@ -109,7 +109,7 @@ class GemmArgs(C.Structure):
                 ("label_logit", C.c_void_p), ("row_scale", C.c_void_p), ("col_scale", C.c_void_p), ("a_mx", C.c_void_p), ("out8", C.c_void_p),
                 ("out_mx", C.c_void_p), ("mx_stride", C.c_int64), ("A6", C.c_void_p), ("W6", C.c_void_p), ("K6", C.c_int32), ("f6_build", C.c_int32),
                 ("out6", C.c_void_p), ("swiglu_act", C.c_void_p), ("swiglu_act_ld", C.c_int64), ("swiglu_gu", C.c_void_p), ("swiglu_ld", C.c_int64), ("tile", C.c_int32),
-                ("tile_lo6", C.c_int32)]
+                ("tile_lo6", C.c_int32), ("tile_qkv", C.c_int32)]
 
 
 EPILOGUES = {"bf16": 0, "f32": 1, "resid": 2, "qkv": 3, "swiglu": 4, "lse": 5}
@@ -195,6 +195,8 @@ def load_library(path: str = LIB_PATH):
         "blim_gemm_narrow_threshold": ([], C.c_int32),
         "blim_gemm_narrow_lo6_launches": ([], C.c_int64),
         "blim_gemm_narrow_lo6_threshold": ([], C.c_int32),
+        "blim_gemm_narrow_qkv_launches": ([], C.c_int64),
+        "blim_gemm_narrow_qkv_threshold": ([], C.c_int32),
         "blim_rope_rows_bytes": ([i32], C.c_int64),
         "blim_rope_rows": ([vp, i64, f32, i32, vp, vp, i64, vp], C.c_int),
         "blim_timing_enable": ([vp, i32], C.c_int),
@@ -953,7 +955,7 @@ def grad_stats_raw(g, inv_scale: float, stats, workspace):
 
 _GEMM_POINTERS = ("bias", "resid_in", "rope_rows", "labels", "lse_part", "label_logit", "row_scale", "col_scale", "a_mx", "out8", "out_mx", "A6", "W6", "out6",
                   "swiglu_act", "swiglu_gu")
-_GEMM_INTS = ("act", "w_wrap_k", "lo_off", "rope_cols", "rope_stride", "mx_stride", "K6", "f6_build", "swiglu_act_ld", "swiglu_ld", "tile", "tile_lo6")
+_GEMM_INTS = ("act", "w_wrap_k", "lo_off", "rope_cols", "rope_stride", "mx_stride", "K6", "f6_build", "swiglu_act_ld", "swiglu_ld", "tile", "tile_lo6", "tile_qkv")
 
 
 def gemm(epi: str, dtype: str, a, w, M: int, N: int, K: int, c=None, lda: Optional[int] = None, ldc: Optional[int] = None, scale: float = 1.0,
@@ -963,7 +965,8 @@ def gemm(epi: str, dtype: str, a, w, M: int, N: int, K: int, c=None, lda: Option
     blim.h's blim_gemm_args by keyword: tensors for the pointers (bias, resid_in, rope_rows, labels, lse_part, label_logit, row_scale, col_scale, a_mx, out8,
     out_mx, A6, W6, out6, swiglu_act, swiglu_gu), ints for act, w_wrap_k, lo_off, rope_cols, rope_stride, mx_stride, K6, f6_build, swiglu_act_ld, swiglu_ld,
     tile (0 = 256 x 256 tiles, 1 = auto, 2 = the narrow residual kernel: the same bits; gemm_narrow_launches() tells which kernel ran), tile_lo6 (the same three
-    values for the residual epilogue with A6 / W6: 2 = the narrow kernel with the e2m3 second pass; gemm_narrow_lo6_launches())."""
+    values for the residual epilogue with A6 / W6: 2 = the narrow kernel with the e2m3 second pass; gemm_narrow_lo6_launches()), tile_qkv (the same three values
+    for the QKV epilogue on fp16 / bf16 operands: 2 = the narrow QKV kernel; gemm_narrow_qkv_launches())."""
     lib = load_library()
     g = GemmArgs()
     g.struct_bytes = C.sizeof(GemmArgs)
@@ -1001,6 +1004,16 @@ def gemm_narrow_lo6_launches() -> int:
 def gemm_narrow_lo6_threshold() -> int:
     """The auto rule's constant: tile_lo6 = 1 / option "narrow_lo6" = 1 take that kernel below this many 256 x 256 tiles (blim_gemm_narrow_lo6_threshold)."""
     return int(load_library().blim_gemm_narrow_lo6_threshold())
+
+
+def gemm_narrow_qkv_launches() -> int:
+    """Launches of the narrow QKV GEMM kernel by this process so far (blim_gemm_narrow_qkv_launches): a counter of its own, the other two do not move on them."""
+    return int(load_library().blim_gemm_narrow_qkv_launches())
+
+
+def gemm_narrow_qkv_threshold() -> int:
+    """The auto rule's constant: tile_qkv = 1 / option "narrow_qkv" = 1 take that kernel below this many 256 x 256 tiles (blim_gemm_narrow_qkv_threshold)."""
+    return int(load_library().blim_gemm_narrow_qkv_threshold())
 
 
 def rope_rows(positions, rope_theta: float, max_positions: int, stride: Optional[int] = None):

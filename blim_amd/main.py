@@ -94,6 +94,9 @@ def get_args_parser():
                    help="auto: the same for the compensated o_proj and down launches that carry the e2m3 second pass (fp16 engines; bf16 under --second_pass e2m3), with a "
                         "measured threshold of its own (engine option \"narrow_lo6\" = 1); the scores are the same bit for bit.  Does nothing where the compensated calls "
                         "walk K twice in 16 bits: those launches are --narrow_gemm's.  Refused with --dtype f8")
+    p.add_argument("--narrow_qkv", default="off", choices=["off", "auto"],
+                   help="auto: the decoder layers' QKV projection of SMALL calls runs on the narrow-tile QKV GEMM (plain, compensated and e2m3 second-pass forms alike), with a "
+                        "measured threshold of its own (engine option \"narrow_qkv\" = 1); the scores are the same bit for bit.  Refused with --dtype f8")
     p.add_argument("--calibration_store", default=None, type=str, metavar="DIR",
                    help="keep what --vtg_precise auto | select, --tvg_precise auto and --second_pass auto measure in DIR, one JSON record per weights fingerprint "
                         "(blim_weights_fingerprint: weights, adapters, visual head, config) + numeric options + library build.  A later run on the same key checks the "
@@ -142,7 +145,14 @@ def load_tokenizer(model_path: str):
     return AutoTokenizer.from_pretrained(model_path, trust_remote_code=True)
 
 
+def check_args(args) -> None:
+    """Refusals that need neither a device nor the model (SystemExit with the reason)."""
+    if getattr(args, "narrow_qkv", "off") == "auto" and args.dtype == "f8":
+        raise SystemExit("--narrow_qkv auto needs a 16-bit engine (--dtype f16 | bf16): the narrow QKV GEMM takes fp16 / bf16 operands")
+
+
 def main(args):
+    check_args(args)
     import numpy as np
     import torch
     from . import distributed as D
@@ -228,6 +238,8 @@ def main(args):
         if model.engine.dtype == "f8":
             raise SystemExit("--narrow_lo6 auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM with the e2m3 second pass takes fp16 / bf16 operands")
         model.engine.set_option("narrow_lo6", 1)
+    if args.narrow_qkv == "auto":                                       # (refused with --dtype f8 by check_args)
+        model.engine.set_option("narrow_qkv", 1)
     if model.engine.dtype == "f8":
         finetuned_file = bool(args.resume) and os.path.isfile(args.resume)
         mask = args.f8_mask if args.f8_mask is not None else (12 if finetuned_file else 31)

@@ -60,6 +60,9 @@ def get_args_parser():
                    help="auto: the same for the compensated o_proj and down launches that carry the e2m3 second pass (fp16 engines; bf16 under --second_pass e2m3): engine "
                         "option \"narrow_lo6\" = 1, the same scores bit for bit.  Does nothing where the compensated calls walk K twice in 16 bits (those are "
                         "--narrow_gemm's).  Refused with --dtype f8")
+    p.add_argument("--narrow_qkv", default="off", choices=["off", "auto"],
+                   help="auto: the QKV projection of small scoring calls runs on the narrow-tile QKV GEMM (engine option \"narrow_qkv\" = 1), in the plain, compensated and "
+                        "e2m3 second-pass forms alike: the same scores bit for bit.  Refused with --dtype f8")
     p.add_argument("--max_tokens", default=24576, type=int)
     p.add_argument("--shard", default=None, type=int, nargs=2, metavar=("W", "RANK"))
     p.add_argument("--synthetic", default=0, type=int)
@@ -74,6 +77,8 @@ def check_args(args, world: int = 1) -> None:
         raise SystemExit("search: --narrow_gemm auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM takes fp16 / bf16 operands")
     if getattr(args, "narrow_lo6", "off") == "auto" and args.dtype == "f8":
         raise SystemExit("search: --narrow_lo6 auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM with the e2m3 second pass takes fp16 / bf16 operands")
+    if getattr(args, "narrow_qkv", "off") == "auto" and args.dtype == "f8":
+        raise SystemExit("search: --narrow_qkv auto needs a 16-bit engine (--dtype f16 | bf16): the narrow QKV GEMM takes fp16 / bf16 operands")
     if args.dtype == "f8":
         raise SystemExit("search: --dtype f8 is not supported (the prefix cache needs a 16-bit engine: --dtype f16 | bf16)")
     if args.shard is not None:
@@ -177,6 +182,8 @@ def main(args):
         model.engine.set_option("narrow_gemm", 1)
     if getattr(args, "narrow_lo6", "off") == "auto":
         model.engine.set_option("narrow_lo6", 1)
+    if getattr(args, "narrow_qkv", "off") == "auto":
+        model.engine.set_option("narrow_qkv", 1)
     if model.engine.can_precise:
         model.tvg_precise = args.tvg_precise
         model.vtg_precise = None if args.vtg_precise == "none" else args.vtg_precise
@@ -192,7 +199,7 @@ def main(args):
         return _main_v2t(args, model, scorer, gal, v2t_iv2, vids, len(tvg_ids), t0)
     gal.build(first_stage=None if t2v_iv2 is None else np.ascontiguousarray(np.asarray(t2v_iv2, dtype=np.float32).T))     # v2t first stage: calibration sample
     print(f"gallery: {len(video)} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'} of {gal.cache.bytes // max(gal.n_slots, 1) if gal.cache else 0} bytes, "
-          f"mode {scorer.vtg_mode or 'none'}, narrow_gemm {getattr(args, 'narrow_gemm', 'off')}, narrow_lo6 {getattr(args, 'narrow_lo6', 'off')}, built in {gal.build_seconds:.2f}s (ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
+          f"mode {scorer.vtg_mode or 'none'}, narrow_gemm {getattr(args, 'narrow_gemm', 'off')}, narrow_lo6 {getattr(args, 'narrow_lo6', 'off')}, narrow_qkv {getattr(args, 'narrow_qkv', 'off')}, built in {gal.build_seconds:.2f}s (ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
     n_ds = len(vtg_ids) - len(args.query)
     texts = list(args.query_ids) + list(range(n_ds, len(vtg_ids)))
     names = [f"caption:{i}" for i in args.query_ids] + [f"query:{q}" for q in args.query]
@@ -238,7 +245,7 @@ def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) 
     if finetuned:                                     # a zero-shot blend has no TVG term: no caption cache
         tg.build(first_stage=first)
     print(f"gallery: {n_videos} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'}, mode {scorer.vtg_mode or 'none'}, built in {gal.build_seconds:.2f}s; "
-          f"{n_texts} texts, {tg.n_slots} caption slots of {tg.per_slot_bytes()} bytes, tvg mode {scorer.tvg_mode}, narrow_gemm {getattr(args, 'narrow_gemm', 'off')}, narrow_lo6 {getattr(args, 'narrow_lo6', 'off')}, built in {tg.build_seconds:.2f}s "
+          f"{n_texts} texts, {tg.n_slots} caption slots of {tg.per_slot_bytes()} bytes, tvg mode {scorer.tvg_mode}, narrow_gemm {getattr(args, 'narrow_gemm', 'off')}, narrow_lo6 {getattr(args, 'narrow_lo6', 'off')}, narrow_qkv {getattr(args, 'narrow_qkv', 'off')}, built in {tg.build_seconds:.2f}s "
           f"(ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
     bad = [v for v in args.video_ids if not 0 <= v < n_videos]
     if bad:

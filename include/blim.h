@@ -581,6 +581,7 @@ typedef struct blim_gemm_args {
     int64_t swiglu_ld;
     int32_t tile;          /* 0 = 256 x 256 tiles, 1 = auto, 2 = the narrow kernel (see below) */
     int32_t tile_lo6;      /* the same for BLIM_EPI_RESID with A6 / W6: 0 = 256 x 256 tiles, 1 = auto, 2 = the narrow e2m3 kernel (see below) */
+    int32_t tile_qkv;      /* the same for BLIM_EPI_QKV on fp16 / bf16 operands: 0 = 256 x 256 tiles, 1 = auto, 2 = the narrow QKV kernel (see below) */
 } blim_gemm_args;
 int blim_gemm(const blim_gemm_args* args, void* stream);
 /* tile (added at the end of the struct; the ABI version is unchanged -- a shorter struct reads as 0): BLIM_EPI_RESID on fp16 / bf16 operands without A6 / W6 also exists
@@ -600,6 +601,15 @@ int32_t blim_gemm_narrow_threshold(void);
  * blim_gemm_narrow_lo6_launches(): launches of THAT kernel by this process so far -- a counter of its own; blim_gemm_narrow_launches() does not move on them. */
 int64_t blim_gemm_narrow_lo6_launches(void);
 int32_t blim_gemm_narrow_lo6_threshold(void);
+/* tile_qkv (added behind `tile_lo6`, same rule: a shorter struct reads as 0): BLIM_EPI_QKV on fp16 / bf16 operands exists in 64 x 64 tiles as well, in every 16-bit
+ * form the 256 x 256 kernel has: plain or hi | lo outputs (lo_off) over the plain or the w_wrap_k walk (lda > K included), and hi | lo outputs behind the e2m3 second
+ * pass (A6 / W6).  The K walk is the narrow kernels', the epilogue (bias, RoPE from rope_rows, 16-bit rounding inside the fp16 saturation window, hi | lo) is the
+ * 256 x 256 kernel's per element: every stored element is equal bit for bit.  2 = that kernel; any other epilogue, BLIM_COMPUTE_F8 and A6 without lo_off are refused
+ * with the field named.  1 = auto: that kernel when the form is eligible and ceil(M / 256) * ceil(N / 256) < blim_gemm_narrow_qkv_threshold(), the 256 x 256 kernel
+ * otherwise (an ineligible form is not an error).  Other values: BLIM_ERR_ARG.  `tile` and `tile_lo6` keep every behaviour they have (both still refuse
+ * BLIM_EPI_QKV under 2).  blim_gemm_narrow_qkv_launches(): launches of THAT kernel by this process so far -- a counter of its own; the other two do not move. */
+int64_t blim_gemm_narrow_qkv_launches(void);
+int32_t blim_gemm_narrow_qkv_threshold(void);
 /* cos / sin of every token's position as BLIM_EPI_QKV reads them (csrc/gemm.hpp: rope_rows): out f32 [8 = {cos, sin} x 4 groups of 16 dims][stride rows][16],
  * row t of every chunk = position min(max(positions[t], 0), max_positions - 1); stride >= n_tokens.  workspace: blim_rope_rows_bytes(max_positions) bytes (the
  * cos | sin tables of all positions, built by the call as the engine builds its own at creation); out: 128 * stride floats. */
@@ -653,6 +663,10 @@ int blim_debug_gemm_stamps(void* device_buf);
  *   (the compensated o_proj and down of fp16 engines, of bf16 engines under "precise_lo6" = 1); 1 = auto, 2 = wherever the form is eligible.  Every other launch is
  *   untouched: the plain and w_wrap_k forms stay "narrow_gemm"'s, fp8 engines keep the 256 x 256 kernel.  Like "narrow_gemm" it changes NO value and is no part of a
  *   prefix cache's snapshot, of the calibration store's key or of the weights fingerprint;
+ * "narrow_qkv" (0 / 1 / 2, default 0; other values BLIM_ERR_ARG): blim_gemm's `tile_qkv` for the decoder layers' QKV projection in blim_score, blim_score_cached, blim_hidden
+ *   and blim_decode (the trainer's launch is untouched): plain, w_wrap_k and e2m3 second-pass forms alike, adapters apart included; 1 = auto, 2 = wherever the form is
+ *   eligible; fp8 engines keep the 256 x 256 kernel.  Like "narrow_gemm" it changes NO value -- q, k and v, and with them the K / V a prefix cache captures, are the
+ *   same bits -- and is no part of a prefix cache's snapshot, of the calibration store's key or of the weights fingerprint;
  * "masked_query_zero" (0/1, default 0; 16-bit engines; PARITY-UNPINNED): query positions the key mask hides (blim_batch.key_visible == 0) write a ZERO attention output
  *   instead of attending to their visible keys.  The default is the semantics parity is pinned to -- the reference's eager / SDPA attention classes
  *   (modeling_qwen2_flash.py:288-310, 701-709), where a masked query row is computed like any other.  Its flash-attention-2 class drops such positions before the

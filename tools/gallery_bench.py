@@ -39,7 +39,13 @@ pass), in the compensated modes: t2v under `--modes full,select` (select: layers
 cached TVG leg of one k = 16 query under `--tvg_modes attn,full`.
 
     python tools/gallery_bench.py --narrow_lo6 --modes full,select --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r18_narrow_lo6_gallery.json
-    python tools/gallery_bench.py --narrow_lo6 --direction v2t --n 1000 --k 16 --synthetic_7b --out profiles/r18_narrow_lo6_v2t.json"""
+    python tools/gallery_bench.py --narrow_lo6 --direction v2t --n 1000 --k 16 --synthetic_7b --out profiles/r18_narrow_lo6_v2t.json
+
+`--narrow_qkv`: the same measurements for engine option "narrow_qkv" (the QKV launch in all of its 16-bit forms), t2v under `--modes none,full` and
+the v2t TVG leg.  The two older options stay on auto under BOTH values, so that 0 is the library as it ran with them before this option existed.
+
+    python tools/gallery_bench.py --narrow_qkv --modes none,full --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r19_narrow_qkv_gallery.json
+    python tools/gallery_bench.py --narrow_qkv --direction v2t --n 1000 --k 16 --synthetic_7b --out profiles/r19_narrow_qkv_v2t.json"""
 import argparse
 import json
 import os
@@ -82,6 +88,7 @@ def main():
     ap.add_argument("--host_gb", type=float, default=None, help="the host tier's measurements (t2v): pinned host memory of the tier, GB")
     ap.add_argument("--narrow_gemm", action="store_true", help="engine option narrow_gemm 0 against 1 (t2v, eager index): single-query latency, query stream, timing classes")
     ap.add_argument("--narrow_lo6", action="store_true", help="engine option narrow_lo6 0 against 1 in the compensated modes (t2v: --modes full,select; v2t: the TVG leg)")
+    ap.add_argument("--narrow_qkv", action="store_true", help="engine option narrow_qkv 0 against 1, narrow_gemm and narrow_lo6 on auto throughout (t2v: --modes none,full; v2t: the TVG leg)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -97,12 +104,12 @@ def main():
     tvg = RU.padding_ids(Tt(prob.tvg_ids), Tt(prob.tvg_labels), Tt(prob.tvg_masks), tok)
     video = [torch.from_numpy(v) for v in prob.video]
     q = np.linspace(0, a.n - 1, a.queries).round().astype(np.int64)
-    if a.narrow_lo6 and a.direction == "v2t":
-        return main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if (a.narrow_lo6 or a.narrow_qkv) and a.direction == "v2t":
+        return main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_qkv" if a.narrow_qkv else "narrow_lo6")
     if a.direction == "v2t":
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
-    if a.narrow_gemm or a.narrow_lo6:
-        return main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_lo6" if a.narrow_lo6 else "narrow_gemm")
+    if a.narrow_gemm or a.narrow_lo6 or a.narrow_qkv:
+        return main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_qkv" if a.narrow_qkv else "narrow_lo6" if a.narrow_lo6 else "narrow_gemm")
     if a.host_gb is not None:
         return main_host(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.fill == "lazy":
@@ -151,15 +158,19 @@ def main():
 
 
 def main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_gemm"):
-    """Option "narrow_gemm" (or "narrow_lo6") 0 against 1 on one eager index (see the module text)."""
+    """Option "narrow_gemm" (or "narrow_lo6", "narrow_qkv") 0 against 1 on one eager index (see the module text)."""
     from blim_amd import engine as eng
     e = model.engine
-    launches_of, threshold = ((eng.gemm_narrow_lo6_launches, eng.gemm_narrow_lo6_threshold) if option == "narrow_lo6" else
-                              (eng.gemm_narrow_launches, eng.gemm_narrow_threshold))
+    launches_of, threshold = {"narrow_qkv": (eng.gemm_narrow_qkv_launches, eng.gemm_narrow_qkv_threshold), "narrow_lo6": (eng.gemm_narrow_lo6_launches, eng.gemm_narrow_lo6_threshold),
+                              "narrow_gemm": (eng.gemm_narrow_launches, eng.gemm_narrow_threshold)}[option]
+    if option == "narrow_qkv":                                             # the background of both values: the older options on auto
+        e.set_option("narrow_gemm", 1); e.set_option("narrow_lo6", 1)
     res = {"n": a.n, "queries": a.queries, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc, "reps": a.reps,
            "threshold_tiles": threshold(), "modes": {}}
     if option != "narrow_gemm":
         res["option"] = option
+    if option == "narrow_qkv":
+        res["background"] = {"narrow_gemm": 1, "narrow_lo6": 1}
     med = lambda x: float(np.median(x))
     spread = lambda x: float((max(x) - min(x)) / np.median(x))
     for mode in a.modes.split(","):
@@ -174,21 +185,23 @@ def main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_ge
         gal = GalleryIndex(sc)
         gal.build()
         r = {"latency": {}}
-        for kk in (a.k, a.n):
-            c1 = np.argsort(-prob.t2v_sims[q[0]], kind="stable")[:kk][None]
+
+        def latency(tq, c1):
             ts, launches, ref = {0: [], 1: []}, {}, None
             for v in (0, 1):                                               # warm-up of both kernels' paths
-                e.set_option(option, v); gal.vtg_scores([q[0]], c1)
+                e.set_option(option, v); gal.vtg_scores([tq], c1)
             for _ in range(a.reps):
                 for v in (0, 1):
                     e.set_option(option, v)
                     n0 = launches_of()
-                    dt, got = timed(lambda: gal.vtg_scores([q[0]], c1))
+                    dt, got = timed(lambda: gal.vtg_scores([tq], c1))
                     ts[v].append(dt); launches[v] = launches_of() - n0
                     ref = got if ref is None else ref
                     assert np.array_equal(np.asarray(ref), np.asarray(got)), "scores differ between the option's values 0 and 1"
-            r["latency"][f"k{kk}"] = {"off_ms": 1e3 * med(ts[0]), "auto_ms": 1e3 * med(ts[1]), "off_spread": spread(ts[0]), "auto_spread": spread(ts[1]),
-                                      "off_all_ms": [1e3 * t for t in ts[0]], "auto_all_ms": [1e3 * t for t in ts[1]], "narrow_launches": launches}
+            return {"off_ms": 1e3 * med(ts[0]), "auto_ms": 1e3 * med(ts[1]), "off_spread": spread(ts[0]), "auto_spread": spread(ts[1]),
+                    "off_all_ms": [1e3 * t for t in ts[0]], "auto_all_ms": [1e3 * t for t in ts[1]], "narrow_launches": launches}
+        for kk in (a.k, a.n):
+            r["latency"][f"k{kk}"] = latency(q[0], np.argsort(-prob.t2v_sims[q[0]], kind="stable")[:kk][None])
         cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
         ts = {0: [], 1: []}
 
@@ -203,14 +216,27 @@ def main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_ge
                 assert all(np.array_equal(x, y) for x, y in zip(ref, got)), "stream scores differ between the option's values 0 and 1"
         r["stream"] = {"queries": len(q), "k": a.k, "off_s": med(ts[0]), "auto_s": med(ts[1]), "off_spread": spread(ts[0]), "auto_spread": spread(ts[1]),
                        "off_ms_per_query": 1e3 * med(ts[0]) / len(q), "auto_ms_per_query": 1e3 * med(ts[1]) / len(q)}
-        c1 = np.argsort(-prob.t2v_sims[q[0]], kind="stable")[:a.k][None]
-        r["classes"] = {}
-        for v in (0, 1):
-            e.set_option(option, v)
-            e.timing_enable(True); e.timing_report()
-            gal.vtg_scores([q[0]], c1)
-            r["classes"]["auto" if v else "off"] = {k: x for k, x in e.timing_report().items() if x["calls"]}
-            e.timing_enable(False)
+
+        def classes(tq, c1):
+            out = {}
+            for v in (0, 1):
+                e.set_option(option, v)
+                e.timing_enable(True); e.timing_report()
+                gal.vtg_scores([tq], c1)
+                out["auto" if v else "off"] = {k: x for k, x in e.timing_report().items() if x["calls"]}
+                e.timing_enable(False)
+            return out
+        r["classes"] = classes(q[0], np.argsort(-prob.t2v_sims[q[0]], kind="stable")[:a.k][None])
+        if option == "narrow_qkv":
+            # QKV's N has 18 column tiles where the residual GEMMs' has 14: the same query can sit on the other side of this option's threshold.  The packed tokens of
+            # every query of the stream, how many narrow launches one stream makes, and the same two measurements for the stream's median query (by packed tokens)
+            toks = [int(sum(p.n_tokens for p in gal.iter_plans(np.stack([cand[i], np.full(a.k, t)], axis=1)))) for i, t in enumerate(q)]
+            e.set_option(option, 1)
+            n0 = launches_of(); stream(); r["stream"]["narrow_launches"] = launches_of() - n0
+            r["stream"]["tokens_per_query"] = toks
+            r["stream"]["tokens_first_query"] = toks[0]
+            im = int(np.argsort(toks, kind="stable")[len(toks) // 2])
+            r["median_query"] = {"index": im, "tokens": toks[im], "latency": latency(int(q[im]), cand[im][None]), "classes": classes(int(q[im]), cand[im][None])}
         e.set_option(option, 0)
         res["modes"][mode] = r
         print(json.dumps({mode: r}), flush=True)
@@ -223,14 +249,18 @@ def main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_ge
     model.engine.close()
 
 
-def main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc):
-    """Option "narrow_lo6" 0 against 1 on the cached TVG leg of one v2t query of k candidates, per TVG mode (see the module text)."""
+def main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_lo6"):
+    """Option "narrow_lo6" (or "narrow_qkv") 0 against 1 on the cached TVG leg of one v2t query of k candidates, per TVG mode (see the module text)."""
     from blim_amd import engine as eng
     e = model.engine
+    launches_of, threshold = ((eng.gemm_narrow_qkv_launches, eng.gemm_narrow_qkv_threshold) if option == "narrow_qkv" else
+                              (eng.gemm_narrow_lo6_launches, eng.gemm_narrow_lo6_threshold))
+    if option == "narrow_qkv":                                             # the background of both values: the older options on auto
+        e.set_option("narrow_gemm", 1); e.set_option("narrow_lo6", 1)
     med = lambda x: float(np.median(x))
     spread = lambda x: float((max(x) - min(x)) / np.median(x))
-    res = {"direction": "v2t", "option": "narrow_lo6", "n": a.n, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc,
-           "reps": a.reps, "threshold_tiles": eng.gemm_narrow_lo6_threshold(), "tvg_modes": {}}
+    res = {"direction": "v2t", "option": option, "n": a.n, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc,
+           "reps": a.reps, "threshold_tiles": threshold(), "tvg_modes": {}}
     model.vtg_precise = None
     c1 = np.argsort(-prob.v2t_sims[q[0]], kind="stable")[:a.k]
     p1 = np.stack([np.full(a.k, q[0]), c1], axis=1)
@@ -247,25 +277,25 @@ def main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc):
         tg.build()
         ts, launches, ref = {0: [], 1: []}, {}, None
         for v in (0, 1):
-            e.set_option("narrow_lo6", v); tg.tvg_pairs(p1)
+            e.set_option(option, v); tg.tvg_pairs(p1)
         for _ in range(a.reps):
             for v in (0, 1):
-                e.set_option("narrow_lo6", v)
-                n0 = eng.gemm_narrow_lo6_launches()
+                e.set_option(option, v)
+                n0 = launches_of()
                 dt, got = timed(lambda: tg.tvg_pairs(p1))
-                ts[v].append(dt); launches[v] = eng.gemm_narrow_lo6_launches() - n0
+                ts[v].append(dt); launches[v] = launches_of() - n0
                 ref = got if ref is None else ref
-                assert np.array_equal(ref, got), "TVG scores differ between narrow_lo6 0 and 1"
+                assert np.array_equal(ref, got), "TVG scores differ between the option's values 0 and 1"
         r = {"off_ms": 1e3 * med(ts[0]), "auto_ms": 1e3 * med(ts[1]), "off_spread": spread(ts[0]), "auto_spread": spread(ts[1]),
              "off_all_ms": [1e3 * t for t in ts[0]], "auto_all_ms": [1e3 * t for t in ts[1]], "narrow_launches": launches,
              "tokens_cached": sum(p.n_tokens for p in tg.iter_plans(p1)), "classes": {}}
         for v in (0, 1):
-            e.set_option("narrow_lo6", v)
+            e.set_option(option, v)
             e.timing_enable(True); e.timing_report()
             tg.tvg_pairs(p1)
             r["classes"]["auto" if v else "off"] = {k: x for k, x in e.timing_report().items() if x["calls"]}
             e.timing_enable(False)
-        e.set_option("narrow_lo6", 0)
+        e.set_option(option, 0)
         res["tvg_modes"][mode] = r
         print(json.dumps({mode: r}), flush=True)
         tg.close(); gal.close()
