@@ -19,6 +19,9 @@ mode change.
 slot by that very call (`blim_score_*_admit`), so the calls after it read it.  Which slot is decided per pass -- one vtg_pairs / tvg_pairs call -- by a
 deterministic policy (`_PrefixIndex._begin_pass`): free slots first, then the least recently used slot whose key this pass does not need, else no admission.  `host_budget_bytes` (lazy fill) puts a `HostTier` under the cache: a key that loses its slot is kept as a packed record
 in pinned host memory, and a key that has a record gets a slot back by a copy (blim.h: blim_prefix_cache_export / _import) instead of a decode.
+
+An index follows its scorer: texts that join later (`PairScorer.add_texts`) append keys before the next pass is planned, and
+`GalleryIndex.rerank_requests` scores requests of unequal candidate counts as one pass.
 """
 from __future__ import annotations
 
@@ -250,6 +253,7 @@ class _PrefixIndex:
         self._stamp: Dict = {}           # lazy: resident key -> (pass number, position among the pass's keys) of its last use
         self._pass: Optional[_Pass] = None
         self._n_pass = 0
+        self._n_texts = 0                # the scorer's texts the keys cover (PairScorer.add_texts: texts join later; _sync_texts)
         self.s = scorer
         self.m, self.engine = scorer.m, scorer.engine
         if getattr(self.engine, "dtype", "") == "f8":
@@ -295,6 +299,7 @@ class _PrefixIndex:
         """Resolves the numeric mode, assigns the slots under the budget and fills them in packed calls of up to max_tokens tokens."""
         import time
         import torch
+        self._sync_texts()
         self.resolve_mode(first_stage)
         t0 = time.perf_counter()
         comp = self.compensated()
@@ -388,8 +393,9 @@ class _PrefixIndex:
             victims = sorted((k for k in self.slot_of if k not in needed), key=lambda k: self._stamp.get(k, (0, 0)))
             host = self.host if self.host is not None and self.host.n_records else None
             restores, losers = [], []
+            room = getattr(self.cache, "max_len", None)             # a key that joined after build() may be longer than a slot: it stays in the batch
             for k in need:
-                if k in self.slot_of:
+                if k in self.slot_of or (room is not None and self.prefix_len(k) > room):
                     continue
                 if free:
                     sl, v = free.pop(0), None
@@ -431,6 +437,7 @@ class _PrefixIndex:
     def iter_plans(self, pairs):
         """pairs [P, 2] (video j, text i) -> the engine calls of one pass, planned by PairScorer's planner over this index's slots (the subclass's _plans)."""
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        self._sync_texts()
         p = self._begin_pass(self._needs(pairs))
         for plan in self._plans(pairs):
             plan.pass_ = p
@@ -463,6 +470,14 @@ class _PrefixIndex:
                     st.evicted += 1
                 self.slot_of[k] = int(sl); self._stamp[k] = (p.no, at[k])
                 st.admitted += 1
+
+    def _sync_texts(self) -> None:
+        """The index follows its scorer: texts that joined since the keys were last derived (PairScorer.add_texts) extend them.  Keys are appended only, so the
+        slots, the recency stamps, the stats and the host tier's records stay valid; a new key has no slot until it is admitted (lazy) or the index is built again."""
+        n = self._count_texts()
+        if n != self._n_texts:
+            self._grow(self._n_texts, n)
+            self._n_texts = n
 
     # ---- scoring
     def run(self, plan):
@@ -499,14 +514,27 @@ class GalleryIndex(_PrefixIndex):
     def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, priority: Optional[Sequence[int]] = None, log=None, fill: str = "eager",
                  host_budget_bytes: Optional[int] = None):
         super().__init__(scorer, budget_bytes, priority, log, fill, host_budget_bytes)
-        # the prompt splits of the texts: (pre, post) pairs, in order of first appearance
-        splits: Dict[Tuple[bytes, bytes], Tuple[np.ndarray, np.ndarray]] = {}
-        for pre, post, _ in scorer.vtg_split:
-            splits.setdefault((pre.tobytes(), post.tobytes()), (pre, post))
-        self.splits = splits
-        self.keys: List[Tuple[int, bytes, bytes]] = [(j, k[0], k[1]) for j in range(len(scorer.video)) for k in splits]
-        at = {k: n for n, k in enumerate(splits)}
-        self._split_id = np.array([at[(pre.tobytes(), post.tobytes())] for pre, post, _ in scorer.vtg_split], dtype=np.int64)
+        # the prompt splits of the texts: (pre, post) pairs, in order of first appearance; one key per (video, split), video-major for the texts given here
+        self.splits: Dict[Tuple[bytes, bytes], Tuple[np.ndarray, np.ndarray]] = {}
+        self.keys: List[Tuple[int, bytes, bytes]] = []
+        self._split_id = np.zeros(0, dtype=np.int64)
+        self._sync_texts()
+
+    def _count_texts(self) -> int:
+        return len(self.s.vtg_split)
+
+    def _grow(self, lo: int, hi: int) -> None:
+        """Texts lo .. hi - 1 joined: their split ids, and one key per video for every (pre, post) the index has not seen, appended."""
+        at = {k: n for n, k in enumerate(self.splits)}
+        new, ids = [], []
+        for pre, post, _ in self.s.vtg_split[lo:hi]:
+            k = (pre.tobytes(), post.tobytes())
+            if k not in at:
+                at[k] = len(at); self.splits[k] = (pre, post); new.append(k)
+            ids.append(at[k])
+        videos = range(len(self.s.video))
+        self.keys += [(j, k[0], k[1]) for j in videos for k in new] if not self.keys else [(j, k[0], k[1]) for k in new for j in videos]
+        self._split_id = np.concatenate([self._split_id, np.asarray(ids, dtype=np.int64)])
 
     def prefix_len(self, key) -> int:
         j, pre, post = key
@@ -562,9 +590,10 @@ class GalleryIndex(_PrefixIndex):
         if not len(pairs):
             return []
         order = np.lexsort((pairs[:, 1], pairs[:, 0]))
-        code = (pairs[:, 0] * len(self.splits) + self._split_id[pairs[:, 1]])[order]
+        S, split = len(self.splits), list(self.splits)
+        code = (pairs[:, 0] * S + self._split_id[pairs[:, 1]])[order]
         _, first = np.unique(code, return_index=True)
-        return [self.keys[int(c)] for c in code[np.sort(first)]]
+        return [(int(c) // S,) + split[int(c) % S] for c in code[np.sort(first)]]
 
     def _plans(self, pairs: np.ndarray):
         """pairs [P, 2] (video j, text i) -> engine calls, planned by PairScorer._pack_vtg over this index's slots; each plan carries pfx_slot (device) and the
@@ -599,8 +628,9 @@ class GalleryIndex(_PrefixIndex):
         if state != self._prior_state:
             self._prior, self._prior_state = {}, state
         tp = s.m.tvg_prefix_length
+        s._need_tvg(texts)
         keys = []
-        for i, row in zip(texts, cand):
+        for i, row in zip(texts, cand):                                 # (rows of any lengths: rerank_requests hands in ragged candidate lists)
             pr = s.tvg_split[int(i)]
             keys += [(pr[:tp].tobytes(), len(pr), int(pr[-1]), int(j)) for j in row]
         miss = [k for k in dict.fromkeys(keys) if k not in self._prior]
@@ -612,7 +642,8 @@ class GalleryIndex(_PrefixIndex):
             todo = np.array([first[k] for k in miss], np.int64)
             for k, v in zip(miss, s.tvg(todo, cpn=True)):
                 self._prior[k] = float(v)
-        return np.array([self._prior[k] for k in keys]).reshape(cand.shape)
+        out = np.array([self._prior[k] for k in keys])
+        return out.reshape(cand.shape) if isinstance(cand, np.ndarray) else out
 
     def rerank(self, texts, cand, first_stage=None, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0), finetuned: bool = False):
         """The t2v half of training_utils.combine_and_rank for these queries' candidates: blended = c2 * (c0 * query_likelihood + (1 - c0) * candidate) + (1 - c2) *
@@ -630,11 +661,51 @@ class GalleryIndex(_PrefixIndex):
                 t2v_cand = t2v_cand - alpha[0] * self._t2v_prior(texts, cand)
         else:
             t2v_cand = np.zeros(cand.shape)
+        return self._blend(cand, ql, t2v_cand, fs, c)
+
+    @staticmethod
+    def _blend(cand, ql, t2v_cand, fs, c):
+        """cand, query likelihood, candidate likelihood and first stage, [Q, k] each -> (candidates best first, their blended scores)."""
         c0, _, c2, _ = c
         t2v_lm = c0 * ql + (1 - c0) * t2v_cand
         blended = c2 * t2v_lm + (1 - c2) * fs
         order = np.argsort(-blended, axis=1, kind="stable")
         return np.take_along_axis(cand, order, 1), np.take_along_axis(blended, order, 1)
+
+    def rerank_requests(self, requests, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0), finetuned: bool = False):
+        """rerank() for requests of unequal sizes, scored together: requests = [(text index, candidate video indices [k_q], first_stage [k_q] or None)].  The pairs of
+        all requests are ONE vtg_pairs pass (one pass of a lazy index: its needed keys pinned, its misses admitted under section 12's policy) and, for fine-tuned
+        checkpoints, one PairScorer.tvg call and one prior lookup; the blend is rerank()'s, per request.  A VTG score does not depend on what shares its call, so the
+        query likelihood is bit for bit that of rerank() per request.  -> [(order [k_q], blended [k_q])] in request order."""
+        reqs = [(int(t), np.asarray(cand, dtype=np.int64).reshape(-1), fs) for t, cand, fs in requests]
+        if not reqs:
+            return []
+        if any(len(cand) == 0 for _, cand, _ in reqs):
+            raise ValueError("rerank_requests: a request has no candidates")
+        pairs = np.concatenate([np.stack([cand, np.full(len(cand), t, dtype=np.int64)], axis=1) for t, cand, _ in reqs])
+        ends = np.cumsum([len(cand) for _, cand, _ in reqs])
+        ql = np.split(self.vtg_pairs(pairs), ends[:-1])
+        t2v_cand = None
+        if finetuned:
+            self._tvg_state()
+            has = np.array([self.s.tvg_split[t] is not None for t, _, _ in reqs])
+            if c[0] != 1:                                               # the candidate likelihood has a weight: every text needs its TVG row
+                self.s._need_tvg([t for t, _, _ in reqs])
+            of = np.repeat(has, [len(cand) for _, cand, _ in reqs])    # (a text added without a TVG row keeps a zero term under c0 = 1)
+            t2v_cand = np.zeros(len(pairs), dtype=np.float32)
+            if of.any():
+                t2v_cand[of] = self.s.tvg(pairs[of])
+            if cpn and of.any():
+                prior = np.zeros(len(pairs))
+                prior[of] = self._t2v_prior([t for (t, _, _), h in zip(reqs, has) if h], [cand for (_, cand, _), h in zip(reqs, has) if h])
+                t2v_cand = t2v_cand - alpha[0] * prior
+            t2v_cand = np.split(t2v_cand, ends[:-1])
+        out = []
+        for n, (t, cand, fs) in enumerate(reqs):
+            fs = np.zeros(cand.shape) if fs is None else np.asarray(fs).reshape(cand.shape)
+            order, blended = self._blend(cand[None], ql[n][None], np.zeros((1, len(cand))) if t2v_cand is None else t2v_cand[n][None], fs[None], c)
+            out.append((order[0], blended[0]))
+        return out
 
 
 class TextGalleryIndex(_PrefixIndex):
@@ -652,12 +723,20 @@ class TextGalleryIndex(_PrefixIndex):
             raise ValueError("TextGalleryIndex: video_index must be built on the same scorer")
         self.video_index = video_index
         # one key per distinct caption prompt, in order of first appearance: texts with the same prompt share a slot
-        prompts: Dict[bytes, np.ndarray] = {}
-        for pr in scorer.tvg_split:
-            prompts.setdefault(pr.tobytes(), pr)
-        self.prompts = prompts
-        self.keys: List[bytes] = list(prompts)
+        self.prompts: Dict[bytes, np.ndarray] = {}
+        self.keys: List[bytes] = []
+        self._sync_texts()
         self.exec_tokens = 0                                # packed tokens of the cached TVG calls run so far
+
+    def _count_texts(self) -> int:
+        return len(self.s.tvg_split)
+
+    def _grow(self, lo: int, hi: int) -> None:
+        """Texts lo .. hi - 1 joined: a key per caption prompt the index has not seen, appended (a text added without a TVG row has none)."""
+        for pr in self.s.tvg_split[lo:hi]:
+            if pr is not None and pr.tobytes() not in self.prompts:
+                self.prompts[pr.tobytes()] = pr
+                self.keys.append(pr.tobytes())
 
     def prefix_len(self, key) -> int:
         return len(self.prompts[key])
@@ -697,6 +776,7 @@ class TextGalleryIndex(_PrefixIndex):
     # ---- planning
     def _needs(self, pairs: np.ndarray) -> List:
         """The caption prompts of a pass, in the order _plan_tvg meets its texts."""
+        self.s._need_tvg(pairs[:, 1])
         return list(dict.fromkeys(self.s.tvg_split[int(i)].tobytes() for i in np.unique(pairs[:, 1])))
 
     def _plans(self, pairs: np.ndarray):

@@ -135,8 +135,8 @@ class PairScorer(CalibrationMixin):
             raise ValueError(f"num_clips = {num_clips} but the engine was created with num_clips = {self.m.dims.num_clips}")
         strip = lambda ids, msk, lab: [(np.asarray(ids[i])[np.asarray(msk[i]) != 0], np.asarray(lab[i])[np.asarray(msk[i]) != 0])
                                        for i in range(len(ids))]
-        self.vtg_rows = strip(vtg_ids, vtg_masks, vtg_labels)
-        self.tvg_rows = strip(tvg_ids, tvg_masks, tvg_labels)
+        vtg_rows = strip(vtg_ids, vtg_masks, vtg_labels)
+        tvg_rows = strip(tvg_ids, tvg_masks, tvg_labels)
         self.video = video
         self.tvg_video_labels = np.asarray(tvg_video_labels).astype(np.int32)
         # 16-bit engines: the vocabulary is registered with the engine as hi + lo operands (blim_set_video_vocab) and the TVG calls name none; fp8 engines take the
@@ -156,24 +156,59 @@ class PairScorer(CalibrationMixin):
         self._vfeat: Dict[Tuple[int, bool], object] = {}
         self._upcoming: Dict[bool, List[int]] = {}; self._upcoming_pos: Dict[bool, int] = {}
         self.feat_chunk = int(feat_chunk)
-        # per-text splits
-        self.vtg_split = []
-        for ids, lab in self.vtg_rows:
-            prompt, resp = _split_prompt_response(ids, lab)
-            w = np.nonzero(prompt == IMAGE_TOKEN_INDEX)[0]
-            assert len(w) == 1, "VTG prompt must hold exactly one <image> placeholder"
-            self.vtg_split.append((prompt[: w[0]].astype(np.int64), prompt[w[0] + 1:].astype(np.int64), resp.astype(np.int64)))
         # rows longer than config.tokenizer_model_max_length lose their tail after the splice (modeling_videochat_flash.py:452-457; None = no limit)
         self.max_row_len = getattr(self.m, "tokenizer_model_max_length", None)
-        self.tvg_split = []
-        for ids, lab in self.tvg_rows:
-            prompt, resp = _split_prompt_response(ids, lab)
-            assert len(resp) >= 1 and resp[0] == IMAGE_TOKEN_INDEX, "TVG response must start with the <image> placeholder"
-            if self.max_row_len is not None and len(ids) - 1 + self.num_clips > self.max_row_len:
-                # the reference reads the clip positions relative to the <|im_end|> label of the row's tail (retrieval_utils.py:99-107); a row cut
-                # inside its clip tokens or tail has no such label any more
-                raise ValueError(f"TVG row of {len(ids) - 1 + self.num_clips} tokens exceeds tokenizer_model_max_length = {self.max_row_len}")
-            self.tvg_split.append(prompt.astype(np.int64))
+        # per-text rows and splits: the texts given here and the texts that join later (add_texts) go through the same code
+        self.vtg_rows, self.tvg_rows, self.vtg_split, self.tvg_split = [], [], [], []
+        if len(vtg_rows) != len(tvg_rows):
+            raise ValueError(f"{len(vtg_rows)} VTG rows but {len(tvg_rows)} TVG rows: one of each per text")
+        self.add_texts(vtg_rows, tvg_rows)
+
+    # ---- texts
+    def _text_state(self, vtg_row, tvg_row):
+        """One text's unpadded (ids, labels) rows -> ((pre, post, response) of its VTG row, the caption prompt of its TVG row or None without one), checked."""
+        ids, lab = vtg_row
+        prompt, resp = _split_prompt_response(ids, lab)
+        w = np.nonzero(prompt == IMAGE_TOKEN_INDEX)[0]
+        if len(w) != 1:
+            raise ValueError(f"VTG prompt must hold exactly one <image> placeholder (found {len(w)})")
+        vtg = (prompt[: w[0]].astype(np.int64), prompt[w[0] + 1:].astype(np.int64), resp.astype(np.int64))
+        if tvg_row is None:
+            return vtg, None
+        ids, lab = tvg_row
+        prompt, resp = _split_prompt_response(ids, lab)
+        if not (len(resp) >= 1 and resp[0] == IMAGE_TOKEN_INDEX):
+            raise ValueError("TVG response must start with the <image> placeholder")
+        if self.max_row_len is not None and len(ids) - 1 + self.num_clips > self.max_row_len:
+            # the reference reads the clip positions relative to the <|im_end|> label of the row's tail (retrieval_utils.py:99-107); a row cut
+            # inside its clip tokens or tail has no such label any more
+            raise ValueError(f"TVG row of {len(ids) - 1 + self.num_clips} tokens exceeds tokenizer_model_max_length = {self.max_row_len}")
+        return vtg, prompt.astype(np.int64)
+
+    def add_texts(self, vtg_rows, tvg_rows=None) -> np.ndarray:
+        """Texts that join the scorer: unpadded (ids, labels) rows, one per text; tvg_rows None: the texts have no TVG row (plan_tvg / tvg refuse them).  Every row
+        is checked before any is added: a bad one raises ValueError and adds nothing.  Existing indices never move.  -> the new texts' indices."""
+        as_row = lambda r: (np.asarray(r[0]), np.asarray(r[1]))
+        vtg_rows = [as_row(r) for r in vtg_rows]
+        tvg_rows = [None] * len(vtg_rows) if tvg_rows is None else [as_row(r) for r in tvg_rows]
+        if len(tvg_rows) != len(vtg_rows):
+            raise ValueError(f"add_texts: {len(vtg_rows)} VTG rows but {len(tvg_rows)} TVG rows")
+        for ids, lab in [r for r in vtg_rows + tvg_rows if r is not None]:
+            if ids.ndim != 1 or ids.shape != lab.shape or len(ids) == 0:
+                raise ValueError(f"add_texts: a row is (ids, labels) of one length, got shapes {ids.shape} and {lab.shape}")
+        try:
+            states = [self._text_state(v, t) for v, t in zip(vtg_rows, tvg_rows)]
+        except AssertionError as e:                                      # (_split_prompt_response: a response that is not one trailing span)
+            raise ValueError(str(e)) from None
+        first = len(self.vtg_split)
+        self.vtg_rows += vtg_rows; self.tvg_rows += tvg_rows
+        self.vtg_split += [v for v, _ in states]; self.tvg_split += [t for _, t in states]
+        return np.arange(first, first + len(states), dtype=np.int64)
+
+    def _need_tvg(self, texts) -> None:
+        for i in np.unique(np.asarray(texts, dtype=np.int64)):
+            if self.tvg_split[int(i)] is None:
+                raise ValueError(f"text {int(i)} was added without a TVG row: it has no TVG score")
 
     # ---- projected video features, cached on device (K1 once per video instead of once per pair)
     def video_feat(self, j: int, tvg: bool):
@@ -397,6 +432,8 @@ class PairScorer(CalibrationMixin):
         the slot and each pair's first row is -(slot + 1).  The priors (cpn) have no cached form."""
         C = self.num_clips
         st = box[0]
+        if len(pairs):
+            self._need_tvg(pairs[:, 1])
         # The continuations of one prefix -- the C - 1 clip tokens of every candidate video of a text (prior: last prompt token + clip tokens) -- are
         # packed into ONE sequence whose segments do not see each other (blim_batch.own_start): the 32-query attention blocks are dense instead of
         # holding 3 - 4 queries each (2,919 -> ~500 blocks per 13,700-token call at the reference's shapes) and the planner adds one sequence per

@@ -12,6 +12,19 @@ reports what that tier did.
 `--direction v2t` is the other half: the gallery is the dataset's test captions and the queries are test videos (`--video_ids`).  The candidate likelihood (VTG) is
 served from the same video cache; a fine-tuned checkpoint's query likelihood (TVG) reads the captions' prompts from a second cache (TextGalleryIndex,
 `--text_gallery_gb`), and the CPN prior is kept per text.  One JSON line per query video: the ranked text indices and their blended v2t scores.
+
+`--serve` (t2v): the model is loaded and the gallery built as above, then the command reads one JSON request per line from stdin until EOF and
+writes one JSON line per request to stdout, in arrival order.  A request: `id` (any JSON scalar, echoed); exactly one of `caption` (a test caption's index), `text`
+(free text through the dataset's prompt builder, as `--query`; refused per request under `--synthetic`) and `rows` ({"vtg_ids", "vtg_labels"[, "tvg_ids",
+"tvg_labels"]}, raw token rows); optionally `candidates` (video ids as printed in `videos`) or `candidate_idx` (indices), `first_stage` (floats, parallel to the
+candidates) and `topk` (truncates the answer).  Without candidates a `caption` request takes `--candidates` (`iv2`: its top-`--topk` of the first stage; `all`: the
+gallery); a `text` / `rows` request takes the whole gallery under `all` and gets an error line under `iv2`.  The answer is {"id", "query", "videos", "scores"} or
+{"id", "error"}: a bad request (malformed JSON, an unknown video id, an empty or duplicate candidate list, a row that fails PairScorer.add_texts' checks or leaves no
+response token under tokenizer_model_max_length, a fine-tuned blend with c0 < 1 for rows without a TVG row) gets its error line and the process goes on.
+`--batch_queries B` / `--batch_wait_ms W`: a reader thread queues the lines; the loop takes what is waiting, up to B requests, waits at most W ms for more only while
+fewer are there, and scores the batch as ONE pass (GalleryIndex.rerank_requests) -- the same scores as one pass per request, bit for bit on the VTG term.  Texts join the
+scorer at run time (PairScorer.add_texts); identical `text` / `rows` queries share one text index.  At EOF a `serve:` stderr line counts requests, batches, the mean
+batch size, errors and texts added.
 """
 from __future__ import annotations
 
@@ -68,6 +81,11 @@ def get_args_parser():
     p.add_argument("--synthetic", default=0, type=int)
     p.add_argument("--synthetic_7b", action="store_true")
     p.add_argument("--output", default=None, type=str, help="write the JSON lines here too")
+    p.add_argument("--serve", action="store_true",
+                   help="t2v: after the gallery is built, read one JSON request per line from stdin until EOF and answer each with one JSON line on stdout, in arrival "
+                        "order (see the module text)")
+    p.add_argument("--batch_queries", default=1, type=int, help="--serve: up to this many waiting requests are scored in one pass")
+    p.add_argument("--batch_wait_ms", default=0.0, type=float, help="--serve: with fewer than --batch_queries requests waiting, wait at most this long for more")
     return p
 
 
@@ -93,6 +111,16 @@ def check_args(args, world: int = 1) -> None:
     v2t = getattr(args, "direction", "t2v") == "v2t"
     if args.c is None:                        # the likelihood of the direction alone: t2v c0 = c2 = 1; v2t c1 = 0, c3 = 1
         args.c = [1.0, 0.0, 1.0, 1.0] if v2t else [1.0, 0.0, 1.0, 0.0]
+    serve = bool(getattr(args, "serve", False))
+    if serve:
+        if v2t:
+            raise SystemExit("search: --serve answers text queries over the videos only (--direction t2v); v2t is not served")
+        if args.query or args.query_ids or getattr(args, "video_ids", None):
+            raise SystemExit("search: --serve reads its queries from stdin, one JSON request per line (not --query / --query_ids / --video_ids)")
+        if getattr(args, "batch_queries", 1) < 1 or getattr(args, "batch_wait_ms", 0.0) < 0:
+            raise SystemExit("search: --batch_queries must be at least 1 and --batch_wait_ms must not be negative")
+    elif getattr(args, "batch_queries", 1) != 1 or getattr(args, "batch_wait_ms", 0.0) != 0:
+        raise SystemExit("search: --batch_queries / --batch_wait_ms batch the requests of --serve")
     if v2t:
         if args.query or args.query_ids:
             raise SystemExit("search: --direction v2t takes video queries (--video_ids), not --query / --query_ids")
@@ -101,7 +129,7 @@ def check_args(args, world: int = 1) -> None:
     else:
         if getattr(args, "video_ids", None):
             raise SystemExit("search: --video_ids are the queries of --direction v2t (t2v takes --query_ids and / or --query)")
-        if not args.query_ids and not args.query:
+        if not args.query_ids and not args.query and not serve:
             raise SystemExit("search: give --query_ids and / or --query")
     if args.query and args.candidates == "iv2":
         raise SystemExit("search: free-text queries have no first-stage row: use --candidates all")
@@ -118,6 +146,229 @@ def check_args(args, world: int = 1) -> None:
                          "pass the mode a stored evaluation resolved (--vtg_precise none | full) instead")
     if args.second_pass == "auto":
         raise SystemExit("search: --second_pass auto is not supported (it is measured by evaluation()): give e2m3 or 16bit")
+
+
+class BadRequest(ValueError):
+    """A request that gets an error line; the process goes on."""
+
+
+class Server:
+    """`--serve`: turns request lines into rerank requests of one GalleryIndex and the results into answer lines.  A request is validated in full -- its JSON, its
+    query (a `text` / `rows` query joins the scorer through PairScorer.add_texts, with its checks), its candidates -- before it enters a batch, so a bad request
+    cannot fail the pass its neighbours are scored in.  Identical `text` / `rows` queries share the text index of the first one (a dict from row bytes to index)."""
+
+    def __init__(self, gal, vids, n_captions: int, t2v_iv2, args, finetuned: bool = False, build_rows=None):
+        import numpy as np
+        self.np = np
+        self.gal, self.s = gal, gal.s
+        self.vids = [v for v in vids]
+        self.vid_at = {}
+        for j, v in enumerate(self.vids):          # (an id that appears twice names its first video)
+            self.vid_at.setdefault(str(v), j)
+        self.n_captions, self.t2v_iv2, self.args, self.finetuned, self.build_rows = int(n_captions), t2v_iv2, args, bool(finetuned), build_rows
+        self.n_vid = np.array([int(np.prod(v.shape[-3:-1])) for v in self.s.video], dtype=np.int64)      # video tokens of each prefix, as the planner counts them
+        self.text_of = {}                          # row bytes -> text index
+        self.requests = self.batches = self.errors = self.texts_added = 0
+
+    # ---- one request
+    def _rows(self, req):
+        """-> ((vtg ids, labels), (tvg ids, labels) or None) of a `text` / `rows` request."""
+        np = self.np
+        if "text" in req:
+            if self.build_rows is None:
+                raise BadRequest("a text query needs the dataset's tokenizer (not --synthetic): send rows")
+            if not isinstance(req["text"], str):
+                raise BadRequest("text must be a string")
+            return self.build_rows(req["text"])
+        rows = req["rows"]
+        if not isinstance(rows, dict) or "vtg_ids" not in rows or "vtg_labels" not in rows or ("tvg_ids" in rows) != ("tvg_labels" in rows):
+            raise BadRequest("rows takes vtg_ids and vtg_labels, and tvg_ids with tvg_labels or neither")
+        try:
+            get = lambda k: np.asarray(rows[k], dtype=np.int64).reshape(-1) if len(rows[k]) else np.zeros(0, np.int64)
+            return (get("vtg_ids"), get("vtg_labels")), ((get("tvg_ids"), get("tvg_labels")) if "tvg_ids" in rows else None)
+        except (TypeError, ValueError, OverflowError):
+            raise BadRequest("rows must hold lists of integers") from None
+
+    def _text(self, req):
+        """-> (text index, the answer's `query` field)."""
+        kinds = [k for k in ("caption", "text", "rows") if k in req]
+        if len(kinds) != 1:
+            raise BadRequest("give exactly one of caption, text, rows")
+        if kinds[0] == "caption":
+            i = req["caption"]
+            if isinstance(i, bool) or not isinstance(i, int) or not 0 <= i < self.n_captions:
+                raise BadRequest(f"caption must be an index in 0 .. {self.n_captions - 1}")
+            return i, f"caption:{i}"
+        vtg_row, tvg_row = self._rows(req)
+        key = tuple(self.np.asarray(a).astype(self.np.int64).tobytes() for r in (vtg_row, tvg_row) if r is not None for a in r)
+        t = self.text_of.get(key)
+        if t is None:
+            try:
+                t = int(self.s.add_texts([vtg_row], None if tvg_row is None else [tvg_row])[0])
+            except ValueError as e:
+                raise BadRequest(str(e)) from None
+            self.text_of[key] = t
+            self.texts_added += 1
+        return t, (f"query:{req['text']}" if "text" in req else f"rows:{t}")
+
+    def _candidates(self, req, t: int, is_caption: bool):
+        """-> (candidate video indices, first-stage scores or None)."""
+        np = self.np
+        N = len(self.vids)
+        fs = None
+        if "candidates" in req and "candidate_idx" in req:
+            raise BadRequest("give candidates (video ids) or candidate_idx (indices), not both")
+        if "candidates" in req or "candidate_idx" in req:
+            given = req.get("candidates", req.get("candidate_idx"))
+            if not isinstance(given, list) or not given:
+                raise BadRequest("the candidate list is empty")
+            if "candidates" in req:
+                unknown = [v for v in given if str(v) not in self.vid_at]
+                if unknown:
+                    raise BadRequest(f"unknown video id {unknown[0]!r}")
+                cand = [self.vid_at[str(v)] for v in given]
+            else:
+                if any(isinstance(j, bool) or not isinstance(j, int) or not 0 <= j < N for j in given):
+                    raise BadRequest(f"candidate_idx must hold indices in 0 .. {N - 1}")
+                cand = given
+            if len(set(cand)) != len(cand):
+                raise BadRequest("the candidate list names a video twice")
+            cand = np.asarray(cand, dtype=np.int64)
+        elif self.args.candidates == "iv2":
+            if not is_caption:
+                raise BadRequest("a text / rows query has no first-stage row (--candidates iv2): send candidates")
+            row = np.asarray(self.t2v_iv2[t], dtype=np.float32)
+            cand = np.argsort(-row, kind="stable")[:min(self.args.topk, N)]
+            fs = row[cand]
+        else:
+            cand = np.arange(N)
+            if self.t2v_iv2 is not None and is_caption:
+                fs = np.asarray(self.t2v_iv2[t], dtype=np.float32)[cand]
+        if "first_stage" in req:
+            try:
+                fs = np.asarray(req["first_stage"], dtype=np.float32).reshape(-1)
+            except (TypeError, ValueError):
+                raise BadRequest("first_stage must hold numbers") from None
+            if len(fs) != len(cand) or not np.all(np.isfinite(fs)):
+                raise BadRequest("first_stage must hold one finite number per candidate")
+        return cand, fs
+
+    def parse(self, line: str):
+        """One request line -> a dict(id, query, text, cand, fs, topk); BadRequest (with .id, as far as it was read) for a request that gets an error line."""
+        rid = None
+        try:
+            try:
+                req = json.loads(line)
+            except ValueError:
+                raise BadRequest("malformed JSON") from None
+            if not isinstance(req, dict):
+                raise BadRequest("a request is a JSON object")
+            rid = req.get("id")
+            if isinstance(rid, (dict, list)):
+                rid = None
+                raise BadRequest("id must be a JSON scalar")
+            topk = req.get("topk")
+            if topk is not None and (isinstance(topk, bool) or not isinstance(topk, int) or topk < 1):
+                raise BadRequest("topk must be a positive integer")
+            t, name = self._text(req)
+            cand, fs = self._candidates(req, t, "caption" in req)
+            pre, post, resp = self.s.vtg_split[t]
+            limit = getattr(self.s, "max_row_len", None)
+            if limit is not None and len(pre) + int(self.n_vid[cand].max()) + len(post) >= limit:
+                raise BadRequest(f"tokenizer_model_max_length = {limit} leaves no response token of this query after a candidate's video tokens")
+            if self.finetuned and self.args.c[0] < 1 and self.s.tvg_split[t] is None:
+                raise BadRequest("a fine-tuned blend with c0 < 1 needs the query's TVG row (rows without tvg_ids / tvg_labels have none)")
+            return {"id": rid, "query": name, "text": t, "cand": cand, "fs": fs, "topk": topk}
+        except BadRequest as e:
+            e.id = rid
+            raise
+
+    # ---- one batch
+    def _score(self, reqs):
+        a = self.args
+        return self.gal.rerank_requests([(r["text"], r["cand"], r["fs"]) for r in reqs], cpn=a.cpn, alpha=a.alpha, c=a.c, finetuned=self.finetuned)
+
+    def handle(self, lines, write) -> None:
+        """The requests that arrived together: every good one is scored in ONE rerank_requests pass; one answer line per request, in arrival order."""
+        lines = [ln for ln in lines if ln.strip()]
+        if not lines:
+            return
+        items = []
+        for ln in lines:
+            try:
+                items.append(self.parse(ln))
+            except BadRequest as e:
+                items.append(e)
+        good = [r for r in items if isinstance(r, dict)]
+        if good:
+            try:
+                results = self._score(good)
+            except ValueError as e:                # what validation did not foresee: each request alone, so that only the one at fault gets the error
+                results = [BadRequest(str(e))] if len(good) == 1 else []
+                for r in good if len(good) > 1 else []:
+                    try:
+                        results += self._score([r])
+                    except ValueError as e1:
+                        results.append(BadRequest(str(e1)))
+            for r, res in zip(good, results):
+                r["result"] = res
+        self.requests += len(items)
+        self.batches += 1
+        for r in items:
+            res = r if isinstance(r, BadRequest) else r["result"]
+            if isinstance(res, BadRequest):
+                self.errors += 1
+                write(json.dumps({"id": getattr(r, "id", None) if isinstance(r, BadRequest) else r["id"], "error": str(res)}))
+                continue
+            order, blended = res
+            k = len(order) if r["topk"] is None else min(r["topk"], len(order))
+            write(json.dumps({"id": r["id"], "query": r["query"], "videos": [self.vids[int(j)] for j in order[:k]], "scores": [float(x) for x in blended[:k]]}))
+
+    def summary(self):
+        return {"requests": self.requests, "batches": self.batches, "mean_batch": self.requests / self.batches if self.batches else 0.0, "errors": self.errors,
+                "texts_added": self.texts_added}
+
+
+def serve(lines, write, server, batch_queries: int = 1, batch_wait_ms: float = 0.0):
+    """The serve loop.  A reader thread moves `lines` (any iterable: stdin) into a queue; this loop takes what is waiting, up to batch_queries requests, waits at most
+    batch_wait_ms for more only while fewer are there, and hands the batch to server.handle(batch, write).  Ends at the end of `lines`.  -> server.summary()."""
+    import queue
+    import threading
+    q, eof = queue.Queue(), object()
+
+    def reader():
+        try:
+            for line in lines:
+                q.put(line)
+        finally:
+            q.put(eof)
+    th = threading.Thread(target=reader, name="serve-reader", daemon=True)
+    th.start()
+    ended = False
+    while not ended:
+        item = q.get()
+        if item is eof:
+            break
+        batch = [item]
+        deadline = time.monotonic() + batch_wait_ms / 1e3
+        while len(batch) < batch_queries:
+            try:
+                item = q.get_nowait()
+            except queue.Empty:
+                left = deadline - time.monotonic()
+                if left <= 0:
+                    break
+                try:
+                    item = q.get(timeout=left)
+                except queue.Empty:
+                    break
+            if item is eof:
+                ended = True
+                break
+            batch.append(item)
+        server.handle(batch, write)
+    th.join()
+    return server.summary()
 
 
 def main(args):
@@ -200,6 +451,29 @@ def main(args):
     gal.build(first_stage=None if t2v_iv2 is None else np.ascontiguousarray(np.asarray(t2v_iv2, dtype=np.float32).T))     # v2t first stage: calibration sample
     print(f"gallery: {len(video)} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'} of {gal.cache.bytes // max(gal.n_slots, 1) if gal.cache else 0} bytes, "
           f"mode {scorer.vtg_mode or 'none'}, narrow_gemm {getattr(args, 'narrow_gemm', 'off')}, narrow_lo6 {getattr(args, 'narrow_lo6', 'off')}, narrow_qkv {getattr(args, 'narrow_qkv', 'off')}, built in {gal.build_seconds:.2f}s (ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
+    if getattr(args, "serve", False):
+        build_rows = None
+        if not args.synthetic:                    # free text: the dataset's own prompt builder, as --query above
+            unpad = lambda r: (np.asarray(r[0])[np.asarray(r[2]) != 0], np.asarray(r[1])[np.asarray(r[2]) != 0])
+            build_rows = lambda q: (unpad(ds._ids_labels(f"{DEFAULT_IMAGE_TOKEN}\n{VTG_PROMPTS[ds.dataset]}", q)),
+                                    unpad(ds._ids_labels(f"{TVG_PROMPT}\nCaption: {q}", DEFAULT_IMAGE_TOKEN)))
+        out = open(args.output, "w") if args.output else None
+
+        def write(line):
+            print(line, flush=True)
+            if out:
+                out.write(line + "\n")
+        server = Server(gal, vids, len(vtg_ids), t2v_iv2, args, finetuned=bool(args.resume), build_rows=build_rows)
+        summary = serve(sys.stdin, write, server, args.batch_queries, args.batch_wait_ms)
+        if out:
+            out.close()
+        print(f"gallery stats: {json.dumps(gal.stats.as_dict())}", file=sys.stderr, flush=True)
+        if gal.host is not None:
+            print(f"gallery host tier: {json.dumps(dict(gal.host.stats.as_dict(), records=gal.host.n_records, record_bytes=gal.host.record_bytes))}", file=sys.stderr, flush=True)
+        print(f"serve: {json.dumps(summary)}", file=sys.stderr, flush=True)
+        gal.close()
+        model.engine.close()
+        return 0
     n_ds = len(vtg_ids) - len(args.query)
     texts = list(args.query_ids) + list(range(n_ds, len(vtg_ids)))
     names = [f"caption:{i}" for i in args.query_ids] + [f"query:{q}" for q in args.query]

@@ -45,7 +45,15 @@ cached TVG leg of one k = 16 query under `--tvg_modes attn,full`.
 the v2t TVG leg.  The two older options stay on auto under BOTH values, so that 0 is the library as it ran with them before this option existed.
 
     python tools/gallery_bench.py --narrow_qkv --modes none,full --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r19_narrow_qkv_gallery.json
-    python tools/gallery_bench.py --narrow_qkv --direction v2t --n 1000 --k 16 --synthetic_7b --out profiles/r19_narrow_qkv_v2t.json"""
+    python tools/gallery_bench.py --narrow_qkv --direction v2t --n 1000 --k 16 --synthetic_7b --out profiles/r19_narrow_qkv_v2t.json
+
+`--serve_batch B [B ...]` (t2v): the stream of Q queries x top-k through GalleryIndex.rerank_requests in groups of B, against the per-query loop
+of `python -m blim_amd.search` (one rerank() per query), the three narrow options on auto throughout, alternated `--reps` times in one process on ONE eager all-hit index:
+ms per query, pairs/s, the latency of each request when all Q are queued at once (the time its group's call returned; median and worst), the narrow kernels' launch
+counters and the packed tokens per pass.  Then a lazy index of a quarter of the gallery under `--fill lazy`'s Zipf stream: the loop, B = 1 and B = 8, a fresh index per
+repetition.  Results are checked bit-equal to the per-query loop's on every repetition.
+
+    python tools/gallery_bench.py --serve_batch 1 2 4 8 16 55 --modes none --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r20_serve.json"""
 import argparse
 import json
 import os
@@ -89,6 +97,8 @@ def main():
     ap.add_argument("--narrow_gemm", action="store_true", help="engine option narrow_gemm 0 against 1 (t2v, eager index): single-query latency, query stream, timing classes")
     ap.add_argument("--narrow_lo6", action="store_true", help="engine option narrow_lo6 0 against 1 in the compensated modes (t2v: --modes full,select; v2t: the TVG leg)")
     ap.add_argument("--narrow_qkv", action="store_true", help="engine option narrow_qkv 0 against 1, narrow_gemm and narrow_lo6 on auto throughout (t2v: --modes none,full; v2t: the TVG leg)")
+    ap.add_argument("--serve_batch", type=int, nargs="+", default=None, metavar="B",
+                    help="the query stream through GalleryIndex.rerank_requests in groups of B against the per-query loop, the three narrow options on auto (t2v)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -108,6 +118,8 @@ def main():
         return main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_qkv" if a.narrow_qkv else "narrow_lo6")
     if a.direction == "v2t":
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if a.serve_batch:
+        return main_serve(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.narrow_gemm or a.narrow_lo6 or a.narrow_qkv:
         return main_narrow(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_qkv" if a.narrow_qkv else "narrow_lo6" if a.narrow_lo6 else "narrow_gemm")
     if a.host_gb is not None:
@@ -301,6 +313,114 @@ def main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narro
         tg.close(); gal.close()
         del sc
         torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def main_serve(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    """`--serve_batch`: the stream of Q queries x top-k through GalleryIndex.rerank_requests in groups of B against the per-query loop (see the module text)."""
+    from blim_amd import engine as eng
+    e = model.engine
+    counters = {"narrow_gemm": eng.gemm_narrow_launches, "narrow_lo6": eng.gemm_narrow_lo6_launches, "narrow_qkv": eng.gemm_narrow_qkv_launches}
+    for o in counters:
+        e.set_option(o, 1)
+    med = lambda x: float(np.median(x))
+    spread = lambda x: float((max(x) - min(x)) / np.median(x))
+    Q = len(q)
+    sizes = sorted(set(min(int(b), Q) for b in a.serve_batch))
+    cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
+    reqs = [(int(t), cand[i], None) for i, t in enumerate(q)]
+    res = {"serve_batch": sizes, "n": a.n, "queries": a.queries, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc, "reps": a.reps,
+           "options": {o: 1 for o in counters}, "thresholds_tiles": {"narrow_gemm": eng.gemm_narrow_threshold(), "narrow_lo6": eng.gemm_narrow_lo6_threshold(),
+                                                                     "narrow_qkv": eng.gemm_narrow_qkv_threshold()}, "modes": {}}
+
+    def grouped(gal, items, B, stamps=None):
+        out, t0 = [], time.perf_counter()
+        for lo in range(0, len(items), B):
+            out += gal.rerank_requests(items[lo:lo + B])              # (the scores come back to the host: the call has finished when it returns)
+            if stamps is not None:
+                stamps += [time.perf_counter() - t0] * len(items[lo:lo + B])
+        return out
+
+    for mode in a.modes.split(","):
+        model.vtg_precise = None if mode == "none" else mode
+        model.clear_cache()
+        sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, torch.from_numpy(prob.video_vocab),
+                           torch.from_numpy(prob.tvg_video_labels), dims.num_clips, max_tokens=a.max_tokens)
+        sc.set_vtg_mode(model.vtg_mode())
+        sc.vtg(np.stack([np.arange(8), np.full(8, q[0])], axis=1))
+        gal = GalleryIndex(sc)
+        gal.build()
+
+        def loop():                                                      # the per-query loop of `python -m blim_amd.search` without --serve: one rerank() per query
+            return [gal.rerank([t], c[None]) for t, c, _ in reqs]
+        ref = [(o[0], b[0]) for o, b in loop()]
+        legs = ["loop"] + [f"B{B}" for B in sizes]
+        ts = {leg: [] for leg in legs}
+        lat = {leg: [] for leg in legs}
+        for B in sizes:                                                  # warm-up of every batch size's workspaces
+            grouped(gal, reqs, B)
+        for _ in range(a.reps):
+            for leg in legs:
+                stamps = []
+                if leg == "loop":
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    got = []
+                    for t, c, _ in reqs:
+                        o, b = gal.rerank([t], c[None]); got.append((o[0], b[0])); stamps.append(time.perf_counter() - t0)
+                    dt = time.perf_counter() - t0
+                else:
+                    dt, got = timed(lambda: grouped(gal, reqs, int(leg[1:]), stamps))
+                ts[leg].append(dt); lat[leg].append(stamps)
+                assert all(np.array_equal(o, o1) and np.array_equal(b, b1) for (o, b), (o1, b1) in zip(got, ref)), f"{leg}: results differ from the per-query loop"
+        r = {"eager": {}}
+        for leg in legs:
+            B = 1 if leg == "loop" else int(leg[1:])
+            n0 = {o: f() for o, f in counters.items()}
+            if leg == "loop":
+                loop()
+            else:
+                grouped(gal, reqs, B)
+            launches = {o: f() - n0[o] for o, f in counters.items()}
+            tokens = [int(sum(p.n_tokens for p in gal.iter_plans(np.concatenate([np.stack([c, np.full(len(c), t)], axis=1) for t, c, _ in reqs[lo:lo + B]]))))
+                      for lo in range(0, Q, B)]
+            worst = [max(s) for s in lat[leg]]
+            mid = [float(np.median(s)) for s in lat[leg]]
+            r["eager"][leg] = {"s": ts[leg], "ms_per_query": 1e3 * med(ts[leg]) / Q, "pairs_per_s": Q * a.k / med(ts[leg]), "spread": spread(ts[leg]),
+                               "ratio_to_loop": med(ts["loop"]) / med(ts[leg]), "latency_median_ms": 1e3 * med(mid), "latency_worst_ms": 1e3 * med(worst),
+                               "narrow_launches": launches, "passes": len(tokens), "tokens_per_pass_median": float(np.median(tokens)), "tokens_per_pass_max": int(max(tokens))}
+        # the lazy index under a quarter of the gallery, r11's Zipf stream: the per-query loop, B = 1 and B = 8; a fresh index per repetition and leg
+        per = gal.per_slot_bytes()
+        gal.close()
+        rng = np.random.RandomState(0)
+        w = 1.0 / np.arange(1, Q + 1); w /= w.sum()
+        order = rng.choice(Q, size=a.stream_draws, p=w)
+        zreqs = [reqs[i] for i in order]
+        zlegs = ["loop"] + [f"B{B}" for B in (1, 8) if B <= Q]
+        zt, zs = {leg: [] for leg in zlegs}, {}
+        for _ in range(a.reps):
+            for leg in zlegs:
+                g = GalleryIndex(sc, budget_bytes=(a.n // 4) * per, fill="lazy").build()
+                if leg == "loop":
+                    dt, got = timed(lambda: [(o[0], b[0]) for o, b in (g.rerank([t], c[None]) for t, c, _ in zreqs)])
+                else:
+                    dt, got = timed(lambda: grouped(g, zreqs, int(leg[1:])))
+                assert all(np.array_equal(o, ref[i][0]) and np.array_equal(b, ref[i][1]) for (o, b), i in zip(got, order)), f"lazy {leg}: results differ from the eager per-query loop"
+                st = g.stats.as_dict()
+                zt[leg].append(dt); zs[leg] = dict(st, hit_rate=st["hits"] / max(st["hits"] + st["misses"], 1))
+                g.close()
+        r["lazy_zipf"] = {"slots": a.n // 4, "draws": int(a.stream_draws),
+                          **{leg: dict(zs[leg], s=zt[leg], ms_per_query=1e3 * med(zt[leg]) / len(order), pairs_per_s=len(order) * a.k / med(zt[leg]), spread=spread(zt[leg]),
+                                       ratio_to_loop=med(zt["loop"]) / med(zt[leg])) for leg in zlegs}}
+        res["modes"][mode] = r
+        print(json.dumps({mode: r}), flush=True)
+        del sc
+        torch.cuda.empty_cache()
+    for o in counters:
+        e.set_option(o, 0)
     if a.out:
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
         json.dump(res, open(a.out, "w"), indent=1)
