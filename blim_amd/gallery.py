@@ -22,6 +22,10 @@ in pinned host memory, and a key that has a record gets a slot back by a copy (b
 
 An index follows its scorer: texts that join later (`PairScorer.add_texts`) append keys before the next pass is planned, and
 `GalleryIndex.rerank_requests` scores requests of unequal candidate counts as one pass.
+
+The shortlist needs no first stage on a fine-tuned checkpoint: `GalleryIndex.shortlist` ranks the whole gallery by the TVG candidate term of
+the blend (`PairScorer.tvg_gallery`: fixed chunks, so a value depends on its text and the gallery alone), `search_requests` reranks the best K with that term reused,
+in one pass with requests that name their candidates; `TextGalleryIndex.shortlist` / `rerank_shortlist` are the v2t form over the cached caption prompts.
 """
 from __future__ import annotations
 
@@ -519,6 +523,7 @@ class GalleryIndex(_PrefixIndex):
         self.keys: List[Tuple[int, bytes, bytes]] = []
         self._split_id = np.zeros(0, dtype=np.int64)
         self._sync_texts()
+        self.shortlist_stats = {"queries": 0, "passes": 0, "pairs": 0}      # texts shortlisted, stage-1 passes (one tvg_gallery each), the (text, video) pairs those scored
 
     def _count_texts(self) -> int:
         return len(self.s.vtg_split)
@@ -676,34 +681,99 @@ class GalleryIndex(_PrefixIndex):
         """rerank() for requests of unequal sizes, scored together: requests = [(text index, candidate video indices [k_q], first_stage [k_q] or None)].  The pairs of
         all requests are ONE vtg_pairs pass (one pass of a lazy index: its needed keys pinned, its misses admitted under section 12's policy) and, for fine-tuned
         checkpoints, one PairScorer.tvg call and one prior lookup; the blend is rerank()'s, per request.  A VTG score does not depend on what shares its call, so the
-        query likelihood is bit for bit that of rerank() per request.  -> [(order [k_q], blended [k_q])] in request order."""
-        reqs = [(int(t), np.asarray(cand, dtype=np.int64).reshape(-1), fs) for t, cand, fs in requests]
+        query likelihood is bit for bit that of rerank() per request.  -> [(order [k_q], blended [k_q])] in request order.  (search_requests with no shortlist request.)"""
+        reqs = [(t, cand, fs, None) for t, cand, fs in requests]
+        if any(len(np.asarray(cand).reshape(-1)) == 0 for _, cand, _, _ in reqs):
+            raise ValueError("rerank_requests: a request has no candidates")
+        return self.search_requests(reqs, cpn=cpn, alpha=alpha, c=c, finetuned=finetuned)
+
+    # ---- the shortlist (DESIGN.md section 18): the gallery ranked by the TVG candidate term, the best K reranked
+    def _stage1(self, texts, cpn: bool, alpha) -> np.ndarray:
+        """-> [Q, N]: the candidate term of rerank()'s fine-tuned blend for every video of the gallery -- PairScorer.tvg_gallery (one pass for all texts), minus
+        alpha[0] x the candidate prior with cpn.  A text without a TVG row is refused by name."""
+        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
+        self.s._need_tvg(texts)
+        self._tvg_state()
+        N = len(self.s.video)
+        stage = self.s.tvg_gallery(texts)
+        st = self.shortlist_stats
+        st["queries"] += len(texts); st["passes"] += 1; st["pairs"] += len(np.unique(texts)) * N
+        if cpn:
+            stage = stage - alpha[0] * self._t2v_prior(texts, np.tile(np.arange(N), (len(texts), 1)))
+        return stage
+
+    @staticmethod
+    def _best(stage: np.ndarray, k: int):
+        """One text's stage-1 row [N] -> (the best min(k, N) videos, their values): descending, ties to the lower video index."""
+        order = np.argsort(-stage, kind="stable")[:max(min(int(k), len(stage)), 0)]
+        return order.astype(np.int64), stage[order]
+
+    def shortlist(self, texts, k: int, cpn: bool = False, alpha=(0.0, 0.0)):
+        """The whole gallery ranked by the TVG candidate term of each text: -> (cand [Q, min(k, N)] video indices, best first; their stage-1 scores)."""
+        if int(k) < 1:
+            raise ValueError(f"shortlist: k = {k}: at least one video")
+        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
+        stage = self._stage1(texts, cpn, alpha)
+        best = [self._best(row, k) for row in stage]
+        k = min(int(k), stage.shape[1])
+        return (np.stack([b[0] for b in best]) if best else np.zeros((0, k), np.int64),
+                np.stack([b[1] for b in best]) if best else np.zeros((0, k), stage.dtype))
+
+    def search_requests(self, requests, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0), finetuned: bool = False):
+        """rerank_requests() with requests that may take their candidates from the shortlist: requests = [(text index, candidate video indices [k_q] or None,
+        first_stage [k_q] or None, shortlist K or None)], exactly one of candidates and K per request.  A request with candidates is rerank_requests' (its TVG term
+        one PairScorer.tvg call over the explicit requests' pairs).  The shortlist requests of the batch share ONE stage-1 pass (_stage1) over the whole gallery;
+        each keeps its best K videos as candidates, its first-stage term is zero, and the TVG candidate term of its blend IS its stage-1 value: it is not computed a
+        second time.  All requests then share ONE vtg_pairs pass (one pass of a lazy index).  -> [(order [k_q], blended [k_q])] in request order."""
+        reqs = []
+        for t, cand, fs, K in requests:
+            if (cand is None) == (K is None):
+                raise ValueError("search_requests: a request takes candidates or a shortlist K, one of the two")
+            if K is not None:
+                if isinstance(K, bool) or int(K) != K or int(K) < 1:
+                    raise ValueError(f"search_requests: shortlist K = {K!r}: a positive integer")
+                if fs is not None:
+                    raise ValueError("search_requests: a first stage is parallel to a request's candidates; a shortlist request has none")
+                reqs.append([int(t), None, None, int(K)])
+            else:
+                cand = np.asarray(cand, dtype=np.int64).reshape(-1)
+                if len(cand) == 0:
+                    raise ValueError("search_requests: a request has no candidates")
+                reqs.append([int(t), cand, fs, None])
         if not reqs:
             return []
-        if any(len(cand) == 0 for _, cand, _ in reqs):
-            raise ValueError("rerank_requests: a request has no candidates")
-        pairs = np.concatenate([np.stack([cand, np.full(len(cand), t, dtype=np.int64)], axis=1) for t, cand, _ in reqs])
-        ends = np.cumsum([len(cand) for _, cand, _ in reqs])
+        short = [n for n, r in enumerate(reqs) if r[3] is not None]
+        stage1 = {}
+        if short:
+            if not finetuned:
+                raise ValueError("search_requests: a shortlist ranks by the TVG likelihood, which a zero-shot model does not have (finetuned=False)")
+            for n, row in zip(short, self._stage1([reqs[n][0] for n in short], cpn, alpha)):
+                reqs[n][1], stage1[n] = self._best(row, reqs[n][3])
+        pairs = np.concatenate([np.stack([cand, np.full(len(cand), t, dtype=np.int64)], axis=1) for t, cand, _, _ in reqs])
+        ends = np.cumsum([len(cand) for _, cand, _, _ in reqs])
         ql = np.split(self.vtg_pairs(pairs), ends[:-1])
-        t2v_cand = None
-        if finetuned:
+        given = [n for n, r in enumerate(reqs) if r[3] is None]
+        t2v_cand = dict(stage1)
+        if finetuned and given:
             self._tvg_state()
-            has = np.array([self.s.tvg_split[t] is not None for t, _, _ in reqs])
+            sub = [reqs[n] for n in given]
+            sub_pairs = np.concatenate([np.stack([cand, np.full(len(cand), t, dtype=np.int64)], axis=1) for t, cand, _, _ in sub])
+            has = np.array([self.s.tvg_split[t] is not None for t, _, _, _ in sub])
             if c[0] != 1:                                               # the candidate likelihood has a weight: every text needs its TVG row
-                self.s._need_tvg([t for t, _, _ in reqs])
-            of = np.repeat(has, [len(cand) for _, cand, _ in reqs])    # (a text added without a TVG row keeps a zero term under c0 = 1)
-            t2v_cand = np.zeros(len(pairs), dtype=np.float32)
+                self.s._need_tvg([t for t, _, _, _ in sub])
+            of = np.repeat(has, [len(cand) for _, cand, _, _ in sub])  # (a text added without a TVG row keeps a zero term under c0 = 1)
+            term = np.zeros(len(sub_pairs), dtype=np.float32)
             if of.any():
-                t2v_cand[of] = self.s.tvg(pairs[of])
+                term[of] = self.s.tvg(sub_pairs[of])
             if cpn and of.any():
-                prior = np.zeros(len(pairs))
-                prior[of] = self._t2v_prior([t for (t, _, _), h in zip(reqs, has) if h], [cand for (_, cand, _), h in zip(reqs, has) if h])
-                t2v_cand = t2v_cand - alpha[0] * prior
-            t2v_cand = np.split(t2v_cand, ends[:-1])
+                prior = np.zeros(len(sub_pairs))
+                prior[of] = self._t2v_prior([t for (t, _, _, _), h in zip(sub, has) if h], [cand for (_, cand, _, _), h in zip(sub, has) if h])
+                term = term - alpha[0] * prior
+            t2v_cand.update(zip(given, np.split(term, np.cumsum([len(cand) for _, cand, _, _ in sub])[:-1])))
         out = []
-        for n, (t, cand, fs) in enumerate(reqs):
+        for n, (t, cand, fs, _) in enumerate(reqs):
             fs = np.zeros(cand.shape) if fs is None else np.asarray(fs).reshape(cand.shape)
-            order, blended = self._blend(cand[None], ql[n][None], np.zeros((1, len(cand))) if t2v_cand is None else t2v_cand[n][None], fs[None], c)
+            order, blended = self._blend(cand[None], ql[n][None], t2v_cand[n][None] if n in t2v_cand else np.zeros((1, len(cand))), fs[None], c)
             out.append((order[0], blended[0]))
         return out
 
@@ -840,5 +910,36 @@ class TextGalleryIndex(_PrefixIndex):
         _, c1, _, c3 = c
         v2t_lm = c1 * self.tvg_pairs(pairs).reshape(cand.shape) + (1 - c1) * v2t_cand if finetuned else v2t_cand
         blended = c3 * v2t_lm + (1 - c3) * fs
+        order = np.argsort(-blended, axis=1, kind="stable")
+        return np.take_along_axis(cand, order, 1), np.take_along_axis(blended, order, 1)
+
+    # ---- the shortlist, v2t
+    def shortlist(self, videos, k: int):
+        """Every caption ranked by a query video's TVG likelihood, log P(video | text), over the cached prompts: one tvg_pairs pass per query video, so every text has
+        one video and a value is that of any other pass that scores the pair so (section 11).  Descending, ties to the lower text index.
+        -> (cand [Q, min(k, texts)] text indices, best first; their stage-1 scores)."""
+        if int(k) < 1:
+            raise ValueError(f"shortlist: k = {k}: at least one text")
+        videos = np.asarray(videos, dtype=np.int64).reshape(-1)
+        n = len(self.s.tvg_split)
+        k = min(int(k), n)
+        cand, stage = np.zeros((len(videos), k), np.int64), np.zeros((len(videos), k), np.float32)
+        for q, v in enumerate(videos):
+            row = self.tvg_pairs(np.stack([np.full(n, v, dtype=np.int64), np.arange(n)], axis=1))
+            order = np.argsort(-row, kind="stable")[:k]
+            cand[q], stage[q] = order, row[order]
+        return cand, stage
+
+    def rerank_shortlist(self, videos, k: int, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0)):
+        """rerank(videos, shortlist(videos, k), finetuned=True) without a first stage, the query likelihood of the blend being the shortlist's stage-1 value: the TVG
+        term is not computed a second time.  -> (order [Q, k] of text ids, best first; blended scores in that order)."""
+        videos = np.asarray(videos, dtype=np.int64).reshape(-1)
+        cand, stage = self.shortlist(videos, k)
+        pairs = np.stack([np.repeat(videos, cand.shape[1]), cand.reshape(-1)], axis=1)
+        v2t_cand = self.vtg_pairs(pairs).reshape(cand.shape)
+        if cpn:
+            v2t_cand = v2t_cand - alpha[1] * self.v2t_prior(videos, cand)
+        _, c1, _, c3 = c
+        blended = c3 * (c1 * stage + (1 - c1) * v2t_cand) + (1 - c3) * np.zeros(cand.shape)
         order = np.argsort(-blended, axis=1, kind="stable")
         return np.take_along_axis(cand, order, 1), np.take_along_axis(blended, order, 1)

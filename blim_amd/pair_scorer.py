@@ -527,6 +527,79 @@ class PairScorer(CalibrationMixin):
                         st.add_pair(rows, np.array([self.tvg_video_labels[int(pairs[idx, 0])]], np.int32), np.array([base + idx]))
                     pos_in += n
 
+    # ---- one text against the WHOLE gallery (the shortlist's stage 1)
+    def gallery_chunk(self) -> int:
+        """Videos per merged sequence of the whole-gallery planner: the bound of _plan_tvg's merged sequences."""
+        return SEG_MAX // max(self.num_clips - 1, 1)
+
+    def gallery_feats(self):
+        """The TVG feature rows of every video as ONE device tensor [N * C, Hw], video j's rows at j * C as video_feat(j, True) lays them out (its own values:
+        a concatenation).  Built once per (weights version, split_tvg) and dropped when either changes; a call of iter_tvg_gallery names it as its feature rows."""
+        import torch
+        key = (getattr(self.engine, "weights_version", None), bool(self.split_tvg))
+        memo = getattr(self, "_gfeat", None)
+        if memo is None or memo[0] != key:
+            N, C = len(self.video), self.num_clips
+            self.expect(np.arange(N), True)
+            rows = [self.video_feat(j, True) for j in range(N)]
+            if any(int(r.shape[0]) != C for r in rows):
+                raise ValueError(f"tvg_gallery: every video must project to num_clips = {C} TVG rows")
+            memo = self._gfeat = (key, torch.cat(rows, dim=0))
+        return memo[1]
+
+    def iter_tvg_gallery(self, texts, chunk: Optional[int] = None):
+        """texts [Q] (text indices) against every video of the scorer: the engine calls of log P(video j | text), output slot of (texts[q], video j) = q * N + j.
+        The likelihood branch of _plan_tvg with two differences.  FIXED CHUNKS: a text's videos are cut into merged sequences of exactly `chunk` videos (default
+        SEG_MAX // max(C - 1, 1); the last one shorter) whatever else shares the call, and a chunk that does not fit the call starts a new one -- a TVG score moves
+        with its neighbours in the merged sequence, so with fixed cuts it depends on its text and the gallery alone.  NO PER-VIDEO PYTHON:
+        the feature rows are gallery_feats(), added once per call, and a chunk's tokens, positions, own_start, rows, labels and output slots are array expressions
+        -- the host cost of a text is O(chunks).  Row conventions are _plan_tvg's: the prompt packed once per call, each pair's first row the prompt's last row."""
+        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
+        C, N = self.num_clips, len(self.video)
+        chunk = self.gallery_chunk() if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"tvg_gallery: chunk = {chunk}: at least one video per merged sequence")
+        if not len(texts) or not N:
+            return
+        self._need_tvg(texts)
+        longest = max(len(self.tvg_split[int(i)]) for i in texts)
+        if longest + min(chunk, N) * (C - 1) > self.max_tokens:
+            raise ValueError(f"tvg_gallery: max_tokens = {self.max_tokens} cannot hold one caption prompt ({longest} tokens) and one chunk of {min(chunk, N)} videos "
+                             f"({min(chunk, N) * (C - 1)} tokens)")
+        feats = self.gallery_feats()
+        clip = np.arange(C - 1)
+        st = _GalleryCall(self, feats)
+        for q, i in enumerate(texts):
+            pr = self.tvg_split[int(i)]
+            plen = len(pr)
+            p0 = None
+            for v0 in range(0, N, chunk):
+                n = min(chunk, N - v0)
+                if st.n_tok and st.n_tok + (plen if p0 is None else 0) + n * (C - 1) > self.max_tokens:
+                    yield st.finish(); st = _GalleryCall(self, feats); p0 = None
+                if p0 is None:                           # the prompt is packed once per engine call; every merged sequence of the text names it
+                    p0 = st.add_seq(pr, np.arange(plen), None, (0, 0))
+                v = np.arange(v0, v0 + n)
+                rows = np.full((n, C), p0 + plen - 1, np.int64)
+                if C > 1:
+                    s0 = st.add_seq(-(1 + v[:, None] * C + clip[None, :]).reshape(-1), np.tile(plen + clip, n), np.repeat(np.arange(n) * (C - 1), C - 1), (p0, plen))
+                    rows[:, 1:] = s0 + np.arange(n)[:, None] * (C - 1) + clip[None, :]
+                st.add_pairs(rows, self.tvg_video_labels[v], q * N + v)
+        if st.n_pairs:
+            yield st.finish()
+
+    def tvg_gallery(self, texts, chunk: Optional[int] = None) -> np.ndarray:
+        """log P(video j | text) of each text against every video -> f32 [Q, N] in video-index order.  Each distinct text is planned once, in ascending index
+        order (iter_tvg_gallery); a value does not depend on which texts are asked for together, in which order, or on where max_tokens cuts the calls."""
+        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
+        N = len(self.video)
+        uniq, inv = np.unique(texts, return_inverse=True)
+        out = np.full(len(uniq) * N, np.nan, dtype=np.float32)
+        done = [(p.out_index, self.run(p)) for p in self.iter_tvg_gallery(uniq, chunk)]
+        for out_index, r in done:
+            out[out_index[:, 0]] = r.float().cpu().numpy()
+        return out.reshape(len(uniq), N)[inv.reshape(-1)]
+
     # ---- execution (device) ---------------------------------------------------------------------
     @contextmanager
     def _call_options(self, kind: str):
@@ -732,3 +805,39 @@ class _PackState:
                     out_index=self.out_index, n_tokens=self.n_tok, n_rows=len(self.rows),
                     pfx_slot=t(self.slot) if cached else None, slots_used=np.array(sorted(self.used), dtype=np.int32) if cached else None,
                     admits=admits, prefix_tokens=n_prefix_tok if cached else 0)
+
+
+class _GalleryCall:
+    """One engine call of PairScorer.iter_tvg_gallery: whole sequences and whole chunks of pairs are added as arrays, then uploaded once.  The feature rows are the
+    scorer's gallery_feats(), named by every call as they are (video j's rows at j * C), so nothing is gathered or copied per call."""
+
+    def __init__(self, scorer: PairScorer, feats):
+        self.s, self.feats = scorer, feats
+        self.tok: List[np.ndarray] = []; self.pos: List[np.ndarray] = []; self.own: List[np.ndarray] = []
+        self.seq_start: List[int] = []; self.seq_len: List[int] = []; self.pfx_start: List[int] = []; self.pfx_len: List[int] = []
+        self.rows: List[np.ndarray] = []; self.labels: List[np.ndarray] = []; self.out: List[np.ndarray] = []
+        self.n_tok = 0; self.n_pairs = 0
+
+    def add_seq(self, toks, pos, own_start, prefix) -> int:
+        start = self.n_tok
+        self.tok.append(np.asarray(toks, np.int64)); self.pos.append(np.asarray(pos, np.int64))
+        self.own.append(np.zeros(len(toks), np.int32) if own_start is None else np.asarray(own_start, np.int32))
+        self.seq_start.append(start); self.seq_len.append(len(toks))
+        self.pfx_start.append(prefix[0]); self.pfx_len.append(prefix[1])
+        self.n_tok += len(toks)
+        return start
+
+    def add_pairs(self, rows, labels, outs) -> None:
+        """A chunk's pairs: rows [n, C], labels [n], output slots [n]."""
+        self.rows.append(rows.reshape(-1)); self.labels.append(np.asarray(labels, np.int32)); self.out.append(np.asarray(outs, np.int64))
+        self.n_pairs += len(outs)
+
+    def finish(self) -> Plan:
+        import torch
+        dev = self.s.device
+        batch = PackedBatch(np.concatenate(self.pos), np.ones(self.n_tok, np.uint8), np.array(self.seq_start), np.array(self.seq_len),
+                            np.array(self.pfx_start), np.array(self.pfx_len), device=dev, own_start=np.concatenate(self.own))
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        rows = np.concatenate(self.rows)
+        return Plan(kind="tvg", batch=batch, src_index=t(np.concatenate(self.tok)), feats=self.feats, rows=t(rows), labels=t(np.concatenate(self.labels)),
+                    row_start=None, n_pairs=self.n_pairs, out_index=np.concatenate(self.out)[:, None], n_tokens=self.n_tok, n_rows=len(rows))

@@ -2,7 +2,12 @@
 
 The gallery is the dataset's test videos; their VTG prefixes are computed once (GalleryIndex.build) and every query is scored on its own response tokens.  Queries
 are test captions (`--query_ids`) and / or free text (`--query TEXT`, tokenised by the dataset's own prompt builder: needs the real tokenizer).  `--candidates iv2`
-takes each dataset query's top-k of the first-stage t2v row, `--candidates all` scores the whole gallery.  One JSON line per query: the ranked video ids and their
+takes each dataset query's top-k of the first-stage t2v row, `--candidates all` scores the whole gallery.  `--candidates tvg` (fine-tuned checkpoints: `--resume`;
+DESIGN.md section 18) needs no first stage: the whole gallery is ranked by the TVG candidate term of the blend, log P(video | text) (minus alpha[0] x its prior with
+`--cpn`; PairScorer.tvg_gallery, the caption prompt once and num_clips - 1 clip tokens per video), the best `--shortlist K` (default `--topk`) are reranked with that
+term reused and a zero first-stage term, the best `--topk` of them are printed, the JSON line gains `"shortlisted": K`, and a `shortlist:` stderr line at the end
+counts the queries, the stage-1 passes and their pairs.  It serves `--query`, `--query_ids` and, under `--direction v2t`, `--video_ids` (there the captions are
+ranked by the query likelihood over the cached prompts: TextGalleryIndex.shortlist).  One JSON line per query: the ranked video ids and their
 blended t2v scores (training_utils.combine_and_rank's t2v half: `--cpn --alpha --c`; zero-shot runs blend the query likelihood with the first stage only).
 `--synthetic N [--synthetic_7b]`: a dry run on synth.make_problem, as main.py's.  `--gallery_fill lazy` computes no prefix up front: the first query runs at once, its
 calls leave their videos' prefixes in the cache, and `--gallery_gb` is the cache's capacity.  The `gallery stats:` stderr line reports the hits
@@ -18,11 +23,15 @@ writes one JSON line per request to stdout, in arrival order.  A request: `id` (
 (free text through the dataset's prompt builder, as `--query`; refused per request under `--synthetic`) and `rows` ({"vtg_ids", "vtg_labels"[, "tvg_ids",
 "tvg_labels"]}, raw token rows); optionally `candidates` (video ids as printed in `videos`) or `candidate_idx` (indices), `first_stage` (floats, parallel to the
 candidates) and `topk` (truncates the answer).  Without candidates a `caption` request takes `--candidates` (`iv2`: its top-`--topk` of the first stage; `all`: the
-gallery); a `text` / `rows` request takes the whole gallery under `all` and gets an error line under `iv2`.  The answer is {"id", "query", "videos", "scores"} or
+gallery; `tvg`: the shortlist); a `text` / `rows` request takes the whole gallery under `all`, the shortlist under `tvg`, and gets an error line under `iv2`.  A
+request may carry `"shortlist": K` itself, under any `--candidates`: its candidates are the best K of the gallery's TVG ranking and its answer gains
+`"shortlisted": K`; with `candidates` / `candidate_idx` or `first_stage`, a K that is no positive integer, a query without a TVG row, or a model without `--resume` it
+gets an error line.  The answer is {"id", "query", "videos", "scores"} or
 {"id", "error"}: a bad request (malformed JSON, an unknown video id, an empty or duplicate candidate list, a row that fails PairScorer.add_texts' checks or leaves no
 response token under tokenizer_model_max_length, a fine-tuned blend with c0 < 1 for rows without a TVG row) gets its error line and the process goes on.
 `--batch_queries B` / `--batch_wait_ms W`: a reader thread queues the lines; the loop takes what is waiting, up to B requests, waits at most W ms for more only while
-fewer are there, and scores the batch as ONE pass (GalleryIndex.rerank_requests) -- the same scores as one pass per request, bit for bit on the VTG term.  Texts join the
+fewer are there, and scores the batch as ONE pass (GalleryIndex.search_requests: the shortlist requests of a batch share one stage-1 pass, all requests one VTG pass)
+-- the same scores as one pass per request, bit for bit on the VTG term and on a shortlist's stage 1.  Texts join the
 scorer at run time (PairScorer.add_texts); identical `text` / `rows` queries share one text index.  At EOF a `serve:` stderr line counts requests, batches, the mean
 batch size, errors and texts added.
 """
@@ -57,7 +66,10 @@ def get_args_parser():
     p.add_argument("--query", default=[], type=str, action="append", help="a free-text query (repeatable)")
     p.add_argument("--direction", default="t2v", choices=["t2v", "v2t"], help="t2v: text queries over the videos; v2t: video queries (--video_ids) over the captions")
     p.add_argument("--video_ids", default=[], type=int, nargs="*", help="test videos (indices) used as queries (--direction v2t)")
-    p.add_argument("--candidates", default="iv2", choices=["iv2", "all"])
+    p.add_argument("--candidates", default="iv2", choices=["iv2", "all", "tvg"],
+                   help="iv2: the first stage's top --topk; all: the whole gallery; tvg (fine-tuned checkpoints, --resume): the whole gallery ranked by the TVG likelihood, "
+                        "the best --shortlist reranked")
+    p.add_argument("--shortlist", default=None, type=int, metavar="K", help="--candidates tvg: candidates kept from the TVG ranking of the gallery (default: --topk)")
     p.add_argument("--gallery_gb", default=None, type=float, help="device memory for the prefix cache (default: every video)")
     p.add_argument("--text_gallery_gb", default=None, type=float, help="v2t: device memory for the caption-prompt cache (default: every distinct prompt)")
     p.add_argument("--gallery_fill", default="eager", choices=["eager", "lazy"],
@@ -87,6 +99,12 @@ def get_args_parser():
     p.add_argument("--batch_queries", default=1, type=int, help="--serve: up to this many waiting requests are scored in one pass")
     p.add_argument("--batch_wait_ms", default=0.0, type=float, help="--serve: with fewer than --batch_queries requests waiting, wait at most this long for more")
     return p
+
+
+def shortlist_k(args) -> int:
+    """--candidates tvg: the candidates kept from the TVG ranking (--shortlist, default --topk)."""
+    k = getattr(args, "shortlist", None)
+    return int(args.topk if k is None else k)
 
 
 def check_args(args, world: int = 1) -> None:
@@ -135,6 +153,13 @@ def check_args(args, world: int = 1) -> None:
         raise SystemExit("search: free-text queries have no first-stage row: use --candidates all")
     if args.query and args.synthetic:
         raise SystemExit("search: free-text queries need the dataset's tokenizer (not --synthetic)")
+    if args.candidates == "tvg" and not args.resume:
+        raise SystemExit("search: --candidates tvg needs a fine-tuned checkpoint (--resume): a zero-shot model's visual head is untrained, so it has no TVG likelihood to "
+                         "rank the gallery by")
+    if getattr(args, "shortlist", None) is not None and args.candidates != "tvg":
+        raise SystemExit("search: --shortlist is the number of candidates --candidates tvg keeps (give --candidates tvg)")
+    if args.candidates == "tvg" and shortlist_k(args) < 1:
+        raise SystemExit("search: --shortlist must be at least 1 (it defaults to --topk)")
     if len(args.c) != 4 or len(args.alpha) != 2:
         raise SystemExit("search: --c takes 4 values, --alpha 2")
     if v2t and args.c[3] == 0:
@@ -212,10 +237,17 @@ class Server:
         return t, (f"query:{req['text']}" if "text" in req else f"rows:{t}")
 
     def _candidates(self, req, t: int, is_caption: bool):
-        """-> (candidate video indices, first-stage scores or None)."""
+        """-> (candidate video indices, first-stage scores or None, None), or (None, None, K): the candidates are the best K of the gallery's TVG ranking."""
         np = self.np
         N = len(self.vids)
         fs = None
+        if "shortlist" in req:
+            K = req["shortlist"]
+            if "candidates" in req or "candidate_idx" in req:
+                raise BadRequest("shortlist ranks the whole gallery: give shortlist or candidates / candidate_idx, not both")
+            if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+                raise BadRequest("shortlist must be a positive integer")
+            return self._shortlisted(req, t, K)
         if "candidates" in req and "candidate_idx" in req:
             raise BadRequest("give candidates (video ids) or candidate_idx (indices), not both")
         if "candidates" in req or "candidate_idx" in req:
@@ -234,6 +266,8 @@ class Server:
             if len(set(cand)) != len(cand):
                 raise BadRequest("the candidate list names a video twice")
             cand = np.asarray(cand, dtype=np.int64)
+        elif self.args.candidates == "tvg":
+            return self._shortlisted(req, t, shortlist_k(self.args))
         elif self.args.candidates == "iv2":
             if not is_caption:
                 raise BadRequest("a text / rows query has no first-stage row (--candidates iv2): send candidates")
@@ -251,10 +285,20 @@ class Server:
                 raise BadRequest("first_stage must hold numbers") from None
             if len(fs) != len(cand) or not np.all(np.isfinite(fs)):
                 raise BadRequest("first_stage must hold one finite number per candidate")
-        return cand, fs
+        return cand, fs, None
+
+    def _shortlisted(self, req, t: int, K: int):
+        """A request whose candidates are the best K videos of the gallery's TVG ranking (GalleryIndex.search_requests): what that needs, checked here."""
+        if not self.finetuned:
+            raise BadRequest("a shortlist ranks the gallery by the TVG likelihood of a fine-tuned checkpoint (--resume): this model has none")
+        if self.s.tvg_split[t] is None:
+            raise BadRequest("a shortlist needs the query's TVG row (rows without tvg_ids / tvg_labels have none)")
+        if "first_stage" in req:
+            raise BadRequest("first_stage is parallel to the candidates: a shortlist request names none")
+        return None, None, int(K)
 
     def parse(self, line: str):
-        """One request line -> a dict(id, query, text, cand, fs, topk); BadRequest (with .id, as far as it was read) for a request that gets an error line."""
+        """One request line -> a dict(id, query, text, cand, fs, topk, shortlist: K with cand None, or None); BadRequest (with .id, as far as it was read) for a request that gets an error line."""
         rid = None
         try:
             try:
@@ -271,14 +315,14 @@ class Server:
             if topk is not None and (isinstance(topk, bool) or not isinstance(topk, int) or topk < 1):
                 raise BadRequest("topk must be a positive integer")
             t, name = self._text(req)
-            cand, fs = self._candidates(req, t, "caption" in req)
+            cand, fs, shortlist = self._candidates(req, t, "caption" in req)
             pre, post, resp = self.s.vtg_split[t]
             limit = getattr(self.s, "max_row_len", None)
-            if limit is not None and len(pre) + int(self.n_vid[cand].max()) + len(post) >= limit:
+            if limit is not None and len(pre) + int((self.n_vid if cand is None else self.n_vid[cand]).max()) + len(post) >= limit:
                 raise BadRequest(f"tokenizer_model_max_length = {limit} leaves no response token of this query after a candidate's video tokens")
             if self.finetuned and self.args.c[0] < 1 and self.s.tvg_split[t] is None:
                 raise BadRequest("a fine-tuned blend with c0 < 1 needs the query's TVG row (rows without tvg_ids / tvg_labels have none)")
-            return {"id": rid, "query": name, "text": t, "cand": cand, "fs": fs, "topk": topk}
+            return {"id": rid, "query": name, "text": t, "cand": cand, "fs": fs, "topk": topk, "shortlist": shortlist}
         except BadRequest as e:
             e.id = rid
             raise
@@ -286,10 +330,10 @@ class Server:
     # ---- one batch
     def _score(self, reqs):
         a = self.args
-        return self.gal.rerank_requests([(r["text"], r["cand"], r["fs"]) for r in reqs], cpn=a.cpn, alpha=a.alpha, c=a.c, finetuned=self.finetuned)
+        return self.gal.search_requests([(r["text"], r["cand"], r["fs"], r["shortlist"]) for r in reqs], cpn=a.cpn, alpha=a.alpha, c=a.c, finetuned=self.finetuned)
 
     def handle(self, lines, write) -> None:
-        """The requests that arrived together: every good one is scored in ONE rerank_requests pass; one answer line per request, in arrival order."""
+        """The requests that arrived together: every good one is scored in ONE search_requests pass; one answer line per request, in arrival order."""
         lines = [ln for ln in lines if ln.strip()]
         if not lines:
             return
@@ -322,7 +366,8 @@ class Server:
                 continue
             order, blended = res
             k = len(order) if r["topk"] is None else min(r["topk"], len(order))
-            write(json.dumps({"id": r["id"], "query": r["query"], "videos": [self.vids[int(j)] for j in order[:k]], "scores": [float(x) for x in blended[:k]]}))
+            more = {} if r["shortlist"] is None else {"shortlisted": r["shortlist"]}
+            write(json.dumps({"id": r["id"], "query": r["query"], "videos": [self.vids[int(j)] for j in order[:k]], "scores": [float(x) for x in blended[:k]], **more}))
 
     def summary(self):
         return {"requests": self.requests, "batches": self.batches, "mean_batch": self.requests / self.batches if self.batches else 0.0, "errors": self.errors,
@@ -471,6 +516,8 @@ def main(args):
         if gal.host is not None:
             print(f"gallery host tier: {json.dumps(dict(gal.host.stats.as_dict(), records=gal.host.n_records, record_bytes=gal.host.record_bytes))}", file=sys.stderr, flush=True)
         print(f"serve: {json.dumps(summary)}", file=sys.stderr, flush=True)
+        if gal.shortlist_stats["passes"]:
+            print(f"shortlist: {json.dumps(_shortlist_line(gal.shortlist_stats))}", file=sys.stderr, flush=True)
         gal.close()
         model.engine.close()
         return 0
@@ -482,26 +529,39 @@ def main(args):
     finetuned = bool(args.resume)
     out = open(args.output, "w") if args.output else None
     for t, name in zip(texts, names):
-        if args.candidates == "iv2":
-            row = np.asarray(t2v_iv2[t], dtype=np.float32)
-            cand = np.argsort(-row, kind="stable")[:k][None]
-            fs = row[cand]
+        more = {}
+        if args.candidates == "tvg":              # the gallery ranked by the TVG candidate term, the best K reranked; the answer is the best --topk of those
+            K = shortlist_k(args)
+            (o, b), = gal.search_requests([(t, None, None, K)], cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
+            order, blended, more = o[None, :k], b[None, :k], {"shortlisted": K}
         else:
-            cand = np.arange(N)[None]
-            fs = None if t2v_iv2 is None else np.asarray(t2v_iv2[t], dtype=np.float32)[cand] if t < n_ds else None
-        order, blended = gal.rerank([t], cand, first_stage=fs, cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
-        line = json.dumps({"query": name, "videos": [vids[int(j)] for j in order[0]], "scores": [float(x) for x in blended[0]]})
+            if args.candidates == "iv2":
+                row = np.asarray(t2v_iv2[t], dtype=np.float32)
+                cand = np.argsort(-row, kind="stable")[:k][None]
+                fs = row[cand]
+            else:
+                cand = np.arange(N)[None]
+                fs = None if t2v_iv2 is None else np.asarray(t2v_iv2[t], dtype=np.float32)[cand] if t < n_ds else None
+            order, blended = gal.rerank([t], cand, first_stage=fs, cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
+        line = json.dumps({"query": name, "videos": [vids[int(j)] for j in order[0]], "scores": [float(x) for x in blended[0]], **more})
         print(line, flush=True)
         if out:
             out.write(line + "\n")
     if out:
         out.close()
     print(f"gallery stats: {json.dumps(gal.stats.as_dict())}", file=sys.stderr, flush=True)
+    if gal.shortlist_stats["passes"]:
+        print(f"shortlist: {json.dumps(_shortlist_line(gal.shortlist_stats))}", file=sys.stderr, flush=True)
     if gal.host is not None:
         print(f"gallery host tier: {json.dumps(dict(gal.host.stats.as_dict(), records=gal.host.n_records, record_bytes=gal.host.record_bytes))}", file=sys.stderr, flush=True)
     gal.close()
     model.engine.close()
     return 0
+
+
+def _shortlist_line(stats):
+    """The `shortlist:` stderr line: queries shortlisted, stage-1 passes and the pairs those scored."""
+    return {"queries": int(stats["queries"]), "stage1_passes": int(stats["passes"]), "stage1_pairs": int(stats["pairs"])}
 
 
 def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) -> int:
@@ -526,21 +586,31 @@ def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) 
         raise SystemExit(f"search: --video_ids {bad} outside 0 .. {n_videos - 1}")
     k = min(args.topk, n_texts)
     out = open(args.output, "w") if args.output else None
+    shortlisted = {"queries": 0, "passes": 0, "pairs": 0}
     for v in args.video_ids:
-        if args.candidates == "iv2":
-            row = np.asarray(v2t_iv2[v], dtype=np.float32)
-            cand = np.argsort(-row, kind="stable")[:k][None]
-            fs = row[cand]
+        more = {}
+        if args.candidates == "tvg":              # the captions ranked by the query likelihood over the cached prompts, the best K reranked
+            K = shortlist_k(args)
+            order, blended = tg.rerank_shortlist([v], K, cpn=args.cpn, alpha=args.alpha, c=args.c)
+            order, blended, more = order[:, :k], blended[:, :k], {"shortlisted": K}
+            shortlisted = {"queries": shortlisted["queries"] + 1, "passes": shortlisted["passes"] + 1, "pairs": shortlisted["pairs"] + n_texts}
         else:
-            cand = np.arange(n_texts)[None]
-            fs = None if v2t_iv2 is None else np.asarray(v2t_iv2[v], dtype=np.float32)[cand]
-        order, blended = tg.rerank([v], cand, first_stage=fs, cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
-        line = json.dumps({"query": f"video:{vids[v]}", "texts": [int(i) for i in order[0]], "scores": [float(x) for x in blended[0]]})
+            if args.candidates == "iv2":
+                row = np.asarray(v2t_iv2[v], dtype=np.float32)
+                cand = np.argsort(-row, kind="stable")[:k][None]
+                fs = row[cand]
+            else:
+                cand = np.arange(n_texts)[None]
+                fs = None if v2t_iv2 is None else np.asarray(v2t_iv2[v], dtype=np.float32)[cand]
+            order, blended = tg.rerank([v], cand, first_stage=fs, cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
+        line = json.dumps({"query": f"video:{vids[v]}", "texts": [int(i) for i in order[0]], "scores": [float(x) for x in blended[0]], **more})
         print(line, flush=True)
         if out:
             out.write(line + "\n")
     if out:
         out.close()
+    if shortlisted["passes"]:
+        print(f"shortlist: {json.dumps(_shortlist_line(shortlisted))}", file=sys.stderr, flush=True)
     print(f"gallery stats: {json.dumps(gal.stats.as_dict())}; text gallery stats: {json.dumps(tg.stats.as_dict())}", file=sys.stderr, flush=True)
     tiers = [(name, ix.host) for name, ix in (("gallery", gal), ("text gallery", tg)) if ix.host is not None]
     if tiers:

@@ -53,7 +53,16 @@ ms per query, pairs/s, the latency of each request when all Q are queued at once
 counters and the packed tokens per pass.  Then a lazy index of a quarter of the gallery under `--fill lazy`'s Zipf stream: the loop, B = 1 and B = 8, a fresh index per
 repetition.  Results are checked bit-equal to the per-query loop's on every repetition.
 
-    python tools/gallery_bench.py --serve_batch 1 2 4 8 16 55 --modes none --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r20_serve.json"""
+    python tools/gallery_bench.py --serve_batch 1 2 4 8 16 55 --modes none --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r20_serve.json
+
+`--shortlist K [K ...]` (t2v): whole-gallery queries on the fine-tuned blend (c0 = 0.5, no first stage, no cpn) through
+GalleryIndex.search_requests, the three narrow options on auto: `all` (every video a candidate: N VTG pairs and N TVG pairs per query) against `tvg` (the gallery
+ranked by PairScorer.tvg_gallery, the best K reranked) at each K, per request and in groups of `--shortlist_batches`, alternated `--reps` times in one process on ONE
+eager index: ms per query with stage 1's and stage 2's shares; stage 1 taken apart into host planning and engine calls; for `--recall_k` the share of queries whose
+`all` top-1 / top-10 lie inside the shortlist -- on random weights, which says nothing about a trained checkpoint.  Every repetition is checked bit-equal to the
+leg's first run, and the shortlisted answers bit-equal across the group sizes.
+
+    python tools/gallery_bench.py --shortlist 16 64 256 --modes none --tvg_modes attn --n 1000 --queries 55 --synthetic_7b --out profiles/r21_shortlist.json"""
 import argparse
 import json
 import os
@@ -99,6 +108,10 @@ def main():
     ap.add_argument("--narrow_qkv", action="store_true", help="engine option narrow_qkv 0 against 1, narrow_gemm and narrow_lo6 on auto throughout (t2v: --modes none,full; v2t: the TVG leg)")
     ap.add_argument("--serve_batch", type=int, nargs="+", default=None, metavar="B",
                     help="the query stream through GalleryIndex.rerank_requests in groups of B against the per-query loop, the three narrow options on auto (t2v)")
+    ap.add_argument("--shortlist", type=int, nargs="+", default=None, metavar="K",
+                    help="whole-gallery queries on the fine-tuned blend: --candidates all against --candidates tvg with a shortlist of K, per request and in batches (t2v)")
+    ap.add_argument("--shortlist_batches", type=int, nargs="+", default=[1, 8], metavar="B", help="--shortlist: requests per pass")
+    ap.add_argument("--recall_k", type=int, nargs="+", default=[16, 64, 256], metavar="K", help="--shortlist: the shortlist sizes whose cover of the `all` top-1 / top-10 is reported")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -118,6 +131,8 @@ def main():
         return main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_qkv" if a.narrow_qkv else "narrow_lo6")
     if a.direction == "v2t":
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if a.shortlist:
+        return main_shortlist(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.serve_batch:
         return main_serve(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.narrow_gemm or a.narrow_lo6 or a.narrow_qkv:
@@ -420,6 +435,110 @@ def main_serve(a, dims, model, prob, vtg, tvg, video, q, tpc):
         del sc
         torch.cuda.empty_cache()
     for o in counters:
+        e.set_option(o, 0)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def main_shortlist(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    """`--shortlist`: whole-gallery queries on the fine-tuned blend, `all` (every video a candidate) against `tvg` (the best K of the TVG ranking), see the module text."""
+    e = model.engine
+    for o in ("narrow_gemm", "narrow_lo6", "narrow_qkv"):
+        e.set_option(o, 1)
+    med = lambda x: float(np.median(x))
+    spread = lambda x: float((max(x) - min(x)) / np.median(x))
+    Q, N = len(q), a.n
+    Ks = sorted(set(min(int(K), N) for K in a.shortlist))
+    Bs = sorted(set(min(int(B), Q) for B in a.shortlist_batches))
+    more = dict(cpn=False, alpha=(0.0, 0.0), c=(0.5, 0.5, 1.0, 0.5), finetuned=True)
+    res = {"shortlist": Ks, "batches": Bs, "n": N, "queries": Q, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc, "reps": a.reps,
+           "blend": {"c": list(more["c"]), "cpn": False}, "options": {"narrow_gemm": 1, "narrow_lo6": 1, "narrow_qkv": 1}, "runs": {}}
+    for mode in a.modes.split(","):
+        for tmode in a.tvg_modes.split(","):
+            model.vtg_precise = None if mode == "none" else mode
+            model.tvg_precise = tmode
+            model.clear_cache()
+            sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, torch.from_numpy(prob.video_vocab),
+                               torch.from_numpy(prob.tvg_video_labels), dims.num_clips, max_tokens=a.max_tokens)
+            sc.set_vtg_mode(model.vtg_mode()); sc.set_tvg_mode(model.tvg_mode())
+            warm = np.stack([np.arange(8), np.full(8, q[0])], axis=1)
+            sc.vtg(warm); sc.tvg(warm)
+            gal = GalleryIndex(sc)
+            t_build, _ = timed(gal.build)
+            t_feats, _ = timed(sc.gallery_feats)                         # once per weights version: the TVG rows of all N videos as one tensor
+            stage1_s, inner = [0.0], gal._stage1
+
+            def stage1(texts, cpn, alpha):                               # stage 1's share of a leg's wall time (its result is on the host when it returns)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = inner(texts, cpn, alpha)
+                stage1_s[0] += time.perf_counter() - t0
+                return out
+            gal._stage1 = stage1
+
+            def run(K, B):
+                reqs = [(int(t), np.arange(N), None, None) if K is None else (int(t), None, None, K) for t in q]
+                return [r for lo in range(0, Q, B) for r in gal.search_requests(reqs[lo:lo + B], **more)]
+            legs = [(K, B) for K in [None] + Ks for B in Bs]
+            name = lambda K, B: f"{'all' if K is None else f'tvg{K}'}_B{B}"
+            ref = {leg: run(*leg) for leg in legs}                       # warm-up of every leg's workspaces; the results every repetition is held to
+            for K in Ks:                                                 # the shortlisted answers do not depend on the batch: bit-equal
+                for B in Bs[1:]:
+                    assert all(np.array_equal(o, o1) and np.array_equal(b, b1) for (o, b), (o1, b1) in zip(ref[(K, B)], ref[(K, Bs[0])])), f"tvg{K}: B = {B} differs from B = {Bs[0]}"
+            ts, s1 = {leg: [] for leg in legs}, {leg: [] for leg in legs}
+            for rep in range(a.reps):
+                for leg in legs:
+                    stage1_s[0] = 0.0
+                    dt, got = timed(lambda: run(*leg))
+                    ts[leg].append(dt); s1[leg].append(stage1_s[0])
+                    print(f"repetition {rep}: {name(*leg)} {dt:.3f} s", file=sys.stderr, flush=True)
+                    assert all(np.array_equal(o, o1) and np.array_equal(b, b1) for (o, b), (o1, b1) in zip(got, ref[leg])), f"{name(*leg)}: results differ between repetitions"
+            # stage 1 taken apart: planning on the host (array expressions and the uploads), then the engine calls alone
+            parts = {}
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for B in Bs:
+                plan_ms, gpu_ms, calls, tokens = [], [], 0, 0
+                for _ in range(a.reps):
+                    tp = tg_ = 0.0
+                    calls = tokens = 0
+                    for lo in range(0, Q, B):
+                        texts = np.unique(q[lo:lo + B])
+                        dt, plans = timed(lambda: list(sc.iter_tvg_gallery(texts)))
+                        tp += dt
+                        ev0.record()
+                        outs = [sc.run(p) for p in plans]
+                        ev1.record()
+                        torch.cuda.synchronize()
+                        tg_ += ev0.elapsed_time(ev1)
+                        calls += len(plans); tokens += sum(p.n_tokens for p in plans)
+                        del outs
+                    plan_ms.append(1e3 * tp / Q); gpu_ms.append(tg_ / Q)
+                parts[B] = {"host_planning_ms_per_query": med(plan_ms), "gpu_ms_per_query": med(gpu_ms), "engine_calls": calls, "tokens": tokens,
+                            "chunk": sc.gallery_chunk(), "spread_planning": spread(plan_ms), "spread_gpu": spread(gpu_ms)}
+            # how much of the `all` answer a shortlist of K keeps -- on RANDOM weights: it says nothing about a trained checkpoint
+            stage = inner(q, False, (0.0, 0.0))
+            rank = np.argsort(-stage, axis=1, kind="stable")
+            top = [o for o, _ in ref[(None, Bs[0])]]
+            cover = {}
+            for K in sorted(set(min(int(K), N) for K in a.recall_k)):
+                kept = [set(rank[i, :K].tolist()) for i in range(Q)]
+                cover[f"K{K}"] = {"all_top1_inside": float(np.mean([int(top[i][0]) in kept[i] for i in range(Q)])),
+                                  "all_top10_inside": float(np.mean([set(top[i][:10].tolist()) <= kept[i] for i in range(Q)]))}
+            r = {"build_s": t_build, "gallery_feats_s": t_feats, "legs": {}, "stage1": {f"B{B}": v for B, v in parts.items()}, "cover_random_weights": cover}
+            for leg in legs:
+                K, B = leg
+                base = med(ts[(None, B)])
+                r["legs"][name(*leg)] = {"s": ts[leg], "ms_per_query": 1e3 * med(ts[leg]) / Q, "spread": spread(ts[leg]), "stage1_ms_per_query": 1e3 * med(s1[leg]) / Q,
+                                         "stage2_ms_per_query": 1e3 * med([t - s for t, s in zip(ts[leg], s1[leg])]) / Q, "ratio_to_all": base / med(ts[leg]),
+                                         "vtg_pairs_per_query": N if K is None else K}
+            res["runs"][f"vtg_{mode}/tvg_{tmode}"] = r
+            print(json.dumps({f"vtg_{mode}/tvg_{tmode}": r}), flush=True)
+            gal.close()
+            del sc
+            torch.cuda.empty_cache()
+    for o in ("narrow_gemm", "narrow_lo6", "narrow_qkv"):
         e.set_option(o, 0)
     if a.out:
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
