@@ -1182,23 +1182,33 @@ __device__ __forceinline__ void narrow_tile(const GemmParams& p, int bid, int& t
     tm = first_m + (pid % width) % gsz;
     tn = (pid % width) / gsz;
 }
-// (This K walk -- stage, the fragment offsets, the counted waits -- is restated in gemm_narrow_lo6_kernel and, for both passes, in gemm_nqkv_kernel below: a change to
-// the ring or to the waits goes to all three.)
-template <int DT>
-__global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams p) {
+// ... and their K walk, from "tile chosen" to "accumulators final": the 16-bit pass over K (w_wrap_k and lda > K included) and, with LO6, the e2m3 second pass over
+// the A operand's lo part behind it, in the SAME accumulators -- one block-scaled e2m3 MFMA per 128-value K-step and accumulator fragment, ascending K, W fragment
+// first: the chain gemm_kernel<.., true>'s phase 2 gives every C element.  The second pass reads the SAME tile images (gemm.hpp, at A6): the 64-row quarter q of a
+// 256-row tile is the four consecutive fragment groups 4 q .. 4 q + 3 of every block -- 6 KiB contiguous -- its A-side scales are the 4-byte word + 4 (q & 1) of every
+// lane's 8-byte entry in the 512-byte half (q >> 1), the W-side scales of the 64-column group qn the 256 bytes at qn * 256.
+// ONE ring for both passes: step t of the nk + nk6 steps lives in slot t & 3 (16 KiB; a second-pass step fills 12 KiB + 1 KiB of scales of it), is requested
+// right behind the barrier that ends step t - 4, and costs every wave FOUR LDS-DMA requests in either pass (second pass: three KiB-blocks of e2m3 and a 256-byte
+// piece of the scales as 16-byte pieces of the first 16 lanes -- see dma6 on why not 4-byte ones; the fourth wave stages a spare copy of the W scales so that the
+// counted vmcnt waits are the same for all waves and across the hand-over).  The first second-pass steps are therefore in flight under the last 16-bit steps.
+// The ring, its depth and the waits counted against it are all in this function: a kernel that calls it owns no LDS of its own and may have global loads in
+// flight at the call (they are older than every request made here, so the counted waits cover them).
+#define N6_Q_BYTES 6144                      // a 64-row quarter of one operand's e2m3 block: four fragment groups of 1536 B
+#define N6_SC_OFF (2 * N6_Q_BYTES)           // the step's scales inside its slot: A half (512 B) | W group (256 B) | spare (256 B)
+struct NarrowAcc { f32x4 v[2][2]; };         // a wave's 32 x 32 of C, [mi][ni].  Returned by value: through a reference parameter hipcc moved one fragment between
+                                             // AGPRs and VGPRs in every 16-bit step of the two residual kernels
+template <int DT, bool LO6>
+__device__ __forceinline__ NarrowAcc narrow_walk(const GemmParams& p, int tm, int tn, int lane, int wave) {
     __shared__ __attribute__((aligned(16))) char smem[NRING * N_STEP_BYTES];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    static_assert(N6_SC_OFF + 1024 <= N_STEP_BYTES, "a second-pass step fits a ring slot");
     const int wm = wave >> 1, wn = wave & 1;
-    int tm, tn;
-    narrow_tile(p, blockIdx.x, tm, tn);
     const int row0 = tm * NBM, col0 = tn * NBN;
 
-    // LDS-DMA sources: wave w stages blocks w and w + 4 (8 rows each) of both operands; lane -> row sr of the block, source chunk sc for its slot lane & 7
+    // ---- first pass.  LDS-DMA sources: wave w stages blocks w and w + 4 (8 rows each) of both operands; lane -> row sr of the block, source chunk sc for its slot lane & 7
     const int sr = lane >> 3;
     const int sc = (lane & 7) ^ (4 * (wave & 1) + (sr >> 1));
-    const int64_t w_ld = p.w_wrap_k > 0 ? p.w_wrap_k : p.K;           // W row stride (elements)
+    const int w_wrap_k = LO6 ? 0 : p.w_wrap_k;                         // (launch_one: the second pass takes no wrapped W)
+    const int64_t w_ld = w_wrap_k > 0 ? w_wrap_k : p.K;               // W row stride (elements)
     uint32_t offA[2], offW[2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -1206,13 +1216,13 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams
         offA[i] = (uint32_t)((int64_t)min(row0 + 8 * b + sr, p.M - 1) * p.lda * 2 + 16 * sc);
         offW[i] = (uint32_t)((int64_t)min(col0 + 8 * b + sr, p.N - 1) * w_ld * 2 + 16 * sc);
     }
-    const char* baseA = (const char*)p.A;
-    const char* baseW = (const char*)p.W;
     const int nk = p.K / 64;                                           // K-steps of 128 bytes
-    const int wrap = p.w_wrap_k > 0 ? p.w_wrap_k / 64 : 0x7fffffff;    // A = [hi | lo]: W's K-step index wraps
+    const int nk6 = LO6 ? p.K6 / 128 : 0;                              // ... of 128 e2m3 values
+    const int nt = nk + nk6;
+    const int wrap = w_wrap_k > 0 ? w_wrap_k / 64 : 0x7fffffff;        // A = [hi | lo]: W's K-step index wraps
     auto stage = [&](int slot, int kt) __attribute__((always_inline)) {
-        const char* ga = baseA + (int64_t)kt * 128;
-        const char* gw = baseW + (int64_t)(kt >= wrap ? kt - wrap : kt) * 128;
+        const char* ga = (const char*)p.A + (int64_t)kt * 128;
+        const char* gw = (const char*)p.W + (int64_t)(kt >= wrap ? kt - wrap : kt) * 128;
         char* d = smem + slot * N_STEP_BYTES + wave * 1024;
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
@@ -1229,115 +1239,20 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams
     const int a_off = (2 * wm) * 2048 + frag_off;                      // + mi * 2048; second read: ^ 64
     const int b_off = N_A_BYTES + (2 * wn) * 2048 + frag_off;          // + ni * 2048
 
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-#pragma unroll
-    for (int s = 0; s < NRING - 1; ++s)
-        if (s < nk) stage(s, s);
-    int slot = 0;
-    for (int kt = 0; kt < nk; ++kt) {
-        // my four requests of step kt have landed: those of the (at most NRING - 2) later steps requested so far may stay in flight
-        if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");            // my LDS reads of step kt - 1 have returned (WAR on the slot refilled below)
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (kt + NRING - 1 < nk) stage((slot + NRING - 1) & (NRING - 1), kt + NRING - 1);
-        const char* ba[2] = {smem + slot * N_STEP_BYTES + a_off, smem + ((slot * N_STEP_BYTES + a_off) ^ 64)};
-        const char* bb[2] = {smem + slot * N_STEP_BYTES + b_off, smem + ((slot * N_STEP_BYTES + b_off) ^ 64)};
-        bf16x8 fa[2][2], fb[2][2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) fb[ks][ni] = *(const bf16x8*)(bb[ks] + ni * 2048);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) fa[ks][mi] = *(const bf16x8*)(ba[ks] + mi * 2048);
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma16<DT>(fb[ks][ni], fa[ks][mi], acc[mi][ni]);
-        slot = (slot + 1) & (NRING - 1);
-    }
-    static_assert(NRING == 4, "the counted waits above are written for three steps in flight");
-
-    narrow_resid_epilogue(p, acc, row0 + 32 * wm, col0 + 32 * wn, lane);
-}
-
-// ---- narrow-tile residual GEMM with the e2m3 second pass (GemmParams::narrow_lo6): gemm_narrow_kernel's tiles, order and 16-bit K walk
-// over the hi operand (lda > K, w_wrap_k = 0), then, in the SAME accumulators, one block-scaled e2m3 MFMA per 128-value K-step and accumulator fragment over the
-// A operand's lo part -- the chain gemm_kernel<EPI_RESID, DT, false, true> gives every C element (its phase 1, then its phase 2 in ascending K, W fragment first,
-// then the same epilogue), so the bits are that kernel's.  The second pass reads the SAME tile images (gemm.hpp, at A6): the 64-row quarter q of a 256-row tile is
-// the four consecutive fragment groups 4 q .. 4 q + 3 of every block -- 6 KiB contiguous -- its A-side scales are the 4-byte word + 4 (q & 1) of every lane's 8-byte
-// entry in the 512-byte half (q >> 1), the W-side scales of the 64-column group qn the 256 bytes at qn * 256.
-// ONE ring for both passes: step t of the nk + nk6 steps lives in slot t & 3 (16 KiB; a second-pass step fills 12 KiB + 1 KiB of scales of it), is requested
-// right behind the barrier that ends step t - 4, and costs every wave FOUR LDS-DMA requests in either pass (second pass: three KiB-blocks of e2m3 and a 256-byte
-// piece of the scales as 16-byte pieces of the first 16 lanes -- see dma6 on why not 4-byte ones; the fourth wave stages a spare copy of the W scales so that the
-// counted vmcnt waits are the same for all waves and across the hand-over).  The first second-pass steps are therefore in flight under the last 16-bit steps.
-#define N6_Q_BYTES 6144                      // a 64-row quarter of one operand's e2m3 block: four fragment groups of 1536 B
-#define N6_SC_OFF (2 * N6_Q_BYTES)           // the step's scales inside its slot: A half (512 B) | W group (256 B) | spare (256 B)
-// (Both passes -- stage, stage6, head, the fragment and scale offsets -- are restated in gemm_nqkv_kernel below: a change to the ring or to the waits goes there too.)
-template <int DT>
-__global__ __launch_bounds__(N_THREADS) void gemm_narrow_lo6_kernel(const GemmParams p) {
-    __shared__ __attribute__((aligned(16))) char smem[NRING * N_STEP_BYTES];
-    static_assert(N6_SC_OFF + 1024 <= N_STEP_BYTES, "a second-pass step fits a ring slot");
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave >> 1, wn = wave & 1;
-    int tm, tn;
-    narrow_tile(p, blockIdx.x, tm, tn);
-    const int row0 = tm * NBM, col0 = tn * NBN;
-
-    // ---- first pass: gemm_narrow_kernel's sources and fragment reads
-    const int sr = lane >> 3;
-    const int sc = (lane & 7) ^ (4 * (wave & 1) + (sr >> 1));
-    uint32_t offA[2], offW[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int b = wave + 4 * i;
-        offA[i] = (uint32_t)((int64_t)min(row0 + 8 * b + sr, p.M - 1) * p.lda * 2 + 16 * sc);
-        offW[i] = (uint32_t)((int64_t)min(col0 + 8 * b + sr, p.N - 1) * p.K * 2 + 16 * sc);
-    }
-    const char* baseA = (const char*)p.A;
-    const char* baseW = (const char*)p.W;
-    const int nk = p.K / 64;                                           // K-steps of 128 bytes
-    const int nk6 = p.K6 / 128;                                        // ... of 128 e2m3 values
-    const int nt = nk + nk6;
-    auto stage = [&](int slot, int kt) __attribute__((always_inline)) {
-        const char* ga = baseA + (int64_t)kt * 128;
-        const char* gw = baseW + (int64_t)kt * 128;
-        char* d = smem + slot * N_STEP_BYTES + wave * 1024;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            uint32_t oa = offA[i], ow = offW[i];
-            asm volatile("" : "+v"(oa), "+v"(ow));
-            glds16(ga + oa, d + i * 4096);
-            glds16(gw + ow, d + N_A_BYTES + i * 4096);
-        }
-    };
-    const int fr = lane & 15, fc = lane >> 4;
-    const int fg = (fr >> 1) & 7;
-    const int frag_off = (fr >> 3) * 1024 + (fr & 7) * 128 + 16 * ((fc ^ (fg & 3)) + 4 * (fg >> 2));
-    const int a_off = (2 * wm) * 2048 + frag_off;
-    const int b_off = N_A_BYTES + (2 * wn) * 2048 + frag_off;
-
-    // ---- second pass: lane-linear copies out of the tile images.  A step's slot: [0, 6 KiB) the A quarter, [6, 12 KiB) the W quarter, then the scales.  Wave w
+    // ---- second pass (LO6): lane-linear copies out of the tile images.  A step's slot: [0, 6 KiB) the A quarter, [6, 12 KiB) the W quarter, then the scales.  Wave w
     // copies KiB-blocks w, w + 4, w + 8 of those twelve and scale piece w (0, 1: the halves of the A half; 2: the W group; 3: the W group again, never read)
-    const int q = tm & 3, qn = tn & 3;
-    const char* g6A = (const char*)p.A6 + (int64_t)(tm >> 2) * nk6 * F6_TILE_BYTES;
-    const char* g6W = (const char*)p.W6 + (int64_t)(tn >> 2) * nk6 * F6_TILE_BYTES;
-    const char* qA = g6A + q * N6_Q_BYTES;
-    const char* qW = g6W + qn * N6_Q_BYTES;
-    const char* src6[4] = {qA + wave * 1024, wave < 2 ? qA + (wave + 4) * 1024 : qW + (wave - 2) * 1024, qW + (wave + 2) * 1024,
-                           wave < 2 ? g6A + 24576 + (q >> 1) * 512 + wave * 256 : g6W + 24576 + qn * 256};
+    const char* src6[4] = {nullptr, nullptr, nullptr, nullptr};
+    if constexpr (LO6) {
+        const int q = tm & 3, qn = tn & 3;
+        const char* g6A = (const char*)p.A6 + (int64_t)(tm >> 2) * nk6 * F6_TILE_BYTES;
+        const char* g6W = (const char*)p.W6 + (int64_t)(tn >> 2) * nk6 * F6_TILE_BYTES;
+        const char* qA = g6A + q * N6_Q_BYTES;
+        const char* qW = g6W + qn * N6_Q_BYTES;
+        src6[0] = qA + wave * 1024;
+        src6[1] = wave < 2 ? qA + (wave + 4) * 1024 : qW + (wave - 2) * 1024;
+        src6[2] = qW + (wave + 2) * 1024;
+        src6[3] = wave < 2 ? g6A + 24576 + (q >> 1) * 512 + wave * 256 : g6W + 24576 + qn * 256;
+    }
     auto stage6 = [&](int slot, int kd) __attribute__((always_inline)) {
         const int64_t ko = (int64_t)kd * F6_TILE_BYTES;
         char* d = smem + slot * N_STEP_BYTES;
@@ -1347,28 +1262,11 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_lo6_kernel(const GemmPa
         for (int i = 0; i < 3; ++i) glds16(src6[i] + ko + o16, d + (wave + 4 * i) * 1024);
         if (lane < 16) glds16(src6[3] + ko + o16, d + N6_SC_OFF + wave * 256);
     };
-    typedef int i32x8 __attribute__((ext_vector_type(8)));
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    typedef int i32x2 __attribute__((ext_vector_type(2)));
-    typedef int i32x1 __attribute__((ext_vector_type(1)));
-    // one 16-row fragment: ds_read_b128 + ds_read_b64, as in gemm_kernel (rd6)
-    auto rd6 = [&](const char* fb) __attribute__((always_inline)) {
-        const i32x4 l = *(const i32x4*)(fb + lane * 16);
-        const i32x2 h = *(const i32x2*)(fb + 1024 + lane * 8);
-        return (i32x8){l[0], l[1], l[2], l[3], h[0], h[1], 0, 0};
-    };
-    const int a6_off = (2 * wm) * 1536, b6_off = N6_Q_BYTES + (2 * wn) * 1536;              // + mi / ni * 1536
-    const int sa_off = N6_SC_OFF + lane * 8 + 4 * (q & 1), sw_off = N6_SC_OFF + 512 + lane * 4;
-    const int sa_sh = 16 * wm, sw_sh = 16 * wn;                                              // this wave's two fragments: bytes 2 wm + mi / 2 wn + ni of the word
 
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
+    f32x4 acc[2][2] = {};
     auto request = [&](int slot, int t) __attribute__((always_inline)) {
-        if (t < nk) stage(slot, t); else stage6(slot, t - nk);
+        if constexpr (LO6) { if (t < nk) stage(slot, t); else stage6(slot, t - nk); }
+        else stage(slot, t);
     };
 #pragma unroll
     for (int s = 0; s < NRING - 1; ++s)
@@ -1385,6 +1283,7 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_lo6_kernel(const GemmPa
         asm volatile("" ::: "memory");
         if (t + NRING - 1 < nt) request((slot + NRING - 1) & (NRING - 1), t + NRING - 1);
     };
+    static_assert(NRING == 4, "head's counted waits are written for three steps of four requests in flight");
     for (int kt = 0; kt < nk; ++kt) {
         head(kt);
         const char* ba[2] = {smem + slot * N_STEP_BYTES + a_off, smem + ((slot * N_STEP_BYTES + a_off) ^ 64)};
@@ -1405,31 +1304,67 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_lo6_kernel(const GemmPa
                 for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma16<DT>(fb[ks][ni], fa[ks][mi], acc[mi][ni]);
         slot = (slot + 1) & (NRING - 1);
     }
-    for (int k6 = 0; k6 < nk6; ++k6) {
-        head(nk + k6);
-        const char* sb = smem + slot * N_STEP_BYTES;
-        // (scales read through ext-vector types like the fragments: see gemm_kernel's rd6_sw)
-        const uint32_t scw = (uint32_t)(*(const i32x1*)(sb + sw_off))[0] >> sw_sh;
-        const uint32_t sca = (uint32_t)(*(const i32x1*)(sb + sa_off))[0] >> sa_sh;
-        i32x8 fa8[2], fb8[2];
+    if constexpr (LO6) {
+        typedef int i32x8 __attribute__((ext_vector_type(8)));
+        typedef int i32x4 __attribute__((ext_vector_type(4)));
+        typedef int i32x2 __attribute__((ext_vector_type(2)));
+        typedef int i32x1 __attribute__((ext_vector_type(1)));
+        // one 16-row fragment: ds_read_b128 + ds_read_b64, as in gemm_kernel (rd6)
+        auto rd6 = [&](const char* fb) __attribute__((always_inline)) {
+            const i32x4 l = *(const i32x4*)(fb + lane * 16);
+            const i32x2 h = *(const i32x2*)(fb + 1024 + lane * 8);
+            return (i32x8){l[0], l[1], l[2], l[3], h[0], h[1], 0, 0};
+        };
+        const int a6_off = (2 * wm) * 1536, b6_off = N6_Q_BYTES + (2 * wn) * 1536;          // + mi / ni * 1536
+        const int sa_off = N6_SC_OFF + lane * 8 + 4 * (tm & 1), sw_off = N6_SC_OFF + 512 + lane * 4;   // (tm & 1: the quarter's half of the 8-byte entry)
+        const int sa_sh = 16 * wm, sw_sh = 16 * wn;                                          // this wave's two fragments: bytes 2 wm + mi / 2 wn + ni of the word
+        for (int k6 = 0; k6 < nk6; ++k6) {
+            head(nk + k6);
+            const char* sb = smem + slot * N_STEP_BYTES;
+            // (scales read through ext-vector types like the fragments: see gemm_kernel's rd6_sw)
+            const uint32_t scw = (uint32_t)(*(const i32x1*)(sb + sw_off))[0] >> sw_sh;
+            const uint32_t sca = (uint32_t)(*(const i32x1*)(sb + sa_off))[0] >> sa_sh;
+            i32x8 fa8[2], fb8[2];
 #pragma unroll
-        for (int ni = 0; ni < 2; ++ni) fb8[ni] = rd6(sb + b6_off + ni * 1536);
+            for (int ni = 0; ni < 2; ++ni) fb8[ni] = rd6(sb + b6_off + ni * 1536);
 #pragma unroll
-        for (int mi = 0; mi < 2; ++mi) fa8[mi] = rd6(sb + a6_off + mi * 1536);
+            for (int mi = 0; mi < 2; ++mi) fa8[mi] = rd6(sb + a6_off + mi * 1536);
 #define N6_MMA(MI, NI) acc[MI][NI] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb8[NI], fa8[MI], acc[MI][NI], 2, 2, NI, (int)scw, MI, (int)sca);   // cbsz = blgp = 2: e2m3
-        N6_MMA(0, 0) N6_MMA(0, 1) N6_MMA(1, 0) N6_MMA(1, 1)
+            N6_MMA(0, 0) N6_MMA(0, 1) N6_MMA(1, 0) N6_MMA(1, 1)
 #undef N6_MMA
-        slot = (slot + 1) & (NRING - 1);
+            slot = (slot + 1) & (NRING - 1);
+        }
     }
-    static_assert(NRING == 4, "the counted waits above are written for three steps in flight");
+    return NarrowAcc{{{acc[0][0], acc[0][1]}, {acc[1][0], acc[1][1]}}};
+}
 
-    narrow_resid_epilogue(p, acc, row0 + 32 * wm, col0 + 32 * wn, lane);
+template <int DT>
+__global__ __launch_bounds__(N_THREADS) void gemm_narrow_kernel(const GemmParams p) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int tm, tn;
+    narrow_tile(p, blockIdx.x, tm, tn);
+    const NarrowAcc acc = narrow_walk<DT, false>(p, tm, tn, lane, wave);
+    narrow_resid_epilogue(p, acc.v, tm * NBM + 32 * (wave >> 1), tn * NBN + 32 * (wave & 1), lane);
+}
+
+// ---- narrow-tile residual GEMM with the e2m3 second pass (GemmParams::narrow_lo6): gemm_narrow_kernel with both passes of the walk
+// (lda > K, w_wrap_k = 0) -- the chain gemm_kernel<EPI_RESID, DT, false, true> gives every C element (its phase 1, then its phase 2, then the same epilogue), so
+// the bits are that kernel's.
+template <int DT>
+__global__ __launch_bounds__(N_THREADS) void gemm_narrow_lo6_kernel(const GemmParams p) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    int tm, tn;
+    narrow_tile(p, blockIdx.x, tm, tn);
+    const NarrowAcc acc = narrow_walk<DT, true>(p, tm, tn, lane, wave);
+    narrow_resid_epilogue(p, acc.v, tm * NBM + 32 * (wave >> 1), tn * NBN + 32 * (wave & 1), lane);
 }
 
 // ---- narrow-tile QKV GEMM (GemmParams::narrow_qkv): EPI_QKV on fp16 / bf16 operands in the narrow kernels' 64 x 64 tiles and tile order.  A small
 // scoring call's QKV projection (N = 4608) is 18 tiles of 256 x 256 per 256 rows -- 36 workgroups at k = 16, 18 on the v2t TVG leg -- and 16 times as many of these.
-// Main loop: gemm_narrow_kernel's 16-bit K walk (w_wrap_k and lda > K included) and, with LO6, gemm_narrow_lo6_kernel's e2m3 steps behind it in the same accumulators and
-// the same four-slot ring, restated here so that those two kernels keep their code.  Epilogue: gemm_kernel<EPI_QKV>'s per element -- x = acc + bias[col]; a wave's 32
+// Main loop: narrow_walk -- the 16-bit pass (w_wrap_k and lda > K included) and, with LO6, the e2m3 steps behind it in the same accumulators and the same
+// four-slot ring.  Epilogue: gemm_kernel<EPI_QKV>'s per element -- x = acc + bias[col]; a wave's 32
 // stored columns are ONE 32-row group g of a head (fragment 0: natural dim d = 16 g + .., fragment 1: its RoPE partner d + 64), rotated with the cos / sin of chunks g and
 // 4 + g of the rope_rows table at row min(row, M - 1) by the same expression text, or (V heads) plain in stored order; rounded through pack2<ODT> inside the same fp16
 // saturation window; SPLIT: hi at C, lo = r16(x - f32(hi)) at C + lo_off.  Every stored element is the 256 x 256 kernel's bit for bit.
@@ -1438,12 +1373,9 @@ __global__ __launch_bounds__(N_THREADS) void gemm_narrow_lo6_kernel(const GemmPa
 template <int DT, bool SPLIT, bool LO6>
 __global__ __launch_bounds__(N_THREADS) void gemm_nqkv_kernel(const GemmParams p) {
     static_assert(!(LO6 && !SPLIT), "the e2m3 second pass has hi | lo outputs only");
-    __shared__ __attribute__((aligned(16))) char smem[NRING * N_STEP_BYTES];
-    static_assert(N6_SC_OFF + 1024 <= N_STEP_BYTES, "a second-pass step fits a ring slot");
     constexpr int ODT = out16<DT>::value;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     int tm, tn;
     narrow_tile(p, blockIdx.x, tm, tn);
@@ -1475,138 +1407,8 @@ __global__ __launch_bounds__(N_THREADS) void gemm_nqkv_kernel(const GemmParams p
         }
     }
 
-    // ---- first pass: gemm_narrow_kernel's sources and fragment reads
-    const int sr = lane >> 3;
-    const int sc = (lane & 7) ^ (4 * (wave & 1) + (sr >> 1));
-    const int64_t w_ld = p.w_wrap_k > 0 ? p.w_wrap_k : p.K;           // W row stride (elements)
-    uint32_t offA[2], offW[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int b = wave + 4 * i;
-        offA[i] = (uint32_t)((int64_t)min(row0 + 8 * b + sr, p.M - 1) * p.lda * 2 + 16 * sc);
-        offW[i] = (uint32_t)((int64_t)min(col0 + 8 * b + sr, p.N - 1) * w_ld * 2 + 16 * sc);
-    }
-    const char* baseA = (const char*)p.A;
-    const char* baseW = (const char*)p.W;
-    const int nk = p.K / 64;                                           // K-steps of 128 bytes
-    const int nk6 = LO6 ? p.K6 / 128 : 0;                              // ... of 128 e2m3 values
-    const int nt = nk + nk6;
-    const int wrap = p.w_wrap_k > 0 ? p.w_wrap_k / 64 : 0x7fffffff;    // A = [hi | lo]: W's K-step index wraps
-    auto stage = [&](int slot, int kt) __attribute__((always_inline)) {
-        const char* ga = baseA + (int64_t)kt * 128;
-        const char* gw = baseW + (int64_t)(kt >= wrap ? kt - wrap : kt) * 128;
-        char* d = smem + slot * N_STEP_BYTES + wave * 1024;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            uint32_t oa = offA[i], ow = offW[i];
-            asm volatile("" : "+v"(oa), "+v"(ow));
-            glds16(ga + oa, d + i * 4096);
-            glds16(gw + ow, d + N_A_BYTES + i * 4096);
-        }
-    };
-    const int fr = lane & 15, fc = lane >> 4;
-    const int fg = (fr >> 1) & 7;
-    const int frag_off = (fr >> 3) * 1024 + (fr & 7) * 128 + 16 * ((fc ^ (fg & 3)) + 4 * (fg >> 2));
-    const int a_off = (2 * wm) * 2048 + frag_off;
-    const int b_off = N_A_BYTES + (2 * wn) * 2048 + frag_off;
-
-    // ---- second pass (LO6): gemm_narrow_lo6_kernel's copies out of the tile images
-    const int q = tm & 3, qn = tn & 3;
-    const char* src6[4] = {nullptr, nullptr, nullptr, nullptr};
-    if constexpr (LO6) {
-        const char* g6A = (const char*)p.A6 + (int64_t)(tm >> 2) * nk6 * F6_TILE_BYTES;
-        const char* g6W = (const char*)p.W6 + (int64_t)(tn >> 2) * nk6 * F6_TILE_BYTES;
-        const char* qA = g6A + q * N6_Q_BYTES;
-        const char* qW = g6W + qn * N6_Q_BYTES;
-        src6[0] = qA + wave * 1024;
-        src6[1] = wave < 2 ? qA + (wave + 4) * 1024 : qW + (wave - 2) * 1024;
-        src6[2] = qW + (wave + 2) * 1024;
-        src6[3] = wave < 2 ? g6A + 24576 + (q >> 1) * 512 + wave * 256 : g6W + 24576 + qn * 256;
-    }
-    auto stage6 = [&](int slot, int kd) __attribute__((always_inline)) {
-        const int64_t ko = (int64_t)kd * F6_TILE_BYTES;
-        char* d = smem + slot * N_STEP_BYTES;
-        uint32_t o16 = (uint32_t)lane * 16u;
-        asm volatile("" : "+v"(o16));
-#pragma unroll
-        for (int i = 0; i < 3; ++i) glds16(src6[i] + ko + o16, d + (wave + 4 * i) * 1024);
-        if (lane < 16) glds16(src6[3] + ko + o16, d + N6_SC_OFF + wave * 256);
-    };
-    typedef int i32x8 __attribute__((ext_vector_type(8)));
-    typedef int i32x4 __attribute__((ext_vector_type(4)));
-    typedef int i32x2 __attribute__((ext_vector_type(2)));
-    typedef int i32x1 __attribute__((ext_vector_type(1)));
-    auto rd6 = [&](const char* fb) __attribute__((always_inline)) {
-        const i32x4 l = *(const i32x4*)(fb + lane * 16);
-        const i32x2 h = *(const i32x2*)(fb + 1024 + lane * 8);
-        return (i32x8){l[0], l[1], l[2], l[3], h[0], h[1], 0, 0};
-    };
-    const int a6_off = (2 * wm) * 1536, b6_off = N6_Q_BYTES + (2 * wn) * 1536;
-    const int sa_off = N6_SC_OFF + lane * 8 + 4 * (q & 1), sw_off = N6_SC_OFF + 512 + lane * 4;
-    const int sa_sh = 16 * wm, sw_sh = 16 * wn;
-
-    f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-
-    auto request = [&](int slot, int t) __attribute__((always_inline)) {
-        if constexpr (LO6) { if (t < nk) stage(slot, t); else stage6(slot, t - nk); }
-        else stage(slot, t);
-    };
-#pragma unroll
-    for (int s = 0; s < NRING - 1; ++s)
-        if (s < nt) request(s, s);
-    int slot = 0;
-    // the head of step t in either pass, as in gemm_narrow_lo6_kernel
-    auto head = [&](int t) __attribute__((always_inline)) {
-        if (t + 2 < nt) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (t + 1 < nt) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (t + NRING - 1 < nt) request((slot + NRING - 1) & (NRING - 1), t + NRING - 1);
-    };
-    for (int kt = 0; kt < nk; ++kt) {
-        head(kt);
-        const char* ba[2] = {smem + slot * N_STEP_BYTES + a_off, smem + ((slot * N_STEP_BYTES + a_off) ^ 64)};
-        const char* bb[2] = {smem + slot * N_STEP_BYTES + b_off, smem + ((slot * N_STEP_BYTES + b_off) ^ 64)};
-        bf16x8 fa[2][2], fb[2][2];
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) fb[ks][ni] = *(const bf16x8*)(bb[ks] + ni * 2048);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) fa[ks][mi] = *(const bf16x8*)(ba[ks] + mi * 2048);
-        }
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = mfma16<DT>(fb[ks][ni], fa[ks][mi], acc[mi][ni]);
-        slot = (slot + 1) & (NRING - 1);
-    }
-    if constexpr (LO6) {
-        for (int k6 = 0; k6 < nk6; ++k6) {
-            head(nk + k6);
-            const char* sb = smem + slot * N_STEP_BYTES;
-            const uint32_t scw = (uint32_t)(*(const i32x1*)(sb + sw_off))[0] >> sw_sh;
-            const uint32_t sca = (uint32_t)(*(const i32x1*)(sb + sa_off))[0] >> sa_sh;
-            i32x8 fa8[2], fb8[2];
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) fb8[ni] = rd6(sb + b6_off + ni * 1536);
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi) fa8[mi] = rd6(sb + a6_off + mi * 1536);
-#define N6_MMA(MI, NI) acc[MI][NI] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb8[NI], fa8[MI], acc[MI][NI], 2, 2, NI, (int)scw, MI, (int)sca);   // cbsz = blgp = 2: e2m3
-            N6_MMA(0, 0) N6_MMA(0, 1) N6_MMA(1, 0) N6_MMA(1, 1)
-#undef N6_MMA
-            slot = (slot + 1) & (NRING - 1);
-        }
-    }
-    static_assert(NRING == 4, "the counted waits above are written for three steps in flight");
+    const NarrowAcc walked = narrow_walk<DT, LO6>(p, tm, tn, lane, wave);
+    const f32x4 (&acc)[2][2] = walked.v;
 
     // ---- epilogue
     if constexpr (ODT == DT_F16) { if (p.f16_saturate) f16_saturate_on(); }          // fp16 stores saturate instead of overflowing to inf
@@ -1728,76 +1530,75 @@ static int launch_t(const GemmParams& p, hipStream_t stream) {
 
 static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream);
 
-// ---- GemmParams::narrow.  The narrow kernel is instantiated for EPI_RESID on plain fp16 / bf16 operands (w_wrap_k and lda > K included); every other form --
-// the e2m3 second pass (A6 / W6: GemmParams::narrow_lo6 below), fp8 (a_mx included), any other epilogue, the timing aids -- keeps the 256 x 256 kernel whatever `narrow` says.
-static std::atomic<int64_t> g_narrow_launches{0};
-extern "C" int64_t blim_gemm_narrow_launches(void) { return g_narrow_launches.load(); }
-extern "C" int32_t blim_gemm_narrow_threshold(void) { return GEMM_NARROW_TILES; }
+// ---- GemmParams::narrow / narrow_lo6 / narrow_qkv: which 16-bit forms have a 64 x 64 kernel.  Every other form -- fp8 (a_mx included), the other epilogues, the
+// timing aids -- keeps the 256 x 256 kernel whatever the fields say.
+//   narrow:     EPI_RESID on plain operands (w_wrap_k and lda > K included);
+//   narrow_lo6: the form `narrow` leaves out, EPI_RESID with the e2m3 second pass (A6 / W6, w_wrap_k = 0) -- `narrow` and blim_gemm_narrow_launches() keep their meaning;
+//   narrow_qkv: EPI_QKV -- plain or hi | lo outputs over the plain or the w_wrap_k walk, hi | lo outputs behind the e2m3 second pass.  A6 without lo_off is no form
+//               of either kernel.  (lo_off % 4: the kernel's 8-byte stores of the lo half; blim_gemm and the engine pass no other)
 static bool narrow_eligible(GemmEpi epi, const GemmParams& p) {
     return epi == EPI_RESID && (p.dtype == DT_F16 || p.dtype == DT_BF16) && !p.A6 && !p.W6 && !p.a_mx && !p.swiglu_act && !p.debug_stamps && !p.debug_skip_epilogue;
 }
-static bool narrow_chosen(GemmEpi epi, const GemmParams& p) {
-    if (p.narrow == 0 || !narrow_eligible(epi, p)) return false;
-    if (p.narrow == 2) return true;
-    return (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) < GEMM_NARROW_TILES;      // auto: gemm.hpp
-}
-// ---- GemmParams::narrow_lo6: the same choice for the form `narrow` leaves out, EPI_RESID with the e2m3 second pass (A6 / W6, w_wrap_k = 0), with a kernel, a
-// counter and a threshold of its own -- `narrow` and blim_gemm_narrow_launches() keep their meaning.
-static std::atomic<int64_t> g_narrow_lo6_launches{0};
-extern "C" int64_t blim_gemm_narrow_lo6_launches(void) { return g_narrow_lo6_launches.load(); }
-extern "C" int32_t blim_gemm_narrow_lo6_threshold(void) { return GEMM_NARROW_LO6_TILES; }
 static bool narrow_lo6_eligible(GemmEpi epi, const GemmParams& p) {
     return epi == EPI_RESID && (p.dtype == DT_F16 || p.dtype == DT_BF16) && p.A6 && p.W6 && p.w_wrap_k == 0 && !p.a_mx && !p.swiglu_act && !p.debug_stamps && !p.debug_skip_epilogue;
 }
-static bool narrow_lo6_chosen(GemmEpi epi, const GemmParams& p) {
-    if (p.narrow_lo6 == 0 || !narrow_lo6_eligible(epi, p)) return false;
-    if (p.narrow_lo6 == 2) return true;
-    return (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) < GEMM_NARROW_LO6_TILES;  // auto: gemm.hpp
-}
-static int launch_narrow_lo6(const GemmParams& p, hipStream_t stream) {
-    const dim3 grid((unsigned)(((p.M + NBM - 1) / NBM) * ((p.N + NBN - 1) / NBN)));
-    if (p.dtype == DT_F16) hipLaunchKernelGGL((gemm_narrow_lo6_kernel<DT_F16>), grid, dim3(N_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL((gemm_narrow_lo6_kernel<DT_BF16>), grid, dim3(N_THREADS), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { blim_set_error("narrow lo6 gemm launch failed: %s", hipGetErrorString(e)); return BLIM_ERR_HIP; }
-    g_narrow_lo6_launches.fetch_add(1);
-    return BLIM_OK;
-}
-// ---- GemmParams::narrow_qkv: the same choice for EPI_QKV on fp16 / bf16 operands -- plain or hi | lo outputs over the plain or the w_wrap_k walk, hi | lo outputs
-// behind the e2m3 second pass -- with a kernel family, a counter and a threshold of its own.  A6 without lo_off is no form of either kernel; fp8 and the timing aids
-// keep the 256 x 256 kernel.
-static std::atomic<int64_t> g_narrow_qkv_launches{0};
-extern "C" int64_t blim_gemm_narrow_qkv_launches(void) { return g_narrow_qkv_launches.load(); }
-extern "C" int32_t blim_gemm_narrow_qkv_threshold(void) { return GEMM_NARROW_QKV_TILES; }
 static bool narrow_qkv_eligible(GemmEpi epi, const GemmParams& p) {
-    return epi == EPI_QKV && (p.dtype == DT_F16 || p.dtype == DT_BF16) && !(p.A6 && p.lo_off == 0) && p.lo_off % 4 == 0 && !p.a_mx && !p.debug_stamps && !p.debug_skip_epilogue;   // (lo_off % 4: the kernel's 8-byte stores of the lo half; blim_gemm and the engine pass no other)
+    return epi == EPI_QKV && (p.dtype == DT_F16 || p.dtype == DT_BF16) && !(p.A6 && p.lo_off == 0) && p.lo_off % 4 == 0 && !p.a_mx && !p.debug_stamps && !p.debug_skip_epilogue;
 }
-static bool narrow_qkv_chosen(GemmEpi epi, const GemmParams& p) {
-    if (p.narrow_qkv == 0 || !narrow_qkv_eligible(epi, p)) return false;
-    if (p.narrow_qkv == 2) return true;
-    return (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) < GEMM_NARROW_QKV_TILES;  // auto: gemm.hpp
+#define NARROW_LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(N_THREADS), 0, stream, p)
+static void launch_narrow(const GemmParams& p, dim3 grid, hipStream_t stream) {
+    if (p.dtype == DT_F16) NARROW_LAUNCH(gemm_narrow_kernel<DT_F16>); else NARROW_LAUNCH(gemm_narrow_kernel<DT_BF16>);
+}
+static void launch_narrow_lo6(const GemmParams& p, dim3 grid, hipStream_t stream) {
+    if (p.dtype == DT_F16) NARROW_LAUNCH(gemm_narrow_lo6_kernel<DT_F16>); else NARROW_LAUNCH(gemm_narrow_lo6_kernel<DT_BF16>);
 }
 template <int DT>
-static int launch_narrow_qkv_t(const GemmParams& p, hipStream_t stream) {
-    const dim3 grid((unsigned)(((p.M + NBM - 1) / NBM) * ((p.N + NBN - 1) / NBN)));
-    if (p.A6) hipLaunchKernelGGL((gemm_nqkv_kernel<DT, true, true>), grid, dim3(N_THREADS), 0, stream, p);
-    else if (p.lo_off != 0) hipLaunchKernelGGL((gemm_nqkv_kernel<DT, true, false>), grid, dim3(N_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL((gemm_nqkv_kernel<DT, false, false>), grid, dim3(N_THREADS), 0, stream, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { blim_set_error("narrow qkv gemm launch failed: %s", hipGetErrorString(e)); return BLIM_ERR_HIP; }
-    g_narrow_qkv_launches.fetch_add(1);
-    return BLIM_OK;
+static void launch_narrow_qkv_t(const GemmParams& p, dim3 grid, hipStream_t stream) {
+    if (p.A6) NARROW_LAUNCH(gemm_nqkv_kernel<DT, true, true>);
+    else if (p.lo_off != 0) NARROW_LAUNCH(gemm_nqkv_kernel<DT, true, false>);
+    else NARROW_LAUNCH(gemm_nqkv_kernel<DT, false, false>);
 }
-static int launch_narrow_qkv(const GemmParams& p, hipStream_t stream) {
-    return p.dtype == DT_F16 ? launch_narrow_qkv_t<DT_F16>(p, stream) : launch_narrow_qkv_t<DT_BF16>(p, stream);
+static void launch_narrow_qkv(const GemmParams& p, dim3 grid, hipStream_t stream) {
+    if (p.dtype == DT_F16) launch_narrow_qkv_t<DT_F16>(p, grid, stream); else launch_narrow_qkv_t<DT_BF16>(p, grid, stream);
 }
-static int launch_narrow(const GemmParams& p, hipStream_t stream) {
-    const dim3 grid((unsigned)(((p.M + NBM - 1) / NBM) * ((p.N + NBN - 1) / NBN)));
-    if (p.dtype == DT_F16) hipLaunchKernelGGL((gemm_narrow_kernel<DT_F16>), grid, dim3(N_THREADS), 0, stream, p);
-    else hipLaunchKernelGGL((gemm_narrow_kernel<DT_BF16>), grid, dim3(N_THREADS), 0, stream, p);
+#undef NARROW_LAUNCH
+// One row per form, tried in this order (under EPI_RESID: plain, then lo6).  Each has a launch counter of its own (without it a bit-equality test passes vacuously
+// on a library that ignores the field) and a threshold of its own for the auto rule (gemm.hpp).
+struct NarrowForm {
+    int GemmParams::*field;
+    const char* name;            // error text: the field, the kernel it selects (range check), the launch (hipGetLastError)
+    const char* kernel;
+    const char* tag;
+    bool (*eligible)(GemmEpi, const GemmParams&);
+    int threshold;
+    void (*launch)(const GemmParams&, dim3, hipStream_t);
+    std::atomic<int64_t> launches;
+};
+static NarrowForm g_narrow_forms[3] = {
+    {&GemmParams::narrow, "narrow", "the narrow kernel", "narrow", narrow_eligible, GEMM_NARROW_TILES, launch_narrow, {0}},
+    {&GemmParams::narrow_lo6, "narrow_lo6", "the narrow e2m3 kernel", "narrow lo6", narrow_lo6_eligible, GEMM_NARROW_LO6_TILES, launch_narrow_lo6, {0}},
+    {&GemmParams::narrow_qkv, "narrow_qkv", "the narrow QKV kernel", "narrow qkv", narrow_qkv_eligible, GEMM_NARROW_QKV_TILES, launch_narrow_qkv, {0}},
+};
+extern "C" int64_t blim_gemm_narrow_launches(void) { return g_narrow_forms[0].launches.load(); }
+extern "C" int32_t blim_gemm_narrow_threshold(void) { return g_narrow_forms[0].threshold; }
+extern "C" int64_t blim_gemm_narrow_lo6_launches(void) { return g_narrow_forms[1].launches.load(); }
+extern "C" int32_t blim_gemm_narrow_lo6_threshold(void) { return g_narrow_forms[1].threshold; }
+extern "C" int64_t blim_gemm_narrow_qkv_launches(void) { return g_narrow_forms[2].launches.load(); }
+extern "C" int32_t blim_gemm_narrow_qkv_threshold(void) { return g_narrow_forms[2].threshold; }
+// The first form that is switched on (2, or 1 = auto: fewer 256 x 256 tiles than its threshold) and eligible for this call; nullptr: the 256 x 256 kernel's call
+static NarrowForm* narrow_chosen(GemmEpi epi, const GemmParams& p) {
+    for (NarrowForm& f : g_narrow_forms) {
+        const int v = p.*f.field;
+        if (v == 0 || !f.eligible(epi, p)) continue;
+        if (v == 2 || (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN) < f.threshold) return &f;
+    }
+    return nullptr;
+}
+static int launch_narrow_form(NarrowForm& f, const GemmParams& p, hipStream_t stream) {
+    f.launch(p, dim3((unsigned)(((p.M + NBM - 1) / NBM) * ((p.N + NBN - 1) / NBN))), stream);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { blim_set_error("narrow gemm launch failed: %s", hipGetErrorString(e)); return BLIM_ERR_HIP; }
-    g_narrow_launches.fetch_add(1);
+    if (e != hipSuccess) { blim_set_error("%s gemm launch failed: %s", f.tag, hipGetErrorString(e)); return BLIM_ERR_HIP; }
+    f.launches.fetch_add(1);
     return BLIM_OK;
 }
 
@@ -1866,9 +1667,8 @@ static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream) {
     ARG_CHECK(!p.out6 || (epi == EPI_SWIGLU && p.A6 && p.lo_off > 0 && p.N % 256 == 0));
     ARG_CHECK(p.w_wrap_k == 0 || (p.K == 2 * p.w_wrap_k && (int64_t)p.w_wrap_k * es % 128 == 0));   // A = [hi | lo]: W is walked twice
     ARG_CHECK(p.lo_off == 0 || epi == EPI_BF16 || epi == EPI_QKV || epi == EPI_SWIGLU);
-    if (p.narrow < 0 || p.narrow > 2) { blim_set_error("gemm: narrow = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = the narrow kernel wherever it is eligible)", p.narrow); return BLIM_ERR_ARG; }
-    if (p.narrow_lo6 < 0 || p.narrow_lo6 > 2) { blim_set_error("gemm: narrow_lo6 = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = the narrow e2m3 kernel wherever it is eligible)", p.narrow_lo6); return BLIM_ERR_ARG; }
-    if (p.narrow_qkv < 0 || p.narrow_qkv > 2) { blim_set_error("gemm: narrow_qkv = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = the narrow QKV kernel wherever it is eligible)", p.narrow_qkv); return BLIM_ERR_ARG; }
+    for (const NarrowForm& f : g_narrow_forms)
+        if (p.*f.field < 0 || p.*f.field > 2) { blim_set_error("gemm: %s = %d (0 = the 256 x 256 kernel, 1 = auto, 2 = %s wherever it is eligible)", f.name, p.*f.field, f.kernel); return BLIM_ERR_ARG; }
     ARG_CHECK((int64_t)p.M * p.lda * es < (1ll << 32) && (int64_t)p.N * (p.w_wrap_k > 0 ? p.w_wrap_k : p.K) * es < (1ll << 32));  // 32-bit operand offsets
     switch (epi) {
         case EPI_BF16:
@@ -1879,12 +1679,11 @@ static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream) {
         case EPI_F32: ARG_CHECK(p.C && p.bias == nullptr); return launch_t<EPI_F32>(p, stream);
         case EPI_RESID:
             ARG_CHECK(p.C && p.ldc % 4 == 0);
-            if (narrow_chosen(epi, p)) return launch_narrow(p, stream);
-            if (narrow_lo6_chosen(epi, p)) return launch_narrow_lo6(p, stream);
+            if (NarrowForm* f = narrow_chosen(epi, p)) return launch_narrow_form(*f, p, stream);
             return launch_t<EPI_RESID>(p, stream);
         case EPI_QKV:
             ARG_CHECK(p.C && p.bias && p.rope_rows && p.rope_stride >= p.M && p.N % 128 == 0 && p.rope_cols % 128 == 0 && p.ldc % 4 == 0);
-            if (narrow_qkv_chosen(epi, p)) return launch_narrow_qkv(p, stream);
+            if (NarrowForm* f = narrow_chosen(epi, p)) return launch_narrow_form(*f, p, stream);
             return launch_t<EPI_QKV>(p, stream);
         case EPI_SWIGLU: ARG_CHECK(p.C && p.N % 32 == 0 && p.ldc % 4 == 0); return launch_t<EPI_SWIGLU>(p, stream);
         case EPI_LSE: ARG_CHECK(p.labels && p.lse_part && p.label_logit); return launch_t<EPI_LSE>(p, stream);

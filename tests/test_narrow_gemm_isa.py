@@ -3,14 +3,12 @@ compiled code object's metadata as tests/test_isa_guards.py reads its kernels': 
 threads -- and every gemm_kernel instantiation that existed before the narrow kernel is still there.  Register, scratch and LDS figures only."""
 import os
 import re
-import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "blim_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+import gemm_isa
+
+pytestmark = pytest.mark.skipif(not os.path.exists(gemm_isa.HIPCC), reason="hipcc not installed")
 
 # gemm_kernel<EPI, DT, SPLIT, MXA> as launch_t instantiates them (gemm.hip): the plain kernels of six epilogues x three dtypes, the split (hi | lo) outputs of the
 # three 16-bit epilogues, the e2m3 second pass (plain outputs: RESID, SWIGLU, LSE; split outputs: QKV, SWIGLU) and the fp8 down projection with an MX-scaled A
@@ -19,18 +17,8 @@ WIDE = ({(e, d, 0, 0) for e in range(6) for d in range(3)} | {(e, d, 1, 0) for e
 
 
 @pytest.fixture(scope="module")
-def metadata(tmp_path_factory):
-    """{mangled kernel name: {field: int}} of gemm.hip compiled for gfx950."""
-    out = os.path.join(str(tmp_path_factory.mktemp("narrow_isa")), "gemm.s")
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-S", os.path.join(CSRC, "gemm.hip"), "-o", out],
-                   check=True, cwd=CSRC, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = {}
-    for m in re.finditer(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", text, re.S):
-        blk = m.group(0)
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(v) for k, v in re.findall(r"\.(group_segment_fixed_size|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|max_flat_workgroup_size|vgpr_count):\s+(\d+)", blk)}
-    return meta
+def metadata():
+    return gemm_isa.metadata()
 
 
 def test_narrow_kernel_resources(metadata):

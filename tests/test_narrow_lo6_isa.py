@@ -4,31 +4,18 @@ VGPR, no scratch, at most 64 KiB of LDS (two workgroups per CU), 256 threads -- 
 still there.  Register, scratch and LDS figures only."""
 import os
 import re
-import subprocess
 
 import pytest
 
+import gemm_isa
 from test_narrow_gemm_isa import WIDE
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "blim_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
-pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
+pytestmark = pytest.mark.skipif(not os.path.exists(gemm_isa.HIPCC), reason="hipcc not installed")
 
 
 @pytest.fixture(scope="module")
-def metadata(tmp_path_factory):
-    """{mangled kernel name: {field: int}} of gemm.hip compiled for gfx950."""
-    out = os.path.join(str(tmp_path_factory.mktemp("narrow_lo6_isa")), "gemm.s")
-    subprocess.run([HIPCC, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "--cuda-device-only", "-S", os.path.join(CSRC, "gemm.hip"), "-o", out],
-                   check=True, cwd=CSRC, stderr=subprocess.DEVNULL)
-    text = open(out).read()
-    meta = {}
-    for m in re.finditer(r"- \.agpr_count:.*?\.wavefront_size:\s+\d+", text, re.S):
-        blk = m.group(0)
-        name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-        meta[name] = {k: int(v) for k, v in re.findall(r"\.(group_segment_fixed_size|private_segment_fixed_size|vgpr_spill_count|sgpr_spill_count|max_flat_workgroup_size|vgpr_count):\s+(\d+)", blk)}
-    return meta
+def metadata():
+    return gemm_isa.metadata()
 
 
 def test_narrow_lo6_kernel_resources(metadata):
