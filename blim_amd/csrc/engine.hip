@@ -1700,6 +1700,35 @@ extern "C" int blim_gemm_f8(const void* A8, int64_t lda, const float* a_scale, c
     GemmParams p = gp8(A8, lda, a_scale, W8, w_scale, M, N, K, C, ldc);
     return launch_gemm(EPI_BF16, p, (hipStream_t)stream);
 }
+// The scoring path's row kernels alone (tests; blim.h): plain pass-throughs to the launchers of kernels.hpp -- no engine, no state.  The launchers check the
+// arguments the engine itself could get wrong; the entries add the ones only a caller of raw pointers can (the dtype, a row stride shorter than the row).
+extern "C" int blim_rmsnorm(const blim_rmsnorm_args* args, void* stream) {
+    ARG_CHECK(args && args->struct_bytes >= (int64_t)sizeof(blim_rmsnorm_args));
+    const blim_rmsnorm_args& a = *args;
+    ARG_CHECK(a.dtype16 == BLIM_COMPUTE_BF16 || a.dtype16 == BLIM_COMPUTE_F16);
+    ARG_CHECK(a.H > 0 && a.ldx >= a.H && (a.ldo == 0 || a.ldo >= a.H) && a.n_rows <= 0x7fffffffll && (!a.rows || a.n_src > 0));
+    return launch_rmsnorm(a.x, a.ldx, a.rows, a.n_rows, a.H, a.w, a.eps, (bf16_t*)a.out16, a.dtype16 == BLIM_COMPUTE_F16 ? DT_F16 : DT_BF16, a.out_f32, (hipStream_t)stream,
+                          a.n_src, a.ldo, (bf16_t*)a.out_lo, a.saturate != 0, (uint8_t*)a.out6);
+}
+extern "C" int blim_rmsnorm_f8(const float* x, int64_t ldx, int64_t n_rows, int32_t H, const float* w, float eps, void* out8, float* scale, void* stream) {
+    ARG_CHECK(H > 0 && ldx >= H);
+    return launch_rmsnorm_f8(x, ldx, n_rows, H, w, eps, (uint8_t*)out8, scale, (hipStream_t)stream);
+}
+extern "C" int blim_lse_combine(const float* part, int32_t n_tiles, const float* label_logit, const int32_t* labels, int64_t n_rows, float* logprob, void* stream) {
+    return launch_lse_combine((const float2*)part, n_tiles, label_logit, labels, n_rows, logprob, (hipStream_t)stream);
+}
+extern "C" int blim_tvg_criterion(const float* logits, int64_t ld, int32_t n_vocab, const int32_t* labels, int32_t n_pairs, int32_t clips, float* score, void* stream) {
+    ARG_CHECK(ld >= n_vocab);
+    return launch_tvg_score(logits, ld, n_vocab, labels, n_pairs, clips, score, (hipStream_t)stream);
+}
+extern "C" int blim_group_mean_rows(void* out, const void* in, int64_t n_out, int32_t group, int32_t H, int32_t dtype16, int32_t split, void* stream) {
+    ARG_CHECK(dtype16 == BLIM_COMPUTE_BF16 || dtype16 == BLIM_COMPUTE_F16);
+    return launch_group_mean((bf16_t*)out, (const bf16_t*)in, n_out, group, H, dtype16 == BLIM_COMPUTE_F16 ? DT_F16 : DT_BF16, (hipStream_t)stream, split != 0);
+}
+extern "C" int blim_assemble_rows(void* out, const int32_t* src_index, int64_t n_tokens, int32_t H, const void* table, const void* feats, int32_t split, void* stream) {
+    ARG_CHECK(H > 0);
+    return launch_assemble((bf16_t*)out, src_index, n_tokens, H, (const bf16_t*)table, (const bf16_t*)feats, (hipStream_t)stream, split != 0);
+}
 // The decoder's attention as a building block (tests): fills AttnParams / AttnPcParams as decode_impl does and launches.  The argument errors are reported here
 // (the launchers repeat theirs), so that the host-only build of this file sees them too.
 extern "C" int blim_attention(const blim_attention_args* args, void* stream) {

@@ -97,6 +97,13 @@ class RmsnormBwdArgs(C.Structure):
                 ("seed", C.c_uint64)]
 
 
+class RmsnormArgs(C.Structure):
+    """blim_rmsnorm_args (include/blim.h)."""
+    _fields_ = [("struct_bytes", C.c_int64), ("x", C.c_void_p), ("ldx", C.c_int64), ("rows", C.c_void_p), ("n_rows", C.c_int64), ("n_src", C.c_int64),
+                ("H", C.c_int32), ("dtype16", C.c_int32), ("w", C.c_void_p), ("eps", C.c_float), ("saturate", C.c_int32), ("out16", C.c_void_p),
+                ("ldo", C.c_int64), ("out_lo", C.c_void_p), ("out_f32", C.c_void_p), ("out6", C.c_void_p)]
+
+
 LORA_DB, LORA_DU, LORA_DA = 1, 2, 4
 
 
@@ -190,6 +197,12 @@ def load_library(path: str = LIB_PATH):
         "blim_adamw_raw": ([vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, f32, i32, vp], C.c_int),
         "blim_grad_stats_workspace_bytes": ([i64], C.c_int64),
         "blim_grad_stats_raw": ([vp, i64, f32, vp, vp, i64, vp], C.c_int),
+        "blim_rmsnorm": ([C.POINTER(RmsnormArgs), vp], C.c_int),
+        "blim_rmsnorm_f8": ([vp, i64, i64, i32, vp, f32, vp, vp, vp], C.c_int),
+        "blim_lse_combine": ([vp, i32, vp, vp, i64, vp, vp], C.c_int),
+        "blim_tvg_criterion": ([vp, i64, i32, vp, i32, i32, vp, vp], C.c_int),
+        "blim_group_mean_rows": ([vp, vp, i64, i32, i32, i32, i32, vp], C.c_int),
+        "blim_assemble_rows": ([vp, vp, i64, i32, vp, vp, i32, vp], C.c_int),
         "blim_gemm": ([C.POINTER(GemmArgs), vp], C.c_int),
         "blim_gemm_narrow_launches": ([], C.c_int64),
         "blim_gemm_narrow_threshold": ([], C.c_int32),
@@ -727,14 +740,58 @@ class PrefixCache:
         return self.engine.score_tvg(batch, embeds, rows, vocab_clip_major, labels, cache=self, pfx_slot=pfx_slot, slots_used=slots_used, admits=admits)
 
 
-def ce_rows(logits, labels):
-    """logprob[r] = log_softmax(logits[r])[labels[r]] (0 where labels[r] < 0); logits f32 [n, V], labels int32 [n]."""
+def ce_rows(logits, labels, V: Optional[int] = None):
+    """logprob[r] = log_softmax(logits[r, :V])[labels[r]] (0 where labels[r] < 0); logits f32 [n, ld], labels int32 [n]; V = ld unless given."""
     import torch
     lib = load_library()
-    n, v = logits.shape
+    n, ld = logits.shape
     out = torch.empty(n, dtype=torch.float32, device=logits.device)
-    _check(lib.blim_ce_rows(None, _ptr(logits), v, v, _ptr(labels), n, _ptr(out), _stream()), "blim_ce_rows")
+    _check(lib.blim_ce_rows(None, _ptr(logits), ld, ld if V is None else V, _ptr(labels), n, _ptr(out), _stream()), "blim_ce_rows")
     return out
+
+
+# ---- the scoring path's row kernels alone (tests; include/blim.h): pass-throughs to the launchers of csrc/kernels.hip over caller-owned device tensors.
+def rmsnorm(x, w, eps: float, n_rows: int, H: int, dtype: str, ldx: Optional[int] = None, rows=None, n_src: int = 0, out16=None, ldo: int = 0, out_lo=None,
+            lo_offset: Optional[int] = None, out_f32=None, saturate: bool = True, out6=None):
+    """blim_rmsnorm: x f32 [*, ldx], w f32 [H]; out16 16-bit rows of stride ldo (0 = H), out_lo a tensor of its own or, with lo_offset, that many 16-bit elements
+    into out16 (the [hi | lo] rows of the compensated mode); out_f32 f32 [n_rows, H]; out6 uint8 [f6_tiles_bytes(n_rows, H)]."""
+    a = RmsnormArgs()
+    a.struct_bytes = C.sizeof(RmsnormArgs)
+    a.x = _ptr(x); a.ldx = x.shape[1] if ldx is None else ldx; a.rows = _ptr(rows); a.n_rows = n_rows; a.n_src = n_src; a.H = H; a.dtype16 = COMPUTE_DTYPES[dtype]
+    a.w = _ptr(w); a.eps = eps; a.saturate = int(saturate); a.out16 = _ptr(out16); a.ldo = ldo
+    a.out_lo = _ptr(out16) + 2 * lo_offset if lo_offset is not None else _ptr(out_lo)
+    a.out_f32 = _ptr(out_f32); a.out6 = _ptr(out6)
+    _check(load_library().blim_rmsnorm(C.byref(a), _stream()), "blim_rmsnorm")
+
+
+def f6_tiles_bytes(n_rows: int, K: int) -> int:
+    return int(load_library().blim_f6_tiles_bytes(n_rows, K))
+
+
+def rmsnorm_f8(x, w, eps: float, n_rows: int, H: int, out8, scale, ldx: Optional[int] = None):
+    """blim_rmsnorm_f8: out8 uint8 [n_rows, H] e4m3 bytes, scale f32 [n_rows]."""
+    _check(load_library().blim_rmsnorm_f8(_ptr(x), x.shape[1] if ldx is None else ldx, n_rows, H, _ptr(w), eps, _ptr(out8), _ptr(scale), _stream()), "blim_rmsnorm_f8")
+
+
+def lse_combine(part, label_logit, labels, logprob):
+    """blim_lse_combine: part f32 [n_rows, n_tiles, 2] = (max, sum exp) partials; logprob f32 [>= n_rows] is written."""
+    n_rows, n_tiles = part.shape[0], part.shape[1]
+    _check(load_library().blim_lse_combine(_ptr(part), n_tiles, _ptr(label_logit), _ptr(labels), n_rows, _ptr(logprob), _stream()), "blim_lse_combine")
+
+
+def tvg_criterion(logits, n_vocab: int, labels, n_pairs: int, clips: int, score):
+    """blim_tvg_criterion: logits f32 [n_pairs * clips, ld], labels int32 [n_pairs]; score f32 [>= n_pairs] is written."""
+    _check(load_library().blim_tvg_criterion(_ptr(logits), logits.shape[1], n_vocab, _ptr(labels), n_pairs, clips, _ptr(score), _stream()), "blim_tvg_criterion")
+
+
+def group_mean_rows(out, inp, n_out: int, group: int, H: int, dtype: str, split: bool = False):
+    """blim_group_mean_rows: inp 16-bit [n_out * group, H] (split: 2 H) -> out [n_out, H] (split: 2 H)."""
+    _check(load_library().blim_group_mean_rows(_ptr(out), _ptr(inp), n_out, group, H, COMPUTE_DTYPES[dtype], int(split), _stream()), "blim_group_mean_rows")
+
+
+def assemble_rows(out, src_index, n_tokens: int, H: int, table, feats, split: bool = False):
+    """blim_assemble_rows: out[t] = table[src[t]] (src[t] >= 0) or feats[-(src[t] + 1)]; split: out / feats rows are [hi | lo] of width 2 H."""
+    _check(load_library().blim_assemble_rows(_ptr(out), _ptr(src_index), n_tokens, H, _ptr(table), _ptr(feats), int(split), _stream()), "blim_assemble_rows")
 
 
 def segment_mean(logprob, row_start, mode: int = 0):

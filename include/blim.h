@@ -513,6 +513,46 @@ int blim_adamw_raw(float* p, const float* g, float* exp_avg, float* exp_avg_sq, 
 int64_t blim_grad_stats_workspace_bytes(int64_t n);
 int blim_grad_stats_raw(const float* g, int64_t n, float inv_scale, float* stats, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The scoring path's row kernels alone (tests; additive in ABI v9): the forward RMSNorm in every kernel and output form, the log-sum-exp combine behind
+ * blim_vtg_logprobs, the TVG criterion, the clip mean and the sequence assembly of csrc/kernels.hip, each a plain pass-through to the launcher the engine calls
+ * (csrc/kernels.hpp states the operations), over raw device pointers: no engine, no state.  blim_ce_rows and blim_segment_mean above already are such
+ * pass-throughs.  Labels, table and feature indices are NOT guarded by these kernels: they must be in range.  Only blim_rmsnorm's gather index is guarded.
+ *
+ * blim_rmsnorm: row i of the outputs = w * x[rows ? rows[i] : i, :] * rsqrt(mean(x^2) + eps), x f32 rows of stride ldx; rows (int32 [n_rows]) gathers among
+ * n_src source rows -- an index outside [0, n_src) gives a poisoned row: NaN in out16 and out_f32, zeros in out_lo and in the row's blocks of out6.
+ * out16 16-bit rows of stride ldo (0 = H), out_lo = 16-bit(o - f32(out16)) with the same stride (needs out16), out_f32 f32 [n_rows, H]; at least one of
+ * out16 / out_f32.  saturate: fp16 stores clamp to +-65504 instead of overflowing to inf.  out6: the lo parts as the e2m3 operand tiles of the consuming GEMM,
+ * blim_f6_tiles_bytes(n_rows, H) bytes, the rows up to the next multiple of 256 zero -- needs out16, H % 128 == 0, 256 < H <= 4096, ldo % 8 == 0.
+ * H % 4 == 0, H <= 4096, ldx % 4 == 0, ldo % 4 == 0; x, w, out_f32 16-byte aligned, out16 / out_lo 8-byte (16 where ldo % 8 == 0 and H % 8 == 0). */
+typedef struct blim_rmsnorm_args {
+    int64_t struct_bytes;
+    const float* x;
+    int64_t ldx;
+    const int32_t* rows;
+    int64_t n_rows, n_src;
+    int32_t H, dtype16;
+    const float* w;
+    float eps;
+    int32_t saturate;
+    void* out16;
+    int64_t ldo;
+    void* out_lo;
+    float* out_f32;
+    void* out6;
+} blim_rmsnorm_args;
+int blim_rmsnorm(const blim_rmsnorm_args* args, void* stream);
+/* The fp8 engines' RMSNorm: out8 e4m3 [n_rows, H] = the row / scale, scale [n_rows] = max|row| / 448 (1 for an all-zero row). */
+int blim_rmsnorm_f8(const float* x, int64_t ldx, int64_t n_rows, int32_t H, const float* w, float eps, void* out8, float* scale, void* stream);
+/* logprob[r] = labels[r] < 0 ? 0 : label_logit[r] - logsumexp of row r's n_tiles (max, sum exp(x - max)) partials; part f32 [n_rows, n_tiles, 2], a tile
+ * without columns is (-inf, 0). */
+int blim_lse_combine(const float* part, int32_t n_tiles, const float* label_logit, const int32_t* labels, int64_t n_rows, float* logprob, void* stream);
+/* score[p] = mean over c < clips of log_softmax(logits[p * clips + c, :n_vocab])[labels[p]]; logits f32 rows of stride ld >= n_vocab. */
+int blim_tvg_criterion(const float* logits, int64_t ld, int32_t n_vocab, const int32_t* labels, int32_t n_pairs, int32_t clips, float* score, void* stream);
+/* blim_group_mean / blim_assemble with the engine's fields as arguments: H, the 16-bit type, the embedding table (16-bit [*, H]) and split -- rows [hi | lo] of
+ * width 2 H (feature rows and outputs; a table row's lo half is zero).  H % 8 == 0 for the assembly, H % 4 == 0 for the mean. */
+int blim_group_mean_rows(void* out, const void* in, int64_t n_out, int32_t group, int32_t H, int32_t dtype16, int32_t split, void* stream);
+int blim_assemble_rows(void* out, const int32_t* src_index, int64_t n_tokens, int32_t H, const void* table, const void* feats, int32_t split, void* stream);
+
 /* The GEMM kernel alone (tests; additive in ABI v9): C [M, N] = A [M, K] . W [N, K]^T with every epilogue and operand form the engine and the trainer launch,
  * chosen by the same fields they set (csrc/gemm.hpp states them; a zero / NULL field is "off").  A: row stride lda, W: row stride K (w_wrap_k when set).
  * dtype BLIM_COMPUTE_BF16 / _F16: A, W and 16-bit outputs in that format; BLIM_COMPUTE_F8: A, W e4m3 bytes with row_scale [M] (or the E8M0 table a_mx) and

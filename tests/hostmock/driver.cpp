@@ -571,12 +571,47 @@ static void train_kernel_calls() {
     EXPECT(blim_grad_stats_raw(f32a.data(), 257, 1.f, stats.data(), ws, 4092, nullptr) == BLIM_ERR_ARG && strstr(blim_last_error(), "workspace"));
 }
 
+// the scoring path's row kernels alone (blim.h): pass-throughs -- the launchers are mocked here, so what is seen is the entries' own argument checks
+static void score_kernel_calls() {
+    const int H = 384, n = 5;
+    std::vector<float> x((size_t)n * (H + 12), 0.f), w(H, 1.f), of((size_t)n * H, 0.f), part((size_t)n * 3 * 2, 0.f), ll(n, 0.f), lp(n, 0.f), sc(n, 0.f);
+    std::vector<uint16_t> o16((size_t)n * 2 * H, 0), in16((size_t)n * 3 * 2 * H, 0), table((size_t)4 * H, 0);
+    std::vector<uint8_t> o6((size_t)blim_f6_tiles_bytes(n, H), 0), o8((size_t)n * H, 0);
+    std::vector<int32_t> rows = {3, 1, 0, -1, 4}, labels(n, 2), src = {0, -1, 3, -2, 1};
+    blim_rmsnorm_args a;
+    memset(&a, 0, sizeof a);
+    a.struct_bytes = sizeof a; a.x = x.data(); a.ldx = H + 12; a.n_rows = n; a.H = H; a.dtype16 = BLIM_COMPUTE_F16; a.w = w.data(); a.eps = 1e-6f; a.saturate = 1;
+    a.out16 = o16.data(); a.ldo = 2 * H; a.out_lo = o16.data() + H; a.out_f32 = of.data(); a.out6 = o6.data();
+    const blim_rmsnorm_args good = a;
+    EXPECT(blim_rmsnorm(&a, nullptr) == 0);
+    a.rows = rows.data(); a.n_src = 4; a.dtype16 = BLIM_COMPUTE_BF16; a.out_lo = nullptr; a.ldo = 0;
+    EXPECT(blim_rmsnorm(&a, nullptr) == 0);
+    EXPECT(blim_rmsnorm(nullptr, nullptr) == BLIM_ERR_ARG);
+    a = good; a.struct_bytes = 8;               EXPECT(blim_rmsnorm(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.dtype16 = BLIM_COMPUTE_F8;      EXPECT(blim_rmsnorm(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.H = 0;                          EXPECT(blim_rmsnorm(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.ldx = H - 4;                    EXPECT(blim_rmsnorm(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.ldo = H - 4;                    EXPECT(blim_rmsnorm(&a, nullptr) == BLIM_ERR_ARG);
+    a = good; a.rows = rows.data(); a.n_src = 0; EXPECT(blim_rmsnorm(&a, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_rmsnorm_f8(x.data(), H + 12, n, H, w.data(), 1e-6f, o8.data(), sc.data(), nullptr) == 0);
+    EXPECT(blim_rmsnorm_f8(x.data(), H - 4, n, H, w.data(), 1e-6f, o8.data(), sc.data(), nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_lse_combine(part.data(), 3, ll.data(), labels.data(), n, lp.data(), nullptr) == 0);
+    EXPECT(blim_tvg_criterion(x.data(), H + 12, H, labels.data(), 1, n, sc.data(), nullptr) == 0);
+    EXPECT(blim_tvg_criterion(x.data(), H - 1, H, labels.data(), 1, n, sc.data(), nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_group_mean_rows(o16.data(), in16.data(), n, 3, H, BLIM_COMPUTE_F16, 1, nullptr) == 0);
+    EXPECT(blim_group_mean_rows(o16.data(), in16.data(), n, 3, H, BLIM_COMPUTE_BF16, 0, nullptr) == 0);
+    EXPECT(blim_group_mean_rows(o16.data(), in16.data(), n, 3, H, BLIM_COMPUTE_F8, 0, nullptr) == BLIM_ERR_ARG);
+    EXPECT(blim_assemble_rows(o16.data(), src.data(), n, H, table.data(), in16.data(), 1, nullptr) == 0);
+    EXPECT(blim_assemble_rows(o16.data(), src.data(), n, 0, table.data(), in16.data(), 0, nullptr) == BLIM_ERR_ARG);
+}
+
 int main() {
     EXPECT(blim_abi_version() == BLIM_ABI_VERSION);
     attention_calls();
     attention_bwd_calls();
     gemm_calls();
     train_kernel_calls();
+    score_kernel_calls();
     blim_engine* e = nullptr;
     // ---- creation: bad configurations, no device
     {
