@@ -758,19 +758,19 @@ GemmParams gp(int dt, const void* A, int64_t lda, const void* W, int64_t M, int 
     return p;
 }
 
-// compensated mode: A = [hi | lo] (K counts both halves, W is walked twice); 16-bit outputs as hi at C and lo at C + lo_off
-static GemmParams gp2(const blim_engine* e, const void* A, int64_t K1, const void* W, int64_t M, int N, void* C, int64_t ldc1, int64_t n_out1, bool split) {
-    const int pf = split ? 2 : 1;
-    GemmParams p = gp(e->c.compute_dtype, A, pf * K1, W, M, N, (int)(pf * K1), C, pf * ldc1);
-    if (split) { p.w_wrap_k = (int)K1; p.lo_off = n_out1; }
-    return p;
-}
-
-// one unit of a layer (option "precise_layers"): the rows are `lay` halves wide ([hi | lo] for lay = 2, whether or not this unit reads the lo half); split = the product
-// takes both halves (gp2), lo_out = 16-bit outputs leave as hi at C and lo at C + n_out1; a plain unit over [hi | lo] rows reads their hi halves only (lda = lay * K1)
-static GemmParams gp3(const blim_engine* e, const void* A, int64_t K1, const void* W, int64_t M, int N, void* C, int64_t ldc1, int64_t n_out1, int lay, bool split, bool lo_out) {
-    GemmParams p = split ? gp2(e, A, K1, W, M, N, C, ldc1, n_out1, true) : gp(e->c.compute_dtype, A, lay * K1, W, M, N, (int)K1, C, lay * ldc1);
-    p.lo_off = lo_out ? n_out1 : 0;
+// A 16-bit GEMM over rows of `lay` halves of width K1 ([hi | lo] for lay = 2) against W [N, K1].  The form decides every field:
+//   plain (comp = false):          the hi halves alone (lda = lay * K1, K = K1) -- a plain unit over [hi | lo] rows reads their hi halves only;
+//   compensated, A6 == nullptr:    A = [hi | lo], K counts both halves and W is walked twice (w_wrap_k = K1);
+//   compensated, A6 != nullptr:    option "precise_lo6" -- the plain product of the hi halves plus, in the same kernel and into the same accumulators (gemm.hip, phase 2),
+//                                  the e2m3 pass over the lo halves' operand tiles A6 (kernels.hpp: launch_f6_tiles, or written by the producer) against W's e2m3 image W6.
+// C / ldc / lo_off are the output as it really is: 16-bit outputs leave as hi at C and lo at C + lo_off (0 = no lo output).
+static GemmParams gp_hilo(int dt, const void* rows, int64_t K1, int lay, const void* W, const uint8_t* W6, int64_t n, int N, void* C, int64_t ldc, int64_t lo_off, bool comp,
+                          const uint8_t* A6) {
+    const bool wrap = comp && !A6;
+    GemmParams p = gp(dt, rows, (comp ? 2 : lay) * K1, W, n, N, (int)(wrap ? 2 * K1 : K1), C, ldc);
+    p.lo_off = lo_off;
+    if (wrap) p.w_wrap_k = (int)K1;
+    if (comp && A6) { p.A6 = A6; p.W6 = W6; p.K6 = (int)K1; }
     return p;
 }
 
@@ -796,9 +796,9 @@ extern "C" int blim_project_video(blim_engine* e, const void* feats, int64_t n_r
     if (e->precise) p1.lo_off = Ha;
     TRY(launch_gemm(EPI_BF16, p1, s));
     if (G) TRY(adapter_u(e, e->proj_tmp.p, (int64_t)pf * Ha, e->precise ? Ha : 0, n_rows, H, &e->ad_mlp[which][1], nullptr, nullptr, s));
-    GemmParams p2 = gp(e->c.compute_dtype, e->proj_tmp.p, (int64_t)pf * Ha, G ? (const void*)e->w2_aug[which] : (const void*)e->mlp_w2[which], n_rows, H, pf * Ha, out, (int64_t)pf * H);
+    GemmParams p2 = gp_hilo(e->c.compute_dtype, e->proj_tmp.p, Ha, pf, G ? (const void*)e->w2_aug[which] : (const void*)e->mlp_w2[which], nullptr, n_rows, H, out, (int64_t)pf * H,
+                            e->precise ? H : 0, e->precise, nullptr);
     p2.bias = e->mlp_b2[which];
-    if (e->precise) { p2.w_wrap_k = Ha; p2.lo_off = H; }
     TRY(launch_gemm(EPI_BF16, p2, s));
     return BLIM_OK;
 }
@@ -831,6 +831,17 @@ int engine_rope_rows(blim_engine* e, const blim_batch* b, hipStream_t s, float**
     *out = (float*)e->rope_rows.p; *stride = round_up(T, 256);
     return BLIM_OK;
 }
+
+// option "precise_lo6": the lo halves of [hi | lo] rows of half-width K1 as e2m3 operand tiles in the a6 workspace -- the A6 of the GEMM that follows (gp_hilo).  A launch of
+// its own, timed as TC_QUANT inside the GEMM's span
+static int lo6_tiles(blim_engine* e, hipStream_t s, const bf16_t* rows, int64_t K1, int64_t n, const uint8_t** A6) {
+    SpanGuard gq(e, s, TC_QUANT, 0);
+    TRY(launch_f6_tiles(rows + K1, 2 * K1, n, (int)K1, e->c.compute_dtype, false, (uint8_t*)e->a6.p, s));
+    *A6 = (const uint8_t*)e->a6.p;
+    return BLIM_OK;
+}
+// the decoder layers' o_proj and down launches: options "narrow_gemm" (the plain and w_wrap_k forms) and "narrow_lo6" (the e2m3 second pass); fp8 keeps the 256 x 256 kernel
+static GemmParams narrowed(GemmParams p, const blim_engine* e) { p.narrow = e->narrow_gemm; p.narrow_lo6 = e->narrow_lo6; return p; }
 
 // live_rows / n_live (optional): the rows of the final hidden state the caller will read.  In the LAST layer every other row is dead after the
 // attention (its K / V were needed, its own output is not): the live rows' attention outputs and residuals are gathered and o_proj, the norm
@@ -881,9 +892,8 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
     auto unit_bits = [&](int li) -> int { return masked ? (int)e->layer_bits[li] : e->precise ? (pm ? 15 : 3) : 0; };
     if (e->precise && e->f8) { blim_set_error("option 'precise' needs a 16-bit engine (fp16 or bf16)"); return BLIM_ERR_STATE; }
     // option "precise_lo6": a compensated GEMM = its plain fp16 pass over the hi part + an e2m3 pass over the lo part, in one kernel and into the same accumulators
-    // (gemm.hip, phase 2).  `rows` are [hi | lo] rows (lo at +K elements, row stride ld): the lo halves are written as e2m3 operand tiles into the a6 workspace
-    // (kernels.hpp: launch_f6_tiles) and `p` -- set up as the PLAIN product of the hi halves -- gets the second pass attached; w6 is the matrix's e2m3 image.  With
-    // adapters apart the adapted projections use the augmented weights' images.
+    // (gp_hilo's third form).  The lo halves reach it as e2m3 operand tiles: written into the a6 workspace by lo6_tiles right before the GEMM, or by the rows' producer
+    // (below).  With adapters apart the adapted projections use the augmented weights' images.
     const bool lo6 = e->lo6 && e->precise;
     if (lo6) TRY(ensure(e->a6, f6_tiles_bytes(T, (int)std::max<int64_t>(I, Hq))));
     const bool fuse6_ok = lo6 && e->lo6_fuse && (e->lo6_fuse_mask & 1) && (2 * I) % 256 == 0;    // the gate | up epilogue writes the down GEMM's A6 tiles (gemm.hpp: out6) into a second buffer
@@ -895,12 +905,8 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
     // norm2 -> gate | up input (no adapters on the MLP)
     const bool n1_tiles_ok = lo6 && e->lo6_fuse && (e->lo6_fuse_mask & 2) && !G && rmsnorm_can_write_tiles((int)H, H, pf * Hq);
     const bool n2_tiles_ok = lo6 && e->lo6_fuse && (e->lo6_fuse_mask & 2) && rmsnorm_can_write_tiles((int)H, H, pfm * H);
-    auto attach_lo6_ready = [&](GemmParams& p, int K, const uint8_t* w6) { p.A6 = (const uint8_t*)e->a6.p; p.W6 = w6; p.K6 = K; };
-    auto attach_lo6 = [&](GemmParams& p, const bf16_t* rows, int64_t ld, int64_t n, int K, const uint8_t* w6) -> int {
-        { SpanGuard gq(e, s, TC_QUANT, 0); TRY(launch_f6_tiles(rows + K, ld, n, K, c.compute_dtype, false, (uint8_t*)e->a6.p, s)); }
-        p.A6 = (const uint8_t*)e->a6.p; p.W6 = w6; p.K6 = K;
-        return BLIM_OK;
-    };
+    const int dt = c.compute_dtype;
+    const uint8_t* a6 = (const uint8_t*)e->a6.p; const uint8_t* a6b = (const uint8_t*)e->a6b.p;
     for (int li = 0; li < c.num_layers; ++li) {
         const LayerW& l = e->L[li];
         const int ub = unit_bits(li);
@@ -912,17 +918,16 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
 #ifdef ENGINE_ABLATE_NORMFOLD   // timing-only build (make ablate_normfold; profiles/r06_normfold_bound.md): plain calls skip every RMSNorm pass a residual epilogue could have produced
             else if (!e->precise && !G && li > 0 && e->lse_part.p) { }
 #endif
-            else TRY(launch_rmsnorm(resid, H, nullptr, T, H, l.norm1, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pf * Hq, (cA && !n1_tiles) ? xn + Hq : nullptr, true, n1_tiles ? (uint8_t*)e->a6.p : nullptr));
+            else TRY(launch_rmsnorm(resid, H, nullptr, T, H, l.norm1, c.rms_eps, xn, dt, nullptr, s, 0, pf * Hq, (cA && !n1_tiles) ? xn + Hq : nullptr, true, n1_tiles ? (uint8_t*)a6 : nullptr));
             if (G) TRY(adapter_u(e, xn, pf * Hq, cA ? Hq : 0, T, H, &e->AD[li].ad[0], &e->AD[li].ad[1], &e->AD[li].ad[2], s));
         }
         {
             SpanGuard g(e, s, TC_GEMM_QKV, 2.0 * tok * Hq * e->qkv_n * (cA ? 2 : 1));
+            const uint8_t* t6 = n1_tiles ? a6 : nullptr;
+            if (lo6 && cA && !n1_tiles) TRY(lo6_tiles(e, s, xn, Hq, T, &t6));
             GemmParams p = q8 ? gp8(x8, H, sx, l.wqkv8, l.sqkv, T, e->qkv_n, H, qkv, e->qkv_n)
-                              : gp3(e, xn, Hq, G ? (const void*)e->AD[li].wqkv_aug : (const void*)l.wqkv, T, e->qkv_n, qkv, e->qkv_n, e->qkv_n, pf, cA, cA);
-            if (lo6 && cA) {                                                                    // hi part in fp16, lo part in e2m3; [hi | lo] outputs as before
-                p = gp(c.compute_dtype, xn, 2 * Hq, G ? (const void*)e->AD[li].wqkv_aug : (const void*)l.wqkv, T, e->qkv_n, (int)Hq, qkv, 2 * (int64_t)e->qkv_n); p.lo_off = e->qkv_n;
-                if (n1_tiles) attach_lo6_ready(p, (int)Hq, l.wqkv6); else TRY(attach_lo6(p, xn, 2 * Hq, T, (int)Hq, G ? e->AD[li].wqkv_aug6 : l.wqkv6));
-            }
+                              : gp_hilo(dt, xn, Hq, pf, G ? (const void*)e->AD[li].wqkv_aug : (const void*)l.wqkv, G ? e->AD[li].wqkv_aug6 : l.wqkv6, T, e->qkv_n, qkv, (int64_t)pf * e->qkv_n,
+                                        cA ? e->qkv_n : 0, cA, t6);
             p.bias = l.bqkv; p.rope_cols = (c.num_heads + c.num_kv_heads) * 128; p.rope_rows = rope_rows; p.rope_stride = round_up(T, 256);
             p.narrow_qkv = e->narrow_qkv;                                 // option "narrow_qkv": every 16-bit form of this launch is eligible; fp8 keeps the 256 x 256 kernel
             TRY(launch_gemm(EPI_QKV, p, s));
@@ -937,7 +942,7 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
         {
             SpanGuard g(e, s, TC_ATTN, 0);
             AttnParams a;
-            a.dtype = c.compute_dtype;
+            a.dtype = dt;
             a.qkv = qkv; a.ldq = (int64_t)pf * e->qkv_n; a.num_heads = c.num_heads; a.num_kv_heads = c.num_kv_heads;
             a.key_visible = b->key_visible; a.seq_start = b->seq_start; a.seq_len = b->seq_len; a.pfx_start = b->pfx_start; a.pfx_len = b->pfx_len;
             a.blk_seq = b->blk_seq; a.blk_q0 = b->blk_q0; a.own_start = b->own_start; a.n_blocks = b->n_blocks; a.out = attn; a.ldo = (int64_t)pf * Hq; a.scale = 0.08838834764831845f;
@@ -957,91 +962,66 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
             if (e->masked_query_zero) TRY(launch_zero_rows(attn, (int64_t)pf * Hq, b->key_visible, T, (int)(pf * Hq), s));
         }
         const bool fuse_o = o8 && e->f8_fuse;
-        if (o8 && !fuse_o) { SpanGuard g(e, s, TC_QUANT, 0); TRY(launch_quant_rows(attn, H, T, H, c.compute_dtype, a8, sa, s)); }
-        if (prune && li == c.num_layers - 1) {
-            // ---- last layer, live rows only: gather (attention output -> the free `act` workspace, residual -> resid_live), then the same four kernels on n_live rows
-            bf16_t* attn_live = act;                                         // [n_live, pf * Hq] 16-bit (act is not in use until the gate|up GEMM below)
-            float* rl = (float*)e->resid_live.p;
-            {
-                SpanGuard g0(e, s, TC_MISC, 0);
-                TRY(launch_gather_rows(attn_live, attn, live_rows, n_live, (int64_t)pf * Hq * 2, T, 0u, s));
-                if (G) TRY(adapter_u(e, attn_live, (int64_t)pf * Hq, cO ? Hq : 0, n_live, H, &e->AD[li].ad[3], nullptr, nullptr, s));
-                TRY(launch_gather_rows(rl, resid, live_rows, n_live, (int64_t)H * 4, T, 0x7fc00000u, s));      // a row outside the batch: NaN (poisoned score)
-            }
-            const double tl = (double)n_live;
-            { SpanGuard g(e, s, TC_GEMM_O, 2.0 * tl * Hq * H * (cO ? 2 : 1));
-              GemmParams p = gp3(e, attn_live, Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, n_live, H, rl, H, 0, pf, cO, false); p.ldc = H; p.lo_off = 0;
-              if (lo6 && cO) { p = gp(c.compute_dtype, attn_live, 2 * Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, n_live, H, (int)Hq, rl, H);
-                         TRY(attach_lo6(p, attn_live, 2 * Hq, n_live, (int)Hq, G ? e->AD[li].wo_aug6 : l.wo6)); }
-              p.narrow = e->narrow_gemm; p.narrow_lo6 = e->narrow_lo6; TRY(launch_gemm(EPI_RESID, p, s)); }
-            { SpanGuard g(e, s, TC_NORM, 0);
-              TRY(launch_rmsnorm(rl, H, nullptr, n_live, H, l.norm2, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pfm * H, (cG && !n2_tiles) ? xn + H : nullptr, true, n2_tiles ? (uint8_t*)e->a6.p : nullptr)); }
-            // SwiGLU output [n_live, pfm * I]: `act` holds attn_live only until o_proj above has run (stream order), so it is free again here
-            { SpanGuard g(e, s, TC_GEMM_GATEUP, 4.0 * tl * H * I * (cG ? 2 : 1));
-              GemmParams p = gp3(e, xn, H, l.wgu, n_live, 2 * I, act, I, I, pfm, cG, cD);
-              if (lo6 && cG) { p = gp(c.compute_dtype, xn, 2 * (int64_t)H, l.wgu, n_live, 2 * I, H, act, 2 * (int64_t)I); p.lo_off = cD ? I : 0; if (n2_tiles) attach_lo6_ready(p, (int)H, l.wgu6); else TRY(attach_lo6(p, xn, 2 * (int64_t)H, n_live, H, l.wgu6)); if (fuse6) p.out6 = (uint8_t*)e->a6b.p; }
-              TRY(launch_gemm(EPI_SWIGLU, p, s)); }
-            { SpanGuard g(e, s, TC_GEMM_DOWN, 2.0 * tl * H * I * (cD ? 2 : 1));
-              GemmParams p = gp3(e, act, I, l.wd, n_live, H, rl, H, 0, pfm, cD, false); p.ldc = H; p.lo_off = 0;
-              if (lo6 && cD) { p = gp(c.compute_dtype, act, 2 * (int64_t)I, l.wd, n_live, H, I, rl, H); if (fuse6) { p.A6 = (const uint8_t*)e->a6b.p; p.W6 = l.wd6; p.K6 = (int)I; } else TRY(attach_lo6(p, act, 2 * (int64_t)I, n_live, I, l.wd6)); }
-              p.narrow = e->narrow_gemm; p.narrow_lo6 = e->narrow_lo6; TRY(launch_gemm(EPI_RESID, p, s)); }
-            *final_resid = rl; *final_is_live = true;
-            break;
+        if (o8 && !fuse_o) { SpanGuard g(e, s, TC_QUANT, 0); TRY(launch_quant_rows(attn, H, T, H, dt, a8, sa, s)); }
+        // ---- the post-attention half of the layer: o_proj -> norm 2 -> gate|up -> down over `n` rows: attention outputs `ao`, residual stream `res`.  Every row of the
+        // batch -- or, in the last layer of a call that names its rows, those rows alone (`pruned`).  prune requires !e->f8, so every fp8 flag below is false on pruned rows
+        const bool pruned = prune && li == c.num_layers - 1;
+        bf16_t* ao = attn; int64_t n = T; float* res = resid;
+        if (pruned) {       // gather: attention output -> the free `act` workspace [n_live, pf * Hq] (not in use until the gate|up GEMM), residual -> resid_live
+            SpanGuard g(e, s, TC_MISC, 0);
+            ao = act; n = n_live; res = (float*)e->resid_live.p;
+            TRY(launch_gather_rows(ao, attn, live_rows, n, (int64_t)pf * Hq * 2, T, 0u, s));
+            if (G) TRY(adapter_u(e, ao, (int64_t)pf * Hq, cO ? Hq : 0, n, H, &e->AD[li].ad[3], nullptr, nullptr, s));
+            TRY(launch_gather_rows(res, resid, live_rows, n, (int64_t)H * 4, T, 0x7fc00000u, s));      // a row outside the batch: NaN (poisoned score)
+        } else if (G) {
+            SpanGuard g(e, s, TC_MISC, 0);
+            TRY(adapter_u(e, ao, (int64_t)pf * Hq, cO ? Hq : 0, n, H, &e->AD[li].ad[3], nullptr, nullptr, s));
         }
-        if (G) { SpanGuard g(e, s, TC_MISC, 0); TRY(adapter_u(e, attn, (int64_t)pf * Hq, cO ? Hq : 0, T, H, &e->AD[li].ad[3], nullptr, nullptr, s)); }
+        const double rows = (double)n;
         {
-            SpanGuard g(e, s, TC_GEMM_O, 2.0 * tok * Hq * H * (cO ? 2 : 1));
-            GemmParams p = o8 ? gp8(a8, H, fuse_o ? nullptr : sa, l.wo8, l.so, T, H, H, resid, H)
-                              : gp3(e, attn, Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, T, H, resid, H, 0, pf, cO, false);
+            SpanGuard g(e, s, TC_GEMM_O, 2.0 * rows * Hq * H * (cO ? 2 : 1));
+            const uint8_t* t6 = nullptr;
+            if (lo6 && cO) TRY(lo6_tiles(e, s, ao, Hq, n, &t6));
+            GemmParams p = o8 ? gp8(a8, H, fuse_o ? nullptr : sa, l.wo8, l.so, n, H, H, res, H)
+                              : gp_hilo(dt, ao, Hq, pf, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, G ? e->AD[li].wo_aug6 : l.wo6, n, H, res, H, 0, cO, t6);
             if (fuse_o) { p.a_mx = (const uint8_t*)e->attn_mx.p; p.mx_stride = Tp; }
-            p.ldc = H; p.lo_off = 0;
-            if (lo6 && cO) {
-                p = gp(c.compute_dtype, attn, 2 * Hq, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, T, H, (int)Hq, resid, H);
-                TRY(attach_lo6(p, attn, 2 * Hq, T, (int)Hq, G ? e->AD[li].wo_aug6 : l.wo6));
-            }
 #ifdef ENGINE_ABLATE_NORMFOLD
-            if (!e->precise && !G && !o8 && e->lse_part.p) { p.swiglu_act = (uint16_t*)xn; p.swiglu_act_ld = H; p.col_scale = l.norm2; p.lse_part = (float2*)e->lse_part.p; }
+            if (!pruned && !e->precise && !G && !o8 && e->lse_part.p) { p.swiglu_act = (uint16_t*)xn; p.swiglu_act_ld = H; p.col_scale = l.norm2; p.lse_part = (float2*)e->lse_part.p; }
 #endif
-            p.narrow = e->narrow_gemm; p.narrow_lo6 = e->narrow_lo6;      // options "narrow_gemm" (the plain and w_wrap_k forms) and "narrow_lo6" (the e2m3 second pass); fp8 keeps the 256 x 256 kernel
-            TRY(launch_gemm(EPI_RESID, p, s));
+            TRY(launch_gemm(EPI_RESID, narrowed(p, e), s));
         }
         {
             SpanGuard g(e, s, TC_NORM, 0);
-            if (g8) TRY(launch_rmsnorm_f8(resid, H, T, H, l.norm2, c.rms_eps, x8, sx, s));
+            if (g8) TRY(launch_rmsnorm_f8(res, H, n, H, l.norm2, c.rms_eps, x8, sx, s));
 #ifdef ENGINE_ABLATE_NORMFOLD
-            else if (!e->precise && !G && e->lse_part.p) { }
+            else if (!pruned && !e->precise && !G && e->lse_part.p) { }
 #endif
-            else TRY(launch_rmsnorm(resid, H, nullptr, T, H, l.norm2, c.rms_eps, xn, c.compute_dtype, nullptr, s, 0, pfm * H, (cG && !n2_tiles) ? xn + H : nullptr, true, n2_tiles ? (uint8_t*)e->a6.p : nullptr));
+            else TRY(launch_rmsnorm(res, H, nullptr, n, H, l.norm2, c.rms_eps, xn, dt, nullptr, s, 0, pfm * H, (cG && !n2_tiles) ? xn + H : nullptr, true, n2_tiles ? (uint8_t*)a6 : nullptr));
         }
         const bool fuse = g8 && d8 && e->f8_fuse;      // fp8: the gate|up epilogue emits e4m3 + one E8M0 scale per (token, 128 outputs) itself
-        {
-            SpanGuard g(e, s, TC_GEMM_GATEUP, 4.0 * tok * H * I * (cG ? 2 : 1));
-            GemmParams p = g8 ? gp8(x8, H, sx, l.wgu8, l.sgu, T, 2 * I, H, act, I) : gp3(e, xn, H, l.wgu, T, 2 * I, act, I, I, pfm, cG, cD);
-            if (fuse) { p.C = act8; p.ldc = I; p.out_mx = (uint8_t*)e->act_mx.p; p.mx_stride = Tp; }
-            if (lo6 && cG) {
-                p = gp(c.compute_dtype, xn, 2 * (int64_t)H, l.wgu, T, 2 * I, H, act, 2 * (int64_t)I); p.lo_off = cD ? I : 0;
-                if (n2_tiles) attach_lo6_ready(p, (int)H, l.wgu6); else TRY(attach_lo6(p, xn, 2 * (int64_t)H, T, H, l.wgu6));
-                if (fuse6) p.out6 = (uint8_t*)e->a6b.p;
-            }
+        {   // SwiGLU output [n, pfm * I] into `act`: on pruned rows it held `ao` only until o_proj above has run (stream order), so it is free again here
+            SpanGuard g(e, s, TC_GEMM_GATEUP, 4.0 * rows * H * I * (cG ? 2 : 1));
+            const uint8_t* t6 = n2_tiles ? a6 : nullptr;
+            if (lo6 && cG && !n2_tiles) TRY(lo6_tiles(e, s, xn, H, n, &t6));
+            GemmParams p = g8 ? gp8(x8, H, sx, l.wgu8, l.sgu, n, 2 * I, H, fuse ? (void*)act8 : (void*)act, I)
+                              : gp_hilo(dt, xn, H, pfm, l.wgu, l.wgu6, n, 2 * I, act, (int64_t)pfm * I, cD ? I : 0, cG, t6);
+            if (fuse) { p.out_mx = (uint8_t*)e->act_mx.p; p.mx_stride = Tp; }
+            if (fuse6) p.out6 = (uint8_t*)a6b;          // the epilogue writes the down GEMM's A6 tiles (gemm.hpp: out6)
             TRY(launch_gemm(EPI_SWIGLU, p, s));
         }
-        if (d8 && !fuse) { SpanGuard g(e, s, TC_QUANT, 0); TRY(launch_quant_rows(act, I, T, I, c.compute_dtype, act8, sact, s)); }
+        if (d8 && !fuse) { SpanGuard g(e, s, TC_QUANT, 0); TRY(launch_quant_rows(act, I, n, I, dt, act8, sact, s)); }
         {
-            SpanGuard g(e, s, TC_GEMM_DOWN, 2.0 * tok * H * I * (cD ? 2 : 1));
-            GemmParams p = d8 ? gp8(act8, I, fuse ? nullptr : sact, l.wd8, l.sd, T, H, I, resid, H) : gp3(e, act, I, l.wd, T, H, resid, H, 0, pfm, cD, false);
+            SpanGuard g(e, s, TC_GEMM_DOWN, 2.0 * rows * H * I * (cD ? 2 : 1));
+            const uint8_t* t6 = fuse6 ? a6b : nullptr;
+            if (lo6 && cD && !fuse6) TRY(lo6_tiles(e, s, act, I, n, &t6));
+            GemmParams p = d8 ? gp8(act8, I, fuse ? nullptr : sact, l.wd8, l.sd, n, H, I, res, H) : gp_hilo(dt, act, I, pfm, l.wd, l.wd6, n, H, res, H, 0, cD, t6);
             if (fuse) { p.a_mx = (const uint8_t*)e->act_mx.p; p.mx_stride = Tp; }
-            p.ldc = H; p.lo_off = 0;
-            if (lo6 && cD) {
-                p = gp(c.compute_dtype, act, 2 * (int64_t)I, l.wd, T, H, I, resid, H);
-                if (fuse6) { p.A6 = (const uint8_t*)e->a6b.p; p.W6 = l.wd6; p.K6 = (int)I; }
-                else TRY(attach_lo6(p, act, 2 * (int64_t)I, T, I, l.wd6));
-            }
 #ifdef ENGINE_ABLATE_NORMFOLD
-            if (!e->precise && !G && !d8 && e->lse_part.p && li + 1 < c.num_layers) { p.swiglu_act = (uint16_t*)xn; p.swiglu_act_ld = H; p.col_scale = e->L[li + 1].norm1; p.lse_part = (float2*)e->lse_part.p; }
+            if (!pruned && !e->precise && !G && !d8 && e->lse_part.p && li + 1 < c.num_layers) { p.swiglu_act = (uint16_t*)xn; p.swiglu_act_ld = H; p.col_scale = e->L[li + 1].norm1; p.lse_part = (float2*)e->lse_part.p; }
 #endif
-            p.narrow = e->narrow_gemm; p.narrow_lo6 = e->narrow_lo6;      // options "narrow_gemm" (the plain and w_wrap_k forms) and "narrow_lo6" (the e2m3 second pass); fp8 keeps the 256 x 256 kernel
-            TRY(launch_gemm(EPI_RESID, p, s));
+            TRY(launch_gemm(EPI_RESID, narrowed(p, e), s));
         }
+        if (pruned) { *final_resid = res; *final_is_live = true; }
     }
     return BLIM_OK;
 }
@@ -1119,16 +1099,16 @@ static int vtg_logprobs_impl(blim_engine* e, const void* hidden_bf16, bool split
     }
     {
         SpanGuard g(e, s, TC_LMHEAD_LSE, 2.0 * n_rows * (double)Hl * V * (split ? 2 : 1));
-        GemmParams p = l8 ? gp8(h8, H, hs, e->lm_head8, e->s_lm, n_rows, V, H, nullptr, 0)
-                          : gp(e->c.compute_dtype, A, Hl, e->aug ? (const void*)e->lm_aug : (const void*)e->lm_head, n_rows, V, (int)Hl, nullptr, 0);
-        if (split) { ARG_CHECK(!l8); p.lda = 2 * Hl; p.K = (int)(2 * Hl); p.w_wrap_k = (int)Hl; }
+        if (split) ARG_CHECK(!l8);
+        const uint8_t* h6 = nullptr;
         if (split && e->lo6 && Hl % 128 == 0) {                          // lo6: the rows' lo parts against the head in e2m3 (gemm.hip phase 2), as in the decoder GEMMs
             TRY(finalize_lo6(e));
             TRY(ensure(e->h6, f6_tiles_bytes(n_rows, (int)Hl)));
             TRY(launch_f6_tiles((const bf16_t*)A + Hl, 2 * Hl, n_rows, (int)Hl, e->c.compute_dtype, false, (uint8_t*)e->h6.p, s));
-            p.K = (int)Hl; p.w_wrap_k = 0;
-            p.A6 = (const uint8_t*)e->h6.p; p.W6 = e->lm6; p.K6 = (int)Hl;
+            h6 = (const uint8_t*)e->h6.p;
         }
+        GemmParams p = l8 ? gp8(h8, H, hs, e->lm_head8, e->s_lm, n_rows, V, H, nullptr, 0)
+                          : gp_hilo(e->c.compute_dtype, A, Hl, split ? 2 : 1, e->aug ? (const void*)e->lm_aug : (const void*)e->lm_head, e->lm6, n_rows, V, nullptr, 0, 0, split, h6);
         p.labels = labels; p.lse_part = (float2*)e->lse_part.p; p.label_logit = (float*)e->lab_logit.p;
         TRY(launch_gemm(EPI_LSE, p, s));
     }
@@ -1148,8 +1128,7 @@ static int lm_head_impl(blim_engine* e, const void* hidden_bf16, bool split, int
     const void* A = hidden_bf16; int64_t Hl = H;
     TRY(lm_head_input(e, hidden_bf16, split, wide, n_rows, (hipStream_t)stream, &A, &Hl));
     SpanGuard g(e, (hipStream_t)stream, TC_GEMM_OTHER, 2.0 * n_rows * (double)Hl * V);
-    GemmParams p = gp(e->c.compute_dtype, A, Hl, e->aug ? (const void*)e->lm_aug : (const void*)e->lm_head, n_rows, V, (int)Hl, logits, V);
-    if (split) { p.lda = 2 * Hl; p.K = (int)(2 * Hl); p.w_wrap_k = (int)Hl; }
+    GemmParams p = gp_hilo(e->c.compute_dtype, A, Hl, split ? 2 : 1, e->aug ? (const void*)e->lm_aug : (const void*)e->lm_head, nullptr, n_rows, V, logits, V, 0, split, nullptr);
     return launch_gemm(EPI_F32, p, (hipStream_t)stream);
 }
 extern "C" int blim_lm_head(blim_engine* e, const void* hidden_bf16, int64_t n_rows, float* logits, void* stream) {
