@@ -21,7 +21,9 @@ deterministic policy (`_PrefixIndex._begin_pass`): free slots first, then the le
 in pinned host memory, and a key that has a record gets a slot back by a copy (blim.h: blim_prefix_cache_export / _import) instead of a decode.
 
 An index follows its scorer: texts that join later (`PairScorer.add_texts`) append keys before the next pass is planned, and
-`GalleryIndex.rerank_requests` scores requests of unequal candidate counts as one pass.
+`GalleryIndex.rerank_requests` scores requests of unequal candidate counts as one pass.  Videos join too (`PairScorer.add_videos`): their keys
+are appended, an eager index fills them into its `spare_slots`, a lazy one admits them on demand, and every memo of a TVG value is keyed by the scorer's
+`vocab_version` -- a video that joins moves the softmax normaliser of every TVG score -- while the cached K / V, the host records and the v2t prior stay.
 
 The shortlist needs no first stage on a fine-tuned checkpoint: `GalleryIndex.shortlist` ranks the whole gallery by the TVG candidate term of
 the blend (`PairScorer.tvg_gallery`: fixed chunks, so a value depends on its text and the gallery alone), `search_requests` reranks the best K with that term reused,
@@ -242,9 +244,13 @@ class _PrefixIndex:
     _changed = ""          # the refill's log line opens with it
 
     def __init__(self, scorer: PairScorer, budget_bytes: Optional[int], priority: Optional[Sequence[int]], log, fill: str = "eager",
-                 host_budget_bytes: Optional[int] = None):
+                 host_budget_bytes: Optional[int] = None, spare_slots: int = 0):
         if fill not in ("eager", "lazy"):
             raise ValueError(f"fill {fill!r}: 'eager' or 'lazy'")
+        if int(spare_slots) < 0 or (int(spare_slots) and fill != "eager"):
+            raise ValueError(f"{type(self).__name__}: spare_slots = {spare_slots}: free slots of an eager cache for the keys that join later, not negative; "
+                             "a lazy index's budget is its capacity already")
+        self.spare_slots = int(spare_slots)
         if host_budget_bytes is not None and fill != "lazy":
             raise ValueError(f"{type(self).__name__}: host_budget_bytes keeps the slots a lazy index evicts; an eager index ({fill!r}) evicts none: use fill='lazy'")
         self.host_budget_bytes = host_budget_bytes
@@ -252,12 +258,13 @@ class _PrefixIndex:
         if fill == "lazy" and priority is not None:
             raise ValueError(f"{type(self).__name__}: priority orders the eager fill; a lazy index follows the queries")
         self.fill = fill
-        self.n_slots = 0                 # lazy: the capacity (eager: len(slot_of))
+        self.n_slots = 0                 # lazy: the capacity (eager: the planned slots and the spare ones)
         self.stats = GalleryStats()
         self._stamp: Dict = {}           # lazy: resident key -> (pass number, position among the pass's keys) of its last use
         self._pass: Optional[_Pass] = None
         self._n_pass = 0
         self._n_texts = 0                # the scorer's texts the keys cover (PairScorer.add_texts: texts join later; _sync_texts)
+        self._n_videos = len(scorer.video)   # ... and its videos (PairScorer.add_videos; _sync_videos)
         self.s = scorer
         self.m, self.engine = scorer.m, scorer.engine
         if getattr(self.engine, "dtype", "") == "f8":
@@ -304,6 +311,7 @@ class _PrefixIndex:
         import time
         import torch
         self._sync_texts()
+        self._sync_videos(fill=False)                # (the keys only: every key is planned below)
         self.resolve_mode(first_stage)
         t0 = time.perf_counter()
         comp = self.compensated()
@@ -317,11 +325,12 @@ class _PrefixIndex:
                 self.cache = self.engine.prefix_cache(self.n_slots, L, comp)
                 if self.host_budget_bytes is not None:
                     self.host = HostTier(self.cache, L, self.host_budget_bytes)
-        else:
-            self.slot_of = slot_plan(self.keys, per, self.budget_bytes, self.priority)
-            self.n_slots = len(self.slot_of)
-            if self.slot_of:
-                self.cache = self.engine.prefix_cache(len(self.slot_of), L, comp)
+        else:                                        # the spare slots count against the budget: they are taken off it before the keys are planned
+            spare = self.spare_slots if self.budget_bytes is None else min(self.spare_slots, int(self.budget_bytes) // max(int(per), 1))
+            self.slot_of = slot_plan(self.keys, per, None if self.budget_bytes is None else int(self.budget_bytes) - spare * int(per), self.priority)
+            self.n_slots = len(self.slot_of) + spare
+            if self.n_slots:
+                self.cache = self.engine.prefix_cache(self.n_slots, L, comp)
                 self._fill(sorted(self.slot_of.items(), key=lambda kv: kv[1]))
         if torch.cuda.is_available():
             torch.cuda.synchronize()
@@ -442,6 +451,7 @@ class _PrefixIndex:
         """pairs [P, 2] (video j, text i) -> the engine calls of one pass, planned by PairScorer's planner over this index's slots (the subclass's _plans)."""
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
         self._sync_texts()
+        self._sync_videos()
         p = self._begin_pass(self._needs(pairs))
         for plan in self._plans(pairs):
             plan.pass_ = p
@@ -483,6 +493,37 @@ class _PrefixIndex:
             self._grow(self._n_texts, n)
             self._n_texts = n
 
+    def _sync_videos(self, fill: bool = True) -> None:
+        """The index follows its scorer: videos that joined since the keys were last derived (PairScorer.add_videos) extend them -- after
+        _sync_texts, so that a new video meets every known split once.  Keys are appended only, so the slots, the recency stamps, the stats and the host tier's
+        records stay valid, and no cache is resized.  A lazy index admits a new key on demand like any miss.  An eager index that was built fills the new keys, in key
+        order, into the slots it still has free (spare_slots) with the fill path of build(); the keys beyond them, and a key longer than a slot, keep the in-batch
+        prefix, as a late text's new split does.  The numeric mode is not resolved again (resolve_mode ran on the gallery build() saw)."""
+        n = len(self.s.video)
+        if n == self._n_videos:
+            return
+        new = self._video_keys(self._n_videos, n)
+        self.keys += new
+        self._n_videos = n
+        if not (fill and new and self.fill == "eager" and self._state is not None and self.cache is not None):
+            return
+        taken = set(self.slot_of.values())
+        free = [sl for sl in range(self.n_slots) if sl not in taken]
+        room = getattr(self.cache, "max_len", None)
+        items = []
+        for k in new:
+            if not free:
+                break
+            if room is None or self.prefix_len(k) <= room:
+                items.append((k, free.pop(0)))
+        if items:
+            self._fill(items)
+            self.slot_of.update(items)
+
+    def _video_keys(self, lo: int, hi: int) -> List:
+        """The keys videos lo .. hi - 1 bring (none where the keys do not name a video)."""
+        return []
+
     # ---- scoring
     def run(self, plan):
         if self.fill == "lazy" and getattr(plan, "pass_", None) is not self._pass:
@@ -516,8 +557,8 @@ class GalleryIndex(_PrefixIndex):
     kind, _changed = "vtg", "gallery: weights or numeric mode"
 
     def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, priority: Optional[Sequence[int]] = None, log=None, fill: str = "eager",
-                 host_budget_bytes: Optional[int] = None):
-        super().__init__(scorer, budget_bytes, priority, log, fill, host_budget_bytes)
+                 host_budget_bytes: Optional[int] = None, spare_slots: int = 0):
+        super().__init__(scorer, budget_bytes, priority, log, fill, host_budget_bytes, spare_slots)
         # the prompt splits of the texts: (pre, post) pairs, in order of first appearance; one key per (video, split), video-major for the texts given here
         self.splits: Dict[Tuple[bytes, bytes], Tuple[np.ndarray, np.ndarray]] = {}
         self.keys: List[Tuple[int, bytes, bytes]] = []
@@ -537,9 +578,13 @@ class GalleryIndex(_PrefixIndex):
             if k not in at:
                 at[k] = len(at); self.splits[k] = (pre, post); new.append(k)
             ids.append(at[k])
-        videos = range(len(self.s.video))
+        videos = range(self._n_videos)               # (the videos the keys cover: one that joined since brings its keys in _sync_videos)
         self.keys += [(j, k[0], k[1]) for j in videos for k in new] if not self.keys else [(j, k[0], k[1]) for k in new for j in videos]
         self._split_id = np.concatenate([self._split_id, np.asarray(ids, dtype=np.int64)])
+
+    def _video_keys(self, lo: int, hi: int) -> List:
+        """Videos lo .. hi - 1 joined: one key per (new video, known split), new videos outermost."""
+        return [(j, k[0], k[1]) for j in range(lo, hi) for k in self.splits]
 
     def prefix_len(self, key) -> int:
         j, pre, post = key
@@ -619,15 +664,17 @@ class GalleryIndex(_PrefixIndex):
         return self.vtg_pairs(pairs).reshape(cand.shape)
 
     def _tvg_state(self):
-        """What a TVG score was computed under: the engine's weights (and adapters) and the TVG calls' compensation."""
+        """What a TVG score was computed under: the engine's weights (and adapters), the TVG calls' compensation and the video vocabulary its softmax runs over
+        (PairScorer.vocab_version: a video that joins moves the normaliser of every TVG score, the priors included)."""
         m = self.m
         if hasattr(m, "tvg_mode"):
             self.s.set_tvg_mode(m.tvg_mode())               # as evaluation() does for a caller's scorer: follow what the model asks for / has resolved NOW
-        return (self.engine.weights_version, self.s.tvg_mode, self.s.split_tvg)
+        return (self.engine.weights_version, self.s.tvg_mode, self.s.split_tvg, self.s.vocab_version)
 
     def _t2v_prior(self, texts, cand) -> np.ndarray:
         """The t2v candidate prior (TVG-CPN) of every (text, video) pair, memoised per the planner's prior key: it does not depend on the query's own tokens.
-        The memo holds for one (weights, TVG mode) state: after a weight, adapter or mode change it is dropped and the priors are computed again."""
+        The memo holds for one (weights, TVG mode, vocabulary) state: after a weight, adapter or mode change, or when videos join (add_videos), it is dropped and
+        the priors are computed again."""
         s = self.s
         state = self._tvg_state()
         if state != self._prior_state:
@@ -787,8 +834,8 @@ class TextGalleryIndex(_PrefixIndex):
     kind, _changed = "tvg", "text gallery: weights or TVG mode"
 
     def __init__(self, scorer: PairScorer, budget_bytes: Optional[int] = None, video_index: Optional[GalleryIndex] = None, log=None, fill: str = "eager",
-                 host_budget_bytes: Optional[int] = None):
-        super().__init__(scorer, budget_bytes, None, log, fill, host_budget_bytes)
+                 host_budget_bytes: Optional[int] = None, spare_slots: int = 0):
+        super().__init__(scorer, budget_bytes, None, log, fill, host_budget_bytes, spare_slots)
         if video_index is not None and video_index.s is not scorer:
             raise ValueError("TextGalleryIndex: video_index must be built on the same scorer")
         self.video_index = video_index
@@ -807,6 +854,13 @@ class TextGalleryIndex(_PrefixIndex):
             if pr is not None and pr.tobytes() not in self.prompts:
                 self.prompts[pr.tobytes()] = pr
                 self.keys.append(pr.tobytes())
+
+    def _sync_videos(self, fill: bool = True) -> None:
+        """A caption prompt holds no video: a video that joins brings no key here, and the video index follows it.  (The v2t prior is kept per (text, token count),
+        VTG-side: it does not depend on the vocabulary and is not dropped.)"""
+        super()._sync_videos(fill)
+        if fill and self.video_index is not None:
+            self.video_index._sync_videos()
 
     def prefix_len(self, key) -> int:
         return len(self.prompts[key])

@@ -110,6 +110,8 @@ def lo6_pass_flops(dims, n_tokens: int, n_rows: int, kind: str, mode=None, prune
 
 class PairScorer(CalibrationMixin):
     """Fused scoring of arbitrary (video, text) pairs.  See the module docstring for what is shared."""
+    vocab_version = 0        # (instance state, set by the constructor; here for the indexes' sake: a scorer that never grew reads as version 0)
+    has_vocab = False
 
     def __init__(self, model, vtg_ids, vtg_masks, vtg_labels, tvg_ids, tvg_masks, tvg_labels, video: Sequence, video_vocab,
                  tvg_video_labels, num_clips: int, max_tokens: int = 24576, precise_tvg: bool = True, feat_chunk: int = 64):
@@ -137,19 +139,13 @@ class PairScorer(CalibrationMixin):
                                        for i in range(len(ids))]
         vtg_rows = strip(vtg_ids, vtg_masks, vtg_labels)
         tvg_rows = strip(tvg_ids, tvg_masks, tvg_labels)
-        self.video = video
-        self.tvg_video_labels = np.asarray(tvg_video_labels).astype(np.int32)
-        # 16-bit engines: the vocabulary is registered with the engine as hi + lo operands (blim_set_video_vocab) and the TVG calls name none; fp8 engines take the
-        # plain 16-bit clip-major copy
+        # the videos given here and the videos that join later (add_videos) go through the same code: the list is the scorer's own, the caller's is left alone
+        self.video: List = []
+        self.tvg_video_labels = np.zeros(0, dtype=np.int32)
         self.vocab_cm, self.n_vocab, self._vocab_src, self._vocab_key = None, 0, None, None
-        if video_vocab is not None:
-            self.n_vocab = int(video_vocab.shape[0])
-            if self.split_tvg and hasattr(self.engine, "set_video_vocab"):
-                self._vocab_src = video_vocab
-                self.engine.set_video_vocab(video_vocab)
-                self._vocab_key = self.engine._vocab_key
-            else:
-                self.vocab_cm = _clip_major_vocab(video_vocab, self.device, self.m.dtype)
+        self.has_vocab = video_vocab is not None
+        self.vocab_version = 0           # bumped whenever videos join: what a TVG normaliser, gallery_feats() and every memo of a TVG value were computed over
+        self._join_videos(list(video), video_vocab, np.asarray(tvg_video_labels).astype(np.int32).reshape(-1))
         self.exec_flops = 0.0            # GEMM FLOPs of the engine calls run so far (executed_flops; bench.py's roofline fractions)
         self.exec_flops_lo6 = 0.0        # ... of which on the e2m3 MFMA (lo6_pass_flops: the compensated modes' second pass under the engine's "precise_lo6")
         self.exec_tokens = 0
@@ -204,6 +200,72 @@ class PairScorer(CalibrationMixin):
         self.vtg_rows += vtg_rows; self.tvg_rows += tvg_rows
         self.vtg_split += [v for v, _ in states]; self.tvg_split += [t for _, t in states]
         return np.arange(first, first + len(states), dtype=np.int64)
+
+    # ---- videos
+    def add_videos(self, videos, vocab_rows=None) -> np.ndarray:
+        """Videos that join the scorer: feature tensors as the constructor takes them ([num_clips, tokens, width], what blim_amd.extract writes).
+        vocab_rows [n, num_clips, mm_hidden] float32: the videos' entries of the TVG vocabulary; None: each video's clip means in float32 (dataloader.py:
+        load_video_feature(v).mean(1)).  Every video is checked before any is added: a bad one raises ValueError and adds nothing.  Existing indices and vocabulary
+        labels never move; the new videos take the indices len(video) .. and the labels n_vocab .., one label each.  A TVG score is a softmax over the vocabulary, so
+        the vocabulary is registered again, whole, and vocab_version is bumped: gallery_feats() and every memo of a TVG value keyed by it are computed again.  A
+        scorer built without a vocabulary (no TVG) refuses vocab_rows and adds the videos without an entry (label -1).  -> the new videos' indices."""
+        videos, rows, labels = self.check_videos(videos, vocab_rows)
+        first = len(self.video)
+        self._join_videos(videos, rows, labels)
+        return np.arange(first, first + len(videos), dtype=np.int64)
+
+    def check_videos(self, videos, vocab_rows=None):
+        """add_videos' checks, changing nothing: -> (the videos, their float32 vocabulary rows or None without a vocabulary, their labels); ValueError for a bad one."""
+        import torch
+        videos = list(videos)
+        C = self.num_clips
+        ndim = len(self.video[0].shape) if self.video else 3
+        width = int(self.video[0].shape[-1]) if self.video else None
+        for n, v in enumerate(videos):
+            shape = tuple(getattr(v, "shape", ()))
+            if len(shape) != ndim or len(shape) < 3:
+                raise ValueError(f"add_videos: video {n} has shape {shape}: a feature tensor of rank {ndim}, [num_clips, tokens, width]")
+            if int(shape[0]) != C:
+                raise ValueError(f"add_videos: video {n} has {shape[0]} clips, the scorer was built with num_clips = {C}")
+            if min(shape) < 1:
+                raise ValueError(f"add_videos: video {n} has an empty dimension {shape}")
+            if width is not None and int(shape[-1]) != width:
+                raise ValueError(f"add_videos: video {n} has feature width {shape[-1]}, the scorer's videos have {width}")
+            width = int(shape[-1])
+        if not self.has_vocab:
+            if vocab_rows is not None:
+                raise ValueError("add_videos: this scorer was built without a video vocabulary (no TVG): it takes no vocab_rows")
+            rows, labels = None, np.full(len(videos), -1, dtype=np.int32)
+        else:
+            M = int(self._vocab_src.shape[-1])
+            if vocab_rows is None:
+                if videos and (ndim != 3 or width != M):
+                    raise ValueError(f"add_videos: the clip-mean rule needs [num_clips, tokens, {M}] features (got rank {ndim}, width {width}): pass vocab_rows")
+                rows = torch.stack([torch.as_tensor(v).float().mean(1) for v in videos]) if videos else torch.zeros((0, C, M), dtype=torch.float32)
+            else:
+                rows = torch.as_tensor(vocab_rows)
+                if tuple(rows.shape) != (len(videos), C, M):
+                    raise ValueError(f"add_videos: vocab_rows has shape {tuple(rows.shape)}, {len(videos)} videos need {(len(videos), C, M)}")
+                rows = rows.to(torch.float32)
+            labels = np.arange(self.n_vocab, self.n_vocab + len(videos), dtype=np.int32)
+        return videos, rows, labels
+
+    def _join_videos(self, videos: List, vocab_rows, labels: np.ndarray) -> None:
+        """The bookkeeping of the constructor's videos (vocab_rows: the dataset's vocabulary, labels: the dataset's, one per video, shared among the captions of a
+        video) and of add_videos' (one row and one label of its own per video): the lists are appended to, the vocabulary is registered whole.  16-bit engines: as
+        hi + lo operands with the engine (blim_set_video_vocab; the TVG calls name none); other engines take the plain 16-bit clip-major copy."""
+        import torch
+        self.video += videos
+        self.tvg_video_labels = np.concatenate([self.tvg_video_labels, labels]).astype(np.int32)
+        if vocab_rows is not None and (self._vocab_src is None or int(vocab_rows.shape[0])):
+            src = vocab_rows if self._vocab_src is None else torch.cat([torch.as_tensor(self._vocab_src).to(torch.float32).cpu(), vocab_rows.to(torch.float32).cpu()], dim=0)
+            self._vocab_src, self.n_vocab = src, int(src.shape[0])
+            if self.split_tvg and hasattr(self.engine, "set_video_vocab"):
+                self.engine.set_video_vocab(src)
+                self._vocab_key = self.engine._vocab_key
+            else:
+                self.vocab_cm = _clip_major_vocab(src, self.device, self.m.dtype)
+        self.vocab_version += 1
 
     def _need_tvg(self, texts) -> None:
         for i in np.unique(np.asarray(texts, dtype=np.int64)):
@@ -534,9 +596,10 @@ class PairScorer(CalibrationMixin):
 
     def gallery_feats(self):
         """The TVG feature rows of every video as ONE device tensor [N * C, Hw], video j's rows at j * C as video_feat(j, True) lays them out (its own values:
-        a concatenation).  Built once per (weights version, split_tvg) and dropped when either changes; a call of iter_tvg_gallery names it as its feature rows."""
+        a concatenation).  Built once per (weights version, split_tvg, vocab_version) and dropped when one changes (add_videos bumps the last: the cached per-video rows
+        stay, the concatenation is made again); a call of iter_tvg_gallery names it as its feature rows."""
         import torch
-        key = (getattr(self.engine, "weights_version", None), bool(self.split_tvg))
+        key = (getattr(self.engine, "weights_version", None), bool(self.split_tvg), self.vocab_version)
         memo = getattr(self, "_gfeat", None)
         if memo is None or memo[0] != key:
             N, C = len(self.video), self.num_clips

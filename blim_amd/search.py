@@ -33,7 +33,18 @@ response token under tokenizer_model_max_length, a fine-tuned blend with c0 < 1 
 fewer are there, and scores the batch as ONE pass (GalleryIndex.search_requests: the shortlist requests of a batch share one stage-1 pass, all requests one VTG pass)
 -- the same scores as one pass per request, bit for bit on the VTG term and on a shortlist's stage 1.  Texts join the
 scorer at run time (PairScorer.add_texts); identical `text` / `rows` queries share one text index.  At EOF a `serve:` stderr line counts requests, batches, the mean
-batch size, errors and texts added.
+batch size, errors and texts added (and, once a video was added, `videos_added`).
+
+Videos join a running gallery too.  A request `{"id", "add_video": {"vid": NAME, "features": PATH}}` -- PATH a feature file as blim_amd.extract
+writes it, read with torch.load(weights_only=True) -- is answered with {"id", "added": NAME, "index": j, "videos": N}; it is validated in full first (the file, the
+tensor's shape, a `vid` the gallery does not know yet, features whose content no video added at run time has: engine.hash_device) and a bad one gets its error line.
+An add is a barrier in the stream: a micro-batch never spans it, the requests in front of it are scored against the old gallery and those behind it against the new,
+where `candidates` may name NAME; answers stay in arrival order.  The video's vocabulary row is its clip mean (dataloader.py's rule) and the whole vocabulary is
+registered again, so every later TVG score is normalised over the grown gallery; a run-time video has no first-stage score (a zero term under `--candidates all`).
+`--gallery_spare S` (eager fill) keeps S free slots, counted against `--gallery_gb`, that such videos' prefixes are filled into; beyond them, and always under
+`--gallery_fill lazy`, they are served as any miss.  `--direction v2t --query_video FILE [FILE ...]`: the files' videos join before the indexes are built and the
+captions are ranked for each (`"query": "video:<basename>"`; `--candidates all | tvg`, `iv2` is refused: no first-stage row).  All outside videos of one run share one
+vocabulary, so a TVG term depends on which others were given.
 """
 from __future__ import annotations
 
@@ -70,7 +81,12 @@ def get_args_parser():
                    help="iv2: the first stage's top --topk; all: the whole gallery; tvg (fine-tuned checkpoints, --resume): the whole gallery ranked by the TVG likelihood, "
                         "the best --shortlist reranked")
     p.add_argument("--shortlist", default=None, type=int, metavar="K", help="--candidates tvg: candidates kept from the TVG ranking of the gallery (default: --topk)")
+    p.add_argument("--query_video", default=[], type=str, nargs="*", metavar="FILE",
+                   help="--direction v2t: feature files of videos outside the dataset ([num_clips, tokens, width] tensors as blim_amd.extract writes them) used as queries; "
+                        "they join the scorer (PairScorer.add_videos) before the indexes are built.  --candidates all | tvg")
     p.add_argument("--gallery_gb", default=None, type=float, help="device memory for the prefix cache (default: every video)")
+    p.add_argument("--gallery_spare", default=0, type=int, metavar="S",
+                   help="--gallery_fill eager: S free slots beyond the planned ones, for the videos that join at run time (--serve: add_video).  They count against --gallery_gb")
     p.add_argument("--text_gallery_gb", default=None, type=float, help="v2t: device memory for the caption-prompt cache (default: every distinct prompt)")
     p.add_argument("--gallery_fill", default="eager", choices=["eager", "lazy"],
                    help="eager: every prefix under the budget is computed before the first query; lazy: nothing is, --gallery_gb / --text_gallery_gb are capacities, a "
@@ -126,6 +142,11 @@ def check_args(args, world: int = 1) -> None:
             raise SystemExit(f"search: --{flag} needs --gallery_fill lazy (the host tier keeps the slots a lazy cache evicts; an eager cache is filled once and evicts none)")
         if getattr(args, flag, None) is not None and getattr(args, flag) < 0:
             raise SystemExit(f"search: --{flag} must not be negative")
+    spare = getattr(args, "gallery_spare", 0)
+    if spare < 0:
+        raise SystemExit("search: --gallery_spare must not be negative")
+    if spare and args.gallery_fill != "eager":
+        raise SystemExit("search: --gallery_spare keeps free slots in an eager cache (--gallery_fill eager); a lazy cache admits a video that joins on demand, under --gallery_gb")
     v2t = getattr(args, "direction", "t2v") == "v2t"
     if args.c is None:                        # the likelihood of the direction alone: t2v c0 = c2 = 1; v2t c1 = 0, c3 = 1
         args.c = [1.0, 0.0, 1.0, 1.0] if v2t else [1.0, 0.0, 1.0, 0.0]
@@ -142,9 +163,14 @@ def check_args(args, world: int = 1) -> None:
     if v2t:
         if args.query or args.query_ids:
             raise SystemExit("search: --direction v2t takes video queries (--video_ids), not --query / --query_ids")
-        if not args.video_ids:
+        outside = getattr(args, "query_video", None)
+        if not args.video_ids and not outside:
             raise SystemExit("search: --direction v2t needs --video_ids")
+        if outside and args.candidates == "iv2":
+            raise SystemExit("search: --query_video: a video outside the dataset has no first-stage row (--candidates iv2): use --candidates all, or tvg with --resume")
     else:
+        if getattr(args, "query_video", None):
+            raise SystemExit("search: --query_video files are the queries of --direction v2t (t2v takes --query_ids and / or --query)")
         if getattr(args, "video_ids", None):
             raise SystemExit("search: --video_ids are the queries of --direction v2t (t2v takes --query_ids and / or --query)")
         if not args.query_ids and not args.query and not serve:
@@ -173,6 +199,22 @@ def check_args(args, world: int = 1) -> None:
         raise SystemExit("search: --second_pass auto is not supported (it is measured by evaluation()): give e2m3 or 16bit")
 
 
+def load_video_features(path):
+    """A video's feature file (blim_amd.extract's output: one tensor [num_clips, tokens, width]) -> the tensor, on the host.  ValueError when it cannot be read as one."""
+    import pickle
+
+    import torch
+    if not isinstance(path, str) or not path:
+        raise ValueError("features must be the path of a feature file")
+    try:
+        t = torch.load(path, map_location="cpu", weights_only=True)
+    except (OSError, RuntimeError, ValueError, EOFError, pickle.UnpicklingError) as e:
+        raise ValueError(f"cannot read the feature file {path!r} ({type(e).__name__})") from None
+    if not isinstance(t, torch.Tensor) or not t.is_floating_point():
+        raise ValueError(f"the feature file {path!r} does not hold one floating-point tensor")
+    return t
+
+
 class BadRequest(ValueError):
     """A request that gets an error line; the process goes on."""
 
@@ -182,7 +224,7 @@ class Server:
     query (a `text` / `rows` query joins the scorer through PairScorer.add_texts, with its checks), its candidates -- before it enters a batch, so a bad request
     cannot fail the pass its neighbours are scored in.  Identical `text` / `rows` queries share the text index of the first one (a dict from row bytes to index)."""
 
-    def __init__(self, gal, vids, n_captions: int, t2v_iv2, args, finetuned: bool = False, build_rows=None):
+    def __init__(self, gal, vids, n_captions: int, t2v_iv2, args, finetuned: bool = False, build_rows=None, content_hash=None):
         import numpy as np
         self.np = np
         self.gal, self.s = gal, gal.s
@@ -193,7 +235,9 @@ class Server:
         self.n_captions, self.t2v_iv2, self.args, self.finetuned, self.build_rows = int(n_captions), t2v_iv2, args, bool(finetuned), build_rows
         self.n_vid = np.array([int(np.prod(v.shape[-3:-1])) for v in self.s.video], dtype=np.int64)      # video tokens of each prefix, as the planner counts them
         self.text_of = {}                          # row bytes -> text index
-        self.requests = self.batches = self.errors = self.texts_added = 0
+        self.content_hash = content_hash           # feature tensor -> a digest of its content (engine.hash_device on the device copy), or None: contents are not compared
+        self.content_of = {}                       # digest -> the id of the run-time video that has this content
+        self.requests = self.batches = self.errors = self.texts_added = self.videos_added = 0
 
     # ---- one request
     def _rows(self, req):
@@ -277,7 +321,8 @@ class Server:
         else:
             cand = np.arange(N)
             if self.t2v_iv2 is not None and is_caption:
-                fs = np.asarray(self.t2v_iv2[t], dtype=np.float32)[cand]
+                row = np.asarray(self.t2v_iv2[t], dtype=np.float32)
+                fs = np.concatenate([row, np.zeros(max(N - len(row), 0), np.float32)])[cand]     # (a video that joined at run time has no first-stage score: a zero term)
         if "first_stage" in req:
             try:
                 fs = np.asarray(req["first_stage"], dtype=np.float32).reshape(-1)
@@ -311,6 +356,8 @@ class Server:
             if isinstance(rid, (dict, list)):
                 rid = None
                 raise BadRequest("id must be a JSON scalar")
+            if "add_video" in req:
+                return self._add_request(rid, req)
             topk = req.get("topk")
             if topk is not None and (isinstance(topk, bool) or not isinstance(topk, int) or topk < 1):
                 raise BadRequest("topk must be a positive integer")
@@ -327,22 +374,80 @@ class Server:
             e.id = rid
             raise
 
+    # ---- a video that joins
+    def _add_request(self, rid, req):
+        """`{"id", "add_video": {"vid", "features"}}`, validated in full before anything changes -> dict(id, add: (vid, tensor, digest))."""
+        if any(k in req for k in ("caption", "text", "rows", "candidates", "candidate_idx", "first_stage", "shortlist", "topk")):
+            raise BadRequest("an add_video request carries no query")
+        a = req["add_video"]
+        if not isinstance(a, dict) or set(a) != {"vid", "features"}:
+            raise BadRequest("add_video takes vid (the new video's id) and features (the path of its feature file)")
+        vid = a["vid"]
+        if isinstance(vid, (bool, dict, list)) or vid is None or str(vid) == "":
+            raise BadRequest("vid must be a non-empty string or a number")
+        if str(vid) in self.vid_at:
+            raise BadRequest(f"video id {vid!r} is already in the gallery")
+        try:
+            feat = load_video_features(a["features"])
+            self.s.check_videos([feat])
+        except ValueError as e:
+            raise BadRequest(str(e)) from None
+        digest = None
+        if self.content_hash is not None:
+            digest = self.content_hash(feat)
+            if digest in self.content_of:
+                raise BadRequest(f"these features are those of video {self.content_of[digest]!r}, added earlier")
+        return {"id": rid, "add": (vid, feat, digest)}
+
+    def _add(self, item, write) -> None:
+        """The video joins: the scorer (its vocabulary registered again), the id map; the index follows before its next pass (GalleryIndex._sync_videos)."""
+        vid, feat, digest = item["add"]
+        try:
+            j = int(self.s.add_videos([feat])[0])
+        except ValueError as e:                    # (parse checked it already: what it did not foresee)
+            self.errors += 1
+            write(json.dumps({"id": item["id"], "error": str(e)}))
+            return
+        self.vids.append(vid if isinstance(vid, str) else str(vid))
+        self.vid_at[str(vid)] = j
+        self.n_vid = self.np.append(self.n_vid, int(self.np.prod(feat.shape[-3:-1])))
+        if digest is not None:
+            self.content_of[digest] = self.vids[-1]
+        self.videos_added += 1
+        write(json.dumps({"id": item["id"], "added": self.vids[-1], "index": j, "videos": len(self.vids)}))
+
     # ---- one batch
     def _score(self, reqs):
         a = self.args
         return self.gal.search_requests([(r["text"], r["cand"], r["fs"], r["shortlist"]) for r in reqs], cpn=a.cpn, alpha=a.alpha, c=a.c, finetuned=self.finetuned)
 
     def handle(self, lines, write) -> None:
-        """The requests that arrived together: every good one is scored in ONE search_requests pass; one answer line per request, in arrival order."""
+        """The requests that arrived together: every good one is scored in ONE search_requests pass; one answer line per request, in arrival order.  An add_video
+        request is a barrier: the requests in front of it are parsed, scored against the gallery as it is and answered, then the video joins and is answered, and only
+        then are the requests behind it read -- they may name the new video, and their passes see the new gallery."""
         lines = [ln for ln in lines if ln.strip()]
         if not lines:
             return
+        self.batches += 1
         items = []
         for ln in lines:
             try:
-                items.append(self.parse(ln))
+                item = self.parse(ln)
             except BadRequest as e:
-                items.append(e)
+                item = e
+            if isinstance(item, dict) and "add" in item:
+                self._answer(items, write)
+                items = []
+                self.requests += 1
+                self._add(item, write)
+            else:
+                items.append(item)
+        self._answer(items, write)
+
+    def _answer(self, items, write) -> None:
+        """The parsed requests of one stretch without an add: one pass, one line each."""
+        if not items:
+            return
         good = [r for r in items if isinstance(r, dict)]
         if good:
             try:
@@ -357,7 +462,6 @@ class Server:
             for r, res in zip(good, results):
                 r["result"] = res
         self.requests += len(items)
-        self.batches += 1
         for r in items:
             res = r if isinstance(r, BadRequest) else r["result"]
             if isinstance(res, BadRequest):
@@ -370,8 +474,9 @@ class Server:
             write(json.dumps({"id": r["id"], "query": r["query"], "videos": [self.vids[int(j)] for j in order[:k]], "scores": [float(x) for x in blended[:k]], **more}))
 
     def summary(self):
+        more = {"videos_added": self.videos_added} if self.videos_added else {}             # (a stream without an add_video request: the line it always was)
         return {"requests": self.requests, "batches": self.batches, "mean_batch": self.requests / self.batches if self.batches else 0.0, "errors": self.errors,
-                "texts_added": self.texts_added}
+                "texts_added": self.texts_added, **more}
 
 
 def serve(lines, write, server, batch_queries: int = 1, batch_wait_ms: float = 0.0):
@@ -490,8 +595,16 @@ def main(args):
     scorer = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, vocab, vlab, args.num_clips, max_tokens=args.max_tokens)
     budget = None if args.gallery_gb is None else int(args.gallery_gb * 2**30)
     host = None if args.gallery_host_gb is None else int(args.gallery_host_gb * 2**30)
-    gal = GalleryIndex(scorer, budget_bytes=budget, fill=args.gallery_fill, host_budget_bytes=host)
+    n_dataset = len(video)
+    if getattr(args, "query_video", None):       # v2t: videos outside the dataset join the scorer before the indexes are built; they share one vocabulary
+        try:
+            scorer.add_videos([load_video_features(f) for f in args.query_video])
+        except ValueError as e:
+            raise SystemExit(f"search: --query_video: {e}") from None
+        vids = list(vids) + [os.path.basename(f) for f in args.query_video]
+    gal = GalleryIndex(scorer, budget_bytes=budget, fill=args.gallery_fill, host_budget_bytes=host, spare_slots=getattr(args, "gallery_spare", 0))
     if args.direction == "v2t":
+        args.video_ids = list(args.video_ids) + list(range(n_dataset, len(vids)))
         return _main_v2t(args, model, scorer, gal, v2t_iv2, vids, len(tvg_ids), t0)
     gal.build(first_stage=None if t2v_iv2 is None else np.ascontiguousarray(np.asarray(t2v_iv2, dtype=np.float32).T))     # v2t first stage: calibration sample
     print(f"gallery: {len(video)} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'} of {gal.cache.bytes // max(gal.n_slots, 1) if gal.cache else 0} bytes, "
@@ -508,7 +621,9 @@ def main(args):
             print(line, flush=True)
             if out:
                 out.write(line + "\n")
-        server = Server(gal, vids, len(vtg_ids), t2v_iv2, args, finetuned=bool(args.resume), build_rows=build_rows)
+        from .engine import hash_device
+        content_hash = lambda feat: hash_device(feat.contiguous().to(model.device))      # (one upload and one pass over a feature tensor: a fraction of the projection that follows)
+        server = Server(gal, vids, len(vtg_ids), t2v_iv2, args, finetuned=bool(args.resume), build_rows=build_rows, content_hash=content_hash)
         summary = serve(sys.stdin, write, server, args.batch_queries, args.batch_wait_ms)
         if out:
             out.close()
@@ -601,7 +716,7 @@ def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) 
                 fs = row[cand]
             else:
                 cand = np.arange(n_texts)[None]
-                fs = None if v2t_iv2 is None else np.asarray(v2t_iv2[v], dtype=np.float32)[cand]
+                fs = None if v2t_iv2 is None or v >= len(v2t_iv2) else np.asarray(v2t_iv2[v], dtype=np.float32)[cand]     # (--query_video: no first-stage row)
             order, blended = tg.rerank([v], cand, first_stage=fs, cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
         line = json.dumps({"query": f"video:{vids[v]}", "texts": [int(i) for i in order[0]], "scores": [float(x) for x in blended[0]], **more})
         print(line, flush=True)

@@ -62,7 +62,16 @@ eager index: ms per query with stage 1's and stage 2's shares; stage 1 taken apa
 `all` top-1 / top-10 lie inside the shortlist -- on random weights, which says nothing about a trained checkpoint.  Every repetition is checked bit-equal to the
 leg's first run, and the shortlisted answers bit-equal across the group sizes.
 
-    python tools/gallery_bench.py --shortlist 16 64 256 --modes none --tvg_modes attn --n 1000 --queries 55 --synthetic_7b --out profiles/r21_shortlist.json"""
+    python tools/gallery_bench.py --shortlist 16 64 256 --modes none --tvg_modes attn --n 1000 --queries 55 --synthetic_7b --out profiles/r21_shortlist.json
+
+`--grow K` (t2v): videos that join a running gallery.  Scorers over the first N - K videos, with an eager index (spare_slots = K) and a lazy one
+built, are grown through PairScorer.add_videos -- one video per call on one scorer, all K in one call on another -- and timed per added video: add_videos (the checks,
+the clip means, the vocabulary registered again), the re-registration alone (Engine.set_video_vocab over all rows), the gallery_feats() rebuild, the eager index's
+spare-slot fill (_sync_videos: the projection of the new videos and one packed fill), and the lazy index's first query of a new video (miss and admission) against the
+same query again (hit).  Then the stream of Q queries x top-k over the grown eager index against an index built over all N from the start, alternated `--reps` times
+in one process and checked bit-equal (a tvg_gallery query too), with the engine's timing classes of one stream each: the same classes with the same call counts.
+
+    python tools/gallery_bench.py --grow 8 --modes none --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r24_gallery_grow.json"""
 import argparse
 import json
 import os
@@ -112,6 +121,7 @@ def main():
                     help="whole-gallery queries on the fine-tuned blend: --candidates all against --candidates tvg with a shortlist of K, per request and in batches (t2v)")
     ap.add_argument("--shortlist_batches", type=int, nargs="+", default=[1, 8], metavar="B", help="--shortlist: requests per pass")
     ap.add_argument("--recall_k", type=int, nargs="+", default=[16, 64, 256], metavar="K", help="--shortlist: the shortlist sizes whose cover of the `all` top-1 / top-10 is reported")
+    ap.add_argument("--grow", type=int, default=None, metavar="K", help="the index built over N - K videos and grown by K (PairScorer.add_videos) against one built over all N (t2v)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -131,6 +141,8 @@ def main():
         return main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_qkv" if a.narrow_qkv else "narrow_lo6")
     if a.direction == "v2t":
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if a.grow:
+        return main_grow(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.shortlist:
         return main_shortlist(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.serve_batch:
@@ -436,6 +448,103 @@ def main_serve(a, dims, model, prob, vtg, tvg, video, q, tpc):
         torch.cuda.empty_cache()
     for o in counters:
         e.set_option(o, 0)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def main_grow(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    """`--grow K`: a gallery built over N - K videos and grown by K against one built over all N (see the module text)."""
+    e = model.engine
+    N, K = a.n, int(a.grow)
+    med = lambda x: float(np.median(x))
+    spread = lambda x: float((max(x) - min(x)) / np.median(x)) if len(x) > 1 else 0.0
+    ms = lambda x: [1e3 * float(t) for t in x]
+    vocab, labels = torch.from_numpy(prob.video_vocab), torch.from_numpy(prob.tvg_video_labels)
+    cand = np.argsort(-prob.t2v_sims[q], axis=1, kind="stable")[:, :a.k]
+    res = {"grow": K, "n": N, "queries": a.queries, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc, "reps": a.reps, "modes": {}}
+
+    def scorer(n):
+        sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video[:n], vocab[:n], labels[:n], dims.num_clips, max_tokens=a.max_tokens)
+        sc.set_vtg_mode(model.vtg_mode())
+        return sc
+
+    for mode in a.modes.split(","):
+        model.vtg_precise = None if mode == "none" else mode
+        model.tvg_precise = a.tvg_modes.split(",")[0]
+        model.clear_cache()
+        whole = scorer(N)
+        whole.set_tvg_mode(model.tvg_mode())
+        whole.vtg(np.stack([np.arange(8), np.full(8, q[0])], axis=1))      # warm-up: workspaces sized
+        ref_gal = GalleryIndex(whole)
+        t_build, _ = timed(ref_gal.build)
+        t_feats_whole, _ = timed(whole.gallery_feats)
+        r = {"from_start": {"build_s": t_build, "slots": len(ref_gal.slot_of), "gallery_feats_s": t_feats_whole}}
+
+        def grown(batch):
+            """A scorer over N - K videos with its indexes built and gallery_feats() made, grown by K videos one at a time or in one call."""
+            sc = scorer(N - K)
+            sc.set_tvg_mode(model.tvg_mode())
+            eager = GalleryIndex(sc, spare_slots=K)
+            tb, _ = timed(eager.build)
+            lazy = GalleryIndex(sc, fill="lazy").build()
+            sc.gallery_feats()
+            steps = [list(range(N - K, N))] if batch else [[j] for j in range(N - K, N)]
+            t = {"add_videos": [], "gallery_feats": [], "spare_fill": [], "lazy_first": [], "lazy_again": []}
+            for js in steps:
+                dt, got = timed(lambda: sc.add_videos([video[j] for j in js], vocab[js])); t["add_videos"].append(dt / len(js))
+                assert got.tolist() == js
+                dt, _ = timed(sc.gallery_feats); t["gallery_feats"].append(dt / len(js))
+                dt, _ = timed(eager._sync_videos); t["spare_fill"].append(dt / len(js))
+                assert all(eager.keys[j] in eager.slot_of for j in js)
+                pairs = np.stack([np.asarray(js), np.full(len(js), q[0])], axis=1)
+                dt, first = timed(lambda: lazy.vtg_pairs(pairs)); t["lazy_first"].append(dt / len(js))
+                dt, again = timed(lambda: lazy.vtg_pairs(pairs)); t["lazy_again"].append(dt / len(js))
+                assert np.array_equal(first, again) and np.array_equal(first, ref_gal.vtg_pairs(pairs)), "a grown lazy index's scores differ from the from-start index's"
+            assert lazy.stats.admitted == K and lazy.stats.hits == K
+            lazy.close()
+            out = {"build_s": tb, "calls": len(steps), **{k + "_ms_per_video": {"median": med(ms(v)), "min": min(ms(v)), "max": max(ms(v)), "first_call": ms(v)[0]} for k, v in t.items()}}
+            return sc, eager, out
+
+        sc1, gal1, r["one_at_a_time"] = grown(False)
+        sc2, gal2, r["one_batch"] = grown(True)
+        gal2.close()
+        # the re-registration alone: all N rows through the engine's split
+        t_reg = [timed(lambda: e.set_video_vocab(sc1._vocab_src))[0] for _ in range(max(a.reps, 3))]
+        r["set_video_vocab_ms"] = {"rows": int(sc1.n_vocab), "bytes": int(sc1._vocab_src.numel() * 4), "median": med(ms(t_reg)), "min": min(ms(t_reg)), "spread": spread(t_reg)}
+        on_device = sc1._vocab_src.to(model.device)
+        t_reg = [timed(lambda: e.set_video_vocab(on_device))[0] for _ in range(max(a.reps, 3))]
+        r["set_video_vocab_device_rows_ms"] = {"median": med(ms(t_reg)), "min": min(ms(t_reg)), "spread": spread(t_reg)}
+        # the same stream after the growth and from the start
+        stream = lambda gal: [gal.rerank([int(t)], cand[i][None]) for i, t in enumerate(q)]
+        ref = stream(ref_gal); stream(gal1)
+        ts = {"grown": [], "from_start": []}
+        for _ in range(a.reps):
+            for leg, gal in (("grown", gal1), ("from_start", ref_gal)):
+                dt, got = timed(lambda: stream(gal)); ts[leg].append(dt)
+                assert all(np.array_equal(o, o1) and np.array_equal(b, b1) for (o, b), (o1, b1) in zip(got, ref)), f"{leg}: the stream's results differ"
+        classes = {}
+        for leg, gal in (("grown", gal1), ("from_start", ref_gal)):
+            e.timing_enable(True); e.timing_report()
+            stream(gal)
+            classes[leg] = {k: x for k, x in e.timing_report().items() if x["calls"]}
+            e.timing_enable(False)
+        same = {k: x["calls"] for k, x in classes["grown"].items()} == {k: x["calls"] for k, x in classes["from_start"].items()}
+        tokens = {leg: int(sum(p.n_tokens for i, t in enumerate(q) for p in gal.iter_plans(np.stack([cand[i], np.full(a.k, t)], axis=1))))
+                  for leg, gal in (("grown", gal1), ("from_start", ref_gal))}
+        r["stream"] = {leg: {"s": ts[leg], "ms_per_query": 1e3 * med(ts[leg]) / len(q), "spread": spread(ts[leg]), "packed_tokens": tokens[leg]} for leg in ts}
+        r["stream"].update(ratio_grown_to_from_start=med(ts["grown"]) / med(ts["from_start"]), same_classes_and_calls=bool(same), classes=classes,
+                           new_videos_among_candidates=int(np.sum(cand >= N - K)), stats_grown=gal1.stats.as_dict(), stats_from_start=ref_gal.stats.as_dict())
+        texts = [int(q[0]), int(q[-1])]
+        dt1, g1 = timed(lambda: sc1.tvg_gallery(texts)); dt2, g2 = timed(lambda: whole.tvg_gallery(texts))
+        assert np.array_equal(g1, g2), "tvg_gallery over the grown scorer differs from the from-start scorer's"
+        r["tvg_gallery_two_texts_ms"] = {"grown": 1e3 * dt1, "from_start": 1e3 * dt2, "bit_equal": True}
+        res["modes"][mode] = r
+        print(json.dumps({mode: r}), flush=True)
+        gal1.close(); ref_gal.close()
+        del sc1, sc2, whole
+        torch.cuda.empty_cache()
     if a.out:
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
         json.dump(res, open(a.out, "w"), indent=1)
