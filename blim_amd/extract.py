@@ -9,7 +9,8 @@ dataloader, base_dataset.py:23-31) read.  Chunking over processes as in the refe
 
 Video decoding needs `decord` (as in the reference); where it is not installed, pre-decoded frames are read instead:
 ./data/<DS>/frames/<vid>.npy = uint8 [n, H, W, 3] with the frames ALREADY sampled (--frames_dir overrides the directory).
-`--synthetic SEED` uses seeded random tower weights instead of the checkpoint (dry run without downloads)."""
+`--synthetic SEED` uses seeded random tower weights instead of the checkpoint (dry run without downloads).
+`--preprocess device` moves the resize and the normalisation from the worker threads to the GPU: the files are the same bytes."""
 from __future__ import annotations
 
 import argparse
@@ -34,6 +35,9 @@ def get_args_parser():
     p.add_argument("--dtype", default="f16", choices=["f16", "bf16"])
     p.add_argument("--num_workers", type=int, default=4, help="host threads decoding + preprocessing ahead of the GPU (the reference's DataLoader uses 4 workers)")
     p.add_argument("--synthetic", default=None, type=int, help="seed of synthetic tower weights (dry run)")
+    p.add_argument("--preprocess", default="host", choices=["host", "device"],
+                   help="host: the worker threads resize and normalise each frame with PIL; device: they only decode and sample, and the GPU resizes and normalises "
+                        "in front of the tower (vision.preprocess_device): the same files, byte for byte")
     return p
 
 
@@ -67,14 +71,18 @@ def list_sources(args):
     return [(os.path.basename(f)[:-4], f) for f in files], False
 
 
+def sample_stack(a: np.ndarray, num_frames: int) -> np.ndarray:
+    """A frame stack [n, ...] -> its num_frames frames (a stack that has num_frames already is taken as it is)."""
+    if a.shape[0] != num_frames:
+        from .vision import sample_frame_indices
+        a = a[sample_frame_indices(a.shape[0] + 1, num_frames).clip(0, a.shape[0] - 1)]
+    return a
+
+
 def read_frames(path: str, is_video: bool, dataset: str, num_frames: int) -> np.ndarray:
     """uint8 [num_frames, H, W, 3]."""
     if not is_video:
-        a = np.load(path)
-        if a.shape[0] != num_frames:
-            from .vision import sample_frame_indices
-            a = a[sample_frame_indices(a.shape[0] + 1, num_frames).clip(0, a.shape[0] - 1)]
-        return a
+        return sample_stack(np.load(path), num_frames)
     from decord import VideoReader
     from .vision import sample_frame_indices
     vr = VideoReader(path, num_threads=1)
@@ -86,7 +94,7 @@ def read_frames(path: str, is_video: bool, dataset: str, num_frames: int) -> np.
 
 def main(args):
     import torch
-    from .vision import VisionDims, VisionEncoder, preprocess
+    from .vision import VisionDims, VisionEncoder, preprocess, preprocess_device
     out_dir = f"./data/{args.dataset}/features"
     os.makedirs(out_dir, exist_ok=True)
     if args.clear:                                                        # extract.py:23-27
@@ -108,10 +116,15 @@ def main(args):
     t0, n_done = time.time(), 0
     clips = args.num_frames // dims.num_frames
 
-    def load_one(item):                                                   # host side: decode + resize + normalise (PIL releases the GIL)
+    on_device = getattr(args, "preprocess", "host") == "device"
+
+    def load_one(item):                                                   # host side: decode + resize + normalise (PIL releases the GIL); --preprocess device: decode only
         vid, path = item
         try:
-            return vid, preprocess(read_frames(path, is_video, args.dataset, args.num_frames), dims.image_size)
+            raw = read_frames(path, is_video, args.dataset, args.num_frames)
+            if on_device:
+                return vid, np.ascontiguousarray(raw, dtype=np.uint8)
+            return vid, preprocess(raw, dims.image_size)
         except Exception as e:                                            # extract.py:73-75 skips unreadable videos
             print(f"Error loading video {path}: {e}")
             return vid, None
@@ -133,6 +146,12 @@ def main(args):
         for _ in range(min(args.batch_size, len(sources) - lo)):
             vid, fr = pending.popleft().result()
             refill()
+            if fr is not None and on_device:
+                try:
+                    fr = preprocess_device(fr, dims.image_size, args.dtype, enc.device)      # one upload of the raw frames; resize + normalise on the GPU
+                except ValueError as e:                                  # (a stack that is not [n, H, W, 3]: skipped like an unreadable video)
+                    print(f"Error loading video {vid}: {e}")
+                    fr = None
             if fr is not None:
                 frames.append(fr); vids.append(vid)
         if not vids:

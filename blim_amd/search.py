@@ -45,6 +45,14 @@ registered again, so every later TVG score is normalised over the grown gallery;
 `--gallery_fill lazy`, they are served as any miss.  `--direction v2t --query_video FILE [FILE ...]`: the files' videos join before the indexes are built and the
 captions are ranked for each (`"query": "video:<basename>"`; `--candidates all | tvg`, `iv2` is refused: no first-stage row).  All outside videos of one run share one
 vocabulary, so a TVG term depends on which others were given.
+
+Raw frames.  `{"id", "add_video": {"vid": NAME, "frames": PATH}}` -- PATH a .npy of uint8 [n, H, W, 3], read with allow_pickle=False -- is the
+same request with the features computed here: the frames are sampled to 16 by blim_amd.extract's rule for frame stacks, resized and normalised on the GPU
+(vision.preprocess_device), run through the vision tower, and the fp16 tensor enters the `features` path above (its checks, the duplicate-content digest, the barrier,
+the `added` reply), so a video added from frames and the same video added from its extracted feature file are duplicates and score alike.  Exactly one of `features`
+and `frames`.  An unreadable or non-uint8 file, a wrong rank or channel count, no frame, or a tower that cannot be loaded gets its error line.  A `--query_video` FILE
+ending in `.npy` is such a frame stack too.  The tower is created at the first use of frames, from `--vision_model_path` (default `--model_path`) or, for dry runs,
+`--vision_synthetic SEED`.
 """
 from __future__ import annotations
 
@@ -84,6 +92,10 @@ def get_args_parser():
     p.add_argument("--query_video", default=[], type=str, nargs="*", metavar="FILE",
                    help="--direction v2t: feature files of videos outside the dataset ([num_clips, tokens, width] tensors as blim_amd.extract writes them) used as queries; "
                         "they join the scorer (PairScorer.add_videos) before the indexes are built.  --candidates all | tvg")
+    p.add_argument("--vision_model_path", default=None, type=str,
+                   help="raw frames (--serve: add_video frames; --direction v2t: a --query_video FILE ending in .npy): the checkpoint the vision tower is loaded from "
+                        "at the first use of frames (default: --model_path)")
+    p.add_argument("--vision_synthetic", default=None, type=int, metavar="SEED", help="raw frames: seeded random tower weights instead of the checkpoint (dry run)")
     p.add_argument("--gallery_gb", default=None, type=float, help="device memory for the prefix cache (default: every video)")
     p.add_argument("--gallery_spare", default=0, type=int, metavar="S",
                    help="--gallery_fill eager: S free slots beyond the planned ones, for the videos that join at run time (--serve: add_video).  They count against --gallery_gb")
@@ -197,6 +209,76 @@ def check_args(args, world: int = 1) -> None:
                          "pass the mode a stored evaluation resolved (--vtg_precise none | full) instead")
     if args.second_pass == "auto":
         raise SystemExit("search: --second_pass auto is not supported (it is measured by evaluation()): give e2m3 or 16bit")
+    tower_path, tower_seed = getattr(args, "vision_model_path", None), getattr(args, "vision_synthetic", None)
+    if tower_path is not None and tower_seed is not None:
+        raise SystemExit("search: give --vision_model_path or --vision_synthetic, not both (the tower has one set of weights)")
+    takes_frames = serve or (v2t and any(is_frame_stack(f) for f in (getattr(args, "query_video", None) or [])))
+    if (tower_path is not None or tower_seed is not None) and not takes_frames:
+        raise SystemExit("search: --vision_model_path / --vision_synthetic load the vision tower for raw frames: they act under --serve (add_video frames) and with a "
+                         "--query_video FILE ending in .npy (--direction v2t)")
+
+
+def is_frame_stack(path) -> bool:
+    """--query_video: a FILE ending in .npy is a stack of raw frames, anything else a feature file."""
+    return isinstance(path, str) and path.endswith(".npy")
+
+
+def load_frame_stack(path, num_frames: int):
+    """A video's raw frames (a .npy of uint8 [n, H, W, 3], n >= 1, read with allow_pickle=False) -> uint8 [num_frames, H, W, 3], sampled by blim_amd.extract's
+    rule for frame stacks.  ValueError when the file cannot be read as one."""
+    import numpy as np
+
+    from .extract import sample_stack
+    if not isinstance(path, str) or not path:
+        raise ValueError("frames must be the path of a .npy frame stack")
+    try:
+        a = np.load(path, allow_pickle=False)
+    except (OSError, ValueError, EOFError) as e:
+        raise ValueError(f"cannot read the frame stack {path!r} ({type(e).__name__})") from None
+    if not isinstance(a, np.ndarray) or a.dtype != np.uint8:
+        raise ValueError(f"the frame stack {path!r} does not hold one uint8 array")
+    if a.ndim != 4 or a.shape[3] != 3:
+        raise ValueError(f"the frame stack {path!r} has shape {tuple(a.shape)}: rank 4 with 3 channels, [n, H, W, 3], is needed")
+    if a.shape[0] < 1 or a.shape[1] < 1 or a.shape[2] < 1:
+        raise ValueError(f"the frame stack {path!r} holds no frame (shape {tuple(a.shape)})")
+    return np.ascontiguousarray(sample_stack(a, num_frames))
+
+
+class FrameFeaturiser:
+    """Raw frames -> the feature tensor blim_amd.extract would have written for them: the vision tower, created at the first call
+    (`--vision_synthetic SEED`: seeded weights; else the checkpoint at `--vision_model_path`, default `--model_path`), with the resize and the normalisation
+    on the GPU (VisionEncoder.video_feature_u8).  fp16, as the extractor's default: the features equal an extracted file's bit for bit.  ValueError when the
+    tower cannot be loaded or refuses the frames."""
+
+    def __init__(self, args, dims=None):
+        from .vision import VisionDims
+        self.args, self.dims, self.enc = args, dims or VisionDims(), None
+        self.num_frames = int(args.num_clips) * self.dims.num_frames          # 16: the frames a video is sampled to
+
+    def __call__(self, frames_u8):
+        if self.enc is None:
+            import pickle
+
+            from .vision import VisionEncoder
+            enc = None
+            try:
+                enc = VisionEncoder(self.dims, dtype="f16")
+                seed = getattr(self.args, "vision_synthetic", None)
+                if seed is not None:
+                    enc.init_synthetic_weights(seed)
+                else:
+                    enc.load_checkpoint(getattr(self.args, "vision_model_path", None) or self.args.model_path)
+            except (RuntimeError, OSError, KeyError, ValueError, ImportError, EOFError, pickle.UnpicklingError) as e:      # (engine.BlimError is a RuntimeError)
+                if enc is not None:
+                    enc.close()
+                raise ValueError(f"the vision tower cannot be loaded ({type(e).__name__}: {e})") from None
+            self.enc = enc
+        return self.enc.video_feature_u8(frames_u8)
+
+    def close(self):
+        if self.enc is not None:
+            self.enc.close()
+            self.enc = None
 
 
 def load_video_features(path):
@@ -215,6 +297,25 @@ def load_video_features(path):
     return t
 
 
+def query_video_features(files, args, featuriser=None):
+    """--query_video: each FILE's feature tensor -- read from a feature file, or computed from a .npy frame stack by the vision tower (one tower for the run,
+    created only when a frame stack is there, closed before the indexes are built).  ValueError as load_video_features / load_frame_stack / FrameFeaturiser."""
+    own = None
+    try:
+        feats = []
+        for f in files:
+            if is_frame_stack(f):
+                if featuriser is None:
+                    featuriser = own = FrameFeaturiser(args)
+                feats.append(featuriser(load_frame_stack(f, getattr(featuriser, "num_frames", None) or 16)))
+            else:
+                feats.append(load_video_features(f))
+        return feats
+    finally:
+        if own is not None:
+            own.close()
+
+
 class BadRequest(ValueError):
     """A request that gets an error line; the process goes on."""
 
@@ -224,7 +325,7 @@ class Server:
     query (a `text` / `rows` query joins the scorer through PairScorer.add_texts, with its checks), its candidates -- before it enters a batch, so a bad request
     cannot fail the pass its neighbours are scored in.  Identical `text` / `rows` queries share the text index of the first one (a dict from row bytes to index)."""
 
-    def __init__(self, gal, vids, n_captions: int, t2v_iv2, args, finetuned: bool = False, build_rows=None, content_hash=None):
+    def __init__(self, gal, vids, n_captions: int, t2v_iv2, args, finetuned: bool = False, build_rows=None, content_hash=None, featuriser=None):
         import numpy as np
         self.np = np
         self.gal, self.s = gal, gal.s
@@ -237,6 +338,7 @@ class Server:
         self.text_of = {}                          # row bytes -> text index
         self.content_hash = content_hash           # feature tensor -> a digest of its content (engine.hash_device on the device copy), or None: contents are not compared
         self.content_of = {}                       # digest -> the id of the run-time video that has this content
+        self.featuriser = featuriser               # raw frames uint8 [num_frames, H, W, 3] -> the video's feature tensor (FrameFeaturiser), or None: `frames` is refused
         self.requests = self.batches = self.errors = self.texts_added = self.videos_added = 0
 
     # ---- one request
@@ -376,11 +478,12 @@ class Server:
 
     # ---- a video that joins
     def _add_request(self, rid, req):
-        """`{"id", "add_video": {"vid", "features"}}`, validated in full before anything changes -> dict(id, add: (vid, tensor, digest))."""
+        """`{"id", "add_video": {"vid", "features" | "frames"}}`, validated in full before anything changes -> dict(id, add: (vid, tensor, digest)).  `frames` (a
+        .npy stack of raw frames) goes through the vision tower first and is a `features` request from there on."""
         if any(k in req for k in ("caption", "text", "rows", "candidates", "candidate_idx", "first_stage", "shortlist", "topk")):
             raise BadRequest("an add_video request carries no query")
         a = req["add_video"]
-        if not isinstance(a, dict) or set(a) != {"vid", "features"}:
+        if not isinstance(a, dict) or set(a) not in ({"vid", "features"}, {"vid", "frames"}):
             raise BadRequest("add_video takes vid (the new video's id) and features (the path of its feature file)")
         vid = a["vid"]
         if isinstance(vid, (bool, dict, list)) or vid is None or str(vid) == "":
@@ -388,7 +491,12 @@ class Server:
         if str(vid) in self.vid_at:
             raise BadRequest(f"video id {vid!r} is already in the gallery")
         try:
-            feat = load_video_features(a["features"])
+            if "frames" in a:
+                if self.featuriser is None:
+                    raise ValueError("this server has no vision tower for raw frames: send features")
+                feat = self.featuriser(load_frame_stack(a["frames"], getattr(self.featuriser, "num_frames", None) or 16))
+            else:
+                feat = load_video_features(a["features"])
             self.s.check_videos([feat])
         except ValueError as e:
             raise BadRequest(str(e)) from None
@@ -598,7 +706,7 @@ def main(args):
     n_dataset = len(video)
     if getattr(args, "query_video", None):       # v2t: videos outside the dataset join the scorer before the indexes are built; they share one vocabulary
         try:
-            scorer.add_videos([load_video_features(f) for f in args.query_video])
+            scorer.add_videos(query_video_features(args.query_video, args))
         except ValueError as e:
             raise SystemExit(f"search: --query_video: {e}") from None
         vids = list(vids) + [os.path.basename(f) for f in args.query_video]
@@ -623,8 +731,10 @@ def main(args):
                 out.write(line + "\n")
         from .engine import hash_device
         content_hash = lambda feat: hash_device(feat.contiguous().to(model.device))      # (one upload and one pass over a feature tensor: a fraction of the projection that follows)
-        server = Server(gal, vids, len(vtg_ids), t2v_iv2, args, finetuned=bool(args.resume), build_rows=build_rows, content_hash=content_hash)
+        featuriser = FrameFeaturiser(args)         # (the tower is created when the first add_video request brings frames)
+        server = Server(gal, vids, len(vtg_ids), t2v_iv2, args, finetuned=bool(args.resume), build_rows=build_rows, content_hash=content_hash, featuriser=featuriser)
         summary = serve(sys.stdin, write, server, args.batch_queries, args.batch_wait_ms)
+        featuriser.close()
         if out:
             out.close()
         print(f"gallery stats: {json.dumps(gal.stats.as_dict())}", file=sys.stderr, flush=True)

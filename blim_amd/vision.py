@@ -246,6 +246,11 @@ class VisionEncoder:
         tome, _ = self.encode(frames)
         return tome.to(torch.float16).cpu()
 
+    def video_feature_u8(self, frames_u8):
+        """One video's raw frames, uint8 [n_clips * T, H, W, 3] -> video_feature(preprocess(frames_u8)), bit for bit, with the resize and the normalisation
+        on the device (preprocess_device)."""
+        return self.video_feature(preprocess_device(frames_u8, self.dims.image_size, self.dtype, self.device))
+
 
 def vit_attention(qkv, n_clips: int, heads: int):
     """The encoder's attention alone (blim_vit_attention): qkv 16-bit device tensor [n_clips * L, 3 * heads * 64] -> [n_clips * L, heads * 64]."""
@@ -277,6 +282,154 @@ def preprocess(frames_u8: np.ndarray, image_size: int = 448):
         a = np.asarray(img, dtype=np.float32).transpose(2, 0, 1) * np.float32(1.0 / 255.0)
         out[i] = (a - mean) / std
     return torch.from_numpy(out).half()
+
+
+# ----------------------------------------------------------------------------- preprocessing (device)
+
+_RESIZE_BITS = 22                    # PIL's fixed-point precision for 8-bit images
+_PRE_MAX_DIM = 8192                  # blim_preprocess_frames' limit on T, H, W, S
+_tables: Dict[Tuple[int, int], Tuple[np.ndarray, np.ndarray]] = {}
+
+
+def _bicubic_kernel(x: np.ndarray) -> np.ndarray:
+    """Keys' cubic with a = -0.5 on float64 distances (PIL's BICUBIC)."""
+    a = -0.5
+    x = np.abs(x)
+    near = ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    far = (((x - 5) * x + 8) * x - 4) * a
+    return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
+
+
+def bicubic_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The taps of one axis of PIL's 8-bit bicubic resize from in_size to out_size: (bounds int32 [out, 2] = (first tap, tap count), coeffs int32
+    [out, ksize], zero past the count).  Pillow's coefficient rule in float64: the kernel is stretched by max(scale, 1), a tap window is
+    [int(center - support + 0.5), int(center + support + 0.5)) clipped to the axis, the weights are divided by their sum taken in tap order, and a weight w
+    becomes int(+-0.5 + w * 2**22).  Memoised per size pair; the arrays are read-only."""
+    key = (int(in_size), int(out_size))
+    if key in _tables:
+        return _tables[key]
+    n_in, n_out = key
+    if n_in < 1 or n_out < 1:
+        raise ValueError("bicubic_tables: sizes must be at least 1")
+    scale = n_in / n_out
+    stretch = max(scale, 1.0)
+    support = 2.0 * stretch
+    ksize = 2 * int(np.ceil(support)) + 1
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    first = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)
+    count = np.minimum(np.trunc(center + support + 0.5), n_in).astype(np.int64) - first
+    tap = np.arange(ksize, dtype=np.int64)[None, :]
+    live = tap < count[:, None]
+    w = np.where(live, _bicubic_kernel((tap + first[:, None] - center[:, None] + 0.5) * (1.0 / stretch)), 0.0)
+    total = np.zeros(n_out, dtype=np.float64)
+    for i in range(ksize):                                                 # in tap order: a pairwise sum rounds differently
+        total += w[:, i]
+    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
+    coeffs = np.trunc(np.where(w < 0, -0.5, 0.5) + w * float(1 << _RESIZE_BITS)).astype(np.int32)
+    coeffs[~live] = 0
+    bounds = np.stack([first, count], axis=1).astype(np.int32)
+    assert np.all(bounds[:, 0] >= 0) and np.all(bounds[:, 1] >= 1) and np.all(bounds.sum(axis=1) <= n_in) and np.all(bounds[:, 1] <= ksize)
+    bounds.setflags(write=False); coeffs.setflags(write=False)
+    _tables[key] = (bounds, coeffs)
+    return _tables[key]
+
+
+def normalise_lut(dtype: str = "f16") -> np.ndarray:
+    """uint16 [3, 256]: the 16-bit pattern `preprocess` (followed by VisionEncoder.encode's cast for a bf16 tower) gives channel c of a pixel of value v,
+    computed with preprocess' own expressions, so that a lookup equals the host path by construction."""
+    import torch
+    if dtype not in ("f16", "bf16"):
+        raise ValueError("normalise_lut dtype: f16 or bf16")
+    mean = np.asarray(IMAGE_MEAN, np.float32)[:, None]; std = np.asarray(IMAGE_STD, np.float32)[:, None]
+    a = np.arange(256, dtype=np.float32)[None, :] * np.float32(1.0 / 255.0)
+    t = torch.from_numpy(np.ascontiguousarray((a - mean) / std, dtype=np.float32)).half()
+    if dtype == "bf16":
+        t = t.to(torch.bfloat16)
+    return t.view(torch.int16).numpy().view(np.uint16).copy()
+
+
+_pre_bound = False
+_pre_state: Dict = {}                # per device: uploaded tables and LUTs, the workspace
+
+
+def _pre_lib():
+    global _pre_bound
+    lib = eng.load_library()
+    if not _pre_bound:
+        vp, i32 = C.c_void_p, C.c_int32
+        lib.blim_preprocess_workspace_bytes.argtypes = [i32, i32, i32, i32]; lib.blim_preprocess_workspace_bytes.restype = C.c_int64
+        lib.blim_preprocess_frames.argtypes = [vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]; lib.blim_preprocess_frames.restype = C.c_int
+        _pre_bound = True
+    return lib
+
+
+def _device_tables(state: Dict, device, in_size: int, out_size: int):
+    """(bounds, coeffs, ksize) on the device, uploaded once per size pair; (None, None, 0) for a pass that is skipped."""
+    import torch
+    if in_size == out_size:
+        return None, None, 0
+    key = ("taps", in_size, out_size)
+    if key not in state:
+        bounds, coeffs = bicubic_tables(in_size, out_size)
+        assert int((bounds[:, 0] + bounds[:, 1]).max()) <= in_size and int(bounds[:, 1].max()) <= coeffs.shape[1]       # what the kernel trusts
+        state[key] = (torch.from_numpy(bounds.copy()).to(device), torch.from_numpy(coeffs.copy()).to(device), int(coeffs.shape[1]))
+    return state[key]
+
+
+def preprocess_device(frames_u8, image_size: int = 448, dtype: str = "f16", device=None, lut: Optional[np.ndarray] = None):
+    """`preprocess` on the GPU (blim_preprocess_frames): uint8 RGB frames [T, H, W, 3], a numpy array or a torch tensor (host or device) -> a device tensor
+    [T, 3, S, S] of `dtype` ("f16" | "bf16") that equals preprocess(frames, S) (cast with .to(bfloat16) for bf16) bit for bit.  One upload of the raw frames;
+    the taps, the table and the workspace live on the device and are reused by later calls (stream-ordered: call from one thread per device).  `lut`
+    replaces normalise_lut(dtype) (uint16 [3, 256]; tests read the resized bytes back through it)."""
+    import torch
+    if dtype not in ("f16", "bf16"):
+        raise ValueError("preprocess_device dtype: f16 or bf16")
+    if isinstance(frames_u8, np.ndarray):
+        if frames_u8.dtype != np.uint8:
+            raise ValueError(f"preprocess_device: frames must be uint8 (got {frames_u8.dtype})")
+        if frames_u8.ndim == 4 and not frames_u8.flags["C_CONTIGUOUS"]:
+            raise ValueError("preprocess_device: frames must be contiguous")
+    elif isinstance(frames_u8, torch.Tensor):
+        if frames_u8.dtype != torch.uint8:
+            raise ValueError(f"preprocess_device: frames must be uint8 (got {frames_u8.dtype})")
+        if frames_u8.dim() == 4 and not frames_u8.is_contiguous():
+            raise ValueError("preprocess_device: frames must be contiguous")
+    else:
+        raise ValueError("preprocess_device: frames must be a numpy array or a torch tensor")
+    if len(frames_u8.shape) != 4 or frames_u8.shape[3] != 3:
+        raise ValueError(f"preprocess_device: frames must be [T, H, W, 3] (got {tuple(frames_u8.shape)})")
+    T, H, W = (int(n) for n in frames_u8.shape[:3])
+    S = int(image_size)
+    if min(T, H, W, S) < 1 or max(T, H, W, S) > _PRE_MAX_DIM:
+        raise ValueError(f"preprocess_device: T, H, W and the image size must lie in 1 .. {_PRE_MAX_DIM} (got {T}, {H}, {W}, {S})")
+    if not torch.cuda.is_available():
+        raise eng.BlimError("no HIP device visible: preprocess_device has no CPU fallback (preprocess is the host path)")
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    lib = _pre_lib()
+    state = _pre_state.setdefault(str(device), {})
+    x = (torch.from_numpy(frames_u8) if isinstance(frames_u8, np.ndarray) else frames_u8).to(device)
+    xb, xk, xks = _device_tables(state, device, W, S)
+    yb, yk, yks = _device_tables(state, device, H, S)
+    if lut is None:
+        if ("lut", dtype) not in state:
+            state[("lut", dtype)] = torch.from_numpy(normalise_lut(dtype).view(np.int16)).to(device)
+        table = state[("lut", dtype)]
+    else:
+        lut = np.ascontiguousarray(lut)
+        if lut.dtype != np.uint16 or lut.shape != (3, 256):
+            raise ValueError("preprocess_device: lut must be uint16 [3, 256]")
+        table = torch.from_numpy(lut.view(np.int16)).to(device)
+    need = int(lib.blim_preprocess_workspace_bytes(T, H, W, S))
+    if need < 0:
+        raise eng.BlimError(f"blim_preprocess_workspace_bytes failed (code {need}): {lib.blim_last_error().decode()}")
+    ws = state.get("workspace")
+    if need and (ws is None or ws.numel() < need):
+        ws = state["workspace"] = torch.empty(need, dtype=torch.uint8, device=device)
+    out = torch.empty((T, 3, S, S), dtype=eng.torch_dtype_of(dtype), device=device)
+    with torch.cuda.device(device):
+        eng._check(lib.blim_preprocess_frames(eng._ptr(x), T, H, W, S, eng._ptr(xb), eng._ptr(xk), xks, eng._ptr(yb), eng._ptr(yk), yks, eng._ptr(table), eng._ptr(out),
+                                              eng._ptr(ws) if need else None, eng._stream()), "blim_preprocess_frames")
+    return out
 
 
 def sample_frame_indices(vlen, num_frames: int = 16) -> np.ndarray:

@@ -760,6 +760,28 @@ int blim_vit_attention(const void* qkv, int32_t n_clips, int32_t L, int32_t head
  * mm_projector_builder.py:6-130. */
 int blim_tome_merge(blim_vision* v, const float* x, int32_t b, int32_t p, int32_t c, int32_t heads, int32_t target, float* out, void* stream);
 
+/* Frame preprocessing in front of blim_vision_encode (csrc/preprocess.hip): UMTImageProcessor.preprocess for uint8 RGB frames -- PIL's
+ * bicubic resize to S x S, x 1/255, mean / std -- with the host path's values bit for bit.  PIL's 8-bit resampler is integer arithmetic on 22-bit fixed-point
+ * coefficients, and the normalisation sees 3 x 256 distinct inputs, so the host supplies the taps and a table (blim_amd/vision.py: bicubic_tables,
+ * normalise_lut) and the device does no float arithmetic at all.  The rule:
+ *   horizontal pass, per output pixel x and channel: acc = 1 << 21; acc += xk[x][i] * pixel[first + i] for i < count, in int32, (first, count) = xb[x];
+ *     byte = clip(acc >> 22, 0, 255) with an arithmetic shift, stored into the workspace [T, H, S, 3];
+ *   vertical pass: the same rule down the workspace's rows with yb / yk, then out[t, c, y, x] = lut[c][byte];
+ *   a pass whose input size equals S is skipped (W == S: no workspace, the frames feed the vertical pass; H == S: the bytes go to the table unchanged), as PIL
+ *   skips it.
+ * Two launches on `stream`; no engine handle.  blim_preprocess_workspace_bytes: T * H * S * 3, or 0 when W == S; BLIM_ERR_ARG for sizes outside the limit.
+ * Refused before anything is launched (BLIM_ERR_ARG, the message names the problem): T, H, W or S outside 1 .. 8192; a null frames, lut or out; a pass that
+ * runs without its bounds, its coefficients or (horizontal) the workspace, or with xks / yks < 1.  The tables are trusted to keep first + count <= the input
+ * size and count <= xks / yks (the host asserts it before the upload); a table that broke this is clamped to the row, so it reads nothing outside the frames. */
+int64_t blim_preprocess_workspace_bytes(int32_t T, int32_t H, int32_t W, int32_t S);
+int blim_preprocess_frames(const uint8_t* frames,              /* [T, H, W, 3] RGB */
+                           int32_t T, int32_t H, int32_t W, int32_t S,
+                           const int32_t* xb, const int32_t* xk, int32_t xks,   /* horizontal: bounds [S, 2] = (first tap, tap count), coefficients [S, xks]; ignored when W == S */
+                           const int32_t* yb, const int32_t* yk, int32_t yks,   /* vertical, likewise; ignored when H == S */
+                           const uint16_t* lut,                /* [3, 256] 16-bit patterns: channel c, byte v -> output value */
+                           void* out,                          /* [T, 3, S, S] 16-bit, the layout blim_vision_encode reads */
+                           void* workspace, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Fine-tuning step: what training_utils.py:57-95 does per batch -- the reference's two decoder forwards (VTG rows, TVG rows;
  * here one forward over a packed batch holding both), loss = vtg_loss + tvg_loss, backward into the LoRA adapters of main.py:96-101 (projector mlp / tvg_mlp Linear 0 and 2, every
