@@ -1602,6 +1602,47 @@ extern "C" int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* e
     ARG_CHECK(e && rows && labels && score && n_pairs > 0);       // vocab_bf16 == NULL: the vocabulary registered with blim_set_video_vocab
     return score_tvg_impl(e, nullptr, nullptr, nullptr, 0, b, embeds, rows, vocab_bf16, n_vocab, labels, n_pairs, score, stream);
 }
+// blim_score_tvg up to the visual head over the n_rows + n_prior named rows, the clip-0 logits alone against the registered vocabulary -- the c = 0 launch of
+// tvg_logits_impl with the rows contiguous: a GEMM row does not depend on the rows beside it -- and the rank kernel over the two row blocks
+static int tvg_rank_check_k(int32_t k, int32_t n_vocab);
+extern "C" int blim_score_tvg_first(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, int32_t n_rows, const int32_t* prior_rows, int32_t n_prior,
+                                    const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, void* stream) {
+    ARG_CHECK(e && rows && idx_out && val_out && n_rows > 0 && n_prior >= 0 && (prior_rows || n_prior == 0));
+    if (e->f8) { blim_set_error("blim_score_tvg_first: fp8 engines are not supported"); return BLIM_ERR_STATE; }
+    if (!e->vocab3.p) { blim_set_error("no video vocabulary registered (blim_set_video_vocab)"); return BLIM_ERR_STATE; }
+    const int N = e->n_vocab, M = e->c.mm_hidden_size;
+    TRY(tvg_rank_check_k(k, N));
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t R = (int64_t)n_rows + n_prior;
+    TRY(reserve_rows(e, R));
+    TRY(ensure(e->vh, (size_t)round_up(R, 256) * M * 2 * (e->precise ? 2 : 1)));
+    const int32_t* all = rows;
+    if (n_prior) {                                                // [rows | prior_rows] side by side (lab_logit: R ints reserved above, idle in a TVG call)
+        int32_t* cat = (int32_t*)e->lab_logit.p;
+        HIP_TRY(hipMemcpyAsync(cat, rows, (size_t)n_rows * 4, hipMemcpyDeviceToDevice, s));
+        HIP_TRY(hipMemcpyAsync(cat + n_rows, prior_rows, (size_t)n_prior * 4, hipMemcpyDeviceToDevice, s));
+        all = cat;
+    }
+    TRY(decode_impl(e, b, embeds, all, R, e->hsel.p, e->precise, nullptr, stream));
+    TRY(visual_head_impl(e, e->hsel.p, e->precise, R, e->vh.p, stream));
+    TRY(ensure(e->tvg_logits, (size_t)R * N * 4));
+    float* lg = (float*)e->tvg_logits.p;
+    {
+        SpanGuard g(e, s, TC_GEMM_OTHER, 2.0 * R * (double)M * N * (e->precise ? 3 : 1));
+        GemmParams p;
+        if (e->precise) {
+            TRY(ensure(e->vh3, (size_t)round_up(R, 256) * 3 * M * 2));
+            TRY(launch_split3_hilo((uint16_t*)e->vh3.p, (const uint16_t*)e->vh.p, 2 * (int64_t)M, R, M, s));
+            p = gp(e->c.compute_dtype, e->vh3.p, 3 * (int64_t)M, e->vocab3.p, R, N, 3 * M, lg, N);
+        } else {
+            p = gp(e->c.compute_dtype, e->vh.p, M, e->vocab1.p, R, N, M, lg, N);
+        }
+        p.scale = 1.0f / sqrtf((float)M);
+        TRY(launch_gemm(EPI_F32, p, s));
+    }
+    SpanGuard g(e, s, TC_MISC, 0);
+    return launch_tvg_rank(lg, N, N, n_rows, lg + (int64_t)n_rows * N, N, n_prior, prior_of, alpha, k, idx_out, val_out, logprob_out, N, s);
+}
 extern "C" int blim_score_tvg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
                                      const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab, const int32_t* labels, int32_t n_pairs,
                                      float* score, void* stream) {
@@ -1699,6 +1740,26 @@ extern "C" int blim_lse_combine(const float* part, int32_t n_tiles, const float*
 extern "C" int blim_tvg_criterion(const float* logits, int64_t ld, int32_t n_vocab, const int32_t* labels, int32_t n_pairs, int32_t clips, float* score, void* stream) {
     ARG_CHECK(ld >= n_vocab);
     return launch_tvg_score(logits, ld, n_vocab, labels, n_pairs, clips, score, (hipStream_t)stream);
+}
+// blim_tvg_rank's refusals, each naming its argument (shared with blim_score_tvg_first, which checks k before it launches anything)
+static_assert(TVG_RANK_MAX_K == BLIM_TVG_RANK_MAX_K, "kernels.hpp and blim.h disagree on the largest k");
+static int tvg_rank_check_k(int32_t k, int32_t n_vocab) {
+    if (k < 1 || k > n_vocab) { blim_set_error("tvg_rank: k = %d outside 1 .. n_vocab = %d", k, n_vocab); return BLIM_ERR_ARG; }
+    if (k > BLIM_TVG_RANK_MAX_K) { blim_set_error("tvg_rank: k = %d above BLIM_TVG_RANK_MAX_K = %d", k, BLIM_TVG_RANK_MAX_K); return BLIM_ERR_ARG; }
+    return BLIM_OK;
+}
+extern "C" int blim_tvg_rank(const float* logits, int64_t ld, int32_t n_vocab, int32_t n_rows, const float* prior_logits, int64_t ld_prior, int32_t n_prior,
+                             const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, void* stream) {
+    if (!logits || !idx_out || !val_out) { blim_set_error("tvg_rank: %s is null", !logits ? "logits" : !idx_out ? "idx_out" : "val_out"); return BLIM_ERR_ARG; }
+    if (n_vocab < 1) { blim_set_error("tvg_rank: n_vocab = %d < 1", n_vocab); return BLIM_ERR_ARG; }
+    if (n_rows < 1) { blim_set_error("tvg_rank: n_rows = %d < 1", n_rows); return BLIM_ERR_ARG; }
+    TRY(tvg_rank_check_k(k, n_vocab));
+    if (ld < n_vocab) { blim_set_error("tvg_rank: ld = %lld below n_vocab = %d", (long long)ld, n_vocab); return BLIM_ERR_ARG; }
+    if (n_prior < 0) { blim_set_error("tvg_rank: n_prior = %d < 0", n_prior); return BLIM_ERR_ARG; }
+    if (prior_of && !prior_logits) { blim_set_error("tvg_rank: prior_of without prior_logits"); return BLIM_ERR_ARG; }
+    if (prior_logits && ld_prior < n_vocab) { blim_set_error("tvg_rank: ld_prior = %lld below n_vocab = %d", (long long)ld_prior, n_vocab); return BLIM_ERR_ARG; }
+    if (logprob_out && ld_out < n_vocab) { blim_set_error("tvg_rank: ld_out = %lld below n_vocab = %d", (long long)ld_out, n_vocab); return BLIM_ERR_ARG; }
+    return launch_tvg_rank(logits, ld, n_vocab, n_rows, prior_logits, ld_prior, n_prior, prior_of, alpha, k, idx_out, val_out, logprob_out, ld_out, (hipStream_t)stream);
 }
 extern "C" int blim_group_mean_rows(void* out, const void* in, int64_t n_out, int32_t group, int32_t H, int32_t dtype16, int32_t split, void* stream) {
     ARG_CHECK(dtype16 == BLIM_COMPUTE_BF16 || dtype16 == BLIM_COMPUTE_F16);

@@ -648,6 +648,169 @@ int launch_tvg_score(const float* logits, int64_t ld, int n_vocab, const int32_t
     return BLIM_OK;
 }
 
+// ---------------------------------------------------------------------------- TVG clip-0 rank
+// One workgroup per row: log-softmax over the vocabulary, the optional prior term, and the exact first k of the stable descending order of the result.
+// The normaliser mx + logf(sm) is formed by ONE wave exactly as tvg_score_kernel forms it (lane-strided running sums, wave_max / wave_sum), so lp[j] is, as a
+// float, the criterion's value for label j at clips = 1; wave 1 does the same for the prior row meanwhile.  Every later pass recomputes a column's term from the
+// two rows (L2-resident) with the same expression, so all passes see the same bits.
+// Order: term -> u32 `ord` that grows with the rank wanted (NaN lowest, then -inf, ..., +inf; -0 = +0), ties to the lower index.  Four 8-bit radix passes over
+// LDS histograms (integer atomics only) find T = the ord of the k-th place and how many of the columns with ord == T are still needed; all columns above T and the
+// lowest-indexed `need` of those at T (ballot prefix over contiguous per-wave index ranges) go to LDS as 64-bit keys ord << 32 | ~index and are sorted there.
+struct RankRow { const float* row; const float* prow; float tot, ptot, alpha; int mode; };   // mode 0: term = lp; 1: lp - alpha * pl; 2: NaN (prior_of >= n_prior)
+__device__ __forceinline__ float rank_term(const RankRow& q, int j) {
+#pragma clang fp contract(off)                                 // (__fmul_rn / __fsub_rn are plain operators here and would be fused)
+    const float lp = q.row[j] - q.tot;
+    if (q.mode == 0) return lp;
+    if (q.mode == 2) return __uint_as_float(0x7FC00000u);
+    const float pl = q.prow[j] - q.ptot;
+    const float ap = q.alpha * pl;
+    return lp - ap;                                            // two roundings, no fused multiply-add: numpy f32 arithmetic gives the same bits
+}
+__device__ __forceinline__ uint32_t rank_ord(float t) {
+    if (t != t) return 0u;
+    const uint32_t u = t == 0.f ? 0u : __float_as_uint(t);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float rank_lse(const float* row, int n_vocab, int lane) {
+    float mx = -INFINITY;
+    for (int i = lane; i < n_vocab; i += 64) mx = fmaxf(mx, row[i]);
+    mx = wave_max(mx);
+    float sm = 0.f;
+    for (int i = lane; i < n_vocab; i += 64) sm += expf(row[i] - mx);
+    sm = wave_sum(sm);
+    return mx + logf(sm);
+}
+__global__ __launch_bounds__(256) void tvg_rank_kernel(const float* logits, int64_t ld, int n_vocab, const float* prior_logits, int64_t ld_prior, int n_prior,
+                                                       const int32_t* prior_of, float alpha, int k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out) {
+    __shared__ unsigned long long keys[TVG_RANK_MAX_K];
+    __shared__ int hist[256];
+    __shared__ float tots[2];
+    __shared__ uint32_t sel[2];
+    __shared__ int wcnt[4];
+    __shared__ int n_gt;
+    const int64_t r = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    RankRow q;
+    q.row = logits + r * ld;
+    const int po = prior_of ? prior_of[r] : -1;
+    q.mode = po < 0 ? 0 : po < n_prior ? 1 : 2;
+    q.prow = q.mode == 1 ? prior_logits + (int64_t)po * ld_prior : nullptr;
+    q.alpha = alpha;
+    if (w == 0) {
+        const float t = rank_lse(q.row, n_vocab, lane);
+        if (lane == 0) tots[0] = t;
+    } else if (w == 1 && q.mode == 1) {
+        const float t = rank_lse(q.prow, n_vocab, lane);
+        if (lane == 0) tots[1] = t;
+    }
+    if (tid == 0) n_gt = 0;
+    __syncthreads();
+    q.tot = tots[0];
+    q.ptot = q.mode == 1 ? tots[1] : 0.f;
+    if (logprob_out) {
+        float* lpo = logprob_out + r * ld_out;
+        for (int j = tid; j < n_vocab; j += 256) lpo[j] = q.row[j] - q.tot;
+    }
+    // ---- radix select: T (`prefix`) and how many columns with ord == T the top k holds (`need` >= 1); k - need columns lie above T
+    uint32_t prefix = 0;
+    int need = k;
+    for (int pass = 0; pass < 4; ++pass) {
+        const int shift = 24 - 8 * pass;
+        const uint32_t himask = pass ? 0xFFFFFFFFu << (shift + 8) : 0u;
+        hist[tid] = 0;
+        __syncthreads();
+        for (int j = tid; j < n_vocab; j += 256) {
+            const uint32_t o = rank_ord(rank_term(q, j));
+            if ((o & himask) == prefix) atomicAdd(&hist[(o >> shift) & 255], 1);
+        }
+        __syncthreads();
+        if (w == 0) {                                            // lane l owns digits 255 - 4 l .. 252 - 4 l; inclusive scan from the top digit down
+            const int b0 = 255 - 4 * lane;
+            const int c0 = hist[b0], c1 = hist[b0 - 1], c2 = hist[b0 - 2], c3 = hist[b0 - 3];
+            const int c = c0 + c1 + c2 + c3;
+            int inc = c;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(inc, o);
+                if (lane >= o) inc += v;
+            }
+            const int exc = inc - c;
+            if (exc < need && need <= inc) {                      // exactly one lane: the digit of the need-th column lies in its four
+                int rem = need - exc, b = b0;
+                if (rem > c0) { rem -= c0; b = b0 - 1; if (rem > c1) { rem -= c1; b = b0 - 2; if (rem > c2) { rem -= c2; b = b0 - 3; } } }
+                sel[0] = prefix | ((uint32_t)b << shift);
+                sel[1] = (uint32_t)rem;
+            }
+        }
+        __syncthreads();
+        prefix = sel[0];
+        need = (int)sel[1];
+    }
+    // ---- survivors: wave w walks the contiguous index range [lo, hi) 64 columns at a time, so a ballot prefix ranks the columns at T by index
+    const int g = k - need;
+    const int64_t per = ((int64_t)n_vocab + 255) / 256 * 64;
+    const int lo = (int)min((int64_t)n_vocab, w * per), hi = (int)min((int64_t)n_vocab, (w + 1) * per);
+    int cnt = 0;
+    for (int j0 = lo; j0 < hi; j0 += 64) {
+        const int j = j0 + lane;
+        const bool eq = j < hi && rank_ord(rank_term(q, j)) == prefix;
+        cnt += __popcll(__ballot(eq));
+    }
+    if (lane == 0) wcnt[w] = cnt;
+    __syncthreads();
+    int base = 0;
+    for (int i = 0; i < w; ++i) base += wcnt[i];
+    for (int j0 = lo; j0 < hi; j0 += 64) {
+        const int j = j0 + lane;
+        const bool in = j < hi;
+        const uint32_t o = in ? rank_ord(rank_term(q, j)) : 0u;
+        const unsigned long long key = ((unsigned long long)o << 32) | (uint32_t)~(uint32_t)j;
+        const bool eq = in && o == prefix;
+        const unsigned long long m = __ballot(eq);
+        if (in && o > prefix) {
+            const int slot = atomicAdd(&n_gt, 1);
+            if (slot < g) keys[slot] = key;
+        }
+        if (eq) {
+            const int rk = base + __popcll(m & ((1ull << lane) - 1ull));
+            if (rk < need) keys[g + rk] = key;
+        }
+        base += __popcll(m);
+    }
+    int p2 = 1;
+    while (p2 < k) p2 <<= 1;
+    for (int i = k + tid; i < p2; i += 256) keys[i] = 0ull;       // below every real key (a real key's low word is ~index >= 2^31)
+    __syncthreads();
+    // ---- bitonic sort of the p2 keys, descending
+    for (int size = 2; size <= p2; size <<= 1) {
+        for (int stride = size >> 1; stride > 0; stride >>= 1) {
+            for (int i = tid; i < (p2 >> 1); i += 256) {
+                const int a = 2 * i - (i & (stride - 1)), b = a + stride;
+                const bool desc = (a & size) == 0;
+                const unsigned long long ka = keys[a], kb = keys[b];
+                if ((ka < kb) == desc) { keys[a] = kb; keys[b] = ka; }
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < k; i += 256) {
+        const int j = (int)~(uint32_t)keys[i];
+        const bool ok = (uint32_t)j < (uint32_t)n_vocab;         // (always: every one of the k places received a column's key)
+        idx_out[r * k + i] = ok ? j : -1;
+        val_out[r * k + i] = ok ? rank_term(q, j) : __uint_as_float(0x7FC00000u);
+    }
+}
+int launch_tvg_rank(const float* logits, int64_t ld, int n_vocab, int n_rows, const float* prior_logits, int64_t ld_prior, int n_prior, const int32_t* prior_of,
+                    float alpha, int k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, hipStream_t s) {
+    ARG_CHECK(logits && idx_out && val_out && n_vocab > 0 && n_rows > 0 && ld >= n_vocab);
+    ARG_CHECK(k > 0 && k <= n_vocab && k <= TVG_RANK_MAX_K);
+    ARG_CHECK(n_prior >= 0 && (!prior_of || prior_logits) && (!prior_logits || ld_prior >= n_vocab) && (!logprob_out || ld_out >= n_vocab));
+    hipLaunchKernelGGL(tvg_rank_kernel, dim3(n_rows), dim3(256), 0, s, logits, ld, n_vocab, prior_logits, ld_prior, n_prior, prior_of, alpha, k, idx_out, val_out,
+                       logprob_out, ld_out);
+    LAUNCH_CHECK("tvg_rank");
+    return BLIM_OK;
+}
+
 // ---------------------------------------------------------------------------- fp8 quantisers (DT_F8 mode)
 template <int DT>
 __global__ __launch_bounds__(256) void quant_rows_kernel(const bf16_t* in, int64_t ld, int64_t n_rows, int K, uint8_t* out8, float* scale) {

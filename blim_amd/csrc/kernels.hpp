@@ -1,6 +1,6 @@
 // HBM-bound helper kernels of the scoring path (gfx950): synthetic fill, embedding gather (K2),
 // RMSNorm (K3/K9), log-sum-exp combine + masked mean (K11), cross-entropy on materialised logits,
-// TVG criterion (K15).
+// TVG criterion (K15), TVG clip-0 rank (row log-softmax + exact top k).
 #pragma once
 #include "common.hpp"
 
@@ -62,6 +62,14 @@ int launch_ce_rows(const float* logits, int64_t ld, int V, const int32_t* labels
 
 // TVG criterion: logits [n_pairs*clips, n_vocab] f32 (row p*clips+c = pair p, clip c), label[p] -> score[p] = mean_c log_softmax[label]
 int launch_tvg_score(const float* logits, int64_t ld, int n_vocab, const int32_t* labels, int n_pairs, int clips, float* score, hipStream_t s);
+
+// TVG clip-0 rank: per row r of logits [n_rows, ld] f32, lp = log_softmax(row[:n_vocab]) with the criterion's own normaliser; term = lp, or
+// lp - alpha * pl with pl the same over row prior_of[r] of prior_logits (prior_of NULL or an entry < 0: lp; an entry >= n_prior: NaN).  idx_out / val_out
+// [n_rows, k]: the first k of the stable descending order of term (ties to the lower index, -inf after finite values, NaN last).  logprob_out (optional,
+// [n_rows, ld_out]): the lp rows.
+#define TVG_RANK_MAX_K 1024          // = BLIM_TVG_RANK_MAX_K (blim.h): the survivors are sorted in LDS
+int launch_tvg_rank(const float* logits, int64_t ld, int n_vocab, int n_rows, const float* prior_logits, int64_t ld_prior, int n_prior, const int32_t* prior_of,
+                    float alpha, int k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, hipStream_t s);
 
 // ---- fp8 mode (DT_F8): per-row symmetric quantisation to OCP e4m3, scale = absmax / 448 (1 when the row is all zero)
 // in: 16-bit [n_rows, K] (row stride ld, dtype DT_BF16/DT_F16) -> out8 [n_rows, K] + scale [n_rows].  K % 8 == 0, K <= 20480.

@@ -120,6 +120,7 @@ class GemmArgs(C.Structure):
 
 
 EPILOGUES = {"bf16": 0, "f32": 1, "resid": 2, "qkv": 3, "swiglu": 4, "lse": 5}
+TVG_RANK_MAX_K = 1024            # BLIM_TVG_RANK_MAX_K (include/blim.h): the largest k of blim_tvg_rank / blim_score_tvg_first
 
 
 def declared_symbols(header: str = HEADER_PATH) -> Sequence[str]:
@@ -201,6 +202,8 @@ def load_library(path: str = LIB_PATH):
         "blim_rmsnorm_f8": ([vp, i64, i64, i32, vp, f32, vp, vp, vp], C.c_int),
         "blim_lse_combine": ([vp, i32, vp, vp, i64, vp, vp], C.c_int),
         "blim_tvg_criterion": ([vp, i64, i32, vp, i32, i32, vp, vp], C.c_int),
+        "blim_tvg_rank": ([vp, i64, i32, i32, vp, i64, i32, vp, f32, i32, vp, vp, vp, i64, vp], C.c_int),
+        "blim_score_tvg_first": ([vp, C.POINTER(Batch), vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, vp, vp], C.c_int),
         "blim_group_mean_rows": ([vp, vp, i64, i32, i32, i32, i32, vp], C.c_int),
         "blim_assemble_rows": ([vp, vp, i64, i32, vp, vp, i32, vp], C.c_int),
         "blim_gemm": ([C.POINTER(GemmArgs), vp], C.c_int),
@@ -618,6 +621,21 @@ class Engine:
         n_vocab = self.n_vocab if vocab_clip_major is None else vocab_clip_major.shape[1]
         return self._score("blim_score_tvg", batch, embeds, rows, (_ptr(vocab_clip_major), n_vocab, _ptr(labels)), labels.shape[0], **cached)
 
+    def score_tvg_first(self, batch: PackedBatch, embeds, rows, k: int, prior_rows=None, prior_of=None, alpha: float = 0.0, full: bool = False):
+        """blim_score_tvg_first: rows int32 [n] (device) name the caption prompts' last tokens, prior_rows int32 [n_prior] the prior sequences' scored tokens,
+        prior_of int32 [n] row r's prior row (< 0: none) -> (idx int32 [n, k], val f32 [n, k][, lp f32 [n, n_vocab] with full]): the best k VOCABULARY entries
+        of log P(clip 0 | text) (- alpha * the prior's) in the stable descending order, ranked on the device."""
+        import torch
+        n = int(rows.shape[0])
+        n_prior = 0 if prior_rows is None else int(prior_rows.shape[0])
+        idx = torch.empty((n, int(k)), dtype=torch.int32, device=self.device)
+        val = torch.empty((n, int(k)), dtype=torch.float32, device=self.device)
+        lp = torch.empty((n, self.n_vocab), dtype=torch.float32, device=self.device) if full else None
+        bs = batch.struct(self.max_positions)
+        _check(self.lib.blim_score_tvg_first(self.h, C.byref(bs), _ptr(embeds), _ptr(rows), n, _ptr(prior_rows) if n_prior else None, n_prior, _ptr(prior_of),
+                                             float(alpha), int(k), _ptr(idx), _ptr(val), _ptr(lp), _stream()), "blim_score_tvg_first")
+        return (idx, val, lp) if full else (idx, val)
+
     def forward(self, embeds, mask, want_logits=True, want_hidden=True):
         """Literal forward: embeds [B,L,H] bf16, mask [B,L] uint8 -> (logits f32 [B,L,V] | None, hidden f32 [B,L,H] | None)."""
         import torch
@@ -782,6 +800,16 @@ def lse_combine(part, label_logit, labels, logprob):
 def tvg_criterion(logits, n_vocab: int, labels, n_pairs: int, clips: int, score):
     """blim_tvg_criterion: logits f32 [n_pairs * clips, ld], labels int32 [n_pairs]; score f32 [>= n_pairs] is written."""
     _check(load_library().blim_tvg_criterion(_ptr(logits), logits.shape[1], n_vocab, _ptr(labels), n_pairs, clips, _ptr(score), _stream()), "blim_tvg_criterion")
+
+
+def tvg_rank(logits, n_vocab: int, k: int, idx_out, val_out, prior_logits=None, prior_of=None, alpha: float = 0.0, logprob_out=None, n_rows: Optional[int] = None,
+             n_prior: Optional[int] = None):
+    """blim_tvg_rank: logits f32 [n_rows, ld] (prior_logits f32 [n_prior, ld_prior], prior_of int32 [n_rows]); idx_out int32 / val_out f32 [>= n_rows * k] and the
+    optional logprob_out f32 [n_rows, ld_out] are written."""
+    _check(load_library().blim_tvg_rank(_ptr(logits), 0 if logits is None else logits.shape[1], n_vocab, logits.shape[0] if n_rows is None else n_rows, _ptr(prior_logits),
+                                        0 if prior_logits is None else prior_logits.shape[1], (0 if prior_logits is None else prior_logits.shape[0]) if n_prior is None else n_prior,
+                                        _ptr(prior_of), float(alpha), k, _ptr(idx_out), _ptr(val_out), _ptr(logprob_out), 0 if logprob_out is None else logprob_out.shape[1],
+                                        _stream()), "blim_tvg_rank")
 
 
 def group_mean_rows(out, inp, n_out: int, group: int, H: int, dtype: str, split: bool = False):

@@ -38,6 +38,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .calibration import VTG_SPLIT_MODES
+from .engine import TVG_RANK_MAX_K
 from .pair_scorer import SEG_MAX, PairScorer, _PackState       # noqa: F401  (SEG_MAX: the planner's bound, named here too)
 
 SLOT_ALIGN = 32          # a slot's positions are padded to a multiple of the attention's key tile
@@ -565,6 +566,7 @@ class GalleryIndex(_PrefixIndex):
         self._split_id = np.zeros(0, dtype=np.int64)
         self._sync_texts()
         self.shortlist_stats = {"queries": 0, "passes": 0, "pairs": 0}      # texts shortlisted, stage-1 passes (one tvg_gallery each), the (text, video) pairs those scored
+        self.prefilter_stats = {"queries": 0, "passes": 0, "rows": 0, "kept": 0}   # texts prefiltered, stage-0 passes (one tvg_first each), the logits rows those ranked, the videos kept
 
     def _count_texts(self) -> int:
         return len(self.s.vtg_split)
@@ -766,14 +768,59 @@ class GalleryIndex(_PrefixIndex):
         return (np.stack([b[0] for b in best]) if best else np.zeros((0, k), np.int64),
                 np.stack([b[1] for b in best]) if best else np.zeros((0, k), stage.dtype))
 
+    # ---- the prefilter: the gallery ranked on the device by the clip-0 summand of the TVG score, the best K0 kept for the likelihood
+    def prefilter(self, texts, k0: int, cpn: bool = False, alpha=(0.0, 0.0)) -> np.ndarray:
+        """The K0 videos of each text that log P(clip 0 of the video | text) ranks first (minus alpha[0] x the candidate prior's clip-0 term with cpn): ONE
+        PairScorer.tvg_first pass for all texts, one logits row per distinct prompt whatever the gallery's size.  -> cand [Q, min(k0, N)] video indices, ASCENDING
+        (a set: what ranks it is stage 1).  ValueError for a K0 that is no positive integer or, clipped to N, above the rank kernel's BLIM_TVG_RANK_MAX_K."""
+        if isinstance(k0, bool) or int(k0) != k0 or int(k0) < 1:
+            raise ValueError(f"prefilter: K0 = {k0!r}: a positive integer")
+        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
+        k0 = min(int(k0), len(self.s.video))
+        if k0 > TVG_RANK_MAX_K:
+            raise ValueError(f"prefilter: K0 = {k0} above the rank kernel's limit of {TVG_RANK_MAX_K} (BLIM_TVG_RANK_MAX_K)")
+        kept = self._stage0(texts, [k0] * len(texts), cpn, alpha)
+        return np.stack(kept) if kept else np.zeros((0, k0), np.int64)
+
+    def _stage0(self, texts, k0s, cpn: bool, alpha) -> List[np.ndarray]:
+        """ONE stage-0 pass at the largest K0 (checked and clipped by the caller): text q keeps the first k0s[q] of its own order -- a smaller K0's survivors are a
+        prefix of a larger one's -- sorted ascending."""
+        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
+        if not len(texts):
+            return []
+        self.s._need_tvg(texts)
+        self._tvg_state()
+        idx, _ = self.s.tvg_first(texts, max(k0s), cpn=cpn, alpha=float(alpha[0]))
+        st = self.prefilter_stats
+        st["queries"] += len(texts); st["passes"] += 1; st["rows"] += len(np.unique(texts)); st["kept"] += int(sum(k0s))
+        return [np.sort(row[:k]) for row, k in zip(idx, k0s)]
+
     def search_requests(self, requests, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0), finetuned: bool = False):
         """rerank_requests() with requests that may take their candidates from the shortlist: requests = [(text index, candidate video indices [k_q] or None,
         first_stage [k_q] or None, shortlist K or None)], exactly one of candidates and K per request.  A request with candidates is rerank_requests' (its TVG term
         one PairScorer.tvg call over the explicit requests' pairs).  The shortlist requests of the batch share ONE stage-1 pass (_stage1) over the whole gallery;
         each keeps its best K videos as candidates, its first-stage term is zero, and the TVG candidate term of its blend IS its stage-1 value: it is not computed a
-        second time.  All requests then share ONE vtg_pairs pass (one pass of a lazy index).  -> [(order [k_q], blended [k_q])] in request order."""
-        reqs = []
-        for t, cand, fs, K in requests:
+        second time.  All requests then share ONE vtg_pairs pass (one pass of a lazy index).  -> [(order [k_q], blended [k_q])] in request order.
+        A shortlist request may carry a fifth field, the prefilter's K0 >= K: (text, None, None, K, K0).  The prefiltered requests of the batch share ONE stage-0
+        pass (prefilter, at the largest K0: a smaller K0's survivors are the first K0 of the same order); their stage-1 terms are ONE PairScorer.tvg call over their
+        surviving pairs (minus alpha[0] x the prior over those K0 candidates with cpn), of which each keeps its best K as a shortlist request does."""
+        reqs, pre = [], {}
+        for req in requests:
+            if len(req) == 5:
+                t, cand, fs, K, K0 = req
+                if K0 is not None:
+                    if K is None:
+                        raise ValueError("search_requests: a prefilter K0 narrows a shortlist: the request needs its K")
+                    if isinstance(K0, bool) or int(K0) != K0 or int(K0) < 1:
+                        raise ValueError(f"search_requests: prefilter K0 = {K0!r}: a positive integer")
+                    if not isinstance(K, bool) and int(K) == K and int(K0) < int(K):
+                        raise ValueError(f"search_requests: prefilter K0 = {K0} below the shortlist's K = {K}")
+                    if min(int(K0), len(self.s.video)) > TVG_RANK_MAX_K:
+                        raise ValueError(f"search_requests: prefilter K0 = {min(int(K0), len(self.s.video))} above the rank kernel's limit of {TVG_RANK_MAX_K} "
+                                         f"(BLIM_TVG_RANK_MAX_K)")
+                    pre[len(reqs)] = min(int(K0), len(self.s.video))
+            else:
+                t, cand, fs, K = req
             if (cand is None) == (K is None):
                 raise ValueError("search_requests: a request takes candidates or a shortlist K, one of the two")
             if K is not None:
@@ -789,13 +836,25 @@ class GalleryIndex(_PrefixIndex):
                 reqs.append([int(t), cand, fs, None])
         if not reqs:
             return []
-        short = [n for n, r in enumerate(reqs) if r[3] is not None]
+        short = [n for n, r in enumerate(reqs) if r[3] is not None and n not in pre]
         stage1 = {}
-        if short:
+        if short or pre:
             if not finetuned:
                 raise ValueError("search_requests: a shortlist ranks by the TVG likelihood, which a zero-shot model does not have (finetuned=False)")
+        if short:
             for n, row in zip(short, self._stage1([reqs[n][0] for n in short], cpn, alpha)):
                 reqs[n][1], stage1[n] = self._best(row, reqs[n][3])
+        if pre:
+            ns = sorted(pre)
+            texts = [reqs[n][0] for n in ns]
+            cands = self._stage0(texts, [pre[n] for n in ns], cpn, alpha)
+            pp = np.concatenate([np.stack([cand, np.full(len(cand), t, dtype=np.int64)], axis=1) for t, cand in zip(texts, cands)])
+            term = self.s.tvg(pp)
+            if cpn:
+                term = term - alpha[0] * self._t2v_prior(texts, cands)
+            for n, cand, row in zip(ns, cands, np.split(term, np.cumsum([len(x) for x in cands])[:-1])):
+                order, best = self._best(row, reqs[n][3])
+                reqs[n][1], stage1[n] = cand[order], best
         pairs = np.concatenate([np.stack([cand, np.full(len(cand), t, dtype=np.int64)], axis=1) for t, cand, _, _ in reqs])
         ends = np.cumsum([len(cand) for _, cand, _, _ in reqs])
         ql = np.split(self.vtg_pairs(pairs), ends[:-1])

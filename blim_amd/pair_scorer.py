@@ -30,7 +30,7 @@ def _clip_major_vocab(video_vocab, device, dtype):
 @dataclass
 class Plan:
     """One engine call: packed batch + row bookkeeping, all device-resident."""
-    kind: str                  # "vtg" | "tvg"
+    kind: str                  # "vtg" | "tvg" | "tvg_first"
     batch: PackedBatch
     src_index: object          # int32 [n_tokens]  (assemble input)
     feats: object              # bf16 [n_feat_rows, H]
@@ -45,6 +45,7 @@ class Plan:
     slots_used: Optional[np.ndarray] = None      # ... host int32: every slot the call reads
     admits: Optional[np.ndarray] = None          # ... host int32 [n, 5] = (seq, slot, start, len, row): in-batch prefixes the call also captures into slots (a source with `admit`)
     prefix_tokens: int = 0                       # ... of n_tokens, those of in-batch prefix sequences
+    prior_rows: Optional[object] = None          # kind "tvg_first": device int32, the prior sequences' scored tokens (None without cpn); `labels` is then each row's prior row
 
 
 def _split_prompt_response(ids: np.ndarray, labels: np.ndarray):
@@ -663,6 +664,70 @@ class PairScorer(CalibrationMixin):
             out[out_index[:, 0]] = r.float().cpu().numpy()
         return out.reshape(len(uniq), N)[inv.reshape(-1)]
 
+    # ---- clip 0 of every video from the caption prompt alone (the prefilter's stage 0)
+    def iter_tvg_first(self, texts, cpn: bool = False):
+        """texts [Q] (text indices): the engine calls of log P(clip 0 of video j | text) for EVERY j at once -- a pair's first scored row is its prompt's last
+        row (_plan_tvg), so one row per text carries the whole gallery.  Each distinct caption prompt (by bytes) is packed once, a sequence of its own; its scored
+        row is its last token.  cpn: for each distinct video-independent prior key of _plan_tvg (pr[:tp] bytes, len(pr), pr[-1]) the head pr[:tp] is packed once
+        per call and a one-token sequence [pr[-1]] follows it at position len(pr) - 1, visible as a key when len(pr) - 1 < tp, the head its prefix: the first
+        token of _plan_tvg's prior segment, which predicts clip 0 and does not depend on the video.  Plans of kind "tvg_first": rows = the prompts' rows,
+        prior_rows = the prior tokens' rows, labels = each prompt row's index into prior_rows, out_index = the positions in `texts` each row answers.  Calls are
+        cut at max_tokens; a prompt and its prior share a call."""
+        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
+        if not len(texts):
+            return
+        self._need_tvg(texts)
+        tp = self.m.tvg_prefix_length
+        groups: Dict[bytes, List[int]] = {}
+        for q, i in enumerate(texts):
+            groups.setdefault(self.tvg_split[int(i)].tobytes(), []).append(q)
+        st = _FirstCall(self, cpn)
+        for pbytes, outs in groups.items():
+            pr = np.frombuffer(pbytes, dtype=np.int64)
+            if st.n_tok and st.n_tok + st.need(pr, tp) > self.max_tokens:
+                yield st.finish(); st = _FirstCall(self, cpn)
+            st.add(pr, tp, outs)
+        if st.n_pairs:
+            yield st.finish()
+
+    def _label_inverse(self):
+        """-> (device int64 [n_vocab]: the video of each vocabulary entry, device int64 [N]: tvg_video_labels), memoised per vocab_version.  The rank kernel ranks
+        VOCABULARY entries; they name videos only when tvg_video_labels is a permutation of arange(N)."""
+        import torch
+        memo = getattr(self, "_label_inv", None)
+        if memo is None or memo[0] != self.vocab_version:
+            lab = np.asarray(self.tvg_video_labels, dtype=np.int64)
+            N = len(self.video)
+            if len(lab) != N or self.n_vocab != N or not np.array_equal(np.sort(lab), np.arange(N)):
+                raise ValueError(f"tvg_first: tvg_video_labels must be a permutation of arange({N}) -- one vocabulary entry per video ({self.n_vocab} entries, "
+                                 f"{len(np.unique(lab))} distinct labels)")
+            inv = np.empty(N, dtype=np.int64)
+            inv[lab] = np.arange(N)
+            memo = self._label_inv = (self.vocab_version, torch.from_numpy(inv).to(self.device), torch.from_numpy(lab).to(self.device))
+        return memo[1], memo[2]
+
+    def tvg_first(self, texts, k: int, cpn: bool = False, alpha: float = 0.0, full: bool = False):
+        """The best k videos of each text by log P(clip 0 of the video | text) -- minus alpha x the candidate prior's clip-0 term with cpn -- ranked ON THE DEVICE
+        (Engine.score_tvg_first): -> (idx int64 [Q, k] video indices, val f32 [Q, k], and with full lp f32 [Q, N], the log-probabilities by video index).  The order
+        is descending with ties to the lower VOCABULARY entry.  Each distinct prompt is computed once; a value does not depend on what shares its call."""
+        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
+        inv, lab = self._label_inverse()
+        N, k = self.n_vocab, int(k)
+        if not 1 <= k <= N:
+            raise ValueError(f"tvg_first: k = {k} outside 1 .. {N}")
+        idx = np.zeros((len(texts), k), dtype=np.int64)
+        val = np.zeros((len(texts), k), dtype=np.float32)
+        lp = np.zeros((len(texts), N), dtype=np.float32) if full else None
+        done = [(p.out_index, self.run(p, k=k, alpha=float(alpha), full=full)) for p in self.iter_tvg_first(texts, cpn)]
+        for out_index, res in done:
+            vi, vv = inv[res[0].long()].cpu().numpy(), res[1].cpu().numpy()
+            vl = res[2][:, lab].cpu().numpy() if full else None
+            for r, outs in enumerate(out_index):
+                idx[outs], val[outs] = vi[r], vv[r]
+                if full:
+                    lp[outs] = vl[r]
+        return (idx, val, lp) if full else (idx, val)
+
     # ---- execution (device) ---------------------------------------------------------------------
     @contextmanager
     def _call_options(self, kind: str):
@@ -698,9 +763,20 @@ class PairScorer(CalibrationMixin):
         if lo6 and self.split_tvg and getattr(self.engine, "dtype", "") != "bf16":      # (bf16 engines: TVG calls keep the bf16 second pass, Engine.set_precise)
             self.exec_flops_lo6 += lo6_pass_flops(self.m.dims, plan.n_tokens, plan.n_rows, "tvg", self.tvg_mode, prune=not f8)
 
-    def run(self, plan: Plan, cache=None):
+    def run(self, plan: Plan, cache=None, k: int = 1, alpha: float = 0.0, full: bool = False):
         """One engine call; returns a device f32 tensor [plan.n_pairs].  A plan made over a prefix source (plan.pfx_slot) goes through `cache`, the PrefixCache
-        that holds its slots, and is not counted in exec_*: those count the scorer's own calls."""
+        that holds its slots, and is not counted in exec_*: those count the scorer's own calls.  A plan of kind "tvg_first" (k, alpha, full are its arguments)
+        returns Engine.score_tvg_first's tuple instead."""
+        if plan.kind == "tvg_first":
+            self._count(plan)
+            with self._call_options("tvg"):
+                if self.vocab_cm is not None and (getattr(self, "_first_vocab", None) != (self.vocab_version, getattr(self.engine, "_vocab_key", None))):
+                    self.engine.set_video_vocab(self._vocab_src)            # a scorer whose TVG calls name their vocabulary: the rank runs over the registered one
+                    self._first_vocab = (self.vocab_version, self.engine._vocab_key)
+                embeds = self.engine.assemble(plan.src_index, plan.feats)
+                cpn = plan.prior_rows is not None
+                return self.engine.score_tvg_first(plan.batch, embeds, plan.rows, k, prior_rows=plan.prior_rows, prior_of=plan.labels if cpn else None,
+                                                   alpha=alpha if cpn else 0.0, full=full)
         if plan.pfx_slot is None:
             self._count(plan)
             via, slots = self.engine, ()
@@ -868,6 +944,55 @@ class _PackState:
                     out_index=self.out_index, n_tokens=self.n_tok, n_rows=len(self.rows),
                     pfx_slot=t(self.slot) if cached else None, slots_used=np.array(sorted(self.used), dtype=np.int32) if cached else None,
                     admits=admits, prefix_tokens=n_prefix_tok if cached else 0)
+
+
+class _FirstCall:
+    """One engine call of PairScorer.iter_tvg_first: caption prompts, and with cpn the prior heads and one-token prior sequences, each packed once per call."""
+
+    def __init__(self, scorer: PairScorer, cpn: bool):
+        self.st, self.cpn = _PackState(scorer, "tvg"), bool(cpn)
+        self.heads: Dict[bytes, int] = {}                                  # head bytes -> start of its sequence in this call
+        self.priors: Dict[Tuple, int] = {}                                 # prior key -> index into prior_rows
+        self.prior_rows: List[int] = []
+
+    n_tok = property(lambda self: self.st.n_tok)
+    n_pairs = property(lambda self: self.st.n_pairs)
+
+    def _key(self, pr, tp):
+        return (pr[:tp].tobytes(), len(pr), int(pr[-1]))
+
+    def need(self, pr, tp) -> int:
+        """Tokens the prompt would add to this call."""
+        if not self.cpn:
+            return len(pr)
+        key = self._key(pr, tp)
+        return len(pr) + (0 if key in self.priors else 1 + (0 if key[0] in self.heads else len(pr[:tp])))
+
+    def add(self, pr, tp, outs) -> None:
+        st, plen = self.st, len(pr)
+        at = -1
+        if self.cpn:
+            key = self._key(pr, tp)
+            at = self.priors.get(key, -1)
+            if at < 0:
+                head = pr[:tp]
+                h0 = self.heads.get(key[0])
+                if h0 is None:
+                    h0 = self.heads[key[0]] = st.add_seq(head, np.arange(len(head)), np.ones(len(head), np.uint8), None)
+                row = st.add_seq(pr[-1:], np.array([plen - 1]), np.array([1 if plen - 1 < tp else 0], np.uint8), (h0, len(head)))
+                at = self.priors[key] = len(self.prior_rows)
+                self.prior_rows.append(row)
+        p0 = st.add_seq(pr, np.arange(plen), np.ones(plen, np.uint8), None)
+        st.add_pair([p0 + plen - 1], np.array([at], np.int32), np.asarray(outs, dtype=np.int64))
+
+    def finish(self) -> Plan:
+        import torch
+        plan = self.st.finish()
+        plan.kind = "tvg_first"
+        if self.cpn:
+            plan.prior_rows = torch.from_numpy(np.asarray(self.prior_rows, dtype=np.int32)).to(self.st.s.device)
+            plan.n_rows += len(self.prior_rows)
+        return plan
 
 
 class _GalleryCall:

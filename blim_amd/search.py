@@ -7,7 +7,9 @@ DESIGN.md section 18) needs no first stage: the whole gallery is ranked by the T
 `--cpn`; PairScorer.tvg_gallery, the caption prompt once and num_clips - 1 clip tokens per video), the best `--shortlist K` (default `--topk`) are reranked with that
 term reused and a zero first-stage term, the best `--topk` of them are printed, the JSON line gains `"shortlisted": K`, and a `shortlist:` stderr line at the end
 counts the queries, the stage-1 passes and their pairs.  It serves `--query`, `--query_ids` and, under `--direction v2t`, `--video_ids` (there the captions are
-ranked by the query likelihood over the cached prompts: TextGalleryIndex.shortlist).  One JSON line per query: the ranked video ids and their
+ranked by the query likelihood over the cached prompts: TextGalleryIndex.shortlist).  `--prefilter K0` (t2v) puts a stage in front of that: the
+whole gallery is ranked ON THE DEVICE by the clip-0 term of the TVG likelihood -- one logits row per query, whatever the gallery's size -- and the TVG ranking runs on
+the best K0 only; the JSON line gains `"prefiltered": K0` and a `prefilter:` stderr line is printed at the end.  One JSON line per query: the ranked video ids and their
 blended t2v scores (training_utils.combine_and_rank's t2v half: `--cpn --alpha --c`; zero-shot runs blend the query likelihood with the first stage only).
 `--synthetic N [--synthetic_7b]`: a dry run on synth.make_problem, as main.py's.  `--gallery_fill lazy` computes no prefix up front: the first query runs at once, its
 calls leave their videos' prefixes in the cache, and `--gallery_gb` is the cache's capacity.  The `gallery stats:` stderr line reports the hits
@@ -25,7 +27,8 @@ writes one JSON line per request to stdout, in arrival order.  A request: `id` (
 candidates) and `topk` (truncates the answer).  Without candidates a `caption` request takes `--candidates` (`iv2`: its top-`--topk` of the first stage; `all`: the
 gallery; `tvg`: the shortlist); a `text` / `rows` request takes the whole gallery under `all`, the shortlist under `tvg`, and gets an error line under `iv2`.  A
 request may carry `"shortlist": K` itself, under any `--candidates`: its candidates are the best K of the gallery's TVG ranking and its answer gains
-`"shortlisted": K`; with `candidates` / `candidate_idx` or `first_stage`, a K that is no positive integer, a query without a TVG row, or a model without `--resume` it
+`"shortlisted": K`; next to it (or next to the default K under `--candidates tvg`) `"prefilter": K0` narrows the gallery to K0 >= K videos first and the answer gains
+`"prefiltered": K0`; with `candidates` / `candidate_idx` or `first_stage`, a K that is no positive integer, a query without a TVG row, or a model without `--resume` it
 gets an error line.  The answer is {"id", "query", "videos", "scores"} or
 {"id", "error"}: a bad request (malformed JSON, an unknown video id, an empty or duplicate candidate list, a row that fails PairScorer.add_texts' checks or leaves no
 response token under tokenizer_model_max_length, a fine-tuned blend with c0 < 1 for rows without a TVG row) gets its error line and the process goes on.
@@ -89,6 +92,9 @@ def get_args_parser():
                    help="iv2: the first stage's top --topk; all: the whole gallery; tvg (fine-tuned checkpoints, --resume): the whole gallery ranked by the TVG likelihood, "
                         "the best --shortlist reranked")
     p.add_argument("--shortlist", default=None, type=int, metavar="K", help="--candidates tvg: candidates kept from the TVG ranking of the gallery (default: --topk)")
+    p.add_argument("--prefilter", default=None, type=int, metavar="K0",
+                   help="--candidates tvg, t2v: the whole gallery is first ranked on the device by the clip-0 term of the TVG likelihood (one logits row per query, "
+                        "whatever the gallery's size), the TVG ranking runs on the best K0 >= --shortlist only")
     p.add_argument("--query_video", default=[], type=str, nargs="*", metavar="FILE",
                    help="--direction v2t: feature files of videos outside the dataset ([num_clips, tokens, width] tensors as blim_amd.extract writes them) used as queries; "
                         "they join the scorer (PairScorer.add_videos) before the indexes are built.  --candidates all | tvg")
@@ -198,6 +204,14 @@ def check_args(args, world: int = 1) -> None:
         raise SystemExit("search: --shortlist is the number of candidates --candidates tvg keeps (give --candidates tvg)")
     if args.candidates == "tvg" and shortlist_k(args) < 1:
         raise SystemExit("search: --shortlist must be at least 1 (it defaults to --topk)")
+    K0 = getattr(args, "prefilter", None)
+    if K0 is not None:
+        if v2t:
+            raise SystemExit("search: --prefilter narrows the t2v TVG ranking (--direction t2v): v2t has no prefilter")
+        if args.candidates != "tvg":
+            raise SystemExit("search: --prefilter narrows the gallery before --candidates tvg ranks it (give --candidates tvg)")
+        if K0 < 1 or K0 < shortlist_k(args):
+            raise SystemExit(f"search: --prefilter must be at least --shortlist ({shortlist_k(args)}): the shortlist is taken from the videos it keeps")
     if len(args.c) != 4 or len(args.alpha) != 2:
         raise SystemExit("search: --c takes 4 values, --alpha 2")
     if v2t and args.c[3] == 0:
@@ -444,6 +458,23 @@ class Server:
             raise BadRequest("first_stage is parallel to the candidates: a shortlist request names none")
         return None, None, int(K)
 
+    def _prefilter(self, req, shortlist):
+        """-> the K0 of a shortlisted request: its own `"prefilter"`, else --prefilter for a request that takes the default K; None: not prefiltered."""
+        from .engine import TVG_RANK_MAX_K
+        if "prefilter" not in req:
+            K0 = getattr(self.args, "prefilter", None)
+            return int(K0) if K0 is not None and shortlist is not None and "shortlist" not in req else None
+        K0 = req["prefilter"]
+        if isinstance(K0, bool) or not isinstance(K0, int) or K0 < 1:
+            raise BadRequest("prefilter must be a positive integer")
+        if shortlist is None:
+            raise BadRequest("prefilter narrows a shortlist: give shortlist (or run --candidates tvg), not candidates / candidate_idx")
+        if K0 < shortlist:
+            raise BadRequest(f"prefilter must be at least the shortlist's K = {shortlist}")
+        if min(K0, len(self.vids)) > TVG_RANK_MAX_K:
+            raise BadRequest(f"prefilter keeps at most {TVG_RANK_MAX_K} videos")
+        return K0
+
     def parse(self, line: str):
         """One request line -> a dict(id, query, text, cand, fs, topk, shortlist: K with cand None, or None); BadRequest (with .id, as far as it was read) for a request that gets an error line."""
         rid = None
@@ -465,13 +496,14 @@ class Server:
                 raise BadRequest("topk must be a positive integer")
             t, name = self._text(req)
             cand, fs, shortlist = self._candidates(req, t, "caption" in req)
+            prefilter = self._prefilter(req, shortlist)
             pre, post, resp = self.s.vtg_split[t]
             limit = getattr(self.s, "max_row_len", None)
             if limit is not None and len(pre) + int((self.n_vid if cand is None else self.n_vid[cand]).max()) + len(post) >= limit:
                 raise BadRequest(f"tokenizer_model_max_length = {limit} leaves no response token of this query after a candidate's video tokens")
             if self.finetuned and self.args.c[0] < 1 and self.s.tvg_split[t] is None:
                 raise BadRequest("a fine-tuned blend with c0 < 1 needs the query's TVG row (rows without tvg_ids / tvg_labels have none)")
-            return {"id": rid, "query": name, "text": t, "cand": cand, "fs": fs, "topk": topk, "shortlist": shortlist}
+            return {"id": rid, "query": name, "text": t, "cand": cand, "fs": fs, "topk": topk, "shortlist": shortlist, "prefilter": prefilter}
         except BadRequest as e:
             e.id = rid
             raise
@@ -480,7 +512,7 @@ class Server:
     def _add_request(self, rid, req):
         """`{"id", "add_video": {"vid", "features" | "frames"}}`, validated in full before anything changes -> dict(id, add: (vid, tensor, digest)).  `frames` (a
         .npy stack of raw frames) goes through the vision tower first and is a `features` request from there on."""
-        if any(k in req for k in ("caption", "text", "rows", "candidates", "candidate_idx", "first_stage", "shortlist", "topk")):
+        if any(k in req for k in ("caption", "text", "rows", "candidates", "candidate_idx", "first_stage", "shortlist", "prefilter", "topk")):
             raise BadRequest("an add_video request carries no query")
         a = req["add_video"]
         if not isinstance(a, dict) or set(a) not in ({"vid", "features"}, {"vid", "frames"}):
@@ -527,7 +559,8 @@ class Server:
     # ---- one batch
     def _score(self, reqs):
         a = self.args
-        return self.gal.search_requests([(r["text"], r["cand"], r["fs"], r["shortlist"]) for r in reqs], cpn=a.cpn, alpha=a.alpha, c=a.c, finetuned=self.finetuned)
+        five = lambda r: () if r.get("prefilter") is None else (r["prefilter"],)        # (a request that is not prefiltered: the 4-tuple it always was)
+        return self.gal.search_requests([(r["text"], r["cand"], r["fs"], r["shortlist"]) + five(r) for r in reqs], cpn=a.cpn, alpha=a.alpha, c=a.c, finetuned=self.finetuned)
 
     def handle(self, lines, write) -> None:
         """The requests that arrived together: every good one is scored in ONE search_requests pass; one answer line per request, in arrival order.  An add_video
@@ -579,6 +612,8 @@ class Server:
             order, blended = res
             k = len(order) if r["topk"] is None else min(r["topk"], len(order))
             more = {} if r["shortlist"] is None else {"shortlisted": r["shortlist"]}
+            if r.get("prefilter") is not None:
+                more["prefiltered"] = r["prefilter"]
             write(json.dumps({"id": r["id"], "query": r["query"], "videos": [self.vids[int(j)] for j in order[:k]], "scores": [float(x) for x in blended[:k]], **more}))
 
     def summary(self):
@@ -743,6 +778,8 @@ def main(args):
         print(f"serve: {json.dumps(summary)}", file=sys.stderr, flush=True)
         if gal.shortlist_stats["passes"]:
             print(f"shortlist: {json.dumps(_shortlist_line(gal.shortlist_stats))}", file=sys.stderr, flush=True)
+        if getattr(gal, "prefilter_stats", {"passes": 0})["passes"]:
+            print(f"prefilter: {json.dumps(_prefilter_line(gal.prefilter_stats))}", file=sys.stderr, flush=True)
         gal.close()
         model.engine.close()
         return 0
@@ -756,9 +793,9 @@ def main(args):
     for t, name in zip(texts, names):
         more = {}
         if args.candidates == "tvg":              # the gallery ranked by the TVG candidate term, the best K reranked; the answer is the best --topk of those
-            K = shortlist_k(args)
-            (o, b), = gal.search_requests([(t, None, None, K)], cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
-            order, blended, more = o[None, :k], b[None, :k], {"shortlisted": K}
+            K, K0 = shortlist_k(args), getattr(args, "prefilter", None)
+            (o, b), = gal.search_requests([(t, None, None, K) + (() if K0 is None else (K0,))], cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
+            order, blended, more = o[None, :k], b[None, :k], {"shortlisted": K, **({} if K0 is None else {"prefiltered": K0})}
         else:
             if args.candidates == "iv2":
                 row = np.asarray(t2v_iv2[t], dtype=np.float32)
@@ -777,6 +814,8 @@ def main(args):
     print(f"gallery stats: {json.dumps(gal.stats.as_dict())}", file=sys.stderr, flush=True)
     if gal.shortlist_stats["passes"]:
         print(f"shortlist: {json.dumps(_shortlist_line(gal.shortlist_stats))}", file=sys.stderr, flush=True)
+    if getattr(gal, "prefilter_stats", {"passes": 0})["passes"]:
+        print(f"prefilter: {json.dumps(_prefilter_line(gal.prefilter_stats))}", file=sys.stderr, flush=True)
     if gal.host is not None:
         print(f"gallery host tier: {json.dumps(dict(gal.host.stats.as_dict(), records=gal.host.n_records, record_bytes=gal.host.record_bytes))}", file=sys.stderr, flush=True)
     gal.close()
@@ -787,6 +826,11 @@ def main(args):
 def _shortlist_line(stats):
     """The `shortlist:` stderr line: queries shortlisted, stage-1 passes and the pairs those scored."""
     return {"queries": int(stats["queries"]), "stage1_passes": int(stats["passes"]), "stage1_pairs": int(stats["pairs"])}
+
+
+def _prefilter_line(stats):
+    """The `prefilter:` stderr line: queries prefiltered, stage-0 passes, the logits rows those ranked and the videos kept for stage 1."""
+    return {"queries": int(stats["queries"]), "stage0_passes": int(stats["passes"]), "stage0_rows": int(stats["rows"]), "kept": int(stats["kept"])}
 
 
 def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) -> int:

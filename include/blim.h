@@ -195,6 +195,15 @@ int blim_score_vtg(blim_engine* e, const blim_batch* b, const void* embeds, cons
 /* TVG: rows[p*clips + c] = packed token whose hidden state predicts clip c of pair p. */
 int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, const void* vocab_bf16,
                    int32_t n_vocab, const int32_t* labels, int32_t n_pairs, float* score, void* stream);
+/* TVG, clip 0 against the WHOLE registered vocabulary (additive in ABI v9; blim_amd/pair_scorer.py: tvg_first): every pair of a text scores clip 0 from the caption
+ * prompt's last row, so log P(clip 0 of video j | text) for all j is the log-softmax of ONE logits row.  rows (DEVICE, n_rows) and prior_rows (DEVICE, n_prior; may
+ * be NULL with n_prior 0) name packed tokens; the call is blim_score_tvg up to the visual head over those n_rows + n_prior rows, then the clip-0 logits against the
+ * registered vocabulary (the three-term product on a compensated call) -- each row bit for bit the one blim_score_tvg forms for a pair of that text -- and
+ * blim_tvg_rank over the two row blocks: prior_of (DEVICE [n_rows], may be NULL) names row r's prior row, alpha, k, idx_out / val_out [n_rows, k] and the optional
+ * logprob_out [n_rows, n_vocab] are blim_tvg_rank's.  It runs under the options of the TVG calls.  Refused: no registered vocabulary and an fp8 engine
+ * (BLIM_ERR_STATE), blim_tvg_rank's refusals of k before anything is launched. */
+int blim_score_tvg_first(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, int32_t n_rows, const int32_t* prior_rows, int32_t n_prior,
+                         const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, void* stream);
 
 /* ---- Gallery prefix cache (additive in ABI v9; blim_amd/gallery.py): the K / V of every layer and the last row's final-norm hidden state of prefixes,
  * computed once and kept in device memory, so that a new query is scored on its own continuation tokens alone.  A cache holds prefixes of either kind: a VTG slot
@@ -548,6 +557,17 @@ int blim_rmsnorm_f8(const float* x, int64_t ldx, int64_t n_rows, int32_t H, cons
 int blim_lse_combine(const float* part, int32_t n_tiles, const float* label_logit, const int32_t* labels, int64_t n_rows, float* logprob, void* stream);
 /* score[p] = mean over c < clips of log_softmax(logits[p * clips + c, :n_vocab])[labels[p]]; logits f32 rows of stride ld >= n_vocab. */
 int blim_tvg_criterion(const float* logits, int64_t ld, int32_t n_vocab, const int32_t* labels, int32_t n_pairs, int32_t clips, float* score, void* stream);
+/* Row log-softmax over the vocabulary plus the exact top k, one launch.  lp[r][j] = log_softmax(logits[r, :n_vocab])[j] with blim_tvg_criterion's own normaliser:
+ * as a float, blim_tvg_criterion of row r with label j at clips = 1.  term = lp, or, for 0 <= prior_of[r] < n_prior, lp - alpha * pl with pl the same expression over
+ * row prior_of[r] of prior_logits (f32 rows of stride ld_prior), in f32 with two roundings and no fused multiply-add; prior_of (DEVICE [n_rows]) may be NULL, an entry
+ * < 0 means no prior (term = lp, the same bits), an entry >= n_prior gives a NaN row, never a read outside the buffer (the device array is not read back).
+ * idx_out / val_out [n_rows, k] = the first k of the stable descending order of term: ties to the lower index, -inf after every finite value, NaN last and by
+ * index among themselves; exact and deterministic.  logprob_out (optional, rows of stride ld_out) receives the lp rows; columns >= n_vocab are left alone.
+ * BLIM_ERR_ARG (the message names the argument): a null logits / idx_out / val_out, n_vocab < 1, n_rows < 1, k < 1, k > n_vocab, k > BLIM_TVG_RANK_MAX_K, ld /
+ * ld_prior / ld_out below n_vocab, prior_of without prior_logits, n_prior < 0. */
+#define BLIM_TVG_RANK_MAX_K 1024
+int blim_tvg_rank(const float* logits, int64_t ld, int32_t n_vocab, int32_t n_rows, const float* prior_logits, int64_t ld_prior, int32_t n_prior,
+                  const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, void* stream);
 /* blim_group_mean / blim_assemble with the engine's fields as arguments: H, the 16-bit type, the embedding table (16-bit [*, H]) and split -- rows [hi | lo] of
  * width 2 H (feature rows and outputs; a table row's lo half is zero).  H % 8 == 0 for the assembly, H % 4 == 0 for the mean. */
 int blim_group_mean_rows(void* out, const void* in, int64_t n_out, int32_t group, int32_t H, int32_t dtype16, int32_t split, void* stream);

@@ -71,7 +71,17 @@ spare-slot fill (_sync_videos: the projection of the new videos and one packed f
 same query again (hit).  Then the stream of Q queries x top-k over the grown eager index against an index built over all N from the start, alternated `--reps` times
 in one process and checked bit-equal (a tvg_gallery query too), with the engine's timing classes of one stream each: the same classes with the same call counts.
 
-    python tools/gallery_bench.py --grow 8 --modes none --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r24_gallery_grow.json"""
+    python tools/gallery_bench.py --grow 8 --modes none --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r24_gallery_grow.json
+
+`--shortlist K --prefilter K0 [K0 ...]` (t2v): `--shortlist`'s protocol (the fine-tuned blend, the narrow options on auto, one eager index,
+`--gallery_gb` caps it) for the shortlist of K alone -- the parent's `--candidates tvg`, stage 1 over the whole gallery -- against the cascade at each K0: stage 0
+(GalleryIndex._stage0: one logits row per query, ranked on the device), stage 1 (PairScorer.tvg over the K0 survivors), stage 2 (the cached VTG rerank of the best K),
+per request and in groups of `--shortlist_batches`, alternated `--reps` times in one process; every repetition is checked bit-equal to the leg's first run.  Stage 0
+is taken apart into host planning, the engine call (HIP events) and the rank kernel alone (HIP events, blim_tvg_rank on logits of the call's shape).  The share of
+the parent shortlist's K videos that lie inside the K0 is reported -- on random weights, which says nothing about a trained checkpoint.  `--rank_kernel`: the rank
+kernel alone at N = 1,000 and 100,000, 1 and 8 rows, k = 128, against what it replaces on the parent: the [rows, N] copy to the host plus np.argsort(kind="stable").
+
+    python tools/gallery_bench.py --shortlist 16 --prefilter 64 128 256 --rank_kernel --modes none --tvg_modes attn --n 1000 --queries 55 --synthetic_7b --out profiles/r26_prefilter.json"""
 import argparse
 import json
 import os
@@ -121,6 +131,9 @@ def main():
                     help="whole-gallery queries on the fine-tuned blend: --candidates all against --candidates tvg with a shortlist of K, per request and in batches (t2v)")
     ap.add_argument("--shortlist_batches", type=int, nargs="+", default=[1, 8], metavar="B", help="--shortlist: requests per pass")
     ap.add_argument("--recall_k", type=int, nargs="+", default=[16, 64, 256], metavar="K", help="--shortlist: the shortlist sizes whose cover of the `all` top-1 / top-10 is reported")
+    ap.add_argument("--prefilter", type=int, nargs="+", default=None, metavar="K0", help="--shortlist K: the shortlist alone against the cascade with a prefilter of K0 (t2v)")
+    ap.add_argument("--rank_kernel", action="store_true", help="--prefilter: also the rank kernel alone against the copy to the host plus np.argsort")
+    ap.add_argument("--gallery_gb", type=float, default=None, help="--prefilter: device memory for the prefix cache (default: every video)")
     ap.add_argument("--grow", type=int, default=None, metavar="K", help="the index built over N - K videos and grown by K (PairScorer.add_videos) against one built over all N (t2v)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -143,6 +156,8 @@ def main():
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.grow:
         return main_grow(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if a.shortlist and a.prefilter:
+        return main_prefilter(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.shortlist:
         return main_shortlist(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.serve_batch:
@@ -647,6 +662,146 @@ def main_shortlist(a, dims, model, prob, vtg, tvg, video, q, tpc):
             gal.close()
             del sc
             torch.cuda.empty_cache()
+    for o in ("narrow_gemm", "narrow_lo6", "narrow_qkv"):
+        e.set_option(o, 0)
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def rank_kernel_alone(shapes, k, reps=20):
+    """blim_tvg_rank alone (HIP events) against the [rows, N] copy to the host plus np.argsort(kind="stable") of every row, on Gaussian logits."""
+    from blim_amd import engine as eng
+    out = {}
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for rows, N in shapes:
+        kk = min(k, N)
+        lg = torch.randn((rows, N), dtype=torch.float32, device="cuda")
+        idx, val = torch.empty((rows, kk), dtype=torch.int32, device="cuda"), torch.empty((rows, kk), dtype=torch.float32, device="cuda")
+        lp = torch.empty((rows, N), dtype=torch.float32, device="cuda")
+        for _ in range(3):
+            eng.tvg_rank(lg, N, kk, idx, val)
+        ms = {"select": [], "select_and_lp": []}
+        for name, more in (("select", {}), ("select_and_lp", {"logprob_out": lp})):
+            for _ in range(reps):
+                ev0.record(); eng.tvg_rank(lg, N, kk, idx, val, **more); ev1.record()
+                torch.cuda.synchronize()
+                ms[name].append(ev0.elapsed_time(ev1))
+        host = []
+        for _ in range(reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            h = torch.log_softmax(lg, dim=1).cpu().numpy()
+            order = np.stack([np.argsort(-r, kind="stable")[:kk] for r in h])
+            host.append(1e3 * (time.perf_counter() - t0))
+        assert np.array_equal(order[:, 0], idx.cpu().numpy()[:, 0])
+        out[f"rows{rows}_N{N}"] = {"k": kk, "kernel_ms": float(np.median(ms["select"])), "kernel_with_logprob_out_ms": float(np.median(ms["select_and_lp"])),
+                                   "copy_back_and_argsort_ms": float(np.median(host))}
+    return out
+
+
+def main_prefilter(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    """`--shortlist K --prefilter K0 ...`: the parent's shortlist against the cascade, see the module text."""
+    from blim_amd import engine as eng
+    e = model.engine
+    for o in ("narrow_gemm", "narrow_lo6", "narrow_qkv"):
+        e.set_option(o, 1)
+    med = lambda x: float(np.median(x))
+    spread = lambda x: float((max(x) - min(x)) / np.median(x))
+    Q, N = len(q), a.n
+    K = min(int(a.shortlist[0]), N)
+    K0s = sorted(set(min(int(k0), N) for k0 in a.prefilter))
+    Bs = sorted(set(min(int(B), Q) for B in a.shortlist_batches))
+    more = dict(cpn=False, alpha=(0.0, 0.0), c=(0.5, 0.5, 1.0, 0.5), finetuned=True)
+    res = {"shortlist": K, "prefilter": K0s, "batches": Bs, "n": N, "queries": Q, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc,
+           "reps": a.reps, "blend": {"c": list(more["c"]), "cpn": False}, "options": {"narrow_gemm": 1, "narrow_lo6": 1, "narrow_qkv": 1}, "gallery_gb": a.gallery_gb, "runs": {}}
+    for mode in a.modes.split(","):
+        for tmode in a.tvg_modes.split(","):
+            model.vtg_precise = None if mode == "none" else mode
+            model.tvg_precise = tmode
+            model.clear_cache()
+            sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, torch.from_numpy(prob.video_vocab),
+                               torch.from_numpy(prob.tvg_video_labels), dims.num_clips, max_tokens=a.max_tokens)
+            sc.set_vtg_mode(model.vtg_mode()); sc.set_tvg_mode(model.tvg_mode())
+            warm = np.stack([np.arange(8), np.full(8, q[0])], axis=1)
+            sc.vtg(warm); sc.tvg(warm)
+            gal = GalleryIndex(sc, budget_bytes=None if a.gallery_gb is None else int(a.gallery_gb * 2**30))
+            t_build, _ = timed(gal.build)
+            sc.gallery_feats()
+            clock = {"s0": 0.0, "s1": 0.0}
+
+            def wrap(obj, name, key):
+                inner = getattr(obj, name)
+
+                def f(*args, **kw):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    out = inner(*args, **kw)
+                    clock[key] += time.perf_counter() - t0
+                    return out
+                setattr(obj, name, f)
+            wrap(gal, "_stage0", "s0"); wrap(gal, "_stage1", "s1"); wrap(sc, "tvg", "s1")
+
+            def run(K0, B):
+                reqs = [(int(t), None, None, K) + (() if K0 is None else (K0,)) for t in q]
+                return [r for lo in range(0, Q, B) for r in gal.search_requests(reqs[lo:lo + B], **more)]
+            legs = [(K0, B) for K0 in [None] + K0s for B in Bs]
+            name = lambda K0, B: f"{'parent' if K0 is None else f'pre{K0}'}_tvg{K}_B{B}"
+            ref = {leg: run(*leg) for leg in legs}
+            ts, s0, s1 = ({leg: [] for leg in legs} for _ in range(3))
+            for rep_ in range(a.reps):
+                for leg in legs:
+                    clock["s0"] = clock["s1"] = 0.0
+                    dt, got = timed(lambda: run(*leg))
+                    ts[leg].append(dt); s0[leg].append(clock["s0"]); s1[leg].append(clock["s1"])
+                    print(f"repetition {rep_}: {name(*leg)} {dt:.3f} s", file=sys.stderr, flush=True)
+                    assert all(np.array_equal(o, o1) and np.array_equal(b, b1) for (o, b), (o1, b1) in zip(got, ref[leg])), f"{name(*leg)}: results differ between repetitions"
+            # stage 0 taken apart: planning on the host, the engine call, the rank kernel alone on logits of the call's shape
+            parts = {}
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for B in Bs:
+                for K0 in K0s:
+                    plan_ms, gpu_ms, rank_ms = [], [], []
+                    for _ in range(a.reps):
+                        tp = tg_ = tr = 0.0
+                        for lo in range(0, Q, B):
+                            texts = q[lo:lo + B]
+                            dt, plans = timed(lambda: list(sc.iter_tvg_first(texts)))
+                            tp += dt
+                            ev0.record()
+                            outs = [sc.run(p, k=K0) for p in plans]
+                            ev1.record()
+                            torch.cuda.synchronize()
+                            tg_ += ev0.elapsed_time(ev1)
+                            rows = sum(p.n_pairs for p in plans)
+                            lg = torch.randn((rows, N), dtype=torch.float32, device="cuda")
+                            ev0.record(); eng.tvg_rank(lg, N, K0, outs[0][0].new_empty((rows, K0)), outs[0][1].new_empty((rows, K0))); ev1.record()
+                            torch.cuda.synchronize()
+                            tr += ev0.elapsed_time(ev1)
+                        plan_ms.append(1e3 * tp / Q); gpu_ms.append(tg_ / Q); rank_ms.append(tr / Q)
+                    parts[f"pre{K0}_B{B}"] = {"host_planning_ms_per_query": med(plan_ms), "engine_call_ms_per_query": med(gpu_ms), "rank_kernel_ms_per_query": med(rank_ms)}
+            # how much of the parent shortlist a prefilter of K0 keeps -- on RANDOM weights: it says nothing about a trained checkpoint
+            cover = {}
+            parent = [set(o.tolist()) for o, _ in ref[(None, Bs[0])]]
+            for K0 in K0s:
+                kept = gal.prefilter(q, K0)
+                cover[f"K0_{K0}"] = {"parent_topK_inside": float(np.mean([len(parent[i] & set(kept[i].tolist())) / len(parent[i]) for i in range(Q)]))}
+            r = {"build_s": t_build, "legs": {}, "stage0": parts, "cover_random_weights": cover}
+            for leg in legs:
+                K0, B = leg
+                base = med(ts[(None, B)])
+                r["legs"][name(*leg)] = {"s": ts[leg], "ms_per_query": 1e3 * med(ts[leg]) / Q, "spread": spread(ts[leg]), "stage0_ms_per_query": 1e3 * med(s0[leg]) / Q,
+                                         "stage1_ms_per_query": 1e3 * med(s1[leg]) / Q,
+                                         "stage2_ms_per_query": 1e3 * med([t - x - y for t, x, y in zip(ts[leg], s0[leg], s1[leg])]) / Q, "ratio_to_parent": base / med(ts[leg])}
+            res["runs"][f"vtg_{mode}/tvg_{tmode}"] = r
+            print(json.dumps({f"vtg_{mode}/tvg_{tmode}": r}), flush=True)
+            gal.close()
+            del sc
+            torch.cuda.empty_cache()
+    if a.rank_kernel:
+        res["rank_kernel"] = rank_kernel_alone([(1, 1000), (8, 1000), (1, 100000), (8, 100000)], 128)
+        print(json.dumps({"rank_kernel": res["rank_kernel"]}), flush=True)
     for o in ("narrow_gemm", "narrow_lo6", "narrow_qkv"):
         e.set_option(o, 0)
     if a.out:
