@@ -12,8 +12,6 @@
 //                                          V: chunk c ^ ((r & 3) << 2)  (4 rows of a tr-read block on 4 bank quarters)
 #include "attention.hpp"
 
-#include <stdlib.h>
-
 #include <type_traits>
 
 #define HD 128
@@ -163,17 +161,10 @@ __global__ __launch_bounds__((attn_bound<MAXC, SPLIT>::value)) void attn_kernel(
 
     load_tile(0);
     for (int t = 0; t < n_tiles; ++t) {
-#if defined(ATTN_ABLATE) && ATTN_ABLATE == 1     // ablation builds only (timing; wrong results): the tile is staged once, every iteration computes on it
-        if (t == 0) { __syncthreads(); store_tile(t); __syncthreads(); }
-#else
         __syncthreads();  // everyone finished reading the previous tile
         store_tile(t);
         __syncthreads();
         if (t + 1 < n_tiles) load_tile(t + 1);
-#endif
-#if defined(ATTN_ABLATE) && ATTN_ABLATE == 2     // ... or: staging only, no MFMA / softmax work
-        continue;
-#endif
         if (!worker) continue;                       // (wave-uniform)
 
         int base_tok, k0, seg_len; bool causal;
@@ -366,7 +357,6 @@ static bool stages_tile(int maxc, const dim3& block, bool split) {
 // blocks (transposed V reads, 16-bit engines).  A separate function, so that the uncached dispatch stays as it was.
 static int launch_attention_pc(const AttnPcParams& p, int G, hipStream_t stream) {
     const dim3 grid(p.n_blocks, p.num_kv_heads), block(64 * G);
-    static const int g_split = getenv("BLIM_ATTN_HEAD_GROUPS") ? atoi(getenv("BLIM_ATTN_HEAD_GROUPS")) : 2;
 #define ATTN_PC(MC, SP, OL, GRID, BLOCK)                                                                                           \
     do {                                                                                                                       \
         if (!stages_tile(MC, BLOCK, SP)) return BLIM_ERR_ARG;                                                                  \
@@ -377,14 +367,14 @@ static int launch_attention_pc(const AttnPcParams& p, int G, hipStream_t stream)
         if (p.out_lo_off) { if (G >= 7) ATTN_PC(5, true, true, grid, block); else ATTN_PC(4, true, true, grid, dim3(512)); }
         else { if (G >= 7) ATTN_PC(5, true, false, grid, block); else ATTN_PC(4, true, false, grid, dim3(512)); }
     } else if (p.out_lo_off != 0) {
-        if (G >= 7 && g_split > 1) ATTN_PC(4, false, true, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
-        else if (G >= 5 && g_split > 1) ATTN_PC(8, false, true, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));     // 192 threads: eight chunks each (launch_attention)
+        if (G >= 7) ATTN_PC(4, false, true, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        else if (G >= 5) ATTN_PC(8, false, true, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));     // 192 threads: eight chunks each (launch_attention)
         else if (G >= 4) ATTN_PC(4, false, true, grid, block);
         else if (G >= 2) ATTN_PC(8, false, true, grid, block);
         else ATTN_PC(16, false, true, grid, block);
     } else {
-        if (G >= 7 && g_split > 1) ATTN_PC(4, false, false, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
-        else if (G >= 5 && g_split > 1) ATTN_PC(8, false, false, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));     // 192 threads: eight chunks each (launch_attention)
+        if (G >= 7) ATTN_PC(4, false, false, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        else if (G >= 5) ATTN_PC(8, false, false, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));     // 192 threads: eight chunks each (launch_attention)
         else if (G >= 4) ATTN_PC(4, false, false, grid, block);
         else if (G >= 2) ATTN_PC(8, false, false, grid, block);
         else ATTN_PC(16, false, false, grid, block);
@@ -437,7 +427,6 @@ int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream) {
         if (e2 != hipSuccess) { blim_set_error("attention launch failed: %s", hipGetErrorString(e2)); return BLIM_ERR_HIP; }
         return BLIM_OK;
     }
-    static const int g_split = getenv("BLIM_ATTN_HEAD_GROUPS") ? atoi(getenv("BLIM_ATTN_HEAD_GROUPS")) : 2;
     if (p.out_lo_off != 0) {   // plain products, output as hi + lo (the per-layer mask's QKV-plain, o_proj-compensated form): the plain kernels' grouping, transposed reads
 #define ATTN_LO(MC, GRID, BLOCK)                                                                                                   \
         do {                                                                                                                     \
@@ -445,8 +434,8 @@ int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream) {
             if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<true, MC, DT_F16, false, true>), GRID, BLOCK, 0, stream, p);   \
             else hipLaunchKernelGGL((attn_kernel<true, MC, DT_BF16, false, true>), GRID, BLOCK, 0, stream, p);                \
         } while (0)
-        if (G >= 7 && g_split > 1) ATTN_LO(4, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
-        else if (G >= 5 && g_split > 1) ATTN_LO(8, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));      // 192 threads: eight chunks each (see below)
+        if (G >= 7) ATTN_LO(4, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));
+        else if (G >= 5) ATTN_LO(8, dim3(p.n_blocks, p.num_kv_heads * 2), dim3(64 * ((G + 1) / 2)));      // 192 threads: eight chunks each (see below)
         else if (G >= 4) ATTN_LO(4, grid, block);
         else if (G >= 2) ATTN_LO(8, grid, block);
         else ATTN_LO(16, grid, block);
@@ -461,7 +450,7 @@ int launch_attention(const AttnParams& p, int use_tr_read, hipStream_t stream) {
         if (p.dtype == DT_F16) hipLaunchKernelGGL((attn_kernel<TR, MC, DT_F16>), grid, block, 0, stream, p); \
         else hipLaunchKernelGGL((attn_kernel<TR, MC, DT_BF16>), grid, block, 0, stream, p);                \
     } while (0)
-    if (G >= 5 && g_split > 1 && use_tr_read && !p.out8) {
+    if (G >= 5 && use_tr_read && !p.out8) {
         // two workgroups of ceil(G / 2) waves per (block, KV head): 1,024 chunks / 256 threads = four per thread
         // (G = 5, 6: three waves per workgroup = 192 threads, which stage 768 of the 1,024 chunks at four per thread -- rows 16 .. 31 of every V tile were never
         // written and the result was wrong, tests/test_attention_gpu.py -- so those take eight per thread, the kernels G = 2, 3 run)

@@ -113,6 +113,10 @@ __global__ void dense_batch_kernel(int32_t* pos, int32_t* seq_start, int32_t* se
 }
 
 // ---------------------------------------------------------------------------- create / destroy
+// sizes the e2m3 second pass (lo6) takes: hidden and intermediate sizes multiples of 128, at most 20480
+static bool lo6_sizes_ok(const blim_config& c) {
+    return c.hidden_size % 128 == 0 && c.intermediate_size % 128 == 0 && c.hidden_size <= 20480 && c.intermediate_size <= 20480;
+}
 extern "C" int blim_create(const blim_config* cfg, blim_engine** out) {
     ARG_CHECK(cfg && out);
     ARG_CHECK(cfg->hidden_size > 0 && cfg->num_heads > 0 && cfg->num_kv_heads > 0 && cfg->num_layers > 0);
@@ -134,14 +138,11 @@ extern "C" int blim_create(const blim_config* cfg, blim_engine** out) {
     blim_engine* e = new blim_engine();
     e->c = *cfg;
     if (cfg->compute_dtype == BLIM_COMPUTE_F8) { e->f8 = true; e->c.compute_dtype = BLIM_COMPUTE_F16; }
-    if (getenv("BLIM_F8_FUSE")) e->f8_fuse = atoi(getenv("BLIM_F8_FUSE"));
-    if (getenv("BLIM_PRECISE_MLP")) e->precise_mlp = atoi(getenv("BLIM_PRECISE_MLP")) != 0;
     // fp16 engines: the compensated modes' second pass over K runs in e2m3 (gemm.hip, phase 2) unless BLIM_PRECISE_LO6=0 / option "precise_lo6" = 0.  bf16 engines keep the
     // 16-bit second pass by default (their parity mode: 1 - 3e-6 at 7B depth) and take the e2m3 pass with option "precise_lo6" = 1 / BLIM_PRECISE_LO6=1 (round 6)
-    e->lo6 = !e->f8 && cfg->compute_dtype == DT_F16 && cfg->hidden_size % 128 == 0 && cfg->intermediate_size % 128 == 0 && cfg->hidden_size <= 20480 && cfg->intermediate_size <= 20480;
+    e->lo6 = !e->f8 && cfg->compute_dtype == DT_F16 && lo6_sizes_ok(*cfg);
     if (getenv("BLIM_PRECISE_LO6") && atoi(getenv("BLIM_PRECISE_LO6")) == 0) e->lo6 = false;
-    if (getenv("BLIM_PRECISE_LO6") && atoi(getenv("BLIM_PRECISE_LO6")) == 1 && !e->f8 && cfg->compute_dtype == DT_BF16 && cfg->hidden_size % 128 == 0 && cfg->intermediate_size % 128 == 0 &&
-        cfg->hidden_size <= 20480 && cfg->intermediate_size <= 20480) e->lo6 = true;
+    if (getenv("BLIM_PRECISE_LO6") && atoi(getenv("BLIM_PRECISE_LO6")) == 1 && !e->f8 && cfg->compute_dtype == DT_BF16 && lo6_sizes_ok(*cfg)) e->lo6 = true;
     if (getenv("BLIM_LO6_FUSED_TILES") && atoi(getenv("BLIM_LO6_FUSED_TILES")) == 0) e->lo6_fuse = false;
     if (getenv("BLIM_LO6_FUSED_MASK")) e->lo6_fuse_mask = atoi(getenv("BLIM_LO6_FUSED_MASK"));
     const int H = cfg->hidden_size, I = cfg->intermediate_size, V = cfg->vocab_size, M = cfg->mm_hidden_size;
@@ -915,9 +916,6 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
         {
             SpanGuard g(e, s, TC_NORM, 0);
             if (q8) TRY(launch_rmsnorm_f8(resid, H, T, H, l.norm1, c.rms_eps, x8, sx, s));
-#ifdef ENGINE_ABLATE_NORMFOLD   // timing-only build (make ablate_normfold; profiles/r06_normfold_bound.md): plain calls skip every RMSNorm pass a residual epilogue could have produced
-            else if (!e->precise && !G && li > 0 && e->lse_part.p) { }
-#endif
             else TRY(launch_rmsnorm(resid, H, nullptr, T, H, l.norm1, c.rms_eps, xn, dt, nullptr, s, 0, pf * Hq, (cA && !n1_tiles) ? xn + Hq : nullptr, true, n1_tiles ? (uint8_t*)a6 : nullptr));
             if (G) TRY(adapter_u(e, xn, pf * Hq, cA ? Hq : 0, T, H, &e->AD[li].ad[0], &e->AD[li].ad[1], &e->AD[li].ad[2], s));
         }
@@ -985,17 +983,11 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
             GemmParams p = o8 ? gp8(a8, H, fuse_o ? nullptr : sa, l.wo8, l.so, n, H, H, res, H)
                               : gp_hilo(dt, ao, Hq, pf, G ? (const void*)e->AD[li].wo_aug : (const void*)l.wo, G ? e->AD[li].wo_aug6 : l.wo6, n, H, res, H, 0, cO, t6);
             if (fuse_o) { p.a_mx = (const uint8_t*)e->attn_mx.p; p.mx_stride = Tp; }
-#ifdef ENGINE_ABLATE_NORMFOLD
-            if (!pruned && !e->precise && !G && !o8 && e->lse_part.p) { p.swiglu_act = (uint16_t*)xn; p.swiglu_act_ld = H; p.col_scale = l.norm2; p.lse_part = (float2*)e->lse_part.p; }
-#endif
             TRY(launch_gemm(EPI_RESID, narrowed(p, e), s));
         }
         {
             SpanGuard g(e, s, TC_NORM, 0);
             if (g8) TRY(launch_rmsnorm_f8(res, H, n, H, l.norm2, c.rms_eps, x8, sx, s));
-#ifdef ENGINE_ABLATE_NORMFOLD
-            else if (!pruned && !e->precise && !G && e->lse_part.p) { }
-#endif
             else TRY(launch_rmsnorm(res, H, nullptr, n, H, l.norm2, c.rms_eps, xn, dt, nullptr, s, 0, pfm * H, (cG && !n2_tiles) ? xn + H : nullptr, true, n2_tiles ? (uint8_t*)a6 : nullptr));
         }
         const bool fuse = g8 && d8 && e->f8_fuse;      // fp8: the gate|up epilogue emits e4m3 + one E8M0 scale per (token, 128 outputs) itself
@@ -1016,9 +1008,6 @@ static int run_layers(blim_engine* e, const blim_batch* b, const void* embeds, h
             if (lo6 && cD && !fuse6) TRY(lo6_tiles(e, s, act, I, n, &t6));
             GemmParams p = d8 ? gp8(act8, I, fuse ? nullptr : sact, l.wd8, l.sd, n, H, I, res, H) : gp_hilo(dt, act, I, pfm, l.wd, l.wd6, n, H, res, H, 0, cD, t6);
             if (fuse) { p.a_mx = (const uint8_t*)e->act_mx.p; p.mx_stride = Tp; }
-#ifdef ENGINE_ABLATE_NORMFOLD
-            if (!pruned && !e->precise && !G && !d8 && e->lse_part.p && li + 1 < c.num_layers) { p.swiglu_act = (uint16_t*)xn; p.swiglu_act_ld = H; p.col_scale = e->L[li + 1].norm1; p.lse_part = (float2*)e->lse_part.p; }
-#endif
             TRY(launch_gemm(EPI_RESID, narrowed(p, e), s));
         }
         if (pruned) { *final_resid = res; *final_is_live = true; }
@@ -1982,7 +1971,7 @@ extern "C" int blim_set_option(blim_engine* e, const char* key, int32_t value) {
     }
     if (!strcmp(key, "precise_lo6")) {
         if (value && e->f8) { blim_set_error("option 'precise_lo6' needs a 16-bit engine (fp16: the default; bf16: opt-in)"); return BLIM_ERR_ARG; }
-        if (value && (e->c.hidden_size % 128 || e->c.intermediate_size % 128 || e->c.hidden_size > 20480 || e->c.intermediate_size > 20480)) {
+        if (value && !lo6_sizes_ok(e->c)) {
             blim_set_error("option 'precise_lo6': hidden and intermediate sizes must be multiples of 128, at most 20480"); return BLIM_ERR_ARG; }
         if (value && e->aug && e->aug % 128) { blim_set_error("option 'precise_lo6': adapters were loaded with a %d-column K extension; set the option before loading adapters", e->aug); return BLIM_ERR_STATE; }
         e->lo6 = value != 0; return BLIM_OK;

@@ -234,11 +234,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
         // compensated mode: A is [hi | lo] along K and W is used twice -- the W group's K-step index wraps (scalar select)
         const int wrap = (grp == 0 && p.w_wrap_k > 0) ? p.w_wrap_k * ES / (BK * 2) : 0x7fffffff;
         auto stage8 = [&](int dst, int kt) __attribute__((always_inline)) {   // one operand tile share: 8 LDS-DMA per wave
-#ifdef GEMM_ABLATE_DMA   // ablation builds only: 1 = stage the first two K-steps only, then compute on stale
-                         // LDS; 2 = keep every LDS-DMA but re-read the first two K-steps (L2-resident, no fabric / HBM traffic)
-            if (GEMM_ABLATE_DMA == 1 && kt >= 2) return;
-            if (GEMM_ABLATE_DMA == 2) kt &= 1;
-#endif
             const char* g = gbase + (int64_t)(kt >= wrap ? kt - wrap : kt) * (BK * 2);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
@@ -254,13 +249,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
         auto frags_and_dma = [&](int offA_tile, int offB_tile, int dst, int kt, bool on) __attribute__((always_inline)) {
             const char* ba[2] = {smem + (offA_tile + a_off), smem + ((offA_tile + a_off) ^ 64)};
             const char* bb[2] = {smem + (offB_tile + b_off), smem + ((offB_tile + b_off) ^ 64)};
-#ifdef GEMM_ABLATE_DMA
-            if (GEMM_ABLATE_DMA == 1 && kt >= 2) on = false;
-            if (GEMM_ABLATE_DMA == 2) kt &= 1;
-#endif
-#if defined(GEMM_ABLATE_WREAD) && GEMM_ABLATE_WREAD == 2   // ... and no LDS-DMA of W either after the prologue (group 0 stages W)
-            if (grp == 0 && kt >= 4) on = false;
-#endif
             const char* g = gbase + (int64_t)(kt >= wrap ? kt - wrap : kt) * (BK * 2);
             auto dma1 = [&](int q) __attribute__((always_inline)) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -273,22 +261,11 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
 #pragma unroll
                     for (int j = 3 * q; j < 3 * q + 3; ++j) {
                         const int ks = j / 12, r = j % 12;
-#ifdef GEMM_ABLATE_WREAD   // ablation builds only: the W fragments are NOT read from LDS -- an upper bound on what
-                           // fetching them global -> VGPR instead of through LDS could buy (the loads themselves not even charged)
-                        if (r < 4) { }   // (no read; the MFMAs below take copies of A fragments: keeping stale W fragments live across the back edge spills)
-#else
                         if (r < 4) fb[ks][r] = *(const bf16x8*)(bb[ks] + r * 2048);
-#endif
                         else fa[ks][r - 4] = *(const bf16x8*)(ba[ks] + (r - 4) * 2048);
                     }
                     dma1(q);
                 }
-#ifdef GEMM_ABLATE_WREAD
-#pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) fb[ks][r] = fa[ks][r + 4];
-#endif
             }
         };
         // ---- phase 2 (LO6): acc += (lo part of the A operand) . W^T on the block-scaled MFMA with e2m3 operands, at FOUR times the 16-bit rate (gfx950 issues fp6
@@ -310,12 +287,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
         // (the scale KiB as 16-byte pieces of the first 16 lanes, 256 B per wave: the 4-byte form of the LDS-DMA is tracked by the compiler's wait-count pass as an
         // LDS store any LDS read may alias, and it put an s_waitcnt vmcnt(0) in front of the next step's fragment reads)
         auto dma6 = [&](int q, int dslot, int kd, bool isW, bool on) __attribute__((always_inline)) {
-#if defined(GEMM_ABLATE_P2) && GEMM_ABLATE_P2 == 3   // ablation build: only the tiles requested in front of the pass (K-steps 0 - 2) are staged, then it runs on stale tiles
-            on = on && kd < 3;
-#endif
-#if defined(GEMM_ABLATE_P2) && GEMM_ABLATE_P2 >= 4   // ablation builds (round 6, profiles/r06_lo4_bound.md): the bytes of an e2m1 image instead of an e2m3 one (17 of 25 KiB: pieces 4, 5 not
-            on = on && !((q == 4 || q == 5) && (isW || GEMM_ABLATE_P2 == 5));   // requested, fragments read as ONE ds_read_b128) -- 4 = the W operand, 5 = both.  Timing only, wrong results
-#endif
             if (on) {
                 const char* g = (isW ? g6W : g6A) + (int64_t)kd * F6_TILE_BYTES;
                 char* d = smem + dslot * F6_TILE_BYTES;
@@ -336,21 +307,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
             const i32x2 h = *(const i32x2*)(qb + off);
             return (i32x8){l[0], l[1], l[2], l[3], h[0], h[1], 0, 0};
         };
-#if defined(GEMM_ABLATE_P2) && GEMM_ABLATE_P2 >= 4
-        auto rd6_4 = [&](const char* qa, const char* qb, int off) __attribute__((always_inline)) {
-            const i32x4 l = *(const i32x4*)(qa + off);
-            return (i32x8){l[0], l[1], l[2], l[3], l[0], l[1], 0, 0};
-        };
-#define RD6W rd6_4
-#if GEMM_ABLATE_P2 == 5
-#define RD6A rd6_4
-#else
-#define RD6A rd6
-#endif
-#else
-#define RD6W rd6
-#define RD6A rd6
-#endif
         // (scales read through ext-vector types like the fragments: behind loads typed uint32_t / uint2 the compiler's wait-count pass put an s_waitcnt vmcnt(0) --
         // every outstanding LDS-DMA -- in front of each step's fragment reads)
         typedef int i32x1 __attribute__((ext_vector_type(1)));
@@ -480,29 +436,21 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
             const int qoa = 8 * wm * 1536 + lane * 16, qoa8 = 8 * wm * 1536 + 1024 + lane * 8;       // this lane's byte offsets inside an A / a W tile image
             const int qob = F6_TILE_BYTES + 4 * wn * 1536 + lane * 16, qob8 = F6_TILE_BYTES + 4 * wn * 1536 + 1024 + lane * 8;
             sc6w = rd6_sw(smem + F6_TILE_BYTES); sc6a = rd6_sa(smem);
-            fb8[0] = RD6W(smem + qob, smem + qob8, 0); fb8[1] = RD6W(smem + qob, smem + qob8, 1536);
+            fb8[0] = rd6(smem + qob, smem + qob8, 0); fb8[1] = rd6(smem + qob, smem + qob8, 1536);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) fa8[i] = RD6A(smem + qoa, smem + qoa8, i * 1536);
+            for (int i = 0; i < 4; ++i) fa8[i] = rd6(smem + qoa, smem + qoa8, i * 1536);
             int s3 = 0;                                                  // k % 3
 #ifdef GEMM_WAIT_PROF   // (instrumented build: the sums below are phase 2's alone -- QA + QB | vmcnt | barrier | QC | QD)
             for (int q_ = 0; q_ < 5; ++q_) wp_acc[q_] = 0;
 #endif
-#if defined(GEMM_ABLATE_P2) && GEMM_ABLATE_P2 == 1   // ablation builds (make ablate_p2; timing only, wrong results): 1 = no MFMAs in phase 2, 2 = no fragment refills, 3 = no LDS-DMA
-#define L6_MMA(MI, NI)
-#else
 #define L6_MMA(MI, NI) acc[MI][NI] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fb8[NI], fa8[MI], acc[MI][NI], 2, 2, NI, (int)sc6w, (MI & 3), (int)((MI) < 4 ? sc6a.x : sc6a.y));   // cbsz = blgp = 2: e2m3
-#endif
 #define L6_SB() __builtin_amdgcn_sched_barrier(0)
             auto step6 = [&](int k, auto ca_, auto cb_) __attribute__((always_inline)) {
                 constexpr int CA = decltype(ca_)::value, CB = decltype(cb_)::value;
                 const int s3n = s3 == 2 ? 0 : s3 + 1, s3p = s3 == 0 ? 2 : s3 - 1;      // slots of tile k+1 / of tiles k-1 and k+2
                 const char* t0 = smem + (2 * s3) * F6_TILE_BYTES;                        // this step's tile (A image; the W image follows it)
                 const char* t1 = smem + (2 * s3n) * F6_TILE_BYTES;                       // the next step's
-#if defined(GEMM_ABLATE_P2) && GEMM_ABLATE_P2 == 2
-                const bool rl = false, own = false;
-#else
-                const bool rl = k + 1 < nk6, own = true;                 // there is a next step: refill from its tile
-#endif
+                const bool rl = k + 1 < nk6;                             // there is a next step: refill from its tile
                 const bool on2 = k >= 1 && k + 2 < nk6;                  // pieces 4-6 of tile k+2 (0-3: requested in the previous step) into the slots of tile k-1
                 const bool on3 = k + 3 < nk6;                            // pieces 0-3 of tile k+3 into the slots of tile k, behind the barrier
                 const int d2 = 2 * s3p + (grp == 0 ? 1 : 0), d3 = 2 * s3 + (grp == 0 ? 1 : 0);
@@ -511,17 +459,17 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
                 WP_T(0);
                 __builtin_amdgcn_s_setprio(1);
                 // QA
-                L6_MMA(0, CA) L6_SB(); if (own) fb8[CB] = RD6W(t0 + qob, t0 + qob8, CB * 1536); L6_SB();
+                L6_MMA(0, CA) L6_SB(); fb8[CB] = rd6(t0 + qob, t0 + qob8, CB * 1536); L6_SB();
                 L6_MMA(1, CA) L6_SB(); dma6(4, d2, k + 2, isW, on2); L6_SB();
-                L6_MMA(2, CA) L6_SB(); if (own) fb8[CB + 1] = RD6W(t0 + qob, t0 + qob8, (CB + 1) * 1536); L6_SB();
+                L6_MMA(2, CA) L6_SB(); fb8[CB + 1] = rd6(t0 + qob, t0 + qob8, (CB + 1) * 1536); L6_SB();
                 L6_MMA(3, CA) L6_SB();
-                L6_MMA(0, CA + 1) L6_SB(); if (own) fa8[4] = RD6A(t0 + qoa, t0 + qoa8, 4 * 1536); L6_SB();
+                L6_MMA(0, CA + 1) L6_SB(); fa8[4] = rd6(t0 + qoa, t0 + qoa8, 4 * 1536); L6_SB();
                 L6_MMA(1, CA + 1) L6_SB(); dma6(5, d2, k + 2, isW, on2); L6_SB();
-                L6_MMA(2, CA + 1) L6_SB(); if (own) fa8[5] = RD6A(t0 + qoa, t0 + qoa8, 5 * 1536); L6_SB();
+                L6_MMA(2, CA + 1) L6_SB(); fa8[5] = rd6(t0 + qoa, t0 + qoa8, 5 * 1536); L6_SB();
                 L6_MMA(3, CA + 1) L6_SB();
                 // QB
-                L6_MMA(0, CB) L6_SB(); if (own) fa8[6] = RD6A(t0 + qoa, t0 + qoa8, 6 * 1536); L6_SB();
-                L6_MMA(1, CB) L6_SB(); if (own) fa8[7] = RD6A(t0 + qoa, t0 + qoa8, 7 * 1536); L6_SB();
+                L6_MMA(0, CB) L6_SB(); fa8[6] = rd6(t0 + qoa, t0 + qoa8, 6 * 1536); L6_SB();
+                L6_MMA(1, CB) L6_SB(); fa8[7] = rd6(t0 + qoa, t0 + qoa8, 7 * 1536); L6_SB();
                 L6_MMA(2, CB) L6_SB(); dma6(6, d2, k + 2, isW, on2); L6_SB();
                 L6_MMA(3, CB)
                 L6_MMA(0, CB + 1) L6_MMA(1, CB + 1) L6_MMA(2, CB + 1) L6_MMA(3, CB + 1)
@@ -529,40 +477,29 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
                 WP_T(1);
                 // every read of tile k has been requested (and is awaited in front of the barrier: P2_BARRIER's own lgkmcnt(0)).  Tile k+1: my pieces of it were requested two barriers ago --
                 // only the seven of tile k+2 may stay in flight (k = 0: the W group's fourteen of A(2) W(2))
-#if defined(GEMM_ABLATE_P2) && GEMM_ABLATE_P2 == 6   // ablation build (round 6: is the pass bound by LDS-DMA LATENCY?): the waits let one more tile stay in flight -- tile k+1 is read without
-                                                     // having been awaited (timing only, wrong results).  If the step got much shorter, a deeper ring would be the lever
-                if (k == 0) { if (nk6 > 2) P2_VMCNT(21); else P2_VMCNT(0); }
-                else if (k + 2 < nk6) P2_VMCNT(14);
-                else P2_VMCNT(0);
-#else
                 if (k == 0) { if (nk6 > 2) P2_VMCNT(14); else P2_VMCNT(0); }
                 else if (k + 2 < nk6) P2_VMCNT(7);
                 else P2_VMCNT(0);
-#endif
                 WP_T(2);
-#if defined(GEMM_ABLATE_P2) && GEMM_ABLATE_P2 == 7   // ablation build (round 6: is it the per-step rendezvous of the eight waves?): a barrier every OTHER step only (timing only, wrong results)
-                if (k & 1) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); } else { P2_BARRIER(); }
-#else
                 P2_BARRIER();
-#endif
                 WP_T(3);
                 // QC
-                L6_MMA(4, CB) L6_SB(); if (rl) fa8[0] = RD6A(t1 + qoa, t1 + qoa8, 0); L6_SB();
+                L6_MMA(4, CB) L6_SB(); if (rl) fa8[0] = rd6(t1 + qoa, t1 + qoa8, 0); L6_SB();
                 L6_MMA(5, CB) L6_SB(); dma6(0, d3, k + 3, isW, on3); L6_SB();
-                L6_MMA(6, CB) L6_SB(); if (rl) fa8[1] = RD6A(t1 + qoa, t1 + qoa8, 1536); L6_SB();
+                L6_MMA(6, CB) L6_SB(); if (rl) fa8[1] = rd6(t1 + qoa, t1 + qoa8, 1536); L6_SB();
                 L6_MMA(7, CB) L6_SB(); dma6(1, d3, k + 3, isW, on3); L6_SB();
                 L6_MMA(4, CB + 1) L6_SB(); if (rl) { sc6w_n = rd6_sw(t1 + F6_TILE_BYTES); sc6a_n = rd6_sa(t1); } L6_SB();
                 L6_MMA(5, CB + 1) L6_MMA(6, CB + 1) L6_MMA(7, CB + 1)
                 L6_SB();
                 WP_T(4);
                 // QD (fw[CB], fw[CB + 1] are free: their refills for the next step go first)
-                if (rl) fb8[CB] = RD6W(t1 + qob, t1 + qob8, CB * 1536);
+                if (rl) fb8[CB] = rd6(t1 + qob, t1 + qob8, CB * 1536);
                 L6_SB();
-                L6_MMA(4, CA) L6_SB(); if (rl) fb8[CB + 1] = RD6W(t1 + qob, t1 + qob8, (CB + 1) * 1536); L6_SB();
+                L6_MMA(4, CA) L6_SB(); if (rl) fb8[CB + 1] = rd6(t1 + qob, t1 + qob8, (CB + 1) * 1536); L6_SB();
                 L6_MMA(5, CA) L6_SB(); dma6(2, d3, k + 3, isW, on3); L6_SB();
-                L6_MMA(6, CA) L6_SB(); if (rl) fa8[2] = RD6A(t1 + qoa, t1 + qoa8, 2 * 1536); L6_SB();
+                L6_MMA(6, CA) L6_SB(); if (rl) fa8[2] = rd6(t1 + qoa, t1 + qoa8, 2 * 1536); L6_SB();
                 L6_MMA(7, CA) L6_SB(); dma6(3, d3, k + 3, isW, on3); L6_SB();
-                L6_MMA(4, CA + 1) L6_SB(); if (rl) fa8[3] = RD6A(t1 + qoa, t1 + qoa8, 3 * 1536); L6_SB();
+                L6_MMA(4, CA + 1) L6_SB(); if (rl) fa8[3] = rd6(t1 + qoa, t1 + qoa8, 3 * 1536); L6_SB();
                 L6_MMA(5, CA + 1) L6_MMA(6, CA + 1) L6_MMA(7, CA + 1)
                 L6_SB();
                 __builtin_amdgcn_s_setprio(0);
@@ -580,8 +517,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
                 if (k < nk6) step6(k, std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
             }
 #undef L6_SB
-#undef RD6W
-#undef RD6A
 #undef P2_BARRIER
 #undef P2_VMCNT
 #undef L6_MMA
@@ -1068,21 +1003,6 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(const GemmParams p) {
                             const int row = row0 + 128 * h + rl;
                             const float4 v = *(const float4*)(smem + rl * RS + lane * 16);
                             if (row < p.M) *(float4*)((float*)p.C + (int64_t)row * p.ldc + col) = make_float4(o[i].x + (v.x + rb.x), o[i].y + (v.y + rb.y), o[i].z + (v.z + rb.z), o[i].w + (v.w + rb.w));
-#ifdef GEMM_ABLATE_NORMFOLD   // timing-only build (round 6, profiles/r06_normfold_bound.md; results are wrong by construction): what folding the FOLLOWING RMSNorm into this epilogue
-                              // would add to it -- the 16-bit copy of the new residual row times the norm's weight (the next GEMM's A operand) and the row's sum of squares per
-                              // column tile -- with the row scaled by its tile-local rms so that the values downstream keep the magnitudes of normalised activations
-                            if (p.swiglu_act != nullptr && row < p.M) {
-                                const float4 nv = make_float4(o[i].x + (v.x + rb.x), o[i].y + (v.y + rb.y), o[i].z + (v.z + rb.z), o[i].w + (v.w + rb.w));
-                                float ss = nv.x * nv.x + nv.y * nv.y + nv.z * nv.z + nv.w * nv.w;
-#pragma unroll
-                                for (int m_ = 1; m_ < 64; m_ <<= 1) ss += __shfl_xor(ss, m_);
-                                const float r = rsqrtf(ss * (1.0f / 256.0f) + 1e-6f);
-                                const float4 wv = *(const float4*)(p.col_scale + col);
-                                const uint16_t h0 = to16<ODT>(nv.x * wv.x * r), h1 = to16<ODT>(nv.y * wv.y * r), h2 = to16<ODT>(nv.z * wv.z * r), h3 = to16<ODT>(nv.w * wv.w * r);
-                                *(uint2*)(p.swiglu_act + (int64_t)row * p.swiglu_act_ld + col) = make_uint2((uint32_t)h0 | ((uint32_t)h1 << 16), (uint32_t)h2 | ((uint32_t)h3 << 16));
-                                if (lane == 0) ((float*)p.lse_part)[(int64_t)row * ntn + tn] = ss;
-                            }
-#endif
                         }
                     } else {
 #pragma unroll 1
@@ -1462,10 +1382,6 @@ __global__ __launch_bounds__(N_THREADS) void gemm_nqkv_kernel(const GemmParams p
 #include <stdlib.h>
 #include <algorithm>
 #include <atomic>
-static int g_gemm_persistent = getenv("BLIM_GEMM_PERSISTENT") ? atoi(getenv("BLIM_GEMM_PERSISTENT")) : 1;
-static int g_gemm_tile_map = getenv("BLIM_GEMM_TILE_MAP") ? atoi(getenv("BLIM_GEMM_TILE_MAP")) : -1;   // -1: by shape
-static int g_gemm_group_m = getenv("BLIM_GEMM_GROUP_M") ? atoi(getenv("BLIM_GEMM_GROUP_M")) : GROUP_M;   // M-tiles per band of the tile order
-static int g_f16_saturate = getenv("BLIM_F16_SATURATE") ? atoi(getenv("BLIM_F16_SATURATE")) : 1;   // 0: fp16 stores overflow to inf again (diagnostics)
 static int g_gemm_skip_epi = getenv("BLIM_GEMM_SKIP_EPI") ? atoi(getenv("BLIM_GEMM_SKIP_EPI")) : 0;
 static unsigned long long* g_gemm_stamps = nullptr;
 static int g_stamp_epi = getenv("BLIM_GEMM_STAMP_EPI") ? atoi(getenv("BLIM_GEMM_STAMP_EPI")) : -1;   // stamp only this epilogue / this K (tools/epi_stamps.py)
@@ -1482,44 +1398,36 @@ static int launch_t(const GemmParams& p, hipStream_t stream) {
         n_cu = (n_cu / 8) * 8;   // virtual block ids must keep blockIdx % 8
         if (n_cu < 8) n_cu = 8;
     }
-    const int persistent = g_gemm_persistent ? n_cu : ntm * ntn;
-    const dim3 grid(ntm * ntn < persistent ? ntm * ntn : persistent);
+    const dim3 grid(ntm * ntn < n_cu ? ntm * ntn : n_cu);   // persistent: one workgroup per CU at the most
+    void (*kernel)(const GemmParams) = nullptr;
     if constexpr (EPI == EPI_QKV || EPI == EPI_SWIGLU || EPI == EPI_RESID || EPI == EPI_LSE) {
         if (p.A6) {            // 16-bit main pass + e2m3 pass over the A operand's lo part (phase 2 of the kernel).  fp16 engines: the default second pass; bf16 engines
                                // (round 6): option "precise_lo6" = 1, the fast form of their compensated mode (the lo part is 2^-9 of the value there: DESIGN.md section 4)
-#define LO6_LAUNCH(DTX)                                                                                                                                  \
-            if constexpr (EPI == EPI_RESID || EPI == EPI_LSE) hipLaunchKernelGGL((gemm_kernel<EPI, DTX, false, true>), grid, dim3(NTHREADS), 0, stream, p);   \
-            else if (p.lo_off != 0) hipLaunchKernelGGL((gemm_kernel<EPI, DTX, true, true>), grid, dim3(NTHREADS), 0, stream, p);                            \
-            else if constexpr (EPI == EPI_SWIGLU) hipLaunchKernelGGL((gemm_kernel<EPI, DTX, false, true>), grid, dim3(NTHREADS), 0, stream, p);              \
+#define LO6_KERNEL(DTX)                                                                                    \
+            if constexpr (EPI == EPI_RESID || EPI == EPI_LSE) kernel = gemm_kernel<EPI, DTX, false, true>; \
+            else if (p.lo_off != 0) kernel = gemm_kernel<EPI, DTX, true, true>;                            \
+            else if constexpr (EPI == EPI_SWIGLU) kernel = gemm_kernel<EPI, DTX, false, true>;             \
             else { blim_set_error("lo6 QKV GEMM: hi | lo outputs only"); return BLIM_ERR_ARG; }
-            if (p.dtype == DT_F16) { LO6_LAUNCH(DT_F16) } else { LO6_LAUNCH(DT_BF16) }
-#undef LO6_LAUNCH
-            hipError_t e4 = hipGetLastError();
-            if (e4 != hipSuccess) { blim_set_error("gemm launch failed: %s", hipGetErrorString(e4)); return BLIM_ERR_HIP; }
-            return BLIM_OK;
+            if (p.dtype == DT_F16) { LO6_KERNEL(DT_F16) } else { LO6_KERNEL(DT_BF16) }
+#undef LO6_KERNEL
         }
     }
     if constexpr (EPI == EPI_BF16 || EPI == EPI_QKV || EPI == EPI_SWIGLU) {
-        if (p.lo_off != 0) {   // compensated outputs: 16-bit engines (fp16: ~21 significant bits per activation, bf16: ~16)
-            if (p.dtype == DT_F16) hipLaunchKernelGGL((gemm_kernel<EPI, DT_F16, true>), grid, dim3(NTHREADS), 0, stream, p);
-            else if (p.dtype == DT_BF16) hipLaunchKernelGGL((gemm_kernel<EPI, DT_BF16, true>), grid, dim3(NTHREADS), 0, stream, p);
+        if (!kernel && p.lo_off != 0) {   // compensated outputs: 16-bit engines (fp16: ~21 significant bits per activation, bf16: ~16)
+            if (p.dtype == DT_F16) kernel = gemm_kernel<EPI, DT_F16, true>;
+            else if (p.dtype == DT_BF16) kernel = gemm_kernel<EPI, DT_BF16, true>;
             else { blim_set_error("split (hi|lo) GEMM outputs need a 16-bit engine"); return BLIM_ERR_ARG; }
-            hipError_t e2 = hipGetLastError();
-            if (e2 != hipSuccess) { blim_set_error("gemm launch failed: %s", hipGetErrorString(e2)); return BLIM_ERR_HIP; }
-            return BLIM_OK;
         }
     }
     if constexpr (EPI == EPI_RESID) {
-        if (p.dtype == DT_F8 && p.a_mx) {
-            hipLaunchKernelGGL((gemm_kernel<EPI, DT_F8, false, true>), grid, dim3(NTHREADS), 0, stream, p);
-            hipError_t e3 = hipGetLastError();
-            if (e3 != hipSuccess) { blim_set_error("gemm launch failed: %s", hipGetErrorString(e3)); return BLIM_ERR_HIP; }
-            return BLIM_OK;
-        }
+        if (!kernel && p.dtype == DT_F8 && p.a_mx) kernel = gemm_kernel<EPI, DT_F8, false, true>;
     }
-    if (p.dtype == DT_F8) hipLaunchKernelGGL((gemm_kernel<EPI, DT_F8>), grid, dim3(NTHREADS), 0, stream, p);
-    else if (p.dtype == DT_F16) hipLaunchKernelGGL((gemm_kernel<EPI, DT_F16>), grid, dim3(NTHREADS), 0, stream, p);
-    else hipLaunchKernelGGL((gemm_kernel<EPI, DT_BF16>), grid, dim3(NTHREADS), 0, stream, p);
+    if (!kernel) {
+        if (p.dtype == DT_F8) kernel = gemm_kernel<EPI, DT_F8>;
+        else if (p.dtype == DT_F16) kernel = gemm_kernel<EPI, DT_F16>;
+        else kernel = gemm_kernel<EPI, DT_BF16>;
+    }
+    hipLaunchKernelGGL(kernel, grid, dim3(NTHREADS), 0, stream, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         blim_set_error("gemm launch failed: %s", hipGetErrorString(e));
@@ -1641,16 +1549,13 @@ int launch_gemm(GemmEpi epi, const GemmParams& p, hipStream_t stream) {
 static int launch_one(GemmEpi epi, const GemmParams& p_in, hipStream_t stream) {
     GemmParams p = p_in;
     p.debug_skip_epilogue = g_gemm_skip_epi;
-    static const int dbg_k6 = getenv("BLIM_GEMM_LO6_K6") ? atoi(getenv("BLIM_GEMM_LO6_K6")) : 0;      // timing aid: shorten the e2m3 pass (wrong results)
-    if (p.A6 && dbg_k6 > 0 && dbg_k6 < p.K6) p.K6 = dbg_k6;     // (wrong tiles too: the images are [tile][K6 / 128 steps])
-    if (!g_f16_saturate) p.f16_saturate = 0;
-    p.group_m = g_gemm_group_m > 0 ? g_gemm_group_m : GROUP_M;
+    p.group_m = GROUP_M;
     // measured (one MI355X, A/B in one process): narrow outputs (N = 3584 / 4608: o_proj, down_proj, qkv) gain 3-5 % from the
     // round-robin map, the wide ones (gate|up 37888, lm_head) lose 4 % -- there the XCDs already walk the same W columns in step
     // ... but only with a chip's worth of tiles: the round-robin map hands each XCD 32 consecutive tiles, so a small call (M of 1-2 k rows x N = 3584:
     // 56 tiles) ran on TWO of the eight XCDs and their share of the fabric -- down_proj 2.9 ms instead of 1.0 (round 4, rocprofv3 of the calibration calls)
     const int64_t n_tiles = (int64_t)((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-    p.tile_map = g_gemm_tile_map >= 0 ? g_gemm_tile_map : (((p.N + BN - 1) / BN <= 32 && n_tiles >= 256) ? 1 : 0);
+    p.tile_map = ((p.N + BN - 1) / BN <= 32 && n_tiles >= 256) ? 1 : 0;
     p.debug_stamps = ((g_stamp_epi < 0 || g_stamp_epi == (int)epi) && (g_stamp_k < 0 || g_stamp_k == p.K)) ? g_gemm_stamps : nullptr;
     ARG_CHECK(p.M > 0 && p.N > 0 && p.K > 0);
     ARG_CHECK(p.A && p.W);

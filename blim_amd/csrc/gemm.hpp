@@ -75,8 +75,8 @@ struct GemmParams {
     uint8_t* out6;
     int f16_saturate;        // fp16 outputs: saturate to +-65504 instead of +-inf (common.hpp: f16_saturate_on).  engine.hip's gp() sets it; the one
                              // 16-bit GRADIENT store of the trainer clears it (the loss scaler must see an overflow as inf)
-    int group_m;             // M-tiles per band of the tile order (8; BLIM_GEMM_GROUP_M)
-    int tile_map;            // 1: 32-tile groups round-robin over the XCDs (default), 0: XCD-contiguous chunks (BLIM_GEMM_TILE_MAP)
+    int group_m;             // M-tiles per band of the tile order (launch_one: 8)
+    int tile_map;            // 1: 32-tile groups round-robin over the XCDs, 0: XCD-contiguous chunks (launch_one: by shape)
     int debug_skip_epilogue; // timing aid only (set from BLIM_GEMM_SKIP_EPI)
     unsigned long long* debug_stamps;  // timing aid: [n_workgroups][8] s_memrealtime at {entry, main loop start, main loop end, exit, C staged in LDS, stores issued}
     int narrow;              // EPI_RESID on plain 16-bit operands (gemm.hip: gemm_narrow_kernel, 64 x 64 tiles, the same bits): 0 = the 256 x 256 kernel, 2 = the narrow kernel

@@ -455,10 +455,9 @@ __global__ __launch_bounds__(256) void rmsnorm_wide_kernel(const float* x, int64
     }
     if (out6) tiles();
 }
-static int g_rmsnorm_wide = getenv("BLIM_RMSNORM_WIDE") ? atoi(getenv("BLIM_RMSNORM_WIDE")) : 1;
 bool rmsnorm_can_write_tiles(int H, int64_t ldx, int64_t ldo) {
     if (ldo == 0) ldo = H;
-    return g_rmsnorm_wide && H % 128 == 0 && H <= 4096 && H > 256 && ldo % 8 == 0 && ldx % 4 == 0;
+    return H % 128 == 0 && H <= 4096 && H > 256 && ldo % 8 == 0 && ldx % 4 == 0;
 }
 int launch_rmsnorm(const float* x, int64_t ldx, const int32_t* rows, int64_t n_rows, int H, const float* w, float eps,
                    bf16_t* out_h16, int dtype, float* out_f32, hipStream_t s, int64_t n_src, int64_t ldo, bf16_t* out_lo, bool saturate, uint8_t* out6) {
@@ -470,7 +469,7 @@ int launch_rmsnorm(const float* x, int64_t ldx, const int32_t* rows, int64_t n_r
     ARG_CHECK(!out6 || (out_h16 && rmsnorm_can_write_tiles(H, ldx, ldo)));
     const int nv = H / 4;
     const dim3 grid((unsigned)((n_rows + 3) / 4));
-    if (g_rmsnorm_wide && H % 8 == 0 && H <= 4096 && H > 256 && ldo % 8 == 0 && ldx % 4 == 0) {
+    if (H % 8 == 0 && H <= 4096 && H > 256 && ldo % 8 == 0 && ldx % 4 == 0) {
         const dim3 grid_w(out6 ? (unsigned)(((n_rows + 255) / 256) * 64) : grid.x);
         const size_t lds = out6 ? (size_t)4 * (H + 8) * 2 : 0;
         if (dtype == DT_F16) hipLaunchKernelGGL((rmsnorm_wide_kernel<DT_F16>), grid_w, dim3(256), lds, s, x, ldx, rows, n_rows, H, w, eps, out_h16, out_f32, n_src, ldo, out_lo, sat, out6);

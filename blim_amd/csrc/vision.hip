@@ -5,7 +5,6 @@
 // The linear layers run on the engine's MFMA GEMM (gemm.hip: bias / GELU / residual epilogues); this file adds the patch gather,
 // LayerNorm, a non-causal head_dim-64 flash attention, and ToMe in f32 (metric, best-match search, a bitonic argsort and a
 // deterministic merge: HBM-bound index work, no MFMA).
-#include <stdlib.h>
 #include <string.h>
 
 #include <map>
@@ -689,9 +688,8 @@ extern "C" int blim_vision_encode(blim_vision* v, const void* frames, int32_t n_
     KCHECK("patchify");
     { GemmParams p = vgp(dt, v->patches.p, PK, v->patch_w, M, D, PK, resid, D, nullptr); TRY(launch_gemm(EPI_RESID, p, s)); }
     const dim3 ln_grid((unsigned)((M + 3) / 4));
-    static const int ln_wide = getenv("BLIM_LN_WIDE") ? atoi(getenv("BLIM_LN_WIDE")) : 1;
     auto layernorm = [&](const float* w, const float* b, float eps, bf16_t* o16, float* o32) -> int {
-        if (ln_wide && o16 && !o32 && D % 8 == 0 && D <= 4096) {
+        if (o16 && !o32 && D % 8 == 0 && D <= 4096) {
             if (dt == DT_F16) hipLaunchKernelGGL(layernorm_wide_kernel<DT_F16>, ln_grid, dim3(256), 0, s, (const float*)resid, M, D, w, b, eps, o16);
             else hipLaunchKernelGGL(layernorm_wide_kernel<DT_BF16>, ln_grid, dim3(256), 0, s, (const float*)resid, M, D, w, b, eps, o16);
             KCHECK("layernorm");

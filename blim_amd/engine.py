@@ -343,13 +343,11 @@ class Engine:
         _check(self.lib.blim_create(C.byref(cfg), C.byref(h)), "blim_create")
         self.h = h
         self.device = torch.device("cuda", torch.cuda.current_device())
-        # blim_create honours BLIM_PRECISE_MLP (A/B runs): the Python-side cache of that option starts from the same value, so that set_precise() neither clobbers
-        # an override nor believes in a default the engine does not have
         # mirrors the engine's default of option "precise_lo6" (include/blim.h): the compensated modes' second pass over K in e2m3 on fp16 engines
         # (bf16 engines: off by default -- their parity mode runs the second pass in bf16 -- on with set_option("precise_lo6", 1) / BLIM_PRECISE_LO6=1: round 6)
         lo6_ok = dims.hidden_size % 128 == 0 and dims.intermediate_size % 128 == 0 and max(dims.hidden_size, dims.intermediate_size) <= 20480
         self.lo6 = lo6_ok and ((dtype == "f16" and os.environ.get("BLIM_PRECISE_LO6", "1") != "0") or (dtype == "bf16" and os.environ.get("BLIM_PRECISE_LO6", "0") == "1"))
-        self._precise_mlp = os.environ.get("BLIM_PRECISE_MLP", "1") != "0"
+        self._precise_mlp = True          # the engine's default of option "precise_mlp"
         self.weights_version = 0          # bumped by every weight / adapter change: what a measured numeric mode was measured on (modeling.py: resolve_*)
         self._layer_mask = None           # set_layer_mask: per-layer compensation bits of the VTG calls under `--vtg_precise select` (None: no mask)
         self._layer_bits_live = None      # what the engine's "precise_layer_bits" hold (None: its default, all set)
@@ -464,7 +462,7 @@ class Engine:
         if embeds != getattr(self, "_precise_embeds", False):
             self.set_option("precise_embeds", int(embeds))
             self._precise_embeds = embeds
-        mlp = bool(mlp) and os.environ.get("BLIM_PRECISE_MLP", "1") != "0"
+        mlp = bool(mlp)
         if on and mlp != getattr(self, "_precise_mlp", True):
             self.set_option("precise_mlp", int(mlp))
             self._precise_mlp = mlp

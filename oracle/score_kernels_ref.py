@@ -63,7 +63,7 @@ _quiet = dict(over="ignore", invalid="ignore", divide="ignore")
 
 # ---------------------------------------------------------------------------- RMSNorm
 def rmsnorm_form(H, ldx, ldo):
-    """The kernel launch_rmsnorm picks (BLIM_RMSNORM_WIDE at its default): "wide", "narrow4", "narrow16", or None where it refuses the shape."""
+    """The kernel launch_rmsnorm picks: "wide", "narrow4", "narrow16", or None where it refuses the shape."""
     ldo = ldo or H
     if H % 4 or ldx % 4 or ldo % 4:
         return None

@@ -1,5 +1,4 @@
-"""Development aid: attention class time on the SYN step and on reference-shaped VTG / TVG plans, optionally with an ablation library
-(BLIM_LIB=tools/bin/libblim_hip_ablate_attn{1,2}.so: 1 = compute on a tile staged once, 2 = staging only)."""
+"""Development aid: attention class time on the SYN step and on reference-shaped VTG / TVG plans, optionally with another build of the library (BLIM_LIB=path)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
