@@ -33,7 +33,7 @@ from __future__ import annotations
 
 import sys
 from dataclasses import asdict, dataclass, field
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -42,6 +42,50 @@ from .engine import TVG_RANK_MAX_K
 from .pair_scorer import SEG_MAX, PairScorer, _PackState       # noqa: F401  (SEG_MAX: the planner's bound, named here too)
 
 SLOT_ALIGN = 32          # a slot's positions are padded to a multiple of the attention's key tile
+
+
+class SearchRequest(NamedTuple):
+    """One request of GalleryIndex.search_requests: a text over candidates it names (`cand`, with an optional `first_stage` parallel to them) or over the best
+    `shortlist` = K videos of the gallery's TVG ranking, which `prefilter` = K0 >= K narrows first.  A plain tuple of the first three, four or five fields is the same
+    request."""
+    text: int
+    cand: Optional[Sequence[int]] = None
+    first_stage: Optional[Sequence[float]] = None
+    shortlist: Optional[int] = None
+    prefilter: Optional[int] = None
+
+
+def check_shortlist(K, K0, n_videos: int) -> Tuple[Optional[int], Optional[int]]:
+    """The K / K0 rule, stated once: a shortlist keeps K candidates (None: GalleryIndex.prefilter, a stage 0 on its own), a prefilter keeps K0 videos for it (None:
+    no prefilter); both are positive integers, K0 is at least K and, clipped to the gallery's n_videos, at most the rank kernel's BLIM_TVG_RANK_MAX_K.
+    -> (K, K0 clipped to n_videos), None where None was given; ValueError."""
+    positive = lambda x: not isinstance(x, bool) and int(x) == x and int(x) >= 1
+    if K0 is not None and not positive(K0):
+        raise ValueError(f"prefilter K0 = {K0!r}: a positive integer")
+    if K is not None and not positive(K):
+        raise ValueError(f"shortlist k = {K!r}: a positive integer")
+    if K is not None and K0 is not None and K0 < K:
+        raise ValueError(f"prefilter K0 = {K0} below the shortlist's K = {K}: K0 must be at least the shortlist's K = {K}")
+    if K0 is not None and min(int(K0), int(n_videos)) > TVG_RANK_MAX_K:
+        raise ValueError(f"prefilter K0 = {min(int(K0), int(n_videos))} above the rank kernel's limit of {TVG_RANK_MAX_K} (BLIM_TVG_RANK_MAX_K)")
+    return None if K is None else int(K), None if K0 is None else min(int(K0), int(n_videos))
+
+
+def request_pairs(queries, cands, query_col: int = 1) -> Tuple[np.ndarray, np.ndarray]:
+    """One query index and one candidate list per request -> (the [P, 2] (video j, text i) pairs, request by request in candidate order; the points that split a [P]
+    result back into the requests).  query_col: the column of the query -- 1, a text over candidate videos (t2v); 0, a video over candidate texts (v2t)."""
+    cands = [np.asarray(cand, dtype=np.int64).reshape(-1) for cand in cands]
+    lens = [len(cand) for cand in cands]
+    query = np.repeat(np.asarray(queries, dtype=np.int64).reshape(-1), lens)
+    flat = np.concatenate(cands) if cands else np.zeros(0, np.int64)
+    return np.stack([flat, query] if query_col else [query, flat], axis=1), np.cumsum(lens)[:-1]
+
+
+def grid_pairs(queries, cand, query_col: int = 1) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """request_pairs for queries [Q] with k candidates each, cand [Q, k] -> (queries, cand, as int64 arrays; the [Q * k, 2] pairs, whose results reshape(cand.shape))."""
+    queries = np.asarray(queries, dtype=np.int64).reshape(-1)
+    cand = np.asarray(cand, dtype=np.int64).reshape(len(queries), -1)
+    return queries, cand, request_pairs(queries, cand, query_col)[0]
 
 
 def slot_plan(keys: Sequence[Tuple], per_slot_bytes: int, budget_bytes: Optional[int], priority: Optional[Sequence[int]] = None) -> Dict[Tuple, int]:
@@ -660,9 +704,7 @@ class GalleryIndex(_PrefixIndex):
 
     def vtg_scores(self, texts, cand) -> np.ndarray:
         """t2v query_likelihood of queries `texts` (text indices of the scorer, [Q]) against candidates cand [Q, k] (video indices) -> [Q, k]."""
-        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
-        cand = np.asarray(cand, dtype=np.int64).reshape(len(texts), -1)
-        pairs = np.stack([cand.reshape(-1), np.repeat(texts, cand.shape[1])], axis=1)
+        _, cand, pairs = grid_pairs(texts, cand)
         return self.vtg_pairs(pairs).reshape(cand.shape)
 
     def _tvg_state(self):
@@ -703,13 +745,11 @@ class GalleryIndex(_PrefixIndex):
         """The t2v half of training_utils.combine_and_rank for these queries' candidates: blended = c2 * (c0 * query_likelihood + (1 - c0) * candidate) + (1 - c2) *
         first_stage, candidate = the TVG candidate likelihood (minus alpha[0] x its prior with cpn) for fine-tuned checkpoints and zeros for zero-shot ones, as there.
         -> (order [Q, k] of candidate video ids, best first; blended scores in that order)."""
-        texts = np.asarray(texts, dtype=np.int64).reshape(-1)
-        cand = np.asarray(cand, dtype=np.int64).reshape(len(texts), -1)
+        texts, cand, pairs = grid_pairs(texts, cand)
         ql = self.vtg_scores(texts, cand)
         fs = np.zeros(cand.shape) if first_stage is None else np.asarray(first_stage).reshape(cand.shape)
         if finetuned:
             self._tvg_state()
-            pairs = np.stack([cand.reshape(-1), np.repeat(texts, cand.shape[1])], axis=1)
             t2v_cand = self.s.tvg(pairs).reshape(cand.shape)
             if cpn:
                 t2v_cand = t2v_cand - alpha[0] * self._t2v_prior(texts, cand)
@@ -730,11 +770,9 @@ class GalleryIndex(_PrefixIndex):
         """rerank() for requests of unequal sizes, scored together: requests = [(text index, candidate video indices [k_q], first_stage [k_q] or None)].  The pairs of
         all requests are ONE vtg_pairs pass (one pass of a lazy index: its needed keys pinned, its misses admitted under section 12's policy) and, for fine-tuned
         checkpoints, one PairScorer.tvg call and one prior lookup; the blend is rerank()'s, per request.  A VTG score does not depend on what shares its call, so the
-        query likelihood is bit for bit that of rerank() per request.  -> [(order [k_q], blended [k_q])] in request order.  (search_requests with no shortlist request.)"""
-        reqs = [(t, cand, fs, None) for t, cand, fs in requests]
-        if any(len(np.asarray(cand).reshape(-1)) == 0 for _, cand, _, _ in reqs):
-            raise ValueError("rerank_requests: a request has no candidates")
-        return self.search_requests(reqs, cpn=cpn, alpha=alpha, c=c, finetuned=finetuned)
+        query likelihood is bit for bit that of rerank() per request.  -> [(order [k_q], blended [k_q])] in request order.  (search_requests with no shortlist request: a request without candidates is
+        refused there.)"""
+        return self.search_requests([(t, cand, fs) for t, cand, fs in requests], cpn=cpn, alpha=alpha, c=c, finetuned=finetuned)
 
     # ---- the shortlist (DESIGN.md section 18): the gallery ranked by the TVG candidate term, the best K reranked
     def _stage1(self, texts, cpn: bool, alpha) -> np.ndarray:
@@ -759,8 +797,7 @@ class GalleryIndex(_PrefixIndex):
 
     def shortlist(self, texts, k: int, cpn: bool = False, alpha=(0.0, 0.0)):
         """The whole gallery ranked by the TVG candidate term of each text: -> (cand [Q, min(k, N)] video indices, best first; their stage-1 scores)."""
-        if int(k) < 1:
-            raise ValueError(f"shortlist: k = {k}: at least one video")
+        k, _ = check_shortlist(k, None, len(self.s.video))
         texts = np.asarray(texts, dtype=np.int64).reshape(-1)
         stage = self._stage1(texts, cpn, alpha)
         best = [self._best(row, k) for row in stage]
@@ -772,13 +809,9 @@ class GalleryIndex(_PrefixIndex):
     def prefilter(self, texts, k0: int, cpn: bool = False, alpha=(0.0, 0.0)) -> np.ndarray:
         """The K0 videos of each text that log P(clip 0 of the video | text) ranks first (minus alpha[0] x the candidate prior's clip-0 term with cpn): ONE
         PairScorer.tvg_first pass for all texts, one logits row per distinct prompt whatever the gallery's size.  -> cand [Q, min(k0, N)] video indices, ASCENDING
-        (a set: what ranks it is stage 1).  ValueError for a K0 that is no positive integer or, clipped to N, above the rank kernel's BLIM_TVG_RANK_MAX_K."""
-        if isinstance(k0, bool) or int(k0) != k0 or int(k0) < 1:
-            raise ValueError(f"prefilter: K0 = {k0!r}: a positive integer")
+        (a set: what ranks it is stage 1).  ValueError as check_shortlist."""
+        _, k0 = check_shortlist(None, k0, len(self.s.video))
         texts = np.asarray(texts, dtype=np.int64).reshape(-1)
-        k0 = min(int(k0), len(self.s.video))
-        if k0 > TVG_RANK_MAX_K:
-            raise ValueError(f"prefilter: K0 = {k0} above the rank kernel's limit of {TVG_RANK_MAX_K} (BLIM_TVG_RANK_MAX_K)")
         kept = self._stage0(texts, [k0] * len(texts), cpn, alpha)
         return np.stack(kept) if kept else np.zeros((0, k0), np.int64)
 
@@ -796,92 +829,97 @@ class GalleryIndex(_PrefixIndex):
         return [np.sort(row[:k]) for row, k in zip(idx, k0s)]
 
     def search_requests(self, requests, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0), finetuned: bool = False):
-        """rerank_requests() with requests that may take their candidates from the shortlist: requests = [(text index, candidate video indices [k_q] or None,
-        first_stage [k_q] or None, shortlist K or None)], exactly one of candidates and K per request.  A request with candidates is rerank_requests' (its TVG term
-        one PairScorer.tvg call over the explicit requests' pairs).  The shortlist requests of the batch share ONE stage-1 pass (_stage1) over the whole gallery;
-        each keeps its best K videos as candidates, its first-stage term is zero, and the TVG candidate term of its blend IS its stage-1 value: it is not computed a
-        second time.  All requests then share ONE vtg_pairs pass (one pass of a lazy index).  -> [(order [k_q], blended [k_q])] in request order.
-        A shortlist request may carry a fifth field, the prefilter's K0 >= K: (text, None, None, K, K0).  The prefiltered requests of the batch share ONE stage-0
-        pass (prefilter, at the largest K0: a smaller K0's survivors are the first K0 of the same order); their stage-1 terms are ONE PairScorer.tvg call over their
-        surviving pairs (minus alpha[0] x the prior over those K0 candidates with cpn), of which each keeps its best K as a shortlist request does."""
-        reqs, pre = [], {}
-        for req in requests:
-            if len(req) == 5:
-                t, cand, fs, K, K0 = req
-                if K0 is not None:
-                    if K is None:
-                        raise ValueError("search_requests: a prefilter K0 narrows a shortlist: the request needs its K")
-                    if isinstance(K0, bool) or int(K0) != K0 or int(K0) < 1:
-                        raise ValueError(f"search_requests: prefilter K0 = {K0!r}: a positive integer")
-                    if not isinstance(K, bool) and int(K) == K and int(K0) < int(K):
-                        raise ValueError(f"search_requests: prefilter K0 = {K0} below the shortlist's K = {K}")
-                    if min(int(K0), len(self.s.video)) > TVG_RANK_MAX_K:
-                        raise ValueError(f"search_requests: prefilter K0 = {min(int(K0), len(self.s.video))} above the rank kernel's limit of {TVG_RANK_MAX_K} "
-                                         f"(BLIM_TVG_RANK_MAX_K)")
-                    pre[len(reqs)] = min(int(K0), len(self.s.video))
-            else:
-                t, cand, fs, K = req
-            if (cand is None) == (K is None):
-                raise ValueError("search_requests: a request takes candidates or a shortlist K, one of the two")
-            if K is not None:
-                if isinstance(K, bool) or int(K) != K or int(K) < 1:
-                    raise ValueError(f"search_requests: shortlist K = {K!r}: a positive integer")
-                if fs is not None:
-                    raise ValueError("search_requests: a first stage is parallel to a request's candidates; a shortlist request has none")
-                reqs.append([int(t), None, None, int(K)])
-            else:
-                cand = np.asarray(cand, dtype=np.int64).reshape(-1)
-                if len(cand) == 0:
-                    raise ValueError("search_requests: a request has no candidates")
-                reqs.append([int(t), cand, fs, None])
+        """rerank_requests() with requests that may take their candidates from the shortlist: requests = SearchRequest objects or plain tuples of their first three,
+        four or five fields (text index, candidate video indices [k_q] or None, first_stage [k_q] or None, shortlist K or None, prefilter K0 or None), exactly one of
+        candidates and K per request.  A request with candidates is rerank_requests' (its TVG term one PairScorer.tvg call over the explicit requests' pairs).  The
+        shortlist requests of the batch share ONE stage-1 pass (_stage1) over the whole gallery; each keeps its best K videos as candidates, its first-stage term is
+        zero, and the TVG candidate term of its blend IS its stage-1 value: it is not computed a second time.  A shortlist request with a `prefilter` K0 >= K is
+        narrowed first: the prefiltered requests of the batch share ONE stage-0 pass (prefilter, at the largest K0: a smaller K0's survivors are the first K0 of the
+        same order); their stage-1 terms are ONE PairScorer.tvg call over their surviving pairs (minus alpha[0] x the prior over those K0 candidates with cpn), of
+        which each keeps its best K as a shortlist request does.  All requests then share ONE vtg_pairs pass (one pass of a lazy index).
+        -> [(order [k_q], blended [k_q])] in request order."""
+        reqs = self._checked(requests, finetuned)
         if not reqs:
             return []
-        short = [n for n, r in enumerate(reqs) if r[3] is not None and n not in pre]
-        stage1 = {}
-        if short or pre:
-            if not finetuned:
-                raise ValueError("search_requests: a shortlist ranks by the TVG likelihood, which a zero-shot model does not have (finetuned=False)")
-        if short:
-            for n, row in zip(short, self._stage1([reqs[n][0] for n in short], cpn, alpha)):
-                reqs[n][1], stage1[n] = self._best(row, reqs[n][3])
-        if pre:
-            ns = sorted(pre)
-            texts = [reqs[n][0] for n in ns]
-            cands = self._stage0(texts, [pre[n] for n in ns], cpn, alpha)
-            pp = np.concatenate([np.stack([cand, np.full(len(cand), t, dtype=np.int64)], axis=1) for t, cand in zip(texts, cands)])
-            term = self.s.tvg(pp)
-            if cpn:
-                term = term - alpha[0] * self._t2v_prior(texts, cands)
-            for n, cand, row in zip(ns, cands, np.split(term, np.cumsum([len(x) for x in cands])[:-1])):
-                order, best = self._best(row, reqs[n][3])
-                reqs[n][1], stage1[n] = cand[order], best
-        pairs = np.concatenate([np.stack([cand, np.full(len(cand), t, dtype=np.int64)], axis=1) for t, cand, _, _ in reqs])
-        ends = np.cumsum([len(cand) for _, cand, _, _ in reqs])
-        ql = np.split(self.vtg_pairs(pairs), ends[:-1])
-        given = [n for n, r in enumerate(reqs) if r[3] is None]
-        t2v_cand = dict(stage1)
-        if finetuned and given:
-            self._tvg_state()
-            sub = [reqs[n] for n in given]
-            sub_pairs = np.concatenate([np.stack([cand, np.full(len(cand), t, dtype=np.int64)], axis=1) for t, cand, _, _ in sub])
-            has = np.array([self.s.tvg_split[t] is not None for t, _, _, _ in sub])
-            if c[0] != 1:                                               # the candidate likelihood has a weight: every text needs its TVG row
-                self.s._need_tvg([t for t, _, _, _ in sub])
-            of = np.repeat(has, [len(cand) for _, cand, _, _ in sub])  # (a text added without a TVG row keeps a zero term under c0 = 1)
-            term = np.zeros(len(sub_pairs), dtype=np.float32)
-            if of.any():
-                term[of] = self.s.tvg(sub_pairs[of])
-            if cpn and of.any():
-                prior = np.zeros(len(sub_pairs))
-                prior[of] = self._t2v_prior([t for (t, _, _, _), h in zip(sub, has) if h], [cand for (_, cand, _, _), h in zip(sub, has) if h])
-                term = term - alpha[0] * prior
-            t2v_cand.update(zip(given, np.split(term, np.cumsum([len(cand) for _, cand, _, _ in sub])[:-1])))
+        cands, terms = self._chosen(reqs, cpn, alpha)
+        if finetuned:
+            self._given_terms(reqs, cands, terms, cpn, alpha, c)
+        pairs, cuts = request_pairs([r.text for r in reqs], cands)
         out = []
-        for n, (t, cand, fs, _) in enumerate(reqs):
-            fs = np.zeros(cand.shape) if fs is None else np.asarray(fs).reshape(cand.shape)
-            order, blended = self._blend(cand[None], ql[n][None], t2v_cand[n][None] if n in t2v_cand else np.zeros((1, len(cand))), fs[None], c)
+        for r, cand, ql, term in zip(reqs, cands, np.split(self.vtg_pairs(pairs), cuts), terms):
+            fs = np.zeros(cand.shape) if r.first_stage is None else np.asarray(r.first_stage).reshape(cand.shape)
+            order, blended = self._blend(cand[None], ql[None], np.zeros((1, len(cand))) if term is None else term[None], fs[None], c)
             out.append((order[0], blended[0]))
         return out
+
+    def _checked(self, requests, finetuned: bool) -> List[SearchRequest]:
+        """Step 1 of search_requests: every request a SearchRequest -- its text an int, named candidates an int64 array, K and K0 through check_shortlist (K0
+        clipped to the gallery) -- or the ValueError that names what it lacks."""
+        N, reqs = len(self.s.video), []
+        for r in requests:
+            r = SearchRequest(*r)
+            if r.prefilter is not None and r.shortlist is None:
+                raise ValueError("search_requests: a prefilter K0 narrows a shortlist: the request needs its K")
+            if (r.cand is None) == (r.shortlist is None):
+                raise ValueError("search_requests: a request takes candidates or a shortlist K, one of the two")
+            if r.shortlist is not None:
+                K, K0 = check_shortlist(r.shortlist, r.prefilter, N)
+                if r.first_stage is not None:
+                    raise ValueError("search_requests: a first stage is parallel to a request's candidates; a shortlist request has none")
+                reqs.append(SearchRequest(int(r.text), shortlist=K, prefilter=K0))
+            else:
+                cand = np.asarray(r.cand, dtype=np.int64).reshape(-1)
+                if len(cand) == 0:
+                    raise ValueError("search_requests: a request has no candidates")
+                reqs.append(SearchRequest(int(r.text), cand, r.first_stage))
+        if not finetuned and any(r.shortlist is not None for r in reqs):
+            raise ValueError("search_requests: a shortlist ranks by the TVG likelihood, which a zero-shot model does not have (finetuned=False)")
+        return reqs
+
+    def _chosen(self, reqs: List[SearchRequest], cpn: bool, alpha):
+        """Step 2: -> (candidates, TVG candidate term) per request.  A request that names its candidates keeps them and has no term yet (None).  The plain shortlists
+        take the best K of ONE stage-1 pass; the prefiltered ones the best K of ONE PairScorer.tvg call over what ONE stage-0 pass kept; the value they were ranked
+        by is their term."""
+        cands, terms = [r.cand for r in reqs], [None] * len(reqs)
+        short = [n for n, r in enumerate(reqs) if r.shortlist is not None and r.prefilter is None]
+        pre = [n for n, r in enumerate(reqs) if r.prefilter is not None]
+        if short:
+            for n, row in zip(short, self._stage1([reqs[n].text for n in short], cpn, alpha)):
+                cands[n], terms[n] = self._best(row, reqs[n].shortlist)
+        if pre:
+            texts = [reqs[n].text for n in pre]
+            kept = self._stage0(texts, [reqs[n].prefilter for n in pre], cpn, alpha)
+            pairs, cuts = request_pairs(texts, kept)
+            term = self.s.tvg(pairs)
+            if cpn:
+                term = term - alpha[0] * self._t2v_prior(texts, kept)
+            for n, cand, row in zip(pre, kept, np.split(term, cuts)):
+                order, terms[n] = self._best(row, reqs[n].shortlist)
+                cands[n] = cand[order]
+        return cands, terms
+
+    def _given_terms(self, reqs: List[SearchRequest], cands, terms, cpn: bool, alpha, c) -> None:
+        """Step 3 (fine-tuned blends): the TVG candidate term of the requests that named their candidates, written into `terms`: ONE PairScorer.tvg call over their
+        pairs, minus alpha[0] x the prior with cpn."""
+        given = [n for n, r in enumerate(reqs) if r.shortlist is None]
+        if not given:
+            return
+        self._tvg_state()
+        texts, mine = [reqs[n].text for n in given], [cands[n] for n in given]
+        pairs, cuts = request_pairs(texts, mine)
+        has = np.array([self.s.tvg_split[t] is not None for t in texts])
+        if c[0] != 1:                                                   # the candidate likelihood has a weight: every text needs its TVG row
+            self.s._need_tvg(texts)
+        of = np.repeat(has, [len(cand) for cand in mine])               # (a text added without a TVG row keeps a zero term under c0 = 1)
+        term = np.zeros(len(pairs), dtype=np.float32)
+        if of.any():
+            term[of] = self.s.tvg(pairs[of])
+        if cpn and of.any():
+            prior = np.zeros(len(pairs))
+            prior[of] = self._t2v_prior([t for t, h in zip(texts, has) if h], [cand for cand, h in zip(mine, has) if h])
+            term = term - alpha[0] * prior
+        for n, row in zip(given, np.split(term, cuts)):
+            terms[n] = row
 
 
 class TextGalleryIndex(_PrefixIndex):
@@ -1013,15 +1051,19 @@ class TextGalleryIndex(_PrefixIndex):
         (candidate_likelihood - alpha[1] * candidate_prior)) + (1 - c3) * first_stage; candidate_likelihood is VTG (log P(text | video)), query_likelihood TVG
         (log P(video | text)).  Zero-shot: the likelihood term is the (debiased) candidate likelihood alone and no TVG call is made, as there.
         -> (order [Q, k] of candidate text ids, best first; blended scores in that order)."""
-        videos = np.asarray(videos, dtype=np.int64).reshape(-1)
-        cand = np.asarray(cand, dtype=np.int64).reshape(len(videos), -1)
-        pairs = np.stack([np.repeat(videos, cand.shape[1]), cand.reshape(-1)], axis=1)
+        videos, cand, pairs = grid_pairs(videos, cand, query_col=0)
         v2t_cand = self.vtg_pairs(pairs).reshape(cand.shape)
         fs = np.zeros(cand.shape) if first_stage is None else np.asarray(first_stage).reshape(cand.shape)
         if cpn:
             v2t_cand = v2t_cand - alpha[1] * self.v2t_prior(videos, cand)
+        return self._blend(cand, self.tvg_pairs(pairs).reshape(cand.shape) if finetuned else None, v2t_cand, fs, c)
+
+    @staticmethod
+    def _blend(cand, ql, v2t_cand, fs, c):
+        """cand, query likelihood (None: zero-shot, the candidate likelihood alone), candidate likelihood and first stage, [Q, k] each -> (candidates best first,
+        their blended scores)."""
         _, c1, _, c3 = c
-        v2t_lm = c1 * self.tvg_pairs(pairs).reshape(cand.shape) + (1 - c1) * v2t_cand if finetuned else v2t_cand
+        v2t_lm = v2t_cand if ql is None else c1 * ql + (1 - c1) * v2t_cand
         blended = c3 * v2t_lm + (1 - c3) * fs
         order = np.argsort(-blended, axis=1, kind="stable")
         return np.take_along_axis(cand, order, 1), np.take_along_axis(blended, order, 1)
@@ -1031,11 +1073,9 @@ class TextGalleryIndex(_PrefixIndex):
         """Every caption ranked by a query video's TVG likelihood, log P(video | text), over the cached prompts: one tvg_pairs pass per query video, so every text has
         one video and a value is that of any other pass that scores the pair so (section 11).  Descending, ties to the lower text index.
         -> (cand [Q, min(k, texts)] text indices, best first; their stage-1 scores)."""
-        if int(k) < 1:
-            raise ValueError(f"shortlist: k = {k}: at least one text")
         videos = np.asarray(videos, dtype=np.int64).reshape(-1)
         n = len(self.s.tvg_split)
-        k = min(int(k), n)
+        k = min(check_shortlist(k, None, n)[0], n)
         cand, stage = np.zeros((len(videos), k), np.int64), np.zeros((len(videos), k), np.float32)
         for q, v in enumerate(videos):
             row = self.tvg_pairs(np.stack([np.full(n, v, dtype=np.int64), np.arange(n)], axis=1))
@@ -1046,13 +1086,9 @@ class TextGalleryIndex(_PrefixIndex):
     def rerank_shortlist(self, videos, k: int, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0)):
         """rerank(videos, shortlist(videos, k), finetuned=True) without a first stage, the query likelihood of the blend being the shortlist's stage-1 value: the TVG
         term is not computed a second time.  -> (order [Q, k] of text ids, best first; blended scores in that order)."""
-        videos = np.asarray(videos, dtype=np.int64).reshape(-1)
         cand, stage = self.shortlist(videos, k)
-        pairs = np.stack([np.repeat(videos, cand.shape[1]), cand.reshape(-1)], axis=1)
+        videos, cand, pairs = grid_pairs(videos, cand, query_col=0)
         v2t_cand = self.vtg_pairs(pairs).reshape(cand.shape)
         if cpn:
             v2t_cand = v2t_cand - alpha[1] * self.v2t_prior(videos, cand)
-        _, c1, _, c3 = c
-        blended = c3 * (c1 * stage + (1 - c1) * v2t_cand) + (1 - c3) * np.zeros(cand.shape)
-        order = np.argsort(-blended, axis=1, kind="stable")
-        return np.take_along_axis(cand, order, 1), np.take_along_axis(blended, order, 1)
+        return self._blend(cand, stage, v2t_cand, np.zeros(cand.shape), c)

@@ -145,10 +145,15 @@ def load_tokenizer(model_path: str):
     return AutoTokenizer.from_pretrained(model_path, trust_remote_code=True)
 
 
+# --narrow_gemm / --narrow_lo6 / --narrow_qkv auto: the engine option of the same name, and the GEMM it switches on (for the refusal with an fp8 engine)
+NARROW_GEMMS = {"narrow_gemm": "the narrow residual GEMM", "narrow_lo6": "the narrow residual GEMM with the e2m3 second pass", "narrow_qkv": "the narrow QKV GEMM"}
+
+
 def check_args(args) -> None:
     """Refusals that need neither a device nor the model (SystemExit with the reason)."""
-    if getattr(args, "narrow_qkv", "off") == "auto" and args.dtype == "f8":
-        raise SystemExit("--narrow_qkv auto needs a 16-bit engine (--dtype f16 | bf16): the narrow QKV GEMM takes fp16 / bf16 operands")
+    for flag, gemm in NARROW_GEMMS.items():
+        if getattr(args, flag) == "auto" and args.dtype == "f8":
+            raise SystemExit(f"--{flag} auto needs a 16-bit engine (--dtype f16 | bf16): {gemm} takes fp16 / bf16 operands")
 
 
 def main(args):
@@ -168,10 +173,6 @@ def main(args):
         raise SystemExit("--lr is required for training (main.py:41: absolute learning rate)")
     if not args.eval and args.dtype == "f8":
         raise SystemExit("training needs a 16-bit engine (--dtype f16 | bf16)")
-    if args.narrow_gemm == "auto" and args.dtype == "f8":
-        raise SystemExit("--narrow_gemm auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM takes fp16 / bf16 operands")
-    if args.narrow_lo6 == "auto" and args.dtype == "f8":
-        raise SystemExit("--narrow_lo6 auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM with the e2m3 second pass takes fp16 / bf16 operands")
     t0 = time.time()
     train_loader = None
     if args.synthetic > 0:
@@ -230,16 +231,11 @@ def main(args):
         model.tvg_precise = args.tvg_precise
     if args.vtg_precise is not None and model.engine.can_precise:
         model.vtg_precise = None if args.vtg_precise == "none" else args.vtg_precise        # "auto": resolved by evaluation() on the loaded weights
-    if args.narrow_gemm == "auto":
-        if model.engine.dtype == "f8":
-            raise SystemExit("--narrow_gemm auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM takes fp16 / bf16 operands")
-        model.engine.set_option("narrow_gemm", 1)
-    if args.narrow_lo6 == "auto":
-        if model.engine.dtype == "f8":
-            raise SystemExit("--narrow_lo6 auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM with the e2m3 second pass takes fp16 / bf16 operands")
-        model.engine.set_option("narrow_lo6", 1)
-    if args.narrow_qkv == "auto":                                       # (refused with --dtype f8 by check_args)
-        model.engine.set_option("narrow_qkv", 1)
+    for flag, gemm in NARROW_GEMMS.items():
+        if getattr(args, flag) == "auto":
+            if model.engine.dtype == "f8":                              # (--dtype f8 is refused by check_args: an engine that took f8 from BLIM_DTYPE)
+                raise SystemExit(f"--{flag} auto needs a 16-bit engine (--dtype f16 | bf16): {gemm} takes fp16 / bf16 operands")
+            model.engine.set_option(flag, 1)
     if model.engine.dtype == "f8":
         finetuned_file = bool(args.resume) and os.path.isfile(args.resume)
         mask = args.f8_mask if args.f8_mask is not None else (12 if finetuned_file else 31)

@@ -33,7 +33,8 @@ gets an error line.  The answer is {"id", "query", "videos", "scores"} or
 {"id", "error"}: a bad request (malformed JSON, an unknown video id, an empty or duplicate candidate list, a row that fails PairScorer.add_texts' checks or leaves no
 response token under tokenizer_model_max_length, a fine-tuned blend with c0 < 1 for rows without a TVG row) gets its error line and the process goes on.
 `--batch_queries B` / `--batch_wait_ms W`: a reader thread queues the lines; the loop takes what is waiting, up to B requests, waits at most W ms for more only while
-fewer are there, and scores the batch as ONE pass (GalleryIndex.search_requests: the shortlist requests of a batch share one stage-1 pass, all requests one VTG pass)
+fewer are there, and scores the batch as ONE pass (GalleryIndex.search_requests, one gallery.SearchRequest per request: the shortlist requests of a batch share one
+stage-1 pass, all requests one VTG pass)
 -- the same scores as one pass per request, bit for bit on the VTG term and on a shortlist's stage 1.  Texts join the
 scorer at run time (PairScorer.add_texts); identical `text` / `rows` queries share one text index.  At EOF a `serve:` stderr line counts requests, batches, the mean
 batch size, errors and texts added (and, once a video was added, `videos_added`).
@@ -63,6 +64,8 @@ import argparse
 import json
 import sys
 import time
+
+from .main import NARROW_GEMMS
 
 
 def get_args_parser():
@@ -137,18 +140,14 @@ def get_args_parser():
 
 def shortlist_k(args) -> int:
     """--candidates tvg: the candidates kept from the TVG ranking (--shortlist, default --topk)."""
-    k = getattr(args, "shortlist", None)
-    return int(args.topk if k is None else k)
+    return int(args.topk if args.shortlist is None else args.shortlist)
 
 
 def check_args(args, world: int = 1) -> None:
     """Refusals (SystemExit with the reason): what the gallery index does not cover."""
-    if getattr(args, "narrow_gemm", "off") == "auto" and args.dtype == "f8":
-        raise SystemExit("search: --narrow_gemm auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM takes fp16 / bf16 operands")
-    if getattr(args, "narrow_lo6", "off") == "auto" and args.dtype == "f8":
-        raise SystemExit("search: --narrow_lo6 auto needs a 16-bit engine (--dtype f16 | bf16): the narrow residual GEMM with the e2m3 second pass takes fp16 / bf16 operands")
-    if getattr(args, "narrow_qkv", "off") == "auto" and args.dtype == "f8":
-        raise SystemExit("search: --narrow_qkv auto needs a 16-bit engine (--dtype f16 | bf16): the narrow QKV GEMM takes fp16 / bf16 operands")
+    for flag, gemm in NARROW_GEMMS.items():
+        if getattr(args, flag) == "auto" and args.dtype == "f8":
+            raise SystemExit(f"search: --{flag} auto needs a 16-bit engine (--dtype f16 | bf16): {gemm} takes fp16 / bf16 operands")
     if args.dtype == "f8":
         raise SystemExit("search: --dtype f8 is not supported (the prefix cache needs a 16-bit engine: --dtype f16 | bf16)")
     if args.shard is not None:
@@ -156,40 +155,40 @@ def check_args(args, world: int = 1) -> None:
     if world > 1:
         raise SystemExit(f"search: world size {world} > 1 is not supported (run one process)")
     for flag in ("gallery_host_gb", "text_gallery_host_gb"):
-        if getattr(args, flag, None) is not None and args.gallery_fill != "lazy":
+        if getattr(args, flag) is not None and args.gallery_fill != "lazy":
             raise SystemExit(f"search: --{flag} needs --gallery_fill lazy (the host tier keeps the slots a lazy cache evicts; an eager cache is filled once and evicts none)")
-        if getattr(args, flag, None) is not None and getattr(args, flag) < 0:
+        if getattr(args, flag) is not None and getattr(args, flag) < 0:
             raise SystemExit(f"search: --{flag} must not be negative")
-    spare = getattr(args, "gallery_spare", 0)
+    spare = args.gallery_spare
     if spare < 0:
         raise SystemExit("search: --gallery_spare must not be negative")
     if spare and args.gallery_fill != "eager":
         raise SystemExit("search: --gallery_spare keeps free slots in an eager cache (--gallery_fill eager); a lazy cache admits a video that joins on demand, under --gallery_gb")
-    v2t = getattr(args, "direction", "t2v") == "v2t"
+    v2t = args.direction == "v2t"
     if args.c is None:                        # the likelihood of the direction alone: t2v c0 = c2 = 1; v2t c1 = 0, c3 = 1
         args.c = [1.0, 0.0, 1.0, 1.0] if v2t else [1.0, 0.0, 1.0, 0.0]
-    serve = bool(getattr(args, "serve", False))
+    serve = bool(args.serve)
     if serve:
         if v2t:
             raise SystemExit("search: --serve answers text queries over the videos only (--direction t2v); v2t is not served")
-        if args.query or args.query_ids or getattr(args, "video_ids", None):
+        if args.query or args.query_ids or args.video_ids:
             raise SystemExit("search: --serve reads its queries from stdin, one JSON request per line (not --query / --query_ids / --video_ids)")
-        if getattr(args, "batch_queries", 1) < 1 or getattr(args, "batch_wait_ms", 0.0) < 0:
+        if args.batch_queries < 1 or args.batch_wait_ms < 0:
             raise SystemExit("search: --batch_queries must be at least 1 and --batch_wait_ms must not be negative")
-    elif getattr(args, "batch_queries", 1) != 1 or getattr(args, "batch_wait_ms", 0.0) != 0:
+    elif args.batch_queries != 1 or args.batch_wait_ms != 0:
         raise SystemExit("search: --batch_queries / --batch_wait_ms batch the requests of --serve")
     if v2t:
         if args.query or args.query_ids:
             raise SystemExit("search: --direction v2t takes video queries (--video_ids), not --query / --query_ids")
-        outside = getattr(args, "query_video", None)
+        outside = args.query_video
         if not args.video_ids and not outside:
             raise SystemExit("search: --direction v2t needs --video_ids")
         if outside and args.candidates == "iv2":
             raise SystemExit("search: --query_video: a video outside the dataset has no first-stage row (--candidates iv2): use --candidates all, or tvg with --resume")
     else:
-        if getattr(args, "query_video", None):
+        if args.query_video:
             raise SystemExit("search: --query_video files are the queries of --direction v2t (t2v takes --query_ids and / or --query)")
-        if getattr(args, "video_ids", None):
+        if args.video_ids:
             raise SystemExit("search: --video_ids are the queries of --direction v2t (t2v takes --query_ids and / or --query)")
         if not args.query_ids and not args.query and not serve:
             raise SystemExit("search: give --query_ids and / or --query")
@@ -200,11 +199,11 @@ def check_args(args, world: int = 1) -> None:
     if args.candidates == "tvg" and not args.resume:
         raise SystemExit("search: --candidates tvg needs a fine-tuned checkpoint (--resume): a zero-shot model's visual head is untrained, so it has no TVG likelihood to "
                          "rank the gallery by")
-    if getattr(args, "shortlist", None) is not None and args.candidates != "tvg":
+    if args.shortlist is not None and args.candidates != "tvg":
         raise SystemExit("search: --shortlist is the number of candidates --candidates tvg keeps (give --candidates tvg)")
     if args.candidates == "tvg" and shortlist_k(args) < 1:
         raise SystemExit("search: --shortlist must be at least 1 (it defaults to --topk)")
-    K0 = getattr(args, "prefilter", None)
+    K0 = args.prefilter
     if K0 is not None:
         if v2t:
             raise SystemExit("search: --prefilter narrows the t2v TVG ranking (--direction t2v): v2t has no prefilter")
@@ -223,10 +222,10 @@ def check_args(args, world: int = 1) -> None:
                          "pass the mode a stored evaluation resolved (--vtg_precise none | full) instead")
     if args.second_pass == "auto":
         raise SystemExit("search: --second_pass auto is not supported (it is measured by evaluation()): give e2m3 or 16bit")
-    tower_path, tower_seed = getattr(args, "vision_model_path", None), getattr(args, "vision_synthetic", None)
+    tower_path, tower_seed = args.vision_model_path, args.vision_synthetic
     if tower_path is not None and tower_seed is not None:
         raise SystemExit("search: give --vision_model_path or --vision_synthetic, not both (the tower has one set of weights)")
-    takes_frames = serve or (v2t and any(is_frame_stack(f) for f in (getattr(args, "query_video", None) or [])))
+    takes_frames = serve or (v2t and any(is_frame_stack(f) for f in (args.query_video or [])))
     if (tower_path is not None or tower_seed is not None) and not takes_frames:
         raise SystemExit("search: --vision_model_path / --vision_synthetic load the vision tower for raw frames: they act under --serve (add_video frames) and with a "
                          "--query_video FILE ending in .npy (--direction v2t)")
@@ -277,11 +276,11 @@ class FrameFeaturiser:
             enc = None
             try:
                 enc = VisionEncoder(self.dims, dtype="f16")
-                seed = getattr(self.args, "vision_synthetic", None)
+                seed = self.args.vision_synthetic
                 if seed is not None:
                     enc.init_synthetic_weights(seed)
                 else:
-                    enc.load_checkpoint(getattr(self.args, "vision_model_path", None) or self.args.model_path)
+                    enc.load_checkpoint(self.args.vision_model_path or self.args.model_path)
             except (RuntimeError, OSError, KeyError, ValueError, ImportError, EOFError, pickle.UnpicklingError) as e:      # (engine.BlimError is a RuntimeError)
                 if enc is not None:
                     enc.close()
@@ -328,6 +327,31 @@ def query_video_features(files, args, featuriser=None):
     finally:
         if own is not None:
             own.close()
+
+
+def default_candidates(mode: str, row, n: int, k: int):
+    """The candidates of a query that names none, under `--candidates iv2 | all` -> (candidate indices, their first-stage scores or None).  row: the query's
+    first-stage row, or None for a query that has none (free text, raw rows, a video outside the dataset): then `all` has no first-stage term, and `iv2` is the
+    caller's refusal.  iv2: the stable top-k of the row.  all: the whole gallery of n, the row padded with zeros for the entries that joined at run time."""
+    import numpy as np
+    if row is not None:
+        row = np.asarray(row, dtype=np.float32)
+    if mode == "iv2":
+        cand = np.argsort(-row, kind="stable")[:min(k, n)]
+    else:
+        cand = np.arange(n)
+        if row is not None:
+            row = np.concatenate([row, np.zeros(max(n - len(row), 0), np.float32)])
+    return cand, None if row is None else row[cand]
+
+
+def answer_line(query: str, ranked_as: str, ranked, scores, shortlisted=None, prefiltered=None, head=None) -> str:
+    """One stdout answer: {**head (serve: the request's id), "query", ranked_as ("videos" | "texts"): the ranked ids, "scores", then "shortlisted": K and
+    "prefiltered": K0 where the candidates came from the shortlist / through the prefilter}."""
+    more = {} if shortlisted is None else {"shortlisted": shortlisted}
+    if prefiltered is not None:
+        more["prefiltered"] = prefiltered
+    return json.dumps({**(head or {}), "query": query, ranked_as: list(ranked), "scores": [float(x) for x in scores], **more})
 
 
 class BadRequest(ValueError):
@@ -405,7 +429,7 @@ class Server:
             K = req["shortlist"]
             if "candidates" in req or "candidate_idx" in req:
                 raise BadRequest("shortlist ranks the whole gallery: give shortlist or candidates / candidate_idx, not both")
-            if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+            if isinstance(K, bool) or not isinstance(K, int):
                 raise BadRequest("shortlist must be a positive integer")
             return self._shortlisted(req, t, K)
         if "candidates" in req and "candidate_idx" in req:
@@ -428,17 +452,11 @@ class Server:
             cand = np.asarray(cand, dtype=np.int64)
         elif self.args.candidates == "tvg":
             return self._shortlisted(req, t, shortlist_k(self.args))
-        elif self.args.candidates == "iv2":
-            if not is_caption:
-                raise BadRequest("a text / rows query has no first-stage row (--candidates iv2): send candidates")
-            row = np.asarray(self.t2v_iv2[t], dtype=np.float32)
-            cand = np.argsort(-row, kind="stable")[:min(self.args.topk, N)]
-            fs = row[cand]
         else:
-            cand = np.arange(N)
-            if self.t2v_iv2 is not None and is_caption:
-                row = np.asarray(self.t2v_iv2[t], dtype=np.float32)
-                fs = np.concatenate([row, np.zeros(max(N - len(row), 0), np.float32)])[cand]     # (a video that joined at run time has no first-stage score: a zero term)
+            row = self.t2v_iv2[t] if self.t2v_iv2 is not None and is_caption else None
+            if row is None and self.args.candidates == "iv2":
+                raise BadRequest("a text / rows query has no first-stage row (--candidates iv2): send candidates")
+            cand, fs = default_candidates(self.args.candidates, row, N, self.args.topk)
         if "first_stage" in req:
             try:
                 fs = np.asarray(req["first_stage"], dtype=np.float32).reshape(-1)
@@ -459,20 +477,22 @@ class Server:
         return None, None, int(K)
 
     def _prefilter(self, req, shortlist):
-        """-> the K0 of a shortlisted request: its own `"prefilter"`, else --prefilter for a request that takes the default K; None: not prefiltered."""
-        from .engine import TVG_RANK_MAX_K
-        if "prefilter" not in req:
-            K0 = getattr(self.args, "prefilter", None)
-            return int(K0) if K0 is not None and shortlist is not None and "shortlist" not in req else None
-        K0 = req["prefilter"]
-        if isinstance(K0, bool) or not isinstance(K0, int) or K0 < 1:
-            raise BadRequest("prefilter must be a positive integer")
+        """-> the K0 of a shortlisted request: its own `"prefilter"`, else --prefilter for a request that takes the default K; None: not prefiltered.  The
+        shortlist's K and this K0 are held to gallery.check_shortlist here, before the request enters a batch."""
+        from .gallery import check_shortlist
+        K0 = self.args.prefilter if "shortlist" not in req else None
+        if "prefilter" in req:
+            K0 = req["prefilter"]
+            if isinstance(K0, bool) or not isinstance(K0, int):
+                raise BadRequest("prefilter must be a positive integer")
+            if shortlist is None:
+                raise BadRequest("prefilter narrows a shortlist: give shortlist (or run --candidates tvg), not candidates / candidate_idx")
         if shortlist is None:
-            raise BadRequest("prefilter narrows a shortlist: give shortlist (or run --candidates tvg), not candidates / candidate_idx")
-        if K0 < shortlist:
-            raise BadRequest(f"prefilter must be at least the shortlist's K = {shortlist}")
-        if min(K0, len(self.vids)) > TVG_RANK_MAX_K:
-            raise BadRequest(f"prefilter keeps at most {TVG_RANK_MAX_K} videos")
+            return None
+        try:
+            check_shortlist(shortlist, K0, len(self.vids))
+        except ValueError as e:
+            raise BadRequest(str(e)) from None
         return K0
 
     def parse(self, line: str):
@@ -558,9 +578,10 @@ class Server:
 
     # ---- one batch
     def _score(self, reqs):
+        from .gallery import SearchRequest
         a = self.args
-        five = lambda r: () if r.get("prefilter") is None else (r["prefilter"],)        # (a request that is not prefiltered: the 4-tuple it always was)
-        return self.gal.search_requests([(r["text"], r["cand"], r["fs"], r["shortlist"]) + five(r) for r in reqs], cpn=a.cpn, alpha=a.alpha, c=a.c, finetuned=self.finetuned)
+        return self.gal.search_requests([SearchRequest(r["text"], r["cand"], r["fs"], r["shortlist"], r["prefilter"]) for r in reqs],
+                                        cpn=a.cpn, alpha=a.alpha, c=a.c, finetuned=self.finetuned)
 
     def handle(self, lines, write) -> None:
         """The requests that arrived together: every good one is scored in ONE search_requests pass; one answer line per request, in arrival order.  An add_video
@@ -611,10 +632,7 @@ class Server:
                 continue
             order, blended = res
             k = len(order) if r["topk"] is None else min(r["topk"], len(order))
-            more = {} if r["shortlist"] is None else {"shortlisted": r["shortlist"]}
-            if r.get("prefilter") is not None:
-                more["prefiltered"] = r["prefilter"]
-            write(json.dumps({"id": r["id"], "query": r["query"], "videos": [self.vids[int(j)] for j in order[:k]], "scores": [float(x) for x in blended[:k]], **more}))
+            write(answer_line(r["query"], "videos", [self.vids[int(j)] for j in order[:k]], blended[:k], r["shortlist"], r["prefilter"], head={"id": r["id"]}))
 
     def summary(self):
         more = {"videos_added": self.videos_added} if self.videos_added else {}             # (a stream without an add_video request: the line it always was)
@@ -664,163 +682,127 @@ def serve(lines, write, server, batch_queries: int = 1, batch_wait_ms: float = 0
     return server.summary()
 
 
-def main(args):
+def build_problem(args):
+    """What the run scores over -> a namespace: model (weights loaded, the TVG prefix length set), tok, vtg and tvg ([ids, labels, masks] rows of the texts: the test
+    captions, then one per --query), video, vocab, vlab, vids, the first-stage matrices t2v_iv2 / v2t_iv2 (None: not loaded) and build_rows (--serve: free text ->
+    its unpadded (vtg, tvg) rows; None under --synthetic, which has no tokenizer)."""
     import os
     import types
 
     import numpy as np
     import torch
 
-    from . import distributed as D
-    from . import retrieval_utils as RU
     from . import synth
-    from .gallery import GalleryIndex
-    from .modeling import BlimModel, DDPLike
-
-    check_args(args, int(os.environ.get("WORLD_SIZE", "1")))
-    t0 = time.time()
+    from .modeling import BlimModel
     T = torch.from_numpy
+    p = types.SimpleNamespace(build_rows=None)
     if args.synthetic > 0:
         dims = synth.ModelDims(num_clips=args.num_clips) if args.synthetic_7b else synth.ModelDims(
             vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2, num_kv_heads=1, mm_hidden_size=64, num_clips=args.num_clips)
-        model = BlimModel(dims, dtype=args.dtype)
-        model.engine.init_synthetic_weights(0)
+        p.model = BlimModel(dims, dtype=args.dtype)
+        p.model.engine.init_synthetic_weights(0)
         prob = synth.make_problem(1, args.synthetic, dims, tok_per_clip=64 if args.synthetic_7b else 8, fast_video=args.synthetic > 256)
-        tok = types.SimpleNamespace(pad_token_id=synth.PAD_ID)
-        rows = lambda a: [T(r) for r in a]
-        vtg_ids, vtg_lab, vtg_msk = prob.vtg_ids, prob.vtg_labels, prob.vtg_masks
-        tvg_ids, tvg_lab, tvg_msk = prob.tvg_ids, prob.tvg_labels, prob.tvg_masks
-        video, vocab, vlab = [T(v) for v in prob.video], T(prob.video_vocab), T(prob.tvg_video_labels)
-        t2v_iv2, v2t_iv2 = prob.t2v_sims, prob.v2t_sims
-        vids = [str(j) for j in range(len(video))]
-        model.set_tvg_prefix_length(prob.tvg_prefix_length)
-        vtg_ids, vtg_lab, vtg_msk, tvg_ids, tvg_lab, tvg_msk = (rows(x) for x in (vtg_ids, vtg_lab, vtg_msk, tvg_ids, tvg_lab, tvg_msk))
-    else:
-        from .checkpoint import load_checkpoint
-        from .dataloader import RetrievalDataset
-        from .main import dims_from_config, load_tokenizer
-        tok = load_tokenizer(args.model_path)
-        dims = dims_from_config(args.model_path, args.num_clips)
-        cfg_json = json.load(open(os.path.join(args.model_path, "config.json")))
-        model = BlimModel(dims, dtype=args.dtype, tokenizer_model_max_length=cfg_json.get("tokenizer_model_max_length"))
-        load_checkpoint(model.engine, dims, args.model_path, args.resume or None, lora_r=args.lora_r, lora_alpha=args.lora_alpha)
-        args.eval = True
-        ds = RetrievalDataset(args, tokenizer=tok, split="test")
-        items = [ds[i] for i in range(len(ds))]
-        video = [it["video"] for it in items]
-        vids = [it["vid"] for it in items]
-        vtg_ids, vtg_lab, vtg_msk = [it["vtg_ids"] for it in items], [it["vtg_labels"] for it in items], [it["vtg_masks"] for it in items]
-        tvg_ids, tvg_lab, tvg_msk = [it["tvg_ids"] for it in items], [it["tvg_labels"] for it in items], [it["tvg_masks"] for it in items]
-        from .dataloader import DEFAULT_IMAGE_TOKEN, TVG_PROMPT, VTG_PROMPTS
-        for q in args.query:                      # free text: the dataset's own prompt builder
-            a = ds._ids_labels(f"{DEFAULT_IMAGE_TOKEN}\n{VTG_PROMPTS[ds.dataset]}", q)
-            b = ds._ids_labels(f"{TVG_PROMPT}\nCaption: {q}", DEFAULT_IMAGE_TOKEN)
-            vtg_ids.append(a[0]); vtg_lab.append(a[1]); vtg_msk.append(a[2]); tvg_ids.append(b[0]); tvg_lab.append(b[1]); tvg_msk.append(b[2])
-        vocab, vlab = ds.video_vocab, torch.tensor([it["tvg_video_labels"] for it in items])
-        model.set_tvg_prefix_length(ds.tvg_prefix_length)
-        finetuned_ = bool(args.resume)
-        first = torch.load(f"./scores/{args.dataset.lower()}{'' if finetuned_ else '_zeroshot'}.pth", weights_only=True) if args.candidates == "iv2" else None
-        t2v_iv2 = None if first is None else first["t2v"].numpy()
-        v2t_iv2 = None if first is None else first["v2t"].numpy()
-    if getattr(args, "narrow_gemm", "off") == "auto":
-        model.engine.set_option("narrow_gemm", 1)
-    if getattr(args, "narrow_lo6", "off") == "auto":
-        model.engine.set_option("narrow_lo6", 1)
-    if getattr(args, "narrow_qkv", "off") == "auto":
-        model.engine.set_option("narrow_qkv", 1)
+        p.tok = types.SimpleNamespace(pad_token_id=synth.PAD_ID)
+        p.vtg = [[T(r) for r in x] for x in (prob.vtg_ids, prob.vtg_labels, prob.vtg_masks)]
+        p.tvg = [[T(r) for r in x] for x in (prob.tvg_ids, prob.tvg_labels, prob.tvg_masks)]
+        p.video, p.vocab, p.vlab = [T(v) for v in prob.video], T(prob.video_vocab), T(prob.tvg_video_labels)
+        p.t2v_iv2, p.v2t_iv2 = prob.t2v_sims, prob.v2t_sims
+        p.vids = [str(j) for j in range(len(p.video))]
+        p.model.set_tvg_prefix_length(prob.tvg_prefix_length)
+        return p
+    from .checkpoint import load_checkpoint
+    from .dataloader import DEFAULT_IMAGE_TOKEN, TVG_PROMPT, VTG_PROMPTS, RetrievalDataset
+    from .main import dims_from_config, load_tokenizer
+    p.tok = load_tokenizer(args.model_path)
+    dims = dims_from_config(args.model_path, args.num_clips)
+    cfg_json = json.load(open(os.path.join(args.model_path, "config.json")))
+    p.model = BlimModel(dims, dtype=args.dtype, tokenizer_model_max_length=cfg_json.get("tokenizer_model_max_length"))
+    load_checkpoint(p.model.engine, dims, args.model_path, args.resume or None, lora_r=args.lora_r, lora_alpha=args.lora_alpha)
+    args.eval = True
+    ds = RetrievalDataset(args, tokenizer=p.tok, split="test")
+    items = [ds[i] for i in range(len(ds))]
+    p.video, p.vids = [it["video"] for it in items], [it["vid"] for it in items]
+    p.vtg = [[it[k] for it in items] for k in ("vtg_ids", "vtg_labels", "vtg_masks")]
+    p.tvg = [[it[k] for it in items] for k in ("tvg_ids", "tvg_labels", "tvg_masks")]
+    # free text: the dataset's own prompt builder -> its (vtg, tvg) rows, (ids, labels, masks) each
+    prompts = lambda q: (ds._ids_labels(f"{DEFAULT_IMAGE_TOKEN}\n{VTG_PROMPTS[ds.dataset]}", q), ds._ids_labels(f"{TVG_PROMPT}\nCaption: {q}", DEFAULT_IMAGE_TOKEN))
+    for q in args.query:
+        for rows, row in zip((p.vtg, p.tvg), prompts(q)):
+            for column, x in zip(rows, row):
+                column.append(x)
+    unpad = lambda r: (np.asarray(r[0])[np.asarray(r[2]) != 0], np.asarray(r[1])[np.asarray(r[2]) != 0])
+    p.build_rows = lambda q: tuple(unpad(r) for r in prompts(q))
+    p.vocab, p.vlab = ds.video_vocab, torch.tensor([it["tvg_video_labels"] for it in items])
+    p.model.set_tvg_prefix_length(ds.tvg_prefix_length)
+    first = torch.load(f"./scores/{args.dataset.lower()}{'' if args.resume else '_zeroshot'}.pth", weights_only=True) if args.candidates == "iv2" else None
+    p.t2v_iv2 = None if first is None else first["t2v"].numpy()
+    p.v2t_iv2 = None if first is None else first["v2t"].numpy()
+    return p
+
+
+def build_scorer(args, p):
+    """The command's numeric options on p.model, p's rows padded -> the PairScorer over p's videos and texts."""
+    from . import retrieval_utils as RU
+    from .modeling import DDPLike
+    model = p.model
+    for flag in NARROW_GEMMS:
+        if getattr(args, flag) == "auto":
+            model.engine.set_option(flag, 1)
     if model.engine.can_precise:
         model.tvg_precise = args.tvg_precise
         model.vtg_precise = None if args.vtg_precise == "none" else args.vtg_precise
         if args.second_pass:
             model.second_pass = args.second_pass
-    vtg = RU.padding_ids(vtg_ids, vtg_lab, vtg_msk, tok)
-    tvg = RU.padding_ids(tvg_ids, tvg_lab, tvg_msk, tok)
-    scorer = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], video, vocab, vlab, args.num_clips, max_tokens=args.max_tokens)
-    budget = None if args.gallery_gb is None else int(args.gallery_gb * 2**30)
-    host = None if args.gallery_host_gb is None else int(args.gallery_host_gb * 2**30)
-    n_dataset = len(video)
-    if getattr(args, "query_video", None):       # v2t: videos outside the dataset join the scorer before the indexes are built; they share one vocabulary
-        try:
-            scorer.add_videos(query_video_features(args.query_video, args))
-        except ValueError as e:
-            raise SystemExit(f"search: --query_video: {e}") from None
-        vids = list(vids) + [os.path.basename(f) for f in args.query_video]
-    gal = GalleryIndex(scorer, budget_bytes=budget, fill=args.gallery_fill, host_budget_bytes=host, spare_slots=getattr(args, "gallery_spare", 0))
-    if args.direction == "v2t":
-        args.video_ids = list(args.video_ids) + list(range(n_dataset, len(vids)))
-        return _main_v2t(args, model, scorer, gal, v2t_iv2, vids, len(tvg_ids), t0)
-    gal.build(first_stage=None if t2v_iv2 is None else np.ascontiguousarray(np.asarray(t2v_iv2, dtype=np.float32).T))     # v2t first stage: calibration sample
-    print(f"gallery: {len(video)} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'} of {gal.cache.bytes // max(gal.n_slots, 1) if gal.cache else 0} bytes, "
-          f"mode {scorer.vtg_mode or 'none'}, narrow_gemm {getattr(args, 'narrow_gemm', 'off')}, narrow_lo6 {getattr(args, 'narrow_lo6', 'off')}, narrow_qkv {getattr(args, 'narrow_qkv', 'off')}, built in {gal.build_seconds:.2f}s (ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
-    if getattr(args, "serve", False):
-        build_rows = None
-        if not args.synthetic:                    # free text: the dataset's own prompt builder, as --query above
-            unpad = lambda r: (np.asarray(r[0])[np.asarray(r[2]) != 0], np.asarray(r[1])[np.asarray(r[2]) != 0])
-            build_rows = lambda q: (unpad(ds._ids_labels(f"{DEFAULT_IMAGE_TOKEN}\n{VTG_PROMPTS[ds.dataset]}", q)),
-                                    unpad(ds._ids_labels(f"{TVG_PROMPT}\nCaption: {q}", DEFAULT_IMAGE_TOKEN)))
-        out = open(args.output, "w") if args.output else None
+    vtg, tvg = RU.padding_ids(*p.vtg, p.tok), RU.padding_ids(*p.tvg, p.tok)
+    return RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], p.video, p.vocab, p.vlab, args.num_clips, max_tokens=args.max_tokens)
 
-        def write(line):
-            print(line, flush=True)
-            if out:
-                out.write(line + "\n")
-        from .engine import hash_device
-        content_hash = lambda feat: hash_device(feat.contiguous().to(model.device))      # (one upload and one pass over a feature tensor: a fraction of the projection that follows)
-        featuriser = FrameFeaturiser(args)         # (the tower is created when the first add_video request brings frames)
-        server = Server(gal, vids, len(vtg_ids), t2v_iv2, args, finetuned=bool(args.resume), build_rows=build_rows, content_hash=content_hash, featuriser=featuriser)
-        summary = serve(sys.stdin, write, server, args.batch_queries, args.batch_wait_ms)
-        featuriser.close()
-        if out:
-            out.close()
-        print(f"gallery stats: {json.dumps(gal.stats.as_dict())}", file=sys.stderr, flush=True)
-        if gal.host is not None:
-            print(f"gallery host tier: {json.dumps(dict(gal.host.stats.as_dict(), records=gal.host.n_records, record_bytes=gal.host.record_bytes))}", file=sys.stderr, flush=True)
-        print(f"serve: {json.dumps(summary)}", file=sys.stderr, flush=True)
-        if gal.shortlist_stats["passes"]:
-            print(f"shortlist: {json.dumps(_shortlist_line(gal.shortlist_stats))}", file=sys.stderr, flush=True)
-        if getattr(gal, "prefilter_stats", {"passes": 0})["passes"]:
-            print(f"prefilter: {json.dumps(_prefilter_line(gal.prefilter_stats))}", file=sys.stderr, flush=True)
-        gal.close()
-        model.engine.close()
-        return 0
-    n_ds = len(vtg_ids) - len(args.query)
-    texts = list(args.query_ids) + list(range(n_ds, len(vtg_ids)))
-    names = [f"caption:{i}" for i in args.query_ids] + [f"query:{q}" for q in args.query]
-    N = len(video)
-    k = min(args.topk, N)
-    finetuned = bool(args.resume)
-    out = open(args.output, "w") if args.output else None
-    for t, name in zip(texts, names):
-        more = {}
-        if args.candidates == "tvg":              # the gallery ranked by the TVG candidate term, the best K reranked; the answer is the best --topk of those
-            K, K0 = shortlist_k(args), getattr(args, "prefilter", None)
-            (o, b), = gal.search_requests([(t, None, None, K) + (() if K0 is None else (K0,))], cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
-            order, blended, more = o[None, :k], b[None, :k], {"shortlisted": K, **({} if K0 is None else {"prefiltered": K0})}
-        else:
-            if args.candidates == "iv2":
-                row = np.asarray(t2v_iv2[t], dtype=np.float32)
-                cand = np.argsort(-row, kind="stable")[:k][None]
-                fs = row[cand]
-            else:
-                cand = np.arange(N)[None]
-                fs = None if t2v_iv2 is None else np.asarray(t2v_iv2[t], dtype=np.float32)[cand] if t < n_ds else None
-            order, blended = gal.rerank([t], cand, first_stage=fs, cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
-        line = json.dumps({"query": name, "videos": [vids[int(j)] for j in order[0]], "scores": [float(x) for x in blended[0]], **more})
-        print(line, flush=True)
-        if out:
-            out.write(line + "\n")
-    if out:
-        out.close()
-    print(f"gallery stats: {json.dumps(gal.stats.as_dict())}", file=sys.stderr, flush=True)
-    if gal.shortlist_stats["passes"]:
-        print(f"shortlist: {json.dumps(_shortlist_line(gal.shortlist_stats))}", file=sys.stderr, flush=True)
-    if getattr(gal, "prefilter_stats", {"passes": 0})["passes"]:
-        print(f"prefilter: {json.dumps(_prefilter_line(gal.prefilter_stats))}", file=sys.stderr, flush=True)
-    if gal.host is not None:
-        print(f"gallery host tier: {json.dumps(dict(gal.host.stats.as_dict(), records=gal.host.n_records, record_bytes=gal.host.record_bytes))}", file=sys.stderr, flush=True)
-    gal.close()
-    model.engine.close()
-    return 0
+
+def build_indexes(args, scorer, p):
+    """-> [("gallery", GalleryIndex)], built; under --direction v2t followed by ("text gallery", TextGalleryIndex) over the same video cache."""
+    import numpy as np
+
+    from .gallery import GalleryIndex, TextGalleryIndex
+    gb = lambda x: None if x is None else int(x * 2**30)
+    gal = GalleryIndex(scorer, budget_bytes=gb(args.gallery_gb), fill=args.gallery_fill, host_budget_bytes=gb(args.gallery_host_gb), spare_slots=args.gallery_spare)
+    if args.direction == "t2v":
+        gal.build(first_stage=None if p.t2v_iv2 is None else np.ascontiguousarray(np.asarray(p.t2v_iv2, dtype=np.float32).T))     # v2t first stage: calibration sample
+        return [("gallery", gal)]
+    first = None if p.v2t_iv2 is None else np.ascontiguousarray(np.asarray(p.v2t_iv2, dtype=np.float32))
+    gal.build(first_stage=first)
+    tg = TextGalleryIndex(scorer, budget_bytes=gb(args.text_gallery_gb), video_index=gal, fill=args.gallery_fill, host_budget_bytes=gb(args.text_gallery_host_gb))
+    if args.resume:                                   # a zero-shot blend has no TVG term: no caption cache
+        tg.build(first_stage=first)
+    return [("gallery", gal), ("text gallery", tg)]
+
+
+def gallery_banner(args, indexes, ready: float) -> str:
+    """The `gallery:` stderr line, once the indexes are built: the video cache, under v2t the caption cache too."""
+    gal, s = indexes[0][1], indexes[0][1].s
+    narrow = ", ".join(f"{flag} {getattr(args, flag)}" for flag in NARROW_GEMMS)
+    head = f"gallery: {len(s.video)} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'}"
+    ready = f"(ready {ready:.1f}s after start)"
+    if len(indexes) == 1:
+        return (f"{head} of {gal.cache.bytes // max(gal.n_slots, 1) if gal.cache else 0} bytes, mode {s.vtg_mode or 'none'}, {narrow}, "
+                f"built in {gal.build_seconds:.2f}s {ready}")
+    tg = indexes[1][1]
+    return (f"{head}, mode {s.vtg_mode or 'none'}, built in {gal.build_seconds:.2f}s; {len(s.tvg_split)} texts, {tg.n_slots} caption slots of {tg.per_slot_bytes()} bytes, "
+            f"tvg mode {s.tvg_mode}, {narrow}, built in {tg.build_seconds:.2f}s {ready}")
+
+
+def report_lines(indexes, serve_summary=None, shortlist_stats=None, prefilter_stats=None):
+    """The closing stderr lines of a run over `indexes` ([(name, index)]: "gallery", and "text gallery" under v2t), in one order: what the caches did, what their
+    host tiers did (where there is one), `serve:`, `shortlist:` and `prefilter:` (where a pass of theirs ran)."""
+    tier = lambda h: json.dumps(dict(h.stats.as_dict(), records=h.n_records, record_bytes=h.record_bytes))
+    lines = ["; ".join(f"{name} stats: {json.dumps(ix.stats.as_dict())}" for name, ix in indexes)]
+    if any(ix.host is not None for _, ix in indexes):
+        lines.append("; ".join(f"{name} host tier: {tier(ix.host)}" for name, ix in indexes if ix.host is not None))
+    if serve_summary is not None:
+        lines.append(f"serve: {json.dumps(serve_summary)}")
+    if shortlist_stats is not None and shortlist_stats["passes"]:
+        lines.append(f"shortlist: {json.dumps(_shortlist_line(shortlist_stats))}")
+    if prefilter_stats is not None and prefilter_stats["passes"]:
+        lines.append(f"prefilter: {json.dumps(_prefilter_line(prefilter_stats))}")
+    return lines
 
 
 def _shortlist_line(stats):
@@ -833,62 +815,110 @@ def _prefilter_line(stats):
     return {"queries": int(stats["queries"]), "stage0_passes": int(stats["passes"]), "stage0_rows": int(stats["rows"]), "kept": int(stats["kept"])}
 
 
-def _main_v2t(args, model, scorer, gal, v2t_iv2, vids, n_texts: int, t0: float) -> int:
-    """Video queries over the captions: the VTG leg from the video cache, the fine-tuned TVG leg from the caption-prompt cache."""
-    import numpy as np
+def output_writer(path):
+    """-> (write(line): the line to stdout, flushed, and to the --output file when there is one; close())."""
+    out = open(path, "w") if path else None
 
-    from .gallery import TextGalleryIndex
-    n_videos = len(vids)
-    first = None if v2t_iv2 is None else np.ascontiguousarray(np.asarray(v2t_iv2, dtype=np.float32))
-    gal.build(first_stage=first)
-    finetuned = bool(args.resume)
-    tbudget = None if args.text_gallery_gb is None else int(args.text_gallery_gb * 2**30)
-    thost = None if args.text_gallery_host_gb is None else int(args.text_gallery_host_gb * 2**30)
-    tg = TextGalleryIndex(scorer, budget_bytes=tbudget, video_index=gal, fill=args.gallery_fill, host_budget_bytes=thost)
-    if finetuned:                                     # a zero-shot blend has no TVG term: no caption cache
-        tg.build(first_stage=first)
-    print(f"gallery: {n_videos} videos, fill {gal.fill}, {gal.n_slots} {'slots' if gal.fill == 'lazy' else 'cached slots'}, mode {scorer.vtg_mode or 'none'}, built in {gal.build_seconds:.2f}s; "
-          f"{n_texts} texts, {tg.n_slots} caption slots of {tg.per_slot_bytes()} bytes, tvg mode {scorer.tvg_mode}, narrow_gemm {getattr(args, 'narrow_gemm', 'off')}, narrow_lo6 {getattr(args, 'narrow_lo6', 'off')}, narrow_qkv {getattr(args, 'narrow_qkv', 'off')}, built in {tg.build_seconds:.2f}s "
-          f"(ready {time.time() - t0:.1f}s after start)", file=sys.stderr, flush=True)
-    bad = [v for v in args.video_ids if not 0 <= v < n_videos]
-    if bad:
-        raise SystemExit(f"search: --video_ids {bad} outside 0 .. {n_videos - 1}")
-    k = min(args.topk, n_texts)
-    out = open(args.output, "w") if args.output else None
-    shortlisted = {"queries": 0, "passes": 0, "pairs": 0}
-    for v in args.video_ids:
-        more = {}
-        if args.candidates == "tvg":              # the captions ranked by the query likelihood over the cached prompts, the best K reranked
-            K = shortlist_k(args)
-            order, blended = tg.rerank_shortlist([v], K, cpn=args.cpn, alpha=args.alpha, c=args.c)
-            order, blended, more = order[:, :k], blended[:, :k], {"shortlisted": K}
-            shortlisted = {"queries": shortlisted["queries"] + 1, "passes": shortlisted["passes"] + 1, "pairs": shortlisted["pairs"] + n_texts}
-        else:
-            if args.candidates == "iv2":
-                row = np.asarray(v2t_iv2[v], dtype=np.float32)
-                cand = np.argsort(-row, kind="stable")[:k][None]
-                fs = row[cand]
-            else:
-                cand = np.arange(n_texts)[None]
-                fs = None if v2t_iv2 is None or v >= len(v2t_iv2) else np.asarray(v2t_iv2[v], dtype=np.float32)[cand]     # (--query_video: no first-stage row)
-            order, blended = tg.rerank([v], cand, first_stage=fs, cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=finetuned)
-        line = json.dumps({"query": f"video:{vids[v]}", "texts": [int(i) for i in order[0]], "scores": [float(x) for x in blended[0]], **more})
+    def write(line):
         print(line, flush=True)
         if out:
             out.write(line + "\n")
-    if out:
-        out.close()
-    if shortlisted["passes"]:
-        print(f"shortlist: {json.dumps(_shortlist_line(shortlisted))}", file=sys.stderr, flush=True)
-    print(f"gallery stats: {json.dumps(gal.stats.as_dict())}; text gallery stats: {json.dumps(tg.stats.as_dict())}", file=sys.stderr, flush=True)
-    tiers = [(name, ix.host) for name, ix in (("gallery", gal), ("text gallery", tg)) if ix.host is not None]
-    if tiers:
-        print("; ".join(f"{name} host tier: {json.dumps(dict(h.stats.as_dict(), records=h.n_records, record_bytes=h.record_bytes))}" for name, h in tiers), file=sys.stderr, flush=True)
-    tg.close()
-    gal.close()
-    model.engine.close()
+    return write, (out.close if out else lambda: None)
+
+
+def run_serve(gal, vids, t2v_iv2, args, write, lines, build_rows=None, content_hash=None):
+    """--serve: the request lines answered through `write` until they end -> the counts of the `serve:` line."""
+    featuriser = FrameFeaturiser(args)             # (the tower is created when the first add_video request brings frames)
+    server = Server(gal, vids, len(gal.s.vtg_split), t2v_iv2, args, finetuned=bool(args.resume), build_rows=build_rows, content_hash=content_hash, featuriser=featuriser)
+    summary = serve(lines, write, server, args.batch_queries, args.batch_wait_ms)
+    featuriser.close()
+    return summary
+
+
+def run_t2v(gal, vids, t2v_iv2, args, write) -> None:
+    """The one-shot text queries (--query_ids, then one text per --query at the end of the scorer's texts), one answer line each."""
+    from .gallery import SearchRequest
+    n_texts, N = len(gal.s.vtg_split), len(vids)
+    n_ds = n_texts - len(args.query)
+    names = [f"caption:{i}" for i in args.query_ids] + [f"query:{q}" for q in args.query]
+    blend = dict(cpn=args.cpn, alpha=args.alpha, c=args.c, finetuned=bool(args.resume))
+    for t, name in zip(list(args.query_ids) + list(range(n_ds, n_texts)), names):
+        K = K0 = None
+        if args.candidates == "tvg":              # the gallery ranked by the TVG candidate term, the best K reranked; the answer is the best --topk of those
+            K, K0 = shortlist_k(args), args.prefilter
+            (order, blended), = gal.search_requests([SearchRequest(t, shortlist=K, prefilter=K0)], **blend)
+            order, blended = order[:min(args.topk, N)], blended[:min(args.topk, N)]
+        else:
+            cand, fs = default_candidates(args.candidates, t2v_iv2[t] if t2v_iv2 is not None and t < n_ds else None, N, args.topk)
+            order, blended = (x[0] for x in gal.rerank([t], cand[None], first_stage=None if fs is None else fs[None], **blend))
+        write(answer_line(name, "videos", [vids[int(j)] for j in order], blended, K, K0))
+
+
+def run_v2t(tg, vids, v2t_iv2, args, write):
+    """The one-shot video queries (--video_ids) over the captions: the VTG leg from the video cache, the fine-tuned TVG leg from the caption-prompt cache; one
+    answer line each -> the shortlist's counts, as GalleryIndex.shortlist_stats keeps them."""
+    n_texts = len(tg.s.tvg_split)
+    k = min(args.topk, n_texts)
+    blend = dict(cpn=args.cpn, alpha=args.alpha, c=args.c)
+    shortlisted = {"queries": 0, "passes": 0, "pairs": 0}
+    for v in args.video_ids:
+        K = None
+        if args.candidates == "tvg":              # the captions ranked by the query likelihood over the cached prompts, the best K reranked
+            K = shortlist_k(args)
+            order, blended = (x[0, :k] for x in tg.rerank_shortlist([v], K, **blend))
+            shortlisted = {"queries": shortlisted["queries"] + 1, "passes": shortlisted["passes"] + 1, "pairs": shortlisted["pairs"] + n_texts}
+        else:                                     # (--query_video: no first-stage row)
+            cand, fs = default_candidates(args.candidates, v2t_iv2[v] if v2t_iv2 is not None and v < len(v2t_iv2) else None, n_texts, args.topk)
+            order, blended = (x[0] for x in tg.rerank([v], cand[None], first_stage=None if fs is None else fs[None], finetuned=bool(args.resume), **blend))
+        write(answer_line(f"video:{vids[v]}", "texts", [int(i) for i in order], blended, K))
+    return shortlisted
+
+
+def main(args):
+    import os
+
+    import torch                                  # noqa: F401  (with the package's modules, loaded before the clock starts: `ready ...s after start` counts the work)
+
+    from . import gallery, modeling, retrieval_utils, synth      # noqa: F401
+
+    check_args(args, int(os.environ.get("WORLD_SIZE", "1")))
+    t0 = time.time()
+    p = build_problem(args)
+    scorer = build_scorer(args, p)
+    vids, n_dataset, v2t = p.vids, len(p.video), args.direction == "v2t"
+    if args.query_video:                          # v2t: videos outside the dataset join the scorer before the indexes are built; they share one vocabulary
+        try:
+            scorer.add_videos(query_video_features(args.query_video, args))
+        except ValueError as e:
+            raise SystemExit(f"search: --query_video: {e}") from None
+        vids = list(vids) + [os.path.basename(f) for f in args.query_video]
+    indexes = build_indexes(args, scorer, p)
+    gal = indexes[0][1]
+    print(gallery_banner(args, indexes, time.time() - t0), file=sys.stderr, flush=True)
+    if v2t:
+        args.video_ids = list(args.video_ids) + list(range(n_dataset, len(vids)))
+        bad = [v for v in args.video_ids if not 0 <= v < len(vids)]
+        if bad:
+            raise SystemExit(f"search: --video_ids {bad} outside 0 .. {len(vids) - 1}")
+    write, close_output = output_writer(args.output)
+    summary, shortlisted, prefiltered = None, gal.shortlist_stats, gal.prefilter_stats
+    if args.serve:
+        from .engine import hash_device
+        content_hash = lambda feat: hash_device(feat.contiguous().to(p.model.device))      # (one upload and one pass over a feature tensor: a fraction of the projection that follows)
+        summary = run_serve(gal, vids, p.t2v_iv2, args, write, sys.stdin, p.build_rows, content_hash)
+    elif v2t:
+        shortlisted, prefiltered = run_v2t(indexes[1][1], vids, p.v2t_iv2, args, write), None
+    else:
+        run_t2v(gal, vids, p.t2v_iv2, args, write)
+    close_output()
+    for line in report_lines(indexes, summary, shortlisted, prefiltered):
+        print(line, file=sys.stderr, flush=True)
+    for _, ix in reversed(indexes):
+        ix.close()
+    p.model.engine.close()
     return 0
 
 
 if __name__ == "__main__":
     sys.exit(main(get_args_parser().parse_args()))
+
