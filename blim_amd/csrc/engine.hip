@@ -1594,6 +1594,23 @@ extern "C" int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* e
 // blim_score_tvg up to the visual head over the n_rows + n_prior named rows, the clip-0 logits alone against the registered vocabulary -- the c = 0 launch of
 // tvg_logits_impl with the rows contiguous: a GEMM row does not depend on the rows beside it -- and the rank kernel over the two row blocks
 static int tvg_rank_check_k(int32_t k, int32_t n_vocab);
+// the clip-0 logits of the R visual-head rows in e->vh against the registered vocabulary -> e->tvg_logits [R, n_vocab] (the one statement of them: both callers below)
+static int tvg_first_logits(blim_engine* e, int64_t R, hipStream_t s) {
+    const int N = e->n_vocab, M = e->c.mm_hidden_size;
+    TRY(ensure(e->tvg_logits, (size_t)R * N * 4));
+    float* lg = (float*)e->tvg_logits.p;
+    SpanGuard g(e, s, TC_GEMM_OTHER, 2.0 * R * (double)M * N * (e->precise ? 3 : 1));
+    GemmParams p;
+    if (e->precise) {
+        TRY(ensure(e->vh3, (size_t)round_up(R, 256) * 3 * M * 2));
+        TRY(launch_split3_hilo((uint16_t*)e->vh3.p, (const uint16_t*)e->vh.p, 2 * (int64_t)M, R, M, s));
+        p = gp(e->c.compute_dtype, e->vh3.p, 3 * (int64_t)M, e->vocab3.p, R, N, 3 * M, lg, N);
+    } else {
+        p = gp(e->c.compute_dtype, e->vh.p, M, e->vocab1.p, R, N, M, lg, N);
+    }
+    p.scale = 1.0f / sqrtf((float)M);
+    return launch_gemm(EPI_F32, p, s);
+}
 extern "C" int blim_score_tvg_first(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, int32_t n_rows, const int32_t* prior_rows, int32_t n_prior,
                                     const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, void* stream) {
     ARG_CHECK(e && rows && idx_out && val_out && n_rows > 0 && n_prior >= 0 && (prior_rows || n_prior == 0));
@@ -1614,23 +1631,49 @@ extern "C" int blim_score_tvg_first(blim_engine* e, const blim_batch* b, const v
     }
     TRY(decode_impl(e, b, embeds, all, R, e->hsel.p, e->precise, nullptr, stream));
     TRY(visual_head_impl(e, e->hsel.p, e->precise, R, e->vh.p, stream));
-    TRY(ensure(e->tvg_logits, (size_t)R * N * 4));
-    float* lg = (float*)e->tvg_logits.p;
-    {
-        SpanGuard g(e, s, TC_GEMM_OTHER, 2.0 * R * (double)M * N * (e->precise ? 3 : 1));
-        GemmParams p;
-        if (e->precise) {
-            TRY(ensure(e->vh3, (size_t)round_up(R, 256) * 3 * M * 2));
-            TRY(launch_split3_hilo((uint16_t*)e->vh3.p, (const uint16_t*)e->vh.p, 2 * (int64_t)M, R, M, s));
-            p = gp(e->c.compute_dtype, e->vh3.p, 3 * (int64_t)M, e->vocab3.p, R, N, 3 * M, lg, N);
-        } else {
-            p = gp(e->c.compute_dtype, e->vh.p, M, e->vocab1.p, R, N, M, lg, N);
-        }
-        p.scale = 1.0f / sqrtf((float)M);
-        TRY(launch_gemm(EPI_F32, p, s));
-    }
+    TRY(tvg_first_logits(e, R, s));
+    const float* lg = (const float*)e->tvg_logits.p;
     SpanGuard g(e, s, TC_MISC, 0);
     return launch_tvg_rank(lg, N, N, n_rows, lg + (int64_t)n_rows * N, N, n_prior, prior_of, alpha, k, idx_out, val_out, logprob_out, N, s);
+}
+// The cached counterpart for the other direction: the caption prompts' last rows are the slots' stored hidden rows, so the clip-0 log-probabilities of the named
+// vocabulary entries given every slot's prompt need no decode -- per chunk of slots the gather, the visual head, tvg_first_logits and the column kernel
+static int tvg_first_chunk_rows(int32_t n_vocab) {
+    const int64_t rows = ((int64_t)256 << 20) / (4 * (int64_t)n_vocab);         // the logits workspace stays within 256 MiB
+    return (int)(std::max<int64_t>(256, std::min<int64_t>(rows, 1 << 30)) / 256 * 256);
+}
+extern "C" int blim_tvg_first_cached(blim_engine* e, blim_prefix_cache* pc, const int32_t* slots, int32_t n_slots, const int32_t* cols, int32_t n_cols, float* out,
+                                     int64_t ld_out, int32_t chunk_rows, void* stream) {
+    if (!e || !pc || !slots || !cols || !out) {
+        blim_set_error("blim_tvg_first_cached: %s is null", !e ? "e" : !pc ? "pc" : !slots ? "slots" : !cols ? "cols" : "out");
+        return BLIM_ERR_ARG;
+    }
+    if (e->f8) { blim_set_error("blim_tvg_first_cached: fp8 engines are not supported"); return BLIM_ERR_STATE; }
+    if (pc->e != e) { blim_set_error("blim_tvg_first_cached: pc belongs to another engine"); return BLIM_ERR_ARG; }
+    if (n_slots < 1) { blim_set_error("blim_tvg_first_cached: n_slots = %d < 1", n_slots); return BLIM_ERR_ARG; }
+    if (n_cols < 1) { blim_set_error("blim_tvg_first_cached: n_cols = %d < 1", n_cols); return BLIM_ERR_ARG; }
+    if (ld_out < n_slots) { blim_set_error("blim_tvg_first_cached: ld_out = %lld below n_slots = %d", (long long)ld_out, n_slots); return BLIM_ERR_ARG; }
+    if (chunk_rows < 0 || chunk_rows % 256) { blim_set_error("blim_tvg_first_cached: chunk_rows = %d is not 0 or a multiple of 256", chunk_rows); return BLIM_ERR_ARG; }
+    if (!e->vocab3.p) { blim_set_error("no video vocabulary registered (blim_set_video_vocab)"); return BLIM_ERR_STATE; }
+    const int N = e->n_vocab, H = e->c.hidden_size, M = e->c.mm_hidden_size;
+    const int chunk = chunk_rows ? chunk_rows : tvg_first_chunk_rows(N);
+    hipStream_t s = (hipStream_t)stream;
+    TRY(pc_check_read(e, pc, slots, n_slots));                     // every slot of every chunk, before anything is launched
+    std::vector<int32_t> neg((size_t)n_slots);
+    for (int q = 0; q < n_slots; ++q) neg[q] = -(slots[q] + 1);    // the gather's name of a cached row
+    for (int q0 = 0; q0 < n_slots; q0 += chunk) {
+        const int R = std::min(chunk, n_slots - q0);
+        TRY(reserve_rows(e, R));
+        TRY(ensure(e->vh, (size_t)round_up(R, 256) * M * 2 * (e->precise ? 2 : 1)));
+        int32_t* rows = (int32_t*)e->lab_logit.p;                  // R ints reserved above, idle in a TVG call
+        HIP_TRY(hipMemcpyAsync(rows, neg.data() + q0, (size_t)R * 4, hipMemcpyHostToDevice, s));
+        TRY(pc_gather_rows(e, pc, rows, R, H, s));
+        TRY(visual_head_impl(e, e->hsel.p, e->precise, R, e->vh.p, stream));
+        TRY(tvg_first_logits(e, R, s));
+        SpanGuard g(e, s, TC_MISC, 0);
+        TRY(launch_tvg_cols((const float*)e->tvg_logits.p, N, N, R, cols, n_cols, out, ld_out, q0, s));
+    }
+    return BLIM_OK;
 }
 extern "C" int blim_score_tvg_cached(blim_engine* e, blim_prefix_cache* pc, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
                                      const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab, const int32_t* labels, int32_t n_pairs,
@@ -1749,6 +1792,25 @@ extern "C" int blim_tvg_rank(const float* logits, int64_t ld, int32_t n_vocab, i
     if (prior_logits && ld_prior < n_vocab) { blim_set_error("tvg_rank: ld_prior = %lld below n_vocab = %d", (long long)ld_prior, n_vocab); return BLIM_ERR_ARG; }
     if (logprob_out && ld_out < n_vocab) { blim_set_error("tvg_rank: ld_out = %lld below n_vocab = %d", (long long)ld_out, n_vocab); return BLIM_ERR_ARG; }
     return launch_tvg_rank(logits, ld, n_vocab, n_rows, prior_logits, ld_prior, n_prior, prior_of, alpha, k, idx_out, val_out, logprob_out, ld_out, (hipStream_t)stream);
+}
+extern "C" int blim_rank_rows(const float* values, int64_t ld, int32_t n, int32_t n_rows, int32_t k, int32_t* idx_out, float* val_out, void* stream) {
+    if (!values || !idx_out || !val_out) { blim_set_error("rank_rows: %s is null", !values ? "values" : !idx_out ? "idx_out" : "val_out"); return BLIM_ERR_ARG; }
+    if (n < 1) { blim_set_error("rank_rows: n = %d < 1", n); return BLIM_ERR_ARG; }
+    if (n_rows < 1) { blim_set_error("rank_rows: n_rows = %d < 1", n_rows); return BLIM_ERR_ARG; }
+    TRY(tvg_rank_check_k(k, n));
+    if (ld < n) { blim_set_error("rank_rows: ld = %lld below n = %d", (long long)ld, n); return BLIM_ERR_ARG; }
+    return launch_rank_rows(values, ld, n, n_rows, k, idx_out, val_out, (hipStream_t)stream);
+}
+extern "C" int blim_tvg_cols(const float* logits, int64_t ld, int32_t n_vocab, int32_t n_rows, const int32_t* cols, int32_t n_cols, float* out, int64_t ld_out,
+                             int64_t out0, void* stream) {
+    if (!logits || !cols || !out) { blim_set_error("tvg_cols: %s is null", !logits ? "logits" : !cols ? "cols" : "out"); return BLIM_ERR_ARG; }
+    if (n_vocab < 1) { blim_set_error("tvg_cols: n_vocab = %d < 1", n_vocab); return BLIM_ERR_ARG; }
+    if (n_rows < 1) { blim_set_error("tvg_cols: n_rows = %d < 1", n_rows); return BLIM_ERR_ARG; }
+    if (n_cols < 1) { blim_set_error("tvg_cols: n_cols = %d < 1", n_cols); return BLIM_ERR_ARG; }
+    if (ld < n_vocab) { blim_set_error("tvg_cols: ld = %lld below n_vocab = %d", (long long)ld, n_vocab); return BLIM_ERR_ARG; }
+    if (out0 < 0) { blim_set_error("tvg_cols: out0 = %lld < 0", (long long)out0); return BLIM_ERR_ARG; }
+    if (ld_out - out0 < n_rows) { blim_set_error("tvg_cols: ld_out = %lld below out0 + n_rows = %lld + %d", (long long)ld_out, (long long)out0, n_rows); return BLIM_ERR_ARG; }
+    return launch_tvg_cols(logits, ld, n_vocab, n_rows, cols, n_cols, out, ld_out, out0, (hipStream_t)stream);
 }
 extern "C" int blim_group_mean_rows(void* out, const void* in, int64_t n_out, int32_t group, int32_t H, int32_t dtype16, int32_t split, void* stream) {
     ARG_CHECK(dtype16 == BLIM_COMPUTE_BF16 || dtype16 == BLIM_COMPUTE_F16);

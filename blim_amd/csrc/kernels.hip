@@ -679,37 +679,19 @@ __device__ __forceinline__ float rank_lse(const float* row, int n_vocab, int lan
     sm = wave_sum(sm);
     return mx + logf(sm);
 }
-__global__ __launch_bounds__(256) void tvg_rank_kernel(const float* logits, int64_t ld, int n_vocab, const float* prior_logits, int64_t ld_prior, int n_prior,
-                                                       const int32_t* prior_of, float alpha, int k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out) {
+// The select and sort that tvg_rank_kernel and rank_rows share: the first k of the order above over the n terms rank_term(q, j) of one row, by all 256 threads of the
+// workgroup (every one of them calls it); idx_row / val_row [k].  Q names the term's source: RankRow, or GivenRow -- the caller's own values.
+struct GivenRow { const float* row; };
+__device__ __forceinline__ float rank_term(const GivenRow& q, int j) { return q.row[j]; }
+template <typename Q>
+__device__ __forceinline__ void rank_select(const Q& q, int n_vocab, int k, int32_t* idx_row, float* val_row) {
     __shared__ unsigned long long keys[TVG_RANK_MAX_K];
     __shared__ int hist[256];
-    __shared__ float tots[2];
     __shared__ uint32_t sel[2];
     __shared__ int wcnt[4];
     __shared__ int n_gt;
-    const int64_t r = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    RankRow q;
-    q.row = logits + r * ld;
-    const int po = prior_of ? prior_of[r] : -1;
-    q.mode = po < 0 ? 0 : po < n_prior ? 1 : 2;
-    q.prow = q.mode == 1 ? prior_logits + (int64_t)po * ld_prior : nullptr;
-    q.alpha = alpha;
-    if (w == 0) {
-        const float t = rank_lse(q.row, n_vocab, lane);
-        if (lane == 0) tots[0] = t;
-    } else if (w == 1 && q.mode == 1) {
-        const float t = rank_lse(q.prow, n_vocab, lane);
-        if (lane == 0) tots[1] = t;
-    }
-    if (tid == 0) n_gt = 0;
-    __syncthreads();
-    q.tot = tots[0];
-    q.ptot = q.mode == 1 ? tots[1] : 0.f;
-    if (logprob_out) {
-        float* lpo = logprob_out + r * ld_out;
-        for (int j = tid; j < n_vocab; j += 256) lpo[j] = q.row[j] - q.tot;
-    }
+    if (tid == 0) n_gt = 0;                                       // (read after the select's barriers)
     // ---- radix select: T (`prefix`) and how many columns with ord == T the top k holds (`need` >= 1); k - need columns lie above T
     uint32_t prefix = 0;
     int need = k;
@@ -795,9 +777,43 @@ __global__ __launch_bounds__(256) void tvg_rank_kernel(const float* logits, int6
     for (int i = tid; i < k; i += 256) {
         const int j = (int)~(uint32_t)keys[i];
         const bool ok = (uint32_t)j < (uint32_t)n_vocab;         // (always: every one of the k places received a column's key)
-        idx_out[r * k + i] = ok ? j : -1;
-        val_out[r * k + i] = ok ? rank_term(q, j) : __uint_as_float(0x7FC00000u);
+        idx_row[i] = ok ? j : -1;
+        val_row[i] = ok ? rank_term(q, j) : __uint_as_float(0x7FC00000u);
     }
+}
+__global__ __launch_bounds__(256) void tvg_rank_kernel(const float* logits, int64_t ld, int n_vocab, const float* prior_logits, int64_t ld_prior, int n_prior,
+                                                       const int32_t* prior_of, float alpha, int k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out) {
+    __shared__ float tots[2];
+    const int64_t r = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    RankRow q;
+    q.row = logits + r * ld;
+    const int po = prior_of ? prior_of[r] : -1;
+    q.mode = po < 0 ? 0 : po < n_prior ? 1 : 2;
+    q.prow = q.mode == 1 ? prior_logits + (int64_t)po * ld_prior : nullptr;
+    q.alpha = alpha;
+    if (w == 0) {
+        const float t = rank_lse(q.row, n_vocab, lane);
+        if (lane == 0) tots[0] = t;
+    } else if (w == 1 && q.mode == 1) {
+        const float t = rank_lse(q.prow, n_vocab, lane);
+        if (lane == 0) tots[1] = t;
+    }
+    __syncthreads();
+    q.tot = tots[0];
+    q.ptot = q.mode == 1 ? tots[1] : 0.f;
+    if (logprob_out) {
+        float* lpo = logprob_out + r * ld_out;
+        for (int j = tid; j < n_vocab; j += 256) lpo[j] = q.row[j] - q.tot;
+    }
+    rank_select(q, n_vocab, k, idx_out + r * k, val_out + r * k);
+}
+// rank_select over the caller's own values: one workgroup per row of values [n_rows, ld] f32, n values each; val_out holds the chosen values' own bits
+__global__ __launch_bounds__(256) void rank_rows(const float* values, int64_t ld, int n, int k, int32_t* idx_out, float* val_out) {
+    const int64_t r = blockIdx.x;
+    GivenRow q;
+    q.row = values + r * ld;
+    rank_select(q, n, k, idx_out + r * k, val_out + r * k);
 }
 int launch_tvg_rank(const float* logits, int64_t ld, int n_vocab, int n_rows, const float* prior_logits, int64_t ld_prior, int n_prior, const int32_t* prior_of,
                     float alpha, int k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, hipStream_t s) {
@@ -807,6 +823,41 @@ int launch_tvg_rank(const float* logits, int64_t ld, int n_vocab, int n_rows, co
     hipLaunchKernelGGL(tvg_rank_kernel, dim3(n_rows), dim3(256), 0, s, logits, ld, n_vocab, prior_logits, ld_prior, n_prior, prior_of, alpha, k, idx_out, val_out,
                        logprob_out, ld_out);
     LAUNCH_CHECK("tvg_rank");
+    return BLIM_OK;
+}
+
+int launch_rank_rows(const float* values, int64_t ld, int n, int n_rows, int k, int32_t* idx_out, float* val_out, hipStream_t s) {
+    ARG_CHECK(values && idx_out && val_out && n > 0 && n_rows > 0 && ld >= n);
+    ARG_CHECK(k > 0 && k <= n && k <= TVG_RANK_MAX_K);
+    hipLaunchKernelGGL(rank_rows, dim3(n_rows), dim3(256), 0, s, values, ld, n, k, idx_out, val_out);
+    LAUNCH_CHECK("rank_rows");
+    return BLIM_OK;
+}
+
+// ---------------------------------------------------------------------------- TVG clip-0 columns
+// One workgroup per logits row: wave 0 forms the row's normaliser through rank_lse -- the criterion's and the rank kernel's own --, then all waves store the named
+// columns' log-probabilities TRANSPOSED, out[c][out0 + r]: one out row per column, one out column per logits row.  A column outside the row stores a quiet NaN.
+__global__ __launch_bounds__(256) void tvg_cols_kernel(const float* logits, int64_t ld, int n_vocab, const int32_t* cols, int n_cols, float* out, int64_t ld_out,
+                                                       int64_t out0) {
+    __shared__ float tot;
+    const int64_t r = blockIdx.x;
+    const float* row = logits + r * ld;
+    const int tid = threadIdx.x;
+    if (tid < 64) {
+        const float t = rank_lse(row, n_vocab, tid);
+        if (tid == 0) tot = t;
+    }
+    __syncthreads();
+    const float t = tot;
+    for (int c = tid; c < n_cols; c += 256) {
+        const int j = cols[c];
+        out[c * ld_out + out0 + r] = (uint32_t)j < (uint32_t)n_vocab ? row[j] - t : __uint_as_float(0x7FC00000u);
+    }
+}
+int launch_tvg_cols(const float* logits, int64_t ld, int n_vocab, int n_rows, const int32_t* cols, int n_cols, float* out, int64_t ld_out, int64_t out0, hipStream_t s) {
+    ARG_CHECK(logits && cols && out && n_vocab > 0 && n_rows > 0 && n_cols > 0 && ld >= n_vocab && out0 >= 0 && ld_out >= out0 + n_rows);
+    hipLaunchKernelGGL(tvg_cols_kernel, dim3(n_rows), dim3(256), 0, s, logits, ld, n_vocab, cols, n_cols, out, ld_out, out0);
+    LAUNCH_CHECK("tvg_cols");
     return BLIM_OK;
 }
 

@@ -70,6 +70,13 @@ int launch_tvg_score(const float* logits, int64_t ld, int n_vocab, const int32_t
 #define TVG_RANK_MAX_K 1024          // = BLIM_TVG_RANK_MAX_K (blim.h): the survivors are sorted in LDS
 int launch_tvg_rank(const float* logits, int64_t ld, int n_vocab, int n_rows, const float* prior_logits, int64_t ld_prior, int n_prior, const int32_t* prior_of,
                     float alpha, int k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, hipStream_t s);
+// The rank kernel's select and sort over GIVEN values [n_rows, ld] f32, n per row: idx_out / val_out [n_rows, k] = the first k of the same order (descending, ties
+// to the lower index, -0 = +0, -inf after finite values, NaN last and by index); val_out holds the chosen values' own bits.  1 <= k <= min(n, TVG_RANK_MAX_K).
+int launch_rank_rows(const float* values, int64_t ld, int n, int n_rows, int k, int32_t* idx_out, float* val_out, hipStream_t s);
+// TVG clip-0 columns: out[c * ld_out + out0 + r] = log_softmax(logits[r, :n_vocab])[cols[c]] with the criterion's own normaliser (one wave, as the rank kernel forms
+// it), one workgroup per row r < n_rows; cols DEVICE [n_cols], entries may repeat, an entry outside 0 .. n_vocab - 1 stores a quiet NaN and reads nothing.  No other
+// cell of out is written.  ld >= n_vocab, out0 >= 0, ld_out >= out0 + n_rows.
+int launch_tvg_cols(const float* logits, int64_t ld, int n_vocab, int n_rows, const int32_t* cols, int n_cols, float* out, int64_t ld_out, int64_t out0, hipStream_t s);
 
 // ---- fp8 mode (DT_F8): per-row symmetric quantisation to OCP e4m3, scale = absmax / 448 (1 when the row is all zero)
 // in: 16-bit [n_rows, K] (row stride ld, dtype DT_BF16/DT_F16) -> out8 [n_rows, K] + scale [n_rows].  K % 8 == 0, K <= 20480.

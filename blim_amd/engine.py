@@ -203,7 +203,10 @@ def load_library(path: str = LIB_PATH):
         "blim_lse_combine": ([vp, i32, vp, vp, i64, vp, vp], C.c_int),
         "blim_tvg_criterion": ([vp, i64, i32, vp, i32, i32, vp, vp], C.c_int),
         "blim_tvg_rank": ([vp, i64, i32, i32, vp, i64, i32, vp, f32, i32, vp, vp, vp, i64, vp], C.c_int),
+        "blim_rank_rows": ([vp, i64, i32, i32, i32, vp, vp, vp], C.c_int),
+        "blim_tvg_cols": ([vp, i64, i32, i32, vp, i32, vp, i64, i64, vp], C.c_int),
         "blim_score_tvg_first": ([vp, C.POINTER(Batch), vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, vp, vp], C.c_int),
+        "blim_tvg_first_cached": ([vp, vp, vp, i32, vp, i32, vp, i64, i32, vp], C.c_int),
         "blim_group_mean_rows": ([vp, vp, i64, i32, i32, i32, i32, vp], C.c_int),
         "blim_assemble_rows": ([vp, vp, i64, i32, vp, vp, i32, vp], C.c_int),
         "blim_gemm": ([C.POINTER(GemmArgs), vp], C.c_int),
@@ -634,6 +637,15 @@ class Engine:
                                              float(alpha), int(k), _ptr(idx), _ptr(val), _ptr(lp), _stream()), "blim_score_tvg_first")
         return (idx, val, lp) if full else (idx, val)
 
+    def rank_rows(self, values, k: int):
+        """blim_rank_rows over a device f32 [n_rows, n] -> (idx int32 [n_rows, k], val f32 [n_rows, k]): the first k of every row in blim_tvg_rank's order."""
+        import torch
+        n_rows = int(values.shape[0])
+        idx = torch.empty((n_rows, int(k)), dtype=torch.int32, device=self.device)
+        val = torch.empty((n_rows, int(k)), dtype=torch.float32, device=self.device)
+        rank_rows(values, int(values.shape[1]), int(k), idx, val)
+        return idx, val
+
     def forward(self, embeds, mask, want_logits=True, want_hidden=True):
         """Literal forward: embeds [B,L,H] bf16, mask [B,L] uint8 -> (logits f32 [B,L,V] | None, hidden f32 [B,L,H] | None)."""
         import torch
@@ -755,6 +767,16 @@ class PrefixCache:
         its hidden row predicts clip 0)."""
         return self.engine.score_tvg(batch, embeds, rows, vocab_clip_major, labels, cache=self, pfx_slot=pfx_slot, slots_used=slots_used, admits=admits)
 
+    def tvg_first_cols(self, slots, cols, chunk_rows: int = 0):
+        """blim_tvg_first_cached: slots host ints [n_slots] (caption prompts), cols device int32 [n_cols] (vocabulary entries) -> device f32 [n_cols, n_slots],
+        out[c][q] = log P(clip 0 of entry cols[c] | the prompt in slots[q]), from the slots' stored hidden rows: no decode.  chunk_rows 0: the engine's default."""
+        import torch
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        out = torch.empty((int(cols.shape[0]), len(sl)), dtype=torch.float32, device=self.engine.device)
+        _check(self.lib.blim_tvg_first_cached(self.engine.h, self.h, sl.ctypes.data, len(sl), _ptr(cols), int(cols.shape[0]), _ptr(out), len(sl), int(chunk_rows),
+                                              _stream()), "blim_tvg_first_cached")
+        return out
+
 
 def ce_rows(logits, labels, V: Optional[int] = None):
     """logprob[r] = log_softmax(logits[r, :V])[labels[r]] (0 where labels[r] < 0); logits f32 [n, ld], labels int32 [n]; V = ld unless given."""
@@ -808,6 +830,18 @@ def tvg_rank(logits, n_vocab: int, k: int, idx_out, val_out, prior_logits=None, 
                                         0 if prior_logits is None else prior_logits.shape[1], (0 if prior_logits is None else prior_logits.shape[0]) if n_prior is None else n_prior,
                                         _ptr(prior_of), float(alpha), k, _ptr(idx_out), _ptr(val_out), _ptr(logprob_out), 0 if logprob_out is None else logprob_out.shape[1],
                                         _stream()), "blim_tvg_rank")
+
+
+def tvg_cols(logits, n_vocab: int, cols, out, out0: int = 0, n_rows: Optional[int] = None, n_cols: Optional[int] = None):
+    """blim_tvg_cols: logits f32 [n_rows, ld], cols int32 [n_cols] (device); out f32 [n_cols, ld_out]: out[c, out0 + r] = log_softmax(logits[r, :n_vocab])[cols[c]]."""
+    _check(load_library().blim_tvg_cols(_ptr(logits), 0 if logits is None else logits.shape[1], n_vocab, logits.shape[0] if n_rows is None else n_rows, _ptr(cols),
+                                        cols.shape[0] if n_cols is None else n_cols, _ptr(out), 0 if out is None else out.shape[1], out0, _stream()), "blim_tvg_cols")
+
+
+def rank_rows(values, n: int, k: int, idx_out, val_out, n_rows: Optional[int] = None):
+    """blim_rank_rows: values f32 [n_rows, ld]; idx_out int32 / val_out f32 [>= n_rows * k] are written: the first k of blim_tvg_rank's order on the given values."""
+    _check(load_library().blim_rank_rows(_ptr(values), 0 if values is None else values.shape[1], n, values.shape[0] if n_rows is None else n_rows, k, _ptr(idx_out),
+                                         _ptr(val_out), _stream()), "blim_rank_rows")
 
 
 def group_mean_rows(out, inp, n_out: int, group: int, H: int, dtype: str, split: bool = False):

@@ -27,7 +27,8 @@ are appended, an eager index fills them into its `spare_slots`, a lazy one admit
 
 The shortlist needs no first stage on a fine-tuned checkpoint: `GalleryIndex.shortlist` ranks the whole gallery by the TVG candidate term of
 the blend (`PairScorer.tvg_gallery`: fixed chunks, so a value depends on its text and the gallery alone), `search_requests` reranks the best K with that term reused,
-in one pass with requests that name their candidates; `TextGalleryIndex.shortlist` / `rerank_shortlist` are the v2t form over the cached caption prompts.
+in one pass with requests that name their candidates; `TextGalleryIndex.shortlist` / `rerank_shortlist` are the v2t form over the cached caption prompts, and
+`TextGalleryIndex.prefilter` narrows them first: the clip-0 term of every caption for all query videos from the slots' stored hidden rows.
 """
 from __future__ import annotations
 
@@ -941,6 +942,7 @@ class TextGalleryIndex(_PrefixIndex):
         self.keys: List[bytes] = []
         self._sync_texts()
         self.exec_tokens = 0                                # packed tokens of the cached TVG calls run so far
+        self.prefilter_stats = {"queries": 0, "passes": 0, "rows": 0, "kept": 0}   # videos prefiltered, stage-0 passes, the caption rows those scored, the texts kept
 
     def _count_texts(self) -> int:
         return len(self.s.tvg_split)
@@ -1068,25 +1070,90 @@ class TextGalleryIndex(_PrefixIndex):
         order = np.argsort(-blended, axis=1, kind="stable")
         return np.take_along_axis(cand, order, 1), np.take_along_axis(blended, order, 1)
 
+    # ---- the caption prefilter: every caption ranked on the device by the clip-0 summand of the query likelihood, from the cached rows
+    def _stage0(self, videos, chunk_rows: int = 0):
+        """-> device f32 [Q, texts]: log P(clip 0 of video | text) for every text and every query video, ONE pass for all Q.  A pair's first scored row is the
+        caption prompt's last row, whose hidden state a slot stores: the resident keys go through PairScorer.tvg_first_cached (no decode; cols = the videos'
+        vocabulary entries); a key without a slot -- beyond the budget, or not resident in a lazy index -- is scored by the decoded path, PairScorer.tvg_first(...,
+        full=True), column `video` of its lp: the same row, the same bits.  Nothing is admitted, counted as a hit or a miss, or stamped.  The per-key values are
+        fanned out on the device: texts with the same prompt share a key."""
+        import torch
+        s = self.s
+        dev = getattr(s, "device", "cpu")
+        of_text = self._key_of_text(dev)
+        have = [n for n, k in enumerate(self.keys) if k in self.slot_of] if self.cache is not None else []
+        part = None
+        if have:
+            cols = torch.from_numpy(np.asarray(s.tvg_video_labels, dtype=np.int32)[videos]).to(dev)
+            part = s.tvg_first_cached(self.cache, [self.slot_of[self.keys[n]] for n in have], cols, chunk_rows)
+        if len(have) == len(self.keys):
+            per_key = part
+        else:
+            resident = set(have)
+            lack = [n for n in range(len(self.keys)) if n not in resident]
+            first = {}
+            for i, n in enumerate(of_text[0]):
+                first.setdefault(n, i)
+            lp = s.tvg_first([first[n] for n in lack], 1, full=True)[2]
+            per_key = torch.empty((len(videos), len(self.keys)), dtype=torch.float32, device=dev)
+            if have:
+                per_key[:, torch.as_tensor(have, dtype=torch.int64, device=dev)] = part
+            per_key[:, torch.as_tensor(lack, dtype=torch.int64, device=dev)] = torch.from_numpy(np.ascontiguousarray(lp[:, videos].T)).to(dev)
+        return per_key[:, of_text[1]].contiguous()
+
+    def _key_of_text(self, dev):
+        """-> (every text's key position, the same as a device index), kept while the texts and the keys are the ones it was made for (both are appended only)."""
+        import torch
+        size = (len(self.s.tvg_split), len(self.keys))
+        memo = getattr(self, "_fan", None)
+        if memo is None or memo[0] != size:
+            key_at = {k: n for n, k in enumerate(self.keys)}
+            of_text = [key_at[pr.tobytes()] for pr in self.s.tvg_split]
+            memo = self._fan = (size, of_text, torch.as_tensor(of_text, dtype=torch.int64, device=dev))
+        return memo[1], memo[2]
+
+    def prefilter(self, videos, k0: int, chunk_rows: int = 0):
+        """The K0 captions of each query video that log P(clip 0 of the video | text) ranks first: ONE stage-0 pass for all videos (_stage0: two small GEMMs over
+        the cached rows, no layer), ranked on the device (Engine.rank_rows).  The index follows the model's TVG mode and fills its cache first, as tvg_pairs does.
+        -> (cand int64 [Q, min(k0, texts)] text indices, best first: descending, ties to the lower text index; val f32, their values).  ValueError as
+        check_shortlist (K0 clipped to the texts); a text without a TVG row is refused by name."""
+        videos = np.asarray(videos, dtype=np.int64).reshape(-1)
+        n = len(self.s.tvg_split)
+        _, k0 = check_shortlist(None, k0, n)
+        if not len(videos):
+            return np.zeros((0, k0), np.int64), np.zeros((0, k0), np.float32)
+        if any(pr is None for pr in self.s.tvg_split):
+            self.s._need_tvg(np.arange(n))                     # (raises: every text is ranked)
+        self._fresh()
+        self._sync_texts()
+        self._sync_videos()
+        idx, val = self.engine.rank_rows(self._stage0(videos, chunk_rows), k0)
+        st = self.prefilter_stats
+        st["queries"] += len(videos); st["passes"] += 1; st["rows"] += len(self.keys); st["kept"] += len(videos) * k0
+        return idx.cpu().numpy().astype(np.int64), val.cpu().numpy()
+
     # ---- the shortlist, v2t (DESIGN.md section 18)
-    def shortlist(self, videos, k: int):
+    def shortlist(self, videos, k: int, prefilter: Optional[int] = None):
         """Every caption ranked by a query video's TVG likelihood, log P(video | text), over the cached prompts: one tvg_pairs pass per query video, so every text has
-        one video and a value is that of any other pass that scores the pair so (section 11).  Descending, ties to the lower text index.
+        one video and a value is that of any other pass that scores the pair so (section 11).  Descending, ties to the lower text index.  prefilter = K0 >= k
+        (section 22): ONE prefilter() pass for all videos first, and each video's pass runs over its K0 survivors only, in ascending text order.
         -> (cand [Q, min(k, texts)] text indices, best first; their stage-1 scores)."""
         videos = np.asarray(videos, dtype=np.int64).reshape(-1)
         n = len(self.s.tvg_split)
-        k = min(check_shortlist(k, None, n)[0], n)
+        k = min(check_shortlist(k, prefilter, n)[0], n)
+        kept = None if prefilter is None else np.sort(self.prefilter(videos, prefilter)[0], axis=1)
         cand, stage = np.zeros((len(videos), k), np.int64), np.zeros((len(videos), k), np.float32)
         for q, v in enumerate(videos):
-            row = self.tvg_pairs(np.stack([np.full(n, v, dtype=np.int64), np.arange(n)], axis=1))
+            texts = np.arange(n) if kept is None else kept[q]
+            row = self.tvg_pairs(np.stack([np.full(len(texts), v, dtype=np.int64), texts], axis=1))
             order = np.argsort(-row, kind="stable")[:k]
-            cand[q], stage[q] = order, row[order]
+            cand[q], stage[q] = texts[order], row[order]
         return cand, stage
 
-    def rerank_shortlist(self, videos, k: int, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0)):
+    def rerank_shortlist(self, videos, k: int, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0), prefilter: Optional[int] = None):
         """rerank(videos, shortlist(videos, k), finetuned=True) without a first stage, the query likelihood of the blend being the shortlist's stage-1 value: the TVG
-        term is not computed a second time.  -> (order [Q, k] of text ids, best first; blended scores in that order)."""
-        cand, stage = self.shortlist(videos, k)
+        term is not computed a second time.  prefilter = K0: shortlist's.  -> (order [Q, k] of text ids, best first; blended scores in that order)."""
+        cand, stage = self.shortlist(videos, k) if prefilter is None else self.shortlist(videos, k, prefilter)
         videos, cand, pairs = grid_pairs(videos, cand, query_col=0)
         v2t_cand = self.vtg_pairs(pairs).reshape(cand.shape)
         if cpn:

@@ -763,6 +763,19 @@ class PairScorer(CalibrationMixin):
         if lo6 and self.split_tvg and getattr(self.engine, "dtype", "") != "bf16":      # (bf16 engines: TVG calls keep the bf16 second pass, Engine.set_precise)
             self.exec_flops_lo6 += lo6_pass_flops(self.m.dims, plan.n_tokens, plan.n_rows, "tvg", self.tvg_mode, prune=not f8)
 
+    def _register_first_vocab(self) -> None:
+        """Inside _call_options("tvg"): a scorer whose TVG calls name their vocabulary registers it, since the clip-0 entries run over the registered one."""
+        if self.vocab_cm is not None and (getattr(self, "_first_vocab", None) != (self.vocab_version, getattr(self.engine, "_vocab_key", None))):
+            self.engine.set_video_vocab(self._vocab_src)
+            self._first_vocab = (self.vocab_version, self.engine._vocab_key)
+
+    def tvg_first_cached(self, cache, slots, cols, chunk_rows: int = 0):
+        """log P(clip 0 of vocabulary entry cols[c] | the caption prompt in slots[q]) from the cache's stored hidden rows, under the TVG calls' options
+        (PrefixCache.tvg_first_cols: no decode) -> device f32 [n_cols, n_slots].  slots: host ints; cols: device int32."""
+        with self._call_options("tvg"):
+            self._register_first_vocab()
+            return cache.tvg_first_cols(slots, cols, chunk_rows)
+
     def run(self, plan: Plan, cache=None, k: int = 1, alpha: float = 0.0, full: bool = False):
         """One engine call; returns a device f32 tensor [plan.n_pairs].  A plan made over a prefix source (plan.pfx_slot) goes through `cache`, the PrefixCache
         that holds its slots, and is not counted in exec_*: those count the scorer's own calls.  A plan of kind "tvg_first" (k, alpha, full are its arguments)
@@ -770,9 +783,7 @@ class PairScorer(CalibrationMixin):
         if plan.kind == "tvg_first":
             self._count(plan)
             with self._call_options("tvg"):
-                if self.vocab_cm is not None and (getattr(self, "_first_vocab", None) != (self.vocab_version, getattr(self.engine, "_vocab_key", None))):
-                    self.engine.set_video_vocab(self._vocab_src)            # a scorer whose TVG calls name their vocabulary: the rank runs over the registered one
-                    self._first_vocab = (self.vocab_version, self.engine._vocab_key)
+                self._register_first_vocab()
                 embeds = self.engine.assemble(plan.src_index, plan.feats)
                 cpn = plan.prior_rows is not None
                 return self.engine.score_tvg_first(plan.batch, embeds, plan.rows, k, prior_rows=plan.prior_rows, prior_of=plan.labels if cpn else None,

@@ -9,7 +9,9 @@ term reused and a zero first-stage term, the best `--topk` of them are printed, 
 counts the queries, the stage-1 passes and their pairs.  It serves `--query`, `--query_ids` and, under `--direction v2t`, `--video_ids` (there the captions are
 ranked by the query likelihood over the cached prompts: TextGalleryIndex.shortlist).  `--prefilter K0` (t2v) puts a stage in front of that: the
 whole gallery is ranked ON THE DEVICE by the clip-0 term of the TVG likelihood -- one logits row per query, whatever the gallery's size -- and the TVG ranking runs on
-the best K0 only; the JSON line gains `"prefiltered": K0` and a `prefilter:` stderr line is printed at the end.  One JSON line per query: the ranked video ids and their
+the best K0 only; the JSON line gains `"prefiltered": K0` and a `prefilter:` stderr line is printed at the end.  `--caption_prefilter K0` (v2t, DESIGN.md section
+22) is the other direction's stage: every caption's clip-0 term for the query video comes from the cached prompts' stored rows with no decode
+(TextGalleryIndex.prefilter), the per-video TVG pass runs over the best K0 captions, and the answer line and the `prefilter:` line are the same.  One JSON line per query: the ranked video ids and their
 blended t2v scores (training_utils.combine_and_rank's t2v half: `--cpn --alpha --c`; zero-shot runs blend the query likelihood with the first stage only).
 `--synthetic N [--synthetic_7b]`: a dry run on synth.make_problem, as main.py's.  `--gallery_fill lazy` computes no prefix up front: the first query runs at once, its
 calls leave their videos' prefixes in the cache, and `--gallery_gb` is the cache's capacity.  The `gallery stats:` stderr line reports the hits
@@ -98,6 +100,9 @@ def get_args_parser():
     p.add_argument("--prefilter", default=None, type=int, metavar="K0",
                    help="--candidates tvg, t2v: the whole gallery is first ranked on the device by the clip-0 term of the TVG likelihood (one logits row per query, "
                         "whatever the gallery's size), the TVG ranking runs on the best K0 >= --shortlist only")
+    p.add_argument("--caption_prefilter", default=None, type=int, metavar="K0",
+                   help="--candidates tvg, v2t: every caption is first ranked on the device by the clip-0 term of the query likelihood, read from the cached prompts' "
+                        "stored rows (no decode, one pass for all query videos), the TVG ranking runs on the best K0 >= --shortlist captions only")
     p.add_argument("--query_video", default=[], type=str, nargs="*", metavar="FILE",
                    help="--direction v2t: feature files of videos outside the dataset ([num_clips, tokens, width] tensors as blim_amd.extract writes them) used as queries; "
                         "they join the scorer (PairScorer.add_videos) before the indexes are built.  --candidates all | tvg")
@@ -206,11 +211,20 @@ def check_args(args, world: int = 1) -> None:
     K0 = args.prefilter
     if K0 is not None:
         if v2t:
-            raise SystemExit("search: --prefilter narrows the t2v TVG ranking (--direction t2v): v2t has no prefilter")
+            raise SystemExit("search: --prefilter narrows the t2v TVG ranking (--direction t2v): v2t has no prefilter of the videos.  Its captions are narrowed by "
+                             "--caption_prefilter K0")
         if args.candidates != "tvg":
             raise SystemExit("search: --prefilter narrows the gallery before --candidates tvg ranks it (give --candidates tvg)")
         if K0 < 1 or K0 < shortlist_k(args):
             raise SystemExit(f"search: --prefilter must be at least --shortlist ({shortlist_k(args)}): the shortlist is taken from the videos it keeps")
+    K0 = args.caption_prefilter
+    if K0 is not None:
+        if not v2t:
+            raise SystemExit("search: --caption_prefilter narrows the captions a query video ranks (--direction v2t): t2v narrows its videos with --prefilter")
+        if args.candidates != "tvg":
+            raise SystemExit("search: --caption_prefilter narrows the captions before --candidates tvg ranks them (give --candidates tvg)")
+        if K0 < 1 or K0 < shortlist_k(args):
+            raise SystemExit(f"search: --caption_prefilter must be at least --shortlist ({shortlist_k(args)}): the shortlist is taken from the captions it keeps")
     if len(args.c) != 4 or len(args.alpha) != 2:
         raise SystemExit("search: --c takes 4 values, --alpha 2")
     if v2t and args.c[3] == 0:
@@ -861,16 +875,19 @@ def run_v2t(tg, vids, v2t_iv2, args, write):
     k = min(args.topk, n_texts)
     blend = dict(cpn=args.cpn, alpha=args.alpha, c=args.c)
     shortlisted = {"queries": 0, "passes": 0, "pairs": 0}
+    K0 = getattr(args, "caption_prefilter", None)
+    narrow = {} if K0 is None else {"prefilter": K0}    # (section 22: stage 1 runs over the K0 captions the cached clip-0 rows rank first)
     for v in args.video_ids:
         K = None
         if args.candidates == "tvg":              # the captions ranked by the query likelihood over the cached prompts, the best K reranked
             K = shortlist_k(args)
-            order, blended = (x[0, :k] for x in tg.rerank_shortlist([v], K, **blend))
-            shortlisted = {"queries": shortlisted["queries"] + 1, "passes": shortlisted["passes"] + 1, "pairs": shortlisted["pairs"] + n_texts}
+            order, blended = (x[0, :k] for x in tg.rerank_shortlist([v], K, **blend, **narrow))
+            shortlisted = {"queries": shortlisted["queries"] + 1, "passes": shortlisted["passes"] + 1,
+                           "pairs": shortlisted["pairs"] + (n_texts if K0 is None else min(K0, n_texts))}
         else:                                     # (--query_video: no first-stage row)
             cand, fs = default_candidates(args.candidates, v2t_iv2[v] if v2t_iv2 is not None and v < len(v2t_iv2) else None, n_texts, args.topk)
             order, blended = (x[0] for x in tg.rerank([v], cand[None], first_stage=None if fs is None else fs[None], finetuned=bool(args.resume), **blend))
-        write(answer_line(f"video:{vids[v]}", "texts", [int(i) for i in order], blended, K))
+        write(answer_line(f"video:{vids[v]}", "texts", [int(i) for i in order], blended, K, K0 if K is not None else None))
     return shortlisted
 
 
@@ -907,7 +924,7 @@ def main(args):
         content_hash = lambda feat: hash_device(feat.contiguous().to(p.model.device))      # (one upload and one pass over a feature tensor: a fraction of the projection that follows)
         summary = run_serve(gal, vids, p.t2v_iv2, args, write, sys.stdin, p.build_rows, content_hash)
     elif v2t:
-        shortlisted, prefiltered = run_v2t(indexes[1][1], vids, p.v2t_iv2, args, write), None
+        shortlisted, prefiltered = run_v2t(indexes[1][1], vids, p.v2t_iv2, args, write), getattr(indexes[1][1], "prefilter_stats", None)
     else:
         run_t2v(gal, vids, p.t2v_iv2, args, write)
     close_output()

@@ -267,6 +267,19 @@ int blim_score_vtg_admit(blim_engine* e, blim_prefix_cache* c, const blim_batch*
 int blim_score_tvg_admit(blim_engine* e, blim_prefix_cache* c, const blim_batch* b, const int32_t* pfx_slot, const int32_t* slots_used, int32_t n_used,
                          const blim_pc_admit* admits, int32_t n_admit, const void* embeds, const int32_t* rows, const void* vocab_bf16, int32_t n_vocab,
                          const int32_t* labels, int32_t n_pairs, float* score, void* stream);
+/* TVG, clip 0 of named videos given EVERY cached caption prompt, with no decode (additive in ABI v9; blim_amd/gallery.py: TextGalleryIndex.prefilter): a TVG pair's
+ * first scored row is the caption prompt's last row, and a slot stores that row's final-norm hidden state.  out[c * ld_out + q] = log P(clip 0 of vocabulary entry
+ * cols[c] | the prompt in slots[q]): per chunk of slots the gather of the stored rows, the visual head, the clip-0 logits against the registered vocabulary exactly
+ * as blim_score_tvg_first forms them (one statement of them in the engine; the three-term product on a compensated call) and blim_tvg_cols with out0 = the chunk's
+ * first index -- each value bit for bit blim_score_tvg_first's logprob_out[row of that prompt][cols[c]].  slots HOST [n_slots], cols DEVICE [n_cols] (blim_tvg_cols'
+ * rule for entries outside the vocabulary), out DEVICE f32 [n_cols, ld_out], ld_out >= n_slots.  chunk_rows = 0: max(256, 256 MiB / (4 n_vocab)) rounded down to a
+ * multiple of 256, which bounds the logits workspace at 256 MiB; a value does not depend on the chunking.  It runs under the options of the TVG calls.  Nothing
+ * waits for the device; the only copy from host memory is the slot list.
+ * Refused: null pointers, a cache of another engine, n_slots < 1, n_cols < 1, ld_out < n_slots, chunk_rows < 0 or no multiple of 256 (BLIM_ERR_ARG, the message
+ * names the argument); an fp8 engine, no registered vocabulary (BLIM_ERR_STATE); and the cached calls' refusals of the slots with their messages -- outside the
+ * cache (BLIM_ERR_ARG), never filled, stale, a compensated call on a cache created plain (BLIM_ERR_STATE) -- before anything is launched. */
+int blim_tvg_first_cached(blim_engine* e, blim_prefix_cache* c, const int32_t* slots, int32_t n_slots, const int32_t* cols, int32_t n_cols, float* out, int64_t ld_out,
+                          int32_t chunk_rows, void* stream);
 
 /* ---- Slot export / import (additive in ABI v9; blim_amd/gallery.py: HostTier): a slot leaves the prefix cache as a PACKED RECORD and comes back from one, so that
  * a slot can be produced without running the model.  The record of a slot with `len` filled positions: [num_layers][pos < len][kv_w] 16-bit values, then the slot's
@@ -568,6 +581,19 @@ int blim_tvg_criterion(const float* logits, int64_t ld, int32_t n_vocab, const i
 #define BLIM_TVG_RANK_MAX_K 1024
 int blim_tvg_rank(const float* logits, int64_t ld, int32_t n_vocab, int32_t n_rows, const float* prior_logits, int64_t ld_prior, int32_t n_prior,
                   const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, void* stream);
+/* blim_tvg_rank's select and sort over GIVEN values (f32 rows of stride ld >= n, n per row): idx_out / val_out [n_rows, k] = the first k of blim_tvg_rank's order
+ * applied to the values as they stand -- descending, ties to the lower index, -0 = +0, -inf after every finite value, NaN last and by index among themselves;
+ * exact and deterministic.  val_out holds the chosen values' own bits.
+ * BLIM_ERR_ARG (the message names the argument): a null values / idx_out / val_out, n < 1, n_rows < 1, ld below n, and blim_tvg_rank's refusals of k in its own
+ * words: k < 1, k > n, k > BLIM_TVG_RANK_MAX_K. */
+int blim_rank_rows(const float* values, int64_t ld, int32_t n, int32_t n_rows, int32_t k, int32_t* idx_out, float* val_out, void* stream);
+/* Named columns of the row log-softmax, transposed: out[c * ld_out + out0 + r] = logits[r * ld + cols[c]] - (mx + logf(sm)) of row r, the normaliser formed by
+ * one wave exactly as blim_tvg_criterion and blim_tvg_rank form it -- as a float, blim_tvg_criterion of row r with label cols[c] at clips = 1, and blim_tvg_rank's
+ * logprob_out[r][cols[c]].  cols (DEVICE [n_cols]) may repeat; an entry outside 0 .. n_vocab - 1 stores a quiet NaN, never a read outside the row (the device array
+ * is not read back).  Nothing else in out is written: columns before out0 and from out0 + n_rows on, and rows >= n_cols, are left alone.
+ * BLIM_ERR_ARG (the message names the argument): a null logits / cols / out, n_vocab < 1, n_rows < 1, n_cols < 1, ld < n_vocab, out0 < 0, ld_out < out0 + n_rows. */
+int blim_tvg_cols(const float* logits, int64_t ld, int32_t n_vocab, int32_t n_rows, const int32_t* cols, int32_t n_cols, float* out, int64_t ld_out, int64_t out0,
+                  void* stream);
 /* blim_group_mean / blim_assemble with the engine's fields as arguments: H, the 16-bit type, the embedding table (16-bit [*, H]) and split -- rows [hi | lo] of
  * width 2 H (feature rows and outputs; a table row's lo half is zero).  H % 8 == 0 for the assembly, H % 4 == 0 for the mean. */
 int blim_group_mean_rows(void* out, const void* in, int64_t n_out, int32_t group, int32_t H, int32_t dtype16, int32_t split, void* stream);
