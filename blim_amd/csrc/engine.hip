@@ -1611,13 +1611,10 @@ static int tvg_first_logits(blim_engine* e, int64_t R, hipStream_t s) {
     p.scale = 1.0f / sqrtf((float)M);
     return launch_gemm(EPI_F32, p, s);
 }
-extern "C" int blim_score_tvg_first(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, int32_t n_rows, const int32_t* prior_rows, int32_t n_prior,
-                                    const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, void* stream) {
-    ARG_CHECK(e && rows && idx_out && val_out && n_rows > 0 && n_prior >= 0 && (prior_rows || n_prior == 0));
-    if (e->f8) { blim_set_error("blim_score_tvg_first: fp8 engines are not supported"); return BLIM_ERR_STATE; }
-    if (!e->vocab3.p) { blim_set_error("no video vocabulary registered (blim_set_video_vocab)"); return BLIM_ERR_STATE; }
-    const int N = e->n_vocab, M = e->c.mm_hidden_size;
-    TRY(tvg_rank_check_k(k, N));
+// blim_score_tvg_first up to and including tvg_first_logits (both entries below, after their own refusals): the decode and the visual head over [rows | prior_rows]
+static int tvg_first_decode(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, int32_t n_rows, const int32_t* prior_rows, int32_t n_prior,
+                            void* stream) {
+    const int M = e->c.mm_hidden_size;
     hipStream_t s = (hipStream_t)stream;
     const int64_t R = (int64_t)n_rows + n_prior;
     TRY(reserve_rows(e, R));
@@ -1631,10 +1628,36 @@ extern "C" int blim_score_tvg_first(blim_engine* e, const blim_batch* b, const v
     }
     TRY(decode_impl(e, b, embeds, all, R, e->hsel.p, e->precise, nullptr, stream));
     TRY(visual_head_impl(e, e->hsel.p, e->precise, R, e->vh.p, stream));
-    TRY(tvg_first_logits(e, R, s));
+    return tvg_first_logits(e, R, s);
+}
+extern "C" int blim_score_tvg_first(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, int32_t n_rows, const int32_t* prior_rows, int32_t n_prior,
+                                    const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, void* stream) {
+    ARG_CHECK(e && rows && idx_out && val_out && n_rows > 0 && n_prior >= 0 && (prior_rows || n_prior == 0));
+    if (e->f8) { blim_set_error("blim_score_tvg_first: fp8 engines are not supported"); return BLIM_ERR_STATE; }
+    if (!e->vocab3.p) { blim_set_error("no video vocabulary registered (blim_set_video_vocab)"); return BLIM_ERR_STATE; }
+    const int N = e->n_vocab;
+    TRY(tvg_rank_check_k(k, N));
+    hipStream_t s = (hipStream_t)stream;
+    TRY(tvg_first_decode(e, b, embeds, rows, n_rows, prior_rows, n_prior, stream));
     const float* lg = (const float*)e->tvg_logits.p;
     SpanGuard g(e, s, TC_MISC, 0);
     return launch_tvg_rank(lg, N, N, n_rows, lg + (int64_t)n_rows * N, N, n_prior, prior_of, alpha, k, idx_out, val_out, logprob_out, N, s);
+}
+static int tvg_rank_within_check(const int32_t* within, const int32_t* within_off, int32_t n_q, int32_t n_within, int32_t k);
+extern "C" int blim_score_tvg_first_within(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, int32_t n_rows, const int32_t* prior_rows,
+                                           int32_t n_prior, int32_t n_q, const int32_t* row_of, const int32_t* prior_of, const int32_t* within,
+                                           const int32_t* within_off, int32_t n_within, float alpha, int32_t k, int32_t* idx_out, float* val_out, void* stream) {
+    ARG_CHECK(e && rows && idx_out && val_out && n_rows > 0 && n_prior >= 0 && (prior_rows || n_prior == 0));
+    if (e->f8) { blim_set_error("blim_score_tvg_first_within: fp8 engines are not supported"); return BLIM_ERR_STATE; }
+    if (!e->vocab3.p) { blim_set_error("no video vocabulary registered (blim_set_video_vocab)"); return BLIM_ERR_STATE; }
+    TRY(tvg_rank_within_check(within, within_off, n_q, n_within, k));
+    const int N = e->n_vocab;
+    hipStream_t s = (hipStream_t)stream;
+    TRY(tvg_first_decode(e, b, embeds, rows, n_rows, prior_rows, n_prior, stream));
+    const float* lg = (const float*)e->tvg_logits.p;
+    SpanGuard g(e, s, TC_MISC, 0);
+    return launch_tvg_rank_within(lg, N, N, n_rows, lg + (int64_t)n_rows * N, N, n_prior, n_q, row_of, prior_of, within, within_off, n_within, alpha, k, idx_out,
+                                  val_out, s);
 }
 // The cached counterpart for the other direction: the caption prompts' last rows are the slots' stored hidden rows, so the clip-0 log-probabilities of the named
 // vocabulary entries given every slot's prompt need no decode -- per chunk of slots the gather, the visual head, tvg_first_logits and the column kernel
@@ -1792,6 +1815,29 @@ extern "C" int blim_tvg_rank(const float* logits, int64_t ld, int32_t n_vocab, i
     if (prior_logits && ld_prior < n_vocab) { blim_set_error("tvg_rank: ld_prior = %lld below n_vocab = %d", (long long)ld_prior, n_vocab); return BLIM_ERR_ARG; }
     if (logprob_out && ld_out < n_vocab) { blim_set_error("tvg_rank: ld_out = %lld below n_vocab = %d", (long long)ld_out, n_vocab); return BLIM_ERR_ARG; }
     return launch_tvg_rank(logits, ld, n_vocab, n_rows, prior_logits, ld_prior, n_prior, prior_of, alpha, k, idx_out, val_out, logprob_out, ld_out, (hipStream_t)stream);
+}
+// blim_tvg_rank_within's refusals of its own arguments (shared with blim_score_tvg_first_within, which checks them before it launches anything)
+static int tvg_rank_within_check(const int32_t* within, const int32_t* within_off, int32_t n_q, int32_t n_within, int32_t k) {
+    if (!within || !within_off) { blim_set_error("tvg_rank_within: %s is null", !within ? "within" : "within_off"); return BLIM_ERR_ARG; }
+    if (n_q < 1) { blim_set_error("tvg_rank_within: n_q = %d < 1", n_q); return BLIM_ERR_ARG; }
+    if (n_within < 0) { blim_set_error("tvg_rank_within: n_within = %d < 0", n_within); return BLIM_ERR_ARG; }
+    if (k < 1) { blim_set_error("tvg_rank_within: k = %d < 1", k); return BLIM_ERR_ARG; }
+    if (k > BLIM_TVG_RANK_MAX_K) { blim_set_error("tvg_rank_within: k = %d above BLIM_TVG_RANK_MAX_K = %d", k, BLIM_TVG_RANK_MAX_K); return BLIM_ERR_ARG; }
+    return BLIM_OK;
+}
+extern "C" int blim_tvg_rank_within(const float* logits, int64_t ld, int32_t n_vocab, int32_t n_rows, const float* prior_logits, int64_t ld_prior, int32_t n_prior,
+                                    int32_t n_q, const int32_t* row_of, const int32_t* prior_of, const int32_t* within, const int32_t* within_off, int32_t n_within,
+                                    float alpha, int32_t k, int32_t* idx_out, float* val_out, void* stream) {
+    if (!logits || !idx_out || !val_out) { blim_set_error("tvg_rank_within: %s is null", !logits ? "logits" : !idx_out ? "idx_out" : "val_out"); return BLIM_ERR_ARG; }
+    if (n_vocab < 1) { blim_set_error("tvg_rank_within: n_vocab = %d < 1", n_vocab); return BLIM_ERR_ARG; }
+    if (n_rows < 1) { blim_set_error("tvg_rank_within: n_rows = %d < 1", n_rows); return BLIM_ERR_ARG; }
+    TRY(tvg_rank_within_check(within, within_off, n_q, n_within, k));
+    if (ld < n_vocab) { blim_set_error("tvg_rank_within: ld = %lld below n_vocab = %d", (long long)ld, n_vocab); return BLIM_ERR_ARG; }
+    if (n_prior < 0) { blim_set_error("tvg_rank_within: n_prior = %d < 0", n_prior); return BLIM_ERR_ARG; }
+    if (prior_of && !prior_logits) { blim_set_error("tvg_rank_within: prior_of without prior_logits"); return BLIM_ERR_ARG; }
+    if (prior_logits && ld_prior < n_vocab) { blim_set_error("tvg_rank_within: ld_prior = %lld below n_vocab = %d", (long long)ld_prior, n_vocab); return BLIM_ERR_ARG; }
+    return launch_tvg_rank_within(logits, ld, n_vocab, n_rows, prior_logits, ld_prior, n_prior, n_q, row_of, prior_of, within, within_off, n_within, alpha, k, idx_out,
+                                  val_out, (hipStream_t)stream);
 }
 extern "C" int blim_rank_rows(const float* values, int64_t ld, int32_t n, int32_t n_rows, int32_t k, int32_t* idx_out, float* val_out, void* stream) {
     if (!values || !idx_out || !val_out) { blim_set_error("rank_rows: %s is null", !values ? "values" : !idx_out ? "idx_out" : "val_out"); return BLIM_ERR_ARG; }

@@ -815,6 +815,65 @@ __global__ __launch_bounds__(256) void rank_rows(const float* values, int64_t ld
     q.row = values + r * ld;
     rank_select(q, n, k, idx_out + r * k, val_out + r * k);
 }
+// rank_select inside a caller's list of columns: the third term source wraps a RankRow and the list and is indexed by POSITION, so the select's "lower index" is the
+// lower position and idx_out holds positions.  The term of position p is rank_term(RankRow, list[p]) -- tot / ptot over the whole row, so a value is the unfiltered
+// kernel's for that column --; an entry outside the row, or any entry of a query whose row_of lies outside the rows (`dead`), is a quiet NaN and reads nothing.
+struct WithinRow { RankRow r; const int32_t* list; int n_vocab; bool dead; };
+__device__ __forceinline__ float rank_term(const WithinRow& q, int p) {
+    if (q.dead) return __uint_as_float(0x7FC00000u);
+    const int j = q.list[p];
+    return (uint32_t)j < (uint32_t)q.n_vocab ? rank_term(q.r, j) : __uint_as_float(0x7FC00000u);
+}
+// One workgroup per QUERY q: its logits row is row_of[q] (NULL: q), its prior row prior_of[q] (tvg_rank_kernel's meaning), its list within[within_off[q] ..
+// within_off[q + 1]) with the offsets clamped to 0 .. n_within and a decreasing pair an empty list.  idx_out / val_out [n_q, k]: the first min(k, m_q) positions in
+// rank_select's order, then -1 / quiet NaN.
+__global__ __launch_bounds__(256) void tvg_rank_within_kernel(const float* logits, int64_t ld, int n_vocab, int n_rows, const float* prior_logits, int64_t ld_prior,
+                                                              int n_prior, const int32_t* row_of, const int32_t* prior_of, const int32_t* within,
+                                                              const int32_t* within_off, int n_within, float alpha, int k, int32_t* idx_out, float* val_out) {
+    __shared__ float tots[2];
+    const int64_t qi = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int r = row_of ? row_of[qi] : (int)qi;
+    const int o0 = min(max(within_off[qi], 0), n_within), o1 = min(max(within_off[qi + 1], 0), n_within);
+    const int m = max(o1 - o0, 0);
+    WithinRow q;
+    q.dead = (uint32_t)r >= (uint32_t)n_rows;
+    q.list = within + o0;
+    q.n_vocab = n_vocab;
+    q.r.row = q.dead ? nullptr : logits + (int64_t)r * ld;
+    const int po = prior_of ? prior_of[qi] : -1;
+    q.r.mode = po < 0 ? 0 : po < n_prior ? 1 : 2;
+    q.r.prow = q.r.mode == 1 ? prior_logits + (int64_t)po * ld_prior : nullptr;
+    q.r.alpha = alpha;
+    const int kk = min(k, m);
+    int32_t* idx_row = idx_out + qi * k;
+    float* val_row = val_out + qi * k;
+    for (int i = kk + tid; i < k; i += 256) { idx_row[i] = -1; val_row[i] = __uint_as_float(0x7FC00000u); }
+    if (m == 0) return;                                           // (uniform per workgroup: before every barrier)
+    const bool live = !q.dead;
+    if (w == 0 && live) {
+        const float t = rank_lse(q.r.row, n_vocab, lane);
+        if (lane == 0) tots[0] = t;
+    } else if (w == 1 && live && q.r.mode == 1) {
+        const float t = rank_lse(q.r.prow, n_vocab, lane);
+        if (lane == 0) tots[1] = t;
+    }
+    __syncthreads();
+    q.r.tot = live ? tots[0] : 0.f;
+    q.r.ptot = live && q.r.mode == 1 ? tots[1] : 0.f;
+    rank_select(q, m, kk, idx_row, val_row);
+}
+int launch_tvg_rank_within(const float* logits, int64_t ld, int n_vocab, int n_rows, const float* prior_logits, int64_t ld_prior, int n_prior, int n_q,
+                           const int32_t* row_of, const int32_t* prior_of, const int32_t* within, const int32_t* within_off, int n_within, float alpha, int k,
+                           int32_t* idx_out, float* val_out, hipStream_t s) {
+    ARG_CHECK(logits && within && within_off && idx_out && val_out && n_vocab > 0 && n_rows > 0 && n_q > 0 && n_within >= 0 && ld >= n_vocab);
+    ARG_CHECK(k > 0 && k <= TVG_RANK_MAX_K);
+    ARG_CHECK(n_prior >= 0 && (!prior_of || prior_logits) && (!prior_logits || ld_prior >= n_vocab));
+    hipLaunchKernelGGL(tvg_rank_within_kernel, dim3(n_q), dim3(256), 0, s, logits, ld, n_vocab, n_rows, prior_logits, ld_prior, n_prior, row_of, prior_of, within,
+                       within_off, n_within, alpha, k, idx_out, val_out);
+    LAUNCH_CHECK("tvg_rank_within");
+    return BLIM_OK;
+}
 int launch_tvg_rank(const float* logits, int64_t ld, int n_vocab, int n_rows, const float* prior_logits, int64_t ld_prior, int n_prior, const int32_t* prior_of,
                     float alpha, int k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, hipStream_t s) {
     ARG_CHECK(logits && idx_out && val_out && n_vocab > 0 && n_rows > 0 && ld >= n_vocab);

@@ -70,6 +70,14 @@ int launch_tvg_score(const float* logits, int64_t ld, int n_vocab, const int32_t
 #define TVG_RANK_MAX_K 1024          // = BLIM_TVG_RANK_MAX_K (blim.h): the survivors are sorted in LDS
 int launch_tvg_rank(const float* logits, int64_t ld, int n_vocab, int n_rows, const float* prior_logits, int64_t ld_prior, int n_prior, const int32_t* prior_of,
                     float alpha, int k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, hipStream_t s);
+// The TVG clip-0 rank inside a caller's list of columns, one workgroup per QUERY q < n_q: its logits row is row_of[q] (DEVICE int32, NULL: q itself; outside
+// 0 .. n_rows - 1: every term NaN, nothing read), its prior prior_of[q] with launch_tvg_rank's meaning, its list within[within_off[q] .. within_off[q + 1]) (DEVICE
+// int32; offsets clamped to 0 .. n_within, a decreasing pair is an empty list).  The term of list position p is launch_tvg_rank's term of column within[p] -- the
+// normalisers over the WHOLE row of n_vocab columns --, a quiet NaN for an entry outside 0 .. n_vocab - 1.  idx_out / val_out [n_q, k]: the first min(k, m_q)
+// POSITIONS of the same order (ties to the lower position), then -1 / quiet NaN.  1 <= k <= TVG_RANK_MAX_K; m_q has no limit; entries may repeat.
+int launch_tvg_rank_within(const float* logits, int64_t ld, int n_vocab, int n_rows, const float* prior_logits, int64_t ld_prior, int n_prior, int n_q,
+                           const int32_t* row_of, const int32_t* prior_of, const int32_t* within, const int32_t* within_off, int n_within, float alpha, int k,
+                           int32_t* idx_out, float* val_out, hipStream_t s);
 // The rank kernel's select and sort over GIVEN values [n_rows, ld] f32, n per row: idx_out / val_out [n_rows, k] = the first k of the same order (descending, ties
 // to the lower index, -0 = +0, -inf after finite values, NaN last and by index); val_out holds the chosen values' own bits.  1 <= k <= min(n, TVG_RANK_MAX_K).
 int launch_rank_rows(const float* values, int64_t ld, int n, int n_rows, int k, int32_t* idx_out, float* val_out, hipStream_t s);

@@ -203,9 +203,11 @@ def load_library(path: str = LIB_PATH):
         "blim_lse_combine": ([vp, i32, vp, vp, i64, vp, vp], C.c_int),
         "blim_tvg_criterion": ([vp, i64, i32, vp, i32, i32, vp, vp], C.c_int),
         "blim_tvg_rank": ([vp, i64, i32, i32, vp, i64, i32, vp, f32, i32, vp, vp, vp, i64, vp], C.c_int),
+        "blim_tvg_rank_within": ([vp, i64, i32, i32, vp, i64, i32, i32, vp, vp, vp, vp, i32, f32, i32, vp, vp, vp], C.c_int),
         "blim_rank_rows": ([vp, i64, i32, i32, i32, vp, vp, vp], C.c_int),
         "blim_tvg_cols": ([vp, i64, i32, i32, vp, i32, vp, i64, i64, vp], C.c_int),
         "blim_score_tvg_first": ([vp, C.POINTER(Batch), vp, vp, i32, vp, i32, vp, f32, i32, vp, vp, vp, vp], C.c_int),
+        "blim_score_tvg_first_within": ([vp, C.POINTER(Batch), vp, vp, i32, vp, i32, i32, vp, vp, vp, vp, i32, f32, i32, vp, vp, vp], C.c_int),
         "blim_tvg_first_cached": ([vp, vp, vp, i32, vp, i32, vp, i64, i32, vp], C.c_int),
         "blim_group_mean_rows": ([vp, vp, i64, i32, i32, i32, i32, vp], C.c_int),
         "blim_assemble_rows": ([vp, vp, i64, i32, vp, vp, i32, vp], C.c_int),
@@ -637,6 +639,23 @@ class Engine:
                                              float(alpha), int(k), _ptr(idx), _ptr(val), _ptr(lp), _stream()), "blim_score_tvg_first")
         return (idx, val, lp) if full else (idx, val)
 
+    def score_tvg_first_within(self, batch: PackedBatch, embeds, rows, k: int, row_of, within, within_off, prior_rows=None, prior_of=None, alpha: float = 0.0,
+                               n_within: Optional[int] = None):
+        """blim_score_tvg_first_within: score_tvg_first's rows / prior_rows; per QUERY q (device int32): row_of [n_q] its row of `rows`, prior_of [n_q] its prior row
+        (< 0: none), within[within_off[q] .. within_off[q + 1]) its list of vocabulary entries -> (idx int32 [n_q, k], val f32 [n_q, k]): the best min(k, m_q)
+        POSITIONS of q's list by the whole-vocabulary term, then -1 / NaN.  n_within: the entries of `within` that count (default: all of them)."""
+        import torch
+        n = int(rows.shape[0])
+        n_q = int(within_off.shape[0]) - 1
+        n_prior = 0 if prior_rows is None else int(prior_rows.shape[0])
+        idx = torch.empty((max(n_q, 0), int(k)), dtype=torch.int32, device=self.device)
+        val = torch.empty((max(n_q, 0), int(k)), dtype=torch.float32, device=self.device)
+        bs = batch.struct(self.max_positions)
+        _check(self.lib.blim_score_tvg_first_within(self.h, C.byref(bs), _ptr(embeds), _ptr(rows), n, _ptr(prior_rows) if n_prior else None, n_prior, n_q,
+                                                    _ptr(row_of), _ptr(prior_of), _ptr(within), _ptr(within_off), int(within.shape[0] if n_within is None else n_within), float(alpha), int(k),
+                                                    _ptr(idx), _ptr(val), _stream()), "blim_score_tvg_first_within")
+        return idx, val
+
     def rank_rows(self, values, k: int):
         """blim_rank_rows over a device f32 [n_rows, n] -> (idx int32 [n_rows, k], val f32 [n_rows, k]): the first k of every row in blim_tvg_rank's order."""
         import torch
@@ -830,6 +849,18 @@ def tvg_rank(logits, n_vocab: int, k: int, idx_out, val_out, prior_logits=None, 
                                         0 if prior_logits is None else prior_logits.shape[1], (0 if prior_logits is None else prior_logits.shape[0]) if n_prior is None else n_prior,
                                         _ptr(prior_of), float(alpha), k, _ptr(idx_out), _ptr(val_out), _ptr(logprob_out), 0 if logprob_out is None else logprob_out.shape[1],
                                         _stream()), "blim_tvg_rank")
+
+
+def tvg_rank_within(logits, n_vocab: int, k: int, within, within_off, idx_out, val_out, row_of=None, prior_logits=None, prior_of=None, alpha: float = 0.0,
+                    n_rows: Optional[int] = None, n_prior: Optional[int] = None, n_q: Optional[int] = None, n_within: Optional[int] = None):
+    """blim_tvg_rank_within: logits f32 [n_rows, ld]; per query q (device int32) row_of [n_q] (None: q), prior_of [n_q], within[within_off[q] .. within_off[q + 1]);
+    idx_out int32 / val_out f32 [>= n_q * k] are written: positions into q's list and the terms' bits, -1 / NaN from the list's length on."""
+    _check(load_library().blim_tvg_rank_within(_ptr(logits), 0 if logits is None else logits.shape[1], n_vocab, logits.shape[0] if n_rows is None else n_rows,
+                                               _ptr(prior_logits), 0 if prior_logits is None else prior_logits.shape[1],
+                                               (0 if prior_logits is None else prior_logits.shape[0]) if n_prior is None else n_prior,
+                                               (within_off.shape[0] - 1) if n_q is None else n_q, _ptr(row_of), _ptr(prior_of), _ptr(within), _ptr(within_off),
+                                               (0 if within is None else within.shape[0]) if n_within is None else n_within, float(alpha), k, _ptr(idx_out),
+                                               _ptr(val_out), _stream()), "blim_tvg_rank_within")
 
 
 def tvg_cols(logits, n_vocab: int, cols, out, out0: int = 0, n_rows: Optional[int] = None, n_cols: Optional[int] = None):

@@ -45,15 +45,66 @@ from .pair_scorer import SEG_MAX, PairScorer, _PackState       # noqa: F401  (SE
 SLOT_ALIGN = 32          # a slot's positions are padded to a multiple of the attention's key tile
 
 
-class SearchRequest(NamedTuple):
-    """One request of GalleryIndex.search_requests: a text over candidates it names (`cand`, with an optional `first_stage` parallel to them) or over the best
-    `shortlist` = K videos of the gallery's TVG ranking, which `prefilter` = K0 >= K narrows first.  A plain tuple of the first three, four or five fields is the same
-    request."""
+class _RequestFields(NamedTuple):
     text: int
     cand: Optional[Sequence[int]] = None
     first_stage: Optional[Sequence[float]] = None
     shortlist: Optional[int] = None
     prefilter: Optional[int] = None
+
+
+_KEEP = object()
+
+
+class SearchRequest(_RequestFields):
+    """One request of GalleryIndex.search_requests: a text over candidates it names (`cand`, with an optional `first_stage` parallel to them) or over the best
+    `shortlist` = K videos of the gallery's TVG ranking, which `prefilter` = K0 >= K narrows first.  A plain tuple of the first three, four or five fields is the same
+    request.  `within` (video indices, each once) confines a shortlist request to a set of the caller's: it is ranked inside the set alone, K and K0 clipped to
+    the set's size.  It is the sixth field, given by keyword -- SearchRequest(t, shortlist=K, within=ids) --, and rides beside the five-field tuple, so a request
+    still unpacks to, and compares as, the five fields it always had.  What follows from that: `==` and `hash` do not see `within` (two requests that differ in
+    their sets alone compare equal), and `_fields` / `_asdict()` list the five fields without it.  `_replace` keeps the set unless `within=` is given; `_make`
+    takes it as a keyword; a request built by either without one has `within` None, as every request had."""
+    within = None                                  # (the default of every construction path, tuple.__new__ included)
+
+    def __new__(cls, *fields, within=None, **named):
+        self = super().__new__(cls, *fields, **named)
+        self.within = within
+        return self
+
+    @classmethod
+    def _make(cls, iterable, within=None):
+        self = super()._make(iterable)
+        self.within = within
+        return self
+
+    def _replace(self, within=_KEEP, **named):
+        out = super()._replace(**named)
+        out.within = self.within if within is _KEEP else within
+        return out
+
+    def __repr__(self):
+        return super().__repr__() if self.within is None else f"{super().__repr__()[:-1]}, within={self.within!r})"
+
+
+def check_within(within, n_videos: int) -> np.ndarray:
+    """The rule of a request's set, stated once: non-empty, integer video indices in 0 .. n_videos - 1, none twice.  -> the set ASCENDING, int64 (position order is
+    then the whole gallery's tie order); ValueError names the rule."""
+    try:
+        raw = np.asarray(within)
+        w = raw.astype(np.int64).reshape(-1)
+        whole = raw.dtype != bool and bool((w == raw.reshape(-1)).all())
+    except (TypeError, ValueError):
+        whole = False
+    if not whole:
+        raise ValueError("within: a list of integer video indices")
+    if len(w) == 0:
+        raise ValueError("within: an empty set of videos")
+    if w.min() < 0 or w.max() >= n_videos:
+        raise ValueError(f"within: video index {int(w.min() if w.min() < 0 else w.max())} outside 0 .. {int(n_videos) - 1}")
+    w = np.sort(w)
+    if (w[1:] == w[:-1]).any():
+        raise ValueError(f"within: video index {int(w[1:][w[1:] == w[:-1]][0])} named twice")
+    return w
 
 
 def check_shortlist(K, K0, n_videos: int) -> Tuple[Optional[int], Optional[int]]:
@@ -612,6 +663,7 @@ class GalleryIndex(_PrefixIndex):
         self._sync_texts()
         self.shortlist_stats = {"queries": 0, "passes": 0, "pairs": 0}      # texts shortlisted, stage-1 passes (one tvg_gallery each), the (text, video) pairs those scored
         self.prefilter_stats = {"queries": 0, "passes": 0, "rows": 0, "kept": 0}   # texts prefiltered, stage-0 passes (one tvg_first each), the logits rows those ranked, the videos kept
+        self.within_stats = {"queries": 0, "candidates": 0}                  # texts searched inside a set of the caller's, the videos those sets held
 
     def _count_texts(self) -> int:
         return len(self.s.vtg_split)
@@ -807,24 +859,34 @@ class GalleryIndex(_PrefixIndex):
                 np.stack([b[1] for b in best]) if best else np.zeros((0, k), stage.dtype))
 
     # ---- the prefilter: the gallery ranked on the device by the clip-0 summand of the TVG score, the best K0 kept for the likelihood
-    def prefilter(self, texts, k0: int, cpn: bool = False, alpha=(0.0, 0.0)) -> np.ndarray:
+    def prefilter(self, texts, k0: int, cpn: bool = False, alpha=(0.0, 0.0), within=None):
         """The K0 videos of each text that log P(clip 0 of the video | text) ranks first (minus alpha[0] x the candidate prior's clip-0 term with cpn): ONE
         PairScorer.tvg_first pass for all texts, one logits row per distinct prompt whatever the gallery's size.  -> cand [Q, min(k0, N)] video indices, ASCENDING
-        (a set: what ranks it is stage 1).  ValueError as check_shortlist."""
-        _, k0 = check_shortlist(None, k0, len(self.s.video))
+        (a set: what ranks it is stage 1).  ValueError as check_shortlist.
+        within: one set of video indices per text (check_within's rule) -- text q keeps the min(k0, len(within[q])) videos OF ITS SET that the same values rank
+        first, still one pass and one row per distinct prompt.  -> a list of Q ascending arrays, one per text."""
         texts = np.asarray(texts, dtype=np.int64).reshape(-1)
+        if within is not None:
+            if len(within) != len(texts):
+                raise ValueError(f"prefilter: within holds {len(within)} sets for {len(texts)} texts")
+            sets = [check_within(w, len(self.s.video)) for w in within]
+            k0s = [check_shortlist(None, k0, len(w))[1] for w in sets]
+            self.within_stats["queries"] += len(texts); self.within_stats["candidates"] += int(sum(len(w) for w in sets))
+            return self._stage0(texts, k0s, cpn, alpha, within=sets)
+        _, k0 = check_shortlist(None, k0, len(self.s.video))
         kept = self._stage0(texts, [k0] * len(texts), cpn, alpha)
         return np.stack(kept) if kept else np.zeros((0, k0), np.int64)
 
-    def _stage0(self, texts, k0s, cpn: bool, alpha) -> List[np.ndarray]:
+    def _stage0(self, texts, k0s, cpn: bool, alpha, within=None) -> List[np.ndarray]:
         """ONE stage-0 pass at the largest K0 (checked and clipped by the caller): text q keeps the first k0s[q] of its own order -- a smaller K0's survivors are a
-        prefix of a larger one's -- sorted ascending."""
+        prefix of a larger one's -- sorted ascending.  within: text q's own set (checked by the caller, k0s[q] <= its size): its order is then the set's alone."""
         texts = np.asarray(texts, dtype=np.int64).reshape(-1)
         if not len(texts):
             return []
         self.s._need_tvg(texts)
         self._tvg_state()
-        idx, _ = self.s.tvg_first(texts, max(k0s), cpn=cpn, alpha=float(alpha[0]))
+        more = {} if within is None else {"within": within}
+        idx, _ = self.s.tvg_first(texts, max(k0s), cpn=cpn, alpha=float(alpha[0]), **more)
         st = self.prefilter_stats
         st["queries"] += len(texts); st["passes"] += 1; st["rows"] += len(np.unique(texts)); st["kept"] += int(sum(k0s))
         return [np.sort(row[:k]) for row, k in zip(idx, k0s)]
@@ -837,7 +899,9 @@ class GalleryIndex(_PrefixIndex):
         zero, and the TVG candidate term of its blend IS its stage-1 value: it is not computed a second time.  A shortlist request with a `prefilter` K0 >= K is
         narrowed first: the prefiltered requests of the batch share ONE stage-0 pass (prefilter, at the largest K0: a smaller K0's survivors are the first K0 of the
         same order); their stage-1 terms are ONE PairScorer.tvg call over their surviving pairs (minus alpha[0] x the prior over those K0 candidates with cpn), of
-        which each keeps its best K as a shortlist request does.  All requests then share ONE vtg_pairs pass (one pass of a lazy index).
+        which each keeps its best K as a shortlist request does.  A shortlist request with `within` (SearchRequest's keyword) is ranked inside
+        that set alone: those with a K0 share ONE stage-0 pass of their own (PairScorer.tvg_first(within=), K0 clipped to the set), the others keep their whole set,
+        and ONE PairScorer.tvg call scores what was kept.  All requests then share ONE vtg_pairs pass (one pass of a lazy index).
         -> [(order [k_q], blended [k_q])] in request order."""
         reqs = self._checked(requests, finetuned)
         if not reqs:
@@ -858,9 +922,19 @@ class GalleryIndex(_PrefixIndex):
         clipped to the gallery) -- or the ValueError that names what it lacks."""
         N, reqs = len(self.s.video), []
         for r in requests:
-            r = SearchRequest(*r)
+            r = r if isinstance(r, SearchRequest) else SearchRequest(*r)
             if r.prefilter is not None and r.shortlist is None:
                 raise ValueError("search_requests: a prefilter K0 narrows a shortlist: the request needs its K")
+            if r.within is not None:
+                if r.cand is not None or r.first_stage is not None:
+                    raise ValueError("search_requests: within confines a shortlist to a set of videos; a request that names its candidates"
+                                     f"{'' if r.cand is not None else ' first stage'} takes no within")
+                if r.shortlist is None:
+                    raise ValueError("search_requests: within confines a shortlist: the request needs its K")
+                w = check_within(r.within, N)
+                K, K0 = check_shortlist(r.shortlist, r.prefilter, len(w))
+                reqs.append(SearchRequest(int(r.text), shortlist=K, prefilter=K0, within=w))
+                continue
             if (r.cand is None) == (r.shortlist is None):
                 raise ValueError("search_requests: a request takes candidates or a shortlist K, one of the two")
             if r.shortlist is not None:
@@ -882,21 +956,35 @@ class GalleryIndex(_PrefixIndex):
         take the best K of ONE stage-1 pass; the prefiltered ones the best K of ONE PairScorer.tvg call over what ONE stage-0 pass kept; the value they were ranked
         by is their term."""
         cands, terms = [r.cand for r in reqs], [None] * len(reqs)
-        short = [n for n, r in enumerate(reqs) if r.shortlist is not None and r.prefilter is None]
-        pre = [n for n, r in enumerate(reqs) if r.prefilter is not None]
+        short = [n for n, r in enumerate(reqs) if r.shortlist is not None and r.prefilter is None and r.within is None]
+        pre = [n for n, r in enumerate(reqs) if r.prefilter is not None and r.within is None]
+        win = [n for n, r in enumerate(reqs) if r.within is not None]
         if short:
             for n, row in zip(short, self._stage1([reqs[n].text for n in short], cpn, alpha)):
                 cands[n], terms[n] = self._best(row, reqs[n].shortlist)
-        if pre:
-            texts = [reqs[n].text for n in pre]
-            kept = self._stage0(texts, [reqs[n].prefilter for n in pre], cpn, alpha)
+        def keep_best(ns, texts, kept):                                  # ONE PairScorer.tvg call over what was kept; each request keeps its best K of it
             pairs, cuts = request_pairs(texts, kept)
             term = self.s.tvg(pairs)
             if cpn:
                 term = term - alpha[0] * self._t2v_prior(texts, kept)
-            for n, cand, row in zip(pre, kept, np.split(term, cuts)):
+            for n, cand, row in zip(ns, kept, np.split(term, cuts)):
                 order, terms[n] = self._best(row, reqs[n].shortlist)
                 cands[n] = cand[order]
+        if pre:
+            texts = [reqs[n].text for n in pre]
+            keep_best(pre, texts, self._stage0(texts, [reqs[n].prefilter for n in pre], cpn, alpha))
+        if win:                                                         # (DESIGN.md section 23) inside the caller's set: those with a K0 share a stage-0 pass of their own
+            texts = [reqs[n].text for n in win]
+            self.s._need_tvg(texts)
+            self._tvg_state()
+            st = self.within_stats
+            st["queries"] += len(win); st["candidates"] += int(sum(len(reqs[n].within) for n in win))
+            kept = [reqs[n].within for n in win]
+            narrowed = [i for i, n in enumerate(win) if reqs[n].prefilter is not None]
+            some = self._stage0([texts[i] for i in narrowed], [reqs[win[i]].prefilter for i in narrowed], cpn, alpha, within=[kept[i] for i in narrowed])
+            for i, cand in zip(narrowed, some):
+                kept[i] = cand
+            keep_best(win, texts, kept)
         return cands, terms
 
     def _given_terms(self, reqs: List[SearchRequest], cands, terms, cpn: bool, alpha, c) -> None:

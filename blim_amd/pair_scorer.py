@@ -691,8 +691,8 @@ class PairScorer(CalibrationMixin):
             yield st.finish()
 
     def _label_inverse(self):
-        """-> (device int64 [n_vocab]: the video of each vocabulary entry, device int64 [N]: tvg_video_labels), memoised per vocab_version.  The rank kernel ranks
-        VOCABULARY entries; they name videos only when tvg_video_labels is a permutation of arange(N)."""
+        """-> (device int64 [n_vocab]: the video of each vocabulary entry, device int64 [N]: tvg_video_labels), memoised per vocab_version with their host copies
+        (_label_inverse_host).  The rank kernel ranks VOCABULARY entries; they name videos only when tvg_video_labels is a permutation of arange(N)."""
         import torch
         memo = getattr(self, "_label_inv", None)
         if memo is None or memo[0] != self.vocab_version:
@@ -703,16 +703,27 @@ class PairScorer(CalibrationMixin):
                                  f"{len(np.unique(lab))} distinct labels)")
             inv = np.empty(N, dtype=np.int64)
             inv[lab] = np.arange(N)
-            memo = self._label_inv = (self.vocab_version, torch.from_numpy(inv).to(self.device), torch.from_numpy(lab).to(self.device))
+            memo = self._label_inv = (self.vocab_version, torch.from_numpy(inv).to(self.device), torch.from_numpy(lab).to(self.device), inv, lab)
         return memo[1], memo[2]
 
-    def tvg_first(self, texts, k: int, cpn: bool = False, alpha: float = 0.0, full: bool = False):
+    def _label_inverse_host(self):
+        """_label_inverse's two arrays as numpy int64, from the same memo."""
+        self._label_inverse()
+        return self._label_inv[3], self._label_inv[4]
+
+    def tvg_first(self, texts, k: int, cpn: bool = False, alpha: float = 0.0, full: bool = False, within=None):
         """The best k videos of each text by log P(clip 0 of the video | text) -- minus alpha x the candidate prior's clip-0 term with cpn -- ranked ON THE DEVICE
         (Engine.score_tvg_first): -> (idx int64 [Q, k] video indices, val f32 [Q, k], and with full lp f32 [Q, N], the log-probabilities by video index).  The order
-        is descending with ties to the lower VOCABULARY entry.  Each distinct prompt is computed once; a value does not depend on what shares its call."""
+        is descending with ties to the lower VOCABULARY entry.  Each distinct prompt is computed once; a value does not depend on what shares its call.
+        within: one array of video indices per text -- text q is ranked inside its own set alone (Engine.score_tvg_first_within).  Each set is made unique and
+        sorted by vocabulary entry, so the kernel's position order is the tie order above and the result is the whole-gallery order filtered to the set, every
+        value the same bits (the normaliser stays over the whole vocabulary).  Text q gets min(k, len(within[q])) real places, the rest are -1 / NaN; k is then
+        bounded by TVG_RANK_MAX_K alone.  Texts with one prompt still share one packed row."""
         texts = np.asarray(texts, dtype=np.int64).reshape(-1)
-        inv, lab = self._label_inverse()
         N, k = self.n_vocab, int(k)
+        if within is not None:
+            return self._tvg_first_within(texts, k, cpn, alpha, full, within)
+        inv, lab = self._label_inverse()
         if not 1 <= k <= N:
             raise ValueError(f"tvg_first: k = {k} outside 1 .. {N}")
         idx = np.zeros((len(texts), k), dtype=np.int64)
@@ -727,6 +738,44 @@ class PairScorer(CalibrationMixin):
                 if full:
                     lp[outs] = vl[r]
         return (idx, val, lp) if full else (idx, val)
+
+    def _tvg_first_within(self, texts, k: int, cpn: bool, alpha: float, full: bool, within):
+        """tvg_first(within=): per plan of iter_tvg_first one query per text -- row_of carries the fan-out that out_index carries for the whole-gallery form."""
+        import torch
+        from .engine import TVG_RANK_MAX_K
+        if full:
+            raise ValueError("tvg_first: full=True returns the whole gallery's rows and takes no within")
+        if not 1 <= k <= TVG_RANK_MAX_K:
+            raise ValueError(f"tvg_first: k = {k} outside 1 .. TVG_RANK_MAX_K = {TVG_RANK_MAX_K}")
+        if len(within) != len(texts):
+            raise ValueError(f"tvg_first: within holds {len(within)} sets for {len(texts)} texts")
+        N = self.n_vocab
+        inv, lab = self._label_inverse_host()
+        entries = []                                                         # per text: its set as vocabulary entries, unique and ascending
+        for q, w in enumerate(within):
+            w = np.asarray(w, dtype=np.int64).reshape(-1)
+            if len(w) and (w.min() < 0 or w.max() >= N):
+                raise ValueError(f"tvg_first: within[{q}] names a video outside 0 .. {N - 1}")
+            entries.append(np.unique(lab[w]))
+        idx = np.full((len(texts), k), -1, dtype=np.int64)
+        val = np.full((len(texts), k), np.nan, dtype=np.float32)
+        done = []
+        for p in self.iter_tvg_first(texts, cpn):
+            qs = np.concatenate([np.asarray(outs, dtype=np.int64) for outs in p.out_index])
+            row_of = np.concatenate([np.full(len(outs), r, dtype=np.int32) for r, outs in enumerate(p.out_index)])
+            off = np.zeros(len(qs) + 1, dtype=np.int64)
+            np.cumsum([len(entries[q]) for q in qs], out=off[1:])
+            if off[-1] >= 2 ** 31:
+                raise ValueError(f"tvg_first: the sets of one call hold {int(off[-1])} entries, more than an int32 offset reaches")
+            flat = np.concatenate([entries[q] for q in qs] + [np.zeros(1, np.int64)]).astype(np.int32)          # (one entry of padding: never an empty tensor; n_within counts the real ones)
+            dev = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(self.device)
+            done.append((qs, self.run(p, k=k, alpha=float(alpha), within=(dev(row_of, np.int32), dev(flat, np.int32), dev(off, np.int32), int(off[-1])))))
+        for qs, res in done:
+            pos, vv = res[0].cpu().numpy(), res[1].cpu().numpy()
+            for i, q in enumerate(qs):
+                kk = min(k, len(entries[q]))
+                idx[q, :kk], val[q, :kk] = inv[entries[q][pos[i, :kk]]], vv[i, :kk]
+        return idx, val
 
     # ---- execution (device) ---------------------------------------------------------------------
     @contextmanager
@@ -776,16 +825,21 @@ class PairScorer(CalibrationMixin):
             self._register_first_vocab()
             return cache.tvg_first_cols(slots, cols, chunk_rows)
 
-    def run(self, plan: Plan, cache=None, k: int = 1, alpha: float = 0.0, full: bool = False):
+    def run(self, plan: Plan, cache=None, k: int = 1, alpha: float = 0.0, full: bool = False, within=None):
         """One engine call; returns a device f32 tensor [plan.n_pairs].  A plan made over a prefix source (plan.pfx_slot) goes through `cache`, the PrefixCache
         that holds its slots, and is not counted in exec_*: those count the scorer's own calls.  A plan of kind "tvg_first" (k, alpha, full are its arguments)
-        returns Engine.score_tvg_first's tuple instead."""
+        returns Engine.score_tvg_first's tuple instead -- or, with within = (row_of, within, within_off on the device, n_within), one query per entry of row_of,
+        Engine.score_tvg_first_within's."""
         if plan.kind == "tvg_first":
             self._count(plan)
             with self._call_options("tvg"):
                 self._register_first_vocab()
                 embeds = self.engine.assemble(plan.src_index, plan.feats)
                 cpn = plan.prior_rows is not None
+                if within is not None:
+                    row_of, wi, off, n_within = within
+                    return self.engine.score_tvg_first_within(plan.batch, embeds, plan.rows, k, row_of, wi, off, n_within=n_within, prior_rows=plan.prior_rows,
+                                                              prior_of=plan.labels[row_of.long()].contiguous() if cpn else None, alpha=alpha if cpn else 0.0)
                 return self.engine.score_tvg_first(plan.batch, embeds, plan.rows, k, prior_rows=plan.prior_rows, prior_of=plan.labels if cpn else None,
                                                    alpha=alpha if cpn else 0.0, full=full)
         if plan.pfx_slot is None:

@@ -59,6 +59,15 @@ the `added` reply), so a video added from frames and the same video added from i
 and `frames`.  An unreadable or non-uint8 file, a wrong rank or channel count, no frame, or a tower that cannot be loaded gets its error line.  A `--query_video` FILE
 ending in `.npy` is such a frame stack too.  The tower is created at the first use of frames, from `--vision_model_path` (default `--model_path`) or, for dry runs,
 `--vision_synthetic SEED`.
+
+Inside a set of the caller's.  A request may carry `"within": [video ids]` or `"within_idx": [indices]` next to `"shortlist": K` (or next to the
+default K under `--candidates tvg`), with `"prefilter": K0` or the `--prefilter` default optional: the shortlist -- and the prefilter in front of it -- rank the
+videos of the set alone, K and K0 clipped to its size M, and the answer gains `"within": M`.  The clip-0 values are the whole gallery's (the normaliser still runs
+over every registered video, which keeps a score equal to the evaluation's), so the result is the unfiltered order filtered to the set, at the cost of the unfiltered
+request.  A caller can hide taken-down videos this way; removing a video from the gallery is not built.  Both forms at once, `within` with `candidates` /
+`candidate_idx` / `first_stage`, `within` with neither a shortlist nor `--candidates tvg`, an empty list, an unknown id and a repeated id each get an error line;
+an `add_video` request refuses the keys as it refuses other query keys, and a set behind the barrier may name the new video.  One-shot: `--within_ids FILE` (one
+video id per line; t2v, `--candidates tvg`) confines every query of the run.  A `within:` stderr line counts the requests that carried a set and the videos named.
 """
 from __future__ import annotations
 
@@ -100,6 +109,9 @@ def get_args_parser():
     p.add_argument("--prefilter", default=None, type=int, metavar="K0",
                    help="--candidates tvg, t2v: the whole gallery is first ranked on the device by the clip-0 term of the TVG likelihood (one logits row per query, "
                         "whatever the gallery's size), the TVG ranking runs on the best K0 >= --shortlist only")
+    p.add_argument("--within_ids", default=None, type=str, metavar="FILE",
+                   help="--candidates tvg, t2v one-shot: one video id per line; every query of the run is shortlisted (and, with --prefilter, prefiltered) inside this "
+                        "set of videos alone, K and K0 clipped to its size")
     p.add_argument("--caption_prefilter", default=None, type=int, metavar="K0",
                    help="--candidates tvg, v2t: every caption is first ranked on the device by the clip-0 term of the query likelihood, read from the cached prompts' "
                         "stored rows (no decode, one pass for all query videos), the TVG ranking runs on the best K0 >= --shortlist captions only")
@@ -217,6 +229,13 @@ def check_args(args, world: int = 1) -> None:
             raise SystemExit("search: --prefilter narrows the gallery before --candidates tvg ranks it (give --candidates tvg)")
         if K0 < 1 or K0 < shortlist_k(args):
             raise SystemExit(f"search: --prefilter must be at least --shortlist ({shortlist_k(args)}): the shortlist is taken from the videos it keeps")
+    if getattr(args, "within_ids", None) is not None:
+        if v2t:
+            raise SystemExit("search: --within_ids confines the t2v shortlist to a set of videos (--direction t2v): a set of captions for v2t is not built")
+        if serve:
+            raise SystemExit("search: --within_ids applies to the one-shot queries; a --serve request carries its own set (\"within\" / \"within_idx\")")
+        if args.candidates != "tvg":
+            raise SystemExit("search: --within_ids confines the shortlist --candidates tvg takes (give --candidates tvg)")
     K0 = args.caption_prefilter
     if K0 is not None:
         if not v2t:
@@ -359,12 +378,14 @@ def default_candidates(mode: str, row, n: int, k: int):
     return cand, None if row is None else row[cand]
 
 
-def answer_line(query: str, ranked_as: str, ranked, scores, shortlisted=None, prefiltered=None, head=None) -> str:
+def answer_line(query: str, ranked_as: str, ranked, scores, shortlisted=None, prefiltered=None, head=None, within=None) -> str:
     """One stdout answer: {**head (serve: the request's id), "query", ranked_as ("videos" | "texts"): the ranked ids, "scores", then "shortlisted": K and
-    "prefiltered": K0 where the candidates came from the shortlist / through the prefilter}."""
+    "prefiltered": K0 where the candidates came from the shortlist / through the prefilter, and "within": M, the size of the set the request was confined to}."""
     more = {} if shortlisted is None else {"shortlisted": shortlisted}
     if prefiltered is not None:
         more["prefiltered"] = prefiltered
+    if within is not None:
+        more["within"] = int(within)
     return json.dumps({**(head or {}), "query": query, ranked_as: list(ranked), "scores": [float(x) for x in scores], **more})
 
 
@@ -490,7 +511,40 @@ class Server:
             raise BadRequest("first_stage is parallel to the candidates: a shortlist request names none")
         return None, None, int(K)
 
-    def _prefilter(self, req, shortlist):
+    def _within(self, req, shortlist):
+        """-> the set of a request that carries `"within"` (video ids) or `"within_idx"` (indices), as ascending video indices; None: it carries neither."""
+        np = self.np
+        if "within" not in req and "within_idx" not in req:
+            return None
+        if "within" in req and "within_idx" in req:
+            raise BadRequest("give within (video ids) or within_idx (indices), one form of the set")
+        other = [k for k in ("candidates", "candidate_idx", "first_stage") if k in req]
+        if other:
+            raise BadRequest(f"within confines a shortlist to a set of videos: a request with {other[0]} names its own candidates and takes no within")
+        if shortlist is None:
+            raise BadRequest("within confines a shortlist: give shortlist (or run --candidates tvg)")
+        given = req.get("within", req.get("within_idx"))
+        if not isinstance(given, list):
+            raise BadRequest("within / within_idx must be a list")
+        if not given:
+            raise BadRequest("the within list is empty")
+        if "within" in req:
+            if any(isinstance(v, (dict, list)) for v in given):
+                raise BadRequest("within must hold video ids")
+            unknown = [v for v in given if str(v) not in self.vid_at]
+            if unknown:
+                raise BadRequest(f"within: unknown video id {unknown[0]!r}")
+            idx = [self.vid_at[str(v)] for v in given]
+        else:
+            N = len(self.vids)
+            if any(isinstance(j, bool) or not isinstance(j, int) or not 0 <= j < N for j in given):
+                raise BadRequest(f"within_idx must hold indices in 0 .. {N - 1}")
+            idx = given
+        if len(set(idx)) != len(idx):
+            raise BadRequest("the within list names a video twice")
+        return np.sort(np.asarray(idx, dtype=np.int64))
+
+    def _prefilter(self, req, shortlist, n_videos=None):
         """-> the K0 of a shortlisted request: its own `"prefilter"`, else --prefilter for a request that takes the default K; None: not prefiltered.  The
         shortlist's K and this K0 are held to gallery.check_shortlist here, before the request enters a batch."""
         from .gallery import check_shortlist
@@ -504,7 +558,7 @@ class Server:
         if shortlist is None:
             return None
         try:
-            check_shortlist(shortlist, K0, len(self.vids))
+            check_shortlist(shortlist, K0, len(self.vids) if n_videos is None else n_videos)
         except ValueError as e:
             raise BadRequest(str(e)) from None
         return K0
@@ -530,14 +584,17 @@ class Server:
                 raise BadRequest("topk must be a positive integer")
             t, name = self._text(req)
             cand, fs, shortlist = self._candidates(req, t, "caption" in req)
-            prefilter = self._prefilter(req, shortlist)
+            within = self._within(req, shortlist)
+            prefilter = self._prefilter(req, shortlist, None if within is None else len(within))
             pre, post, resp = self.s.vtg_split[t]
             limit = getattr(self.s, "max_row_len", None)
-            if limit is not None and len(pre) + int((self.n_vid if cand is None else self.n_vid[cand]).max()) + len(post) >= limit:
+            seen = within if within is not None else cand                   # the videos the request may rerank
+            if limit is not None and len(pre) + int((self.n_vid if seen is None else self.n_vid[seen]).max()) + len(post) >= limit:
                 raise BadRequest(f"tokenizer_model_max_length = {limit} leaves no response token of this query after a candidate's video tokens")
             if self.finetuned and self.args.c[0] < 1 and self.s.tvg_split[t] is None:
                 raise BadRequest("a fine-tuned blend with c0 < 1 needs the query's TVG row (rows without tvg_ids / tvg_labels have none)")
-            return {"id": rid, "query": name, "text": t, "cand": cand, "fs": fs, "topk": topk, "shortlist": shortlist, "prefilter": prefilter}
+            more = {} if within is None else {"within": within}             # (a request without the field: the dict it always was)
+            return {"id": rid, "query": name, "text": t, "cand": cand, "fs": fs, "topk": topk, "shortlist": shortlist, "prefilter": prefilter, **more}
         except BadRequest as e:
             e.id = rid
             raise
@@ -546,7 +603,7 @@ class Server:
     def _add_request(self, rid, req):
         """`{"id", "add_video": {"vid", "features" | "frames"}}`, validated in full before anything changes -> dict(id, add: (vid, tensor, digest)).  `frames` (a
         .npy stack of raw frames) goes through the vision tower first and is a `features` request from there on."""
-        if any(k in req for k in ("caption", "text", "rows", "candidates", "candidate_idx", "first_stage", "shortlist", "prefilter", "topk")):
+        if any(k in req for k in ("caption", "text", "rows", "candidates", "candidate_idx", "first_stage", "shortlist", "prefilter", "topk", "within", "within_idx")):
             raise BadRequest("an add_video request carries no query")
         a = req["add_video"]
         if not isinstance(a, dict) or set(a) not in ({"vid", "features"}, {"vid", "frames"}):
@@ -594,7 +651,7 @@ class Server:
     def _score(self, reqs):
         from .gallery import SearchRequest
         a = self.args
-        return self.gal.search_requests([SearchRequest(r["text"], r["cand"], r["fs"], r["shortlist"], r["prefilter"]) for r in reqs],
+        return self.gal.search_requests([SearchRequest(r["text"], r["cand"], r["fs"], r["shortlist"], r["prefilter"], within=r.get("within")) for r in reqs],
                                         cpn=a.cpn, alpha=a.alpha, c=a.c, finetuned=self.finetuned)
 
     def handle(self, lines, write) -> None:
@@ -646,7 +703,8 @@ class Server:
                 continue
             order, blended = res
             k = len(order) if r["topk"] is None else min(r["topk"], len(order))
-            write(answer_line(r["query"], "videos", [self.vids[int(j)] for j in order[:k]], blended[:k], r["shortlist"], r["prefilter"], head={"id": r["id"]}))
+            write(answer_line(r["query"], "videos", [self.vids[int(j)] for j in order[:k]], blended[:k], r["shortlist"], r["prefilter"], head={"id": r["id"]},
+                              within=None if r.get("within") is None else len(r["within"])))
 
     def summary(self):
         more = {"videos_added": self.videos_added} if self.videos_added else {}             # (a stream without an add_video request: the line it always was)
@@ -803,9 +861,9 @@ def gallery_banner(args, indexes, ready: float) -> str:
             f"tvg mode {s.tvg_mode}, {narrow}, built in {tg.build_seconds:.2f}s {ready}")
 
 
-def report_lines(indexes, serve_summary=None, shortlist_stats=None, prefilter_stats=None):
+def report_lines(indexes, serve_summary=None, shortlist_stats=None, prefilter_stats=None, within_stats=None):
     """The closing stderr lines of a run over `indexes` ([(name, index)]: "gallery", and "text gallery" under v2t), in one order: what the caches did, what their
-    host tiers did (where there is one), `serve:`, `shortlist:` and `prefilter:` (where a pass of theirs ran)."""
+    host tiers did (where there is one), `serve:`, `shortlist:` and `prefilter:` (where a pass of theirs ran), `within:` (where a request carried a set)."""
     tier = lambda h: json.dumps(dict(h.stats.as_dict(), records=h.n_records, record_bytes=h.record_bytes))
     lines = ["; ".join(f"{name} stats: {json.dumps(ix.stats.as_dict())}" for name, ix in indexes)]
     if any(ix.host is not None for _, ix in indexes):
@@ -816,6 +874,8 @@ def report_lines(indexes, serve_summary=None, shortlist_stats=None, prefilter_st
         lines.append(f"shortlist: {json.dumps(_shortlist_line(shortlist_stats))}")
     if prefilter_stats is not None and prefilter_stats["passes"]:
         lines.append(f"prefilter: {json.dumps(_prefilter_line(prefilter_stats))}")
+    if within_stats is not None and within_stats["queries"]:
+        lines.append(f"within: {json.dumps(_within_line(within_stats))}")
     return lines
 
 
@@ -827,6 +887,33 @@ def _shortlist_line(stats):
 def _prefilter_line(stats):
     """The `prefilter:` stderr line: queries prefiltered, stage-0 passes, the logits rows those ranked and the videos kept for stage 1."""
     return {"queries": int(stats["queries"]), "stage0_passes": int(stats["passes"]), "stage0_rows": int(stats["rows"]), "kept": int(stats["kept"])}
+
+
+def _within_line(stats):
+    """The `within:` stderr line: queries confined to a set of the caller's, and the videos those sets held."""
+    return {"queries": int(stats["queries"]), "candidates": int(stats["candidates"])}
+
+
+def read_within_ids(path, vids):
+    """--within_ids FILE, one video id per line (blank lines skipped) -> ascending video indices; SystemExit names an empty file, an unknown or a repeated id."""
+    import numpy as np
+    try:
+        with open(path) as f:
+            ids = [ln.strip() for ln in f if ln.strip()]
+    except OSError as e:
+        raise SystemExit(f"search: --within_ids: {e}") from None
+    at = {}
+    for j, v in enumerate(vids):
+        at.setdefault(str(v), j)
+    if not ids:
+        raise SystemExit(f"search: --within_ids {path}: an empty set of videos")
+    unknown = [v for v in ids if v not in at]
+    if unknown:
+        raise SystemExit(f"search: --within_ids: unknown video id {unknown[0]!r}")
+    idx = [at[v] for v in ids]
+    if len(set(idx)) != len(idx):
+        raise SystemExit(f"search: --within_ids names video {ids[[i for i, j in enumerate(idx) if j in idx[:i]][0]]!r} twice")
+    return np.sort(np.asarray(idx, dtype=np.int64))
 
 
 def output_writer(path):
@@ -849,8 +936,9 @@ def run_serve(gal, vids, t2v_iv2, args, write, lines, build_rows=None, content_h
     return summary
 
 
-def run_t2v(gal, vids, t2v_iv2, args, write) -> None:
-    """The one-shot text queries (--query_ids, then one text per --query at the end of the scorer's texts), one answer line each."""
+def run_t2v(gal, vids, t2v_iv2, args, write, within=None) -> None:
+    """The one-shot text queries (--query_ids, then one text per --query at the end of the scorer's texts), one answer line each.  within (--within_ids): the
+    video indices every query's shortlist is confined to."""
     from .gallery import SearchRequest
     n_texts, N = len(gal.s.vtg_split), len(vids)
     n_ds = n_texts - len(args.query)
@@ -860,12 +948,12 @@ def run_t2v(gal, vids, t2v_iv2, args, write) -> None:
         K = K0 = None
         if args.candidates == "tvg":              # the gallery ranked by the TVG candidate term, the best K reranked; the answer is the best --topk of those
             K, K0 = shortlist_k(args), args.prefilter
-            (order, blended), = gal.search_requests([SearchRequest(t, shortlist=K, prefilter=K0)], **blend)
+            (order, blended), = gal.search_requests([SearchRequest(t, shortlist=K, prefilter=K0, within=within)], **blend)
             order, blended = order[:min(args.topk, N)], blended[:min(args.topk, N)]
         else:
             cand, fs = default_candidates(args.candidates, t2v_iv2[t] if t2v_iv2 is not None and t < n_ds else None, N, args.topk)
             order, blended = (x[0] for x in gal.rerank([t], cand[None], first_stage=None if fs is None else fs[None], **blend))
-        write(answer_line(name, "videos", [vids[int(j)] for j in order], blended, K, K0))
+        write(answer_line(name, "videos", [vids[int(j)] for j in order], blended, K, K0, within=None if within is None else len(within)))
 
 
 def run_v2t(tg, vids, v2t_iv2, args, write):
@@ -901,6 +989,8 @@ def main(args):
     check_args(args, int(os.environ.get("WORLD_SIZE", "1")))
     t0 = time.time()
     p = build_problem(args)
+    # --within_ids names videos of the dataset (t2v, one-shot: check_args): a bad file ends the run here, before the scorer and the gallery are built
+    within = None if getattr(args, "within_ids", None) is None else read_within_ids(args.within_ids, p.vids)
     scorer = build_scorer(args, p)
     vids, n_dataset, v2t = p.vids, len(p.video), args.direction == "v2t"
     if args.query_video:                          # v2t: videos outside the dataset join the scorer before the indexes are built; they share one vocabulary
@@ -926,9 +1016,9 @@ def main(args):
     elif v2t:
         shortlisted, prefiltered = run_v2t(indexes[1][1], vids, p.v2t_iv2, args, write), getattr(indexes[1][1], "prefilter_stats", None)
     else:
-        run_t2v(gal, vids, p.t2v_iv2, args, write)
+        run_t2v(gal, vids, p.t2v_iv2, args, write, within)
     close_output()
-    for line in report_lines(indexes, summary, shortlisted, prefiltered):
+    for line in report_lines(indexes, summary, shortlisted, prefiltered, getattr(gal, "within_stats", None)):
         print(line, file=sys.stderr, flush=True)
     for _, ix in reversed(indexes):
         ix.close()

@@ -204,6 +204,13 @@ int blim_score_tvg(blim_engine* e, const blim_batch* b, const void* embeds, cons
  * (BLIM_ERR_STATE), blim_tvg_rank's refusals of k before anything is launched. */
 int blim_score_tvg_first(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, int32_t n_rows, const int32_t* prior_rows, int32_t n_prior,
                          const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, void* stream);
+/* blim_score_tvg_first inside each query's own list of vocabulary entries (additive in ABI v9; pair_scorer.py: tvg_first(within=)): the same launches up to and
+ * including the clip-0 logits of the n_rows + n_prior named rows, the same refusals of state, then blim_tvg_rank_within over the two row blocks: n_q queries,
+ * row_of / prior_of / within / within_off / n_within, alpha, k and idx_out / val_out [n_q, k] are blim_tvg_rank_within's (row_of indexes rows, prior_of indexes
+ * prior_rows).  There is no logprob_out.  blim_tvg_rank_within's refusals of n_q, n_within and k come before anything is launched. */
+int blim_score_tvg_first_within(blim_engine* e, const blim_batch* b, const void* embeds, const int32_t* rows, int32_t n_rows, const int32_t* prior_rows,
+                                int32_t n_prior, int32_t n_q, const int32_t* row_of, const int32_t* prior_of, const int32_t* within, const int32_t* within_off,
+                                int32_t n_within, float alpha, int32_t k, int32_t* idx_out, float* val_out, void* stream);
 
 /* ---- Gallery prefix cache (additive in ABI v9; blim_amd/gallery.py): the K / V of every layer and the last row's final-norm hidden state of prefixes,
  * computed once and kept in device memory, so that a new query is scored on its own continuation tokens alone.  A cache holds prefixes of either kind: a VTG slot
@@ -581,6 +588,19 @@ int blim_tvg_criterion(const float* logits, int64_t ld, int32_t n_vocab, const i
 #define BLIM_TVG_RANK_MAX_K 1024
 int blim_tvg_rank(const float* logits, int64_t ld, int32_t n_vocab, int32_t n_rows, const float* prior_logits, int64_t ld_prior, int32_t n_prior,
                   const int32_t* prior_of, float alpha, int32_t k, int32_t* idx_out, float* val_out, float* logprob_out, int64_t ld_out, void* stream);
+/* blim_tvg_rank inside a caller's list of columns (additive in ABI v9), one workgroup per QUERY q < n_q, since two queries on one logits row may carry different
+ * lists.  All of row_of, prior_of, within and within_off are DEVICE int32 and are never read back.  row_of [n_q] names query q's logits row (NULL: q itself); an
+ * entry outside 0 .. n_rows - 1 makes every term of q a NaN and reads nothing.  prior_of [n_q] is blim_tvg_rank's, per query.  Query q's list is
+ * within[within_off[q] .. within_off[q + 1]) of within [n_within], within_off [n_q + 1]; offsets are clamped to 0 .. n_within and a decreasing pair is an empty
+ * list.  The term of list position p is, bit for bit, blim_tvg_rank's term of column within[p] -- both normalisers stay over the whole row of n_vocab columns --; an
+ * entry outside 0 .. n_vocab - 1 has a quiet-NaN term and reads nothing; a list may repeat an entry, each position is ranked on its own.
+ * idx_out / val_out [n_q, k]: the first min(k, m_q) POSITIONS into q's own list (m_q its length) in blim_tvg_rank's order -- ties to the lower position, NaN last --
+ * and the terms' bits; places from m_q on hold -1 and a quiet NaN.  k > m_q is no error and m_q has no limit.
+ * BLIM_ERR_ARG (the message names the argument): a null logits / within / within_off / idx_out / val_out, n_vocab < 1, n_rows < 1, n_q < 1, n_within < 0, k < 1,
+ * k > BLIM_TVG_RANK_MAX_K, ld / ld_prior below n_vocab, prior_of without prior_logits, n_prior < 0. */
+int blim_tvg_rank_within(const float* logits, int64_t ld, int32_t n_vocab, int32_t n_rows, const float* prior_logits, int64_t ld_prior, int32_t n_prior, int32_t n_q,
+                         const int32_t* row_of, const int32_t* prior_of, const int32_t* within, const int32_t* within_off, int32_t n_within, float alpha, int32_t k,
+                         int32_t* idx_out, float* val_out, void* stream);
 /* blim_tvg_rank's select and sort over GIVEN values (f32 rows of stride ld >= n, n per row): idx_out / val_out [n_rows, k] = the first k of blim_tvg_rank's order
  * applied to the values as they stand -- descending, ties to the lower index, -0 = +0, -inf after every finite value, NaN last and by index among themselves;
  * exact and deterministic.  val_out holds the chosen values' own bits.
