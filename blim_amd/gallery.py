@@ -23,7 +23,10 @@ in pinned host memory, and a key that has a record gets a slot back by a copy (b
 An index follows its scorer: texts that join later (`PairScorer.add_texts`) append keys before the next pass is planned, and
 `GalleryIndex.rerank_requests` scores requests of unequal candidate counts as one pass.  Videos join too (`PairScorer.add_videos`): their keys
 are appended, an eager index fills them into its `spare_slots`, a lazy one admits them on demand, and every memo of a TVG value is keyed by the scorer's
-`vocab_version` -- a video that joins moves the softmax normaliser of every TVG score -- while the cached K / V, the host records and the v2t prior stay.
+`vocab_version` -- a video that joins moves the softmax normaliser of every TVG score -- while the cached K / V, the host records and the v2t prior stay.  Videos
+leave as well (`PairScorer.remove_videos`): indices never move; before the next pass the keys of a removed video leave the key list, `slot_of`,
+the recency stamps, a pending pass's reservations and the host tier (`HostTier.forget`), their slots are free at once -- an eager index with no spare slot can replace
+a video --, a plan made before is refused, and `removed_stats` counts what left.
 
 The shortlist needs no first stage on a fine-tuned checkpoint: `GalleryIndex.shortlist` ranks the whole gallery by the TVG candidate term of
 the blend (`PairScorer.tvg_gallery`: fixed chunks, so a value depends on its text and the gallery alone), `search_requests` reranks the best K with that term reused,
@@ -295,6 +298,17 @@ class HostTier:
                 if committed is not None:
                     committed(key, slot, stamp)
 
+    def forget(self, key) -> bool:
+        """forget_all for one key (its video was removed: DESIGN.md section 24): the record's arena space is free for the next spill, and no later restore can bring
+        the key back.  -> whether the key had a record.  (A copy into the record that is still in flight is ordered before its next use by the stream, as ever.)"""
+        rec = self.rec_of.pop(key, None)
+        self._stamp.pop(key, None)
+        if rec is None:
+            return False
+        self.key_of.pop(rec, None); self.len_of.pop(rec, None); self.tickets.pop(rec, None)
+        self.stats.dropped += 1
+        return True
+
     def forget_all(self) -> None:
         """A weight, adapter or mode change: no record is valid any more (the engine would refuse their slots as stale)."""
         self.stats.dropped += len(self.rec_of)
@@ -362,6 +376,9 @@ class _PrefixIndex:
         self._n_pass = 0
         self._n_texts = 0                # the scorer's texts the keys cover (PairScorer.add_texts: texts join later; _sync_texts)
         self._n_videos = len(scorer.video)   # ... and its videos (PairScorer.add_videos; _sync_videos)
+        self._gone = frozenset(getattr(scorer, "_dead", ()))      # ... and the removed ones it has followed (PairScorer.remove_videos; _sync_videos)
+        self._stale_before = 0               # passes numbered up to this were planned before a removal the index has followed since: run() refuses their plans
+        self.removed_stats = {"videos": 0, "slots_freed": 0, "records_forgotten": 0}     # removed videos followed, the slots their keys gave back, their host records forgotten
         self.s = scorer
         self.m, self.engine = scorer.m, scorer.engine
         if getattr(self.engine, "dtype", "") == "f8":
@@ -392,6 +409,19 @@ class _PrefixIndex:
         evaluation()'s sample and confirmation sample), else a seeded sample of the same sizes."""
         from .calibration import calibration_pairs
         Nv, Nt = len(self.s.video), n_texts
+        if getattr(self.s, "_dead", None):           # (DESIGN.md section 24) live videos only: a refill after a weight change must not sample a tombstone
+            lv = np.nonzero(self.s.live)[0]
+            if first_stage is not None:
+                rows = lv[lv < len(first_stage)]     # (a video that joined at run time has no first-stage row)
+                sub = np.asarray(first_stage)[rows]
+                pairs, confirm = (calibration_pairs(sub, 16, n_queries=q, per_query=8) for q in (32, 256))
+                pairs[:, 0], confirm[:, 0] = rows[pairs[:, 0]], rows[confirm[:, 0]]
+            else:
+                rng = np.random.RandomState(seed)
+                flat = rng.choice(len(lv) * Nt, size=min(2048, len(lv) * Nt), replace=False)
+                both = np.stack([lv[flat // Nt], flat % Nt], axis=1).astype(np.int64)
+                pairs, confirm = both[:256], both
+            return pairs, confirm, len(lv) * min(16, Nt)
         if first_stage is not None:
             pairs = calibration_pairs(first_stage, 16, n_queries=32, per_query=8)
             confirm = calibration_pairs(first_stage, 16, n_queries=256, per_query=8)
@@ -547,6 +577,7 @@ class _PrefixIndex:
     def iter_plans(self, pairs):
         """pairs [P, 2] (video j, text i) -> the engine calls of one pass, planned by PairScorer's planner over this index's slots (the subclass's _plans)."""
         pairs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+        self.s._need_live(pairs[:, 0])               # a removed video is refused by name before the pass opens
         self._sync_texts()
         self._sync_videos()
         p = self._begin_pass(self._needs(pairs))
@@ -595,7 +626,9 @@ class _PrefixIndex:
         _sync_texts, so that a new video meets every known split once.  Keys are appended only, so the slots, the recency stamps, the stats and the host tier's
         records stay valid, and no cache is resized.  A lazy index admits a new key on demand like any miss.  An eager index that was built fills the new keys, in key
         order, into the slots it still has free (spare_slots) with the fill path of build(); the keys beyond them, and a key longer than a slot, keep the in-batch
-        prefix, as a late text's new split does.  The numeric mode is not resolved again (resolve_mode ran on the gallery build() saw)."""
+        prefix, as a late text's new split does.  The numeric mode is not resolved again (resolve_mode ran on the gallery build() saw).
+        Videos that left (PairScorer.remove_videos) are followed first (_follow_removed), so a slot they free is there for a video that joins."""
+        self._follow_removed()
         n = len(self.s.video)
         if n == self._n_videos:
             return
@@ -621,9 +654,28 @@ class _PrefixIndex:
         """The keys videos lo .. hi - 1 bring (none where the keys do not name a video)."""
         return []
 
+    def _follow_removed(self) -> bool:
+        """The index follows the videos that left its scorer since it last looked: what names them is dropped (_forget_videos) and nothing else -- indices never
+        move, no cache is resized or rebuilt, the numeric mode is not resolved again.  A plan made before that may name a slot that is free now, or filled again:
+        the pending pass is dropped and run() refuses every plan of an earlier pass.  -> whether anything left."""
+        dead = frozenset(getattr(self.s, "_dead", ()))
+        if dead == self._gone:
+            return False
+        gone = dead - self._gone
+        self._gone = dead
+        self.removed_stats["videos"] += len(gone)
+        self._forget_videos(gone)
+        self._pass, self._stale_before = None, self._n_pass
+        return True
+
+    def _forget_videos(self, gone) -> None:
+        """The index's state that names the videos `gone` (none where the keys do not name a video)."""
+
     # ---- scoring
     def run(self, plan):
-        if self.fill == "lazy" and getattr(plan, "pass_", None) is not self._pass:
+        self._follow_removed()
+        p = getattr(plan, "pass_", None)
+        if (self.fill == "lazy" and p is not self._pass) or (p is not None and p.no <= self._stale_before):
             raise RuntimeError(f"{type(self).__name__}: this plan belongs to an earlier pass (its slots may have been admitted to other prefixes since): plan again")
         out = self.s.run(plan, self.cache_or_none())
         self._commit(plan)
@@ -677,13 +729,29 @@ class GalleryIndex(_PrefixIndex):
             if k not in at:
                 at[k] = len(at); self.splits[k] = (pre, post); new.append(k)
             ids.append(at[k])
-        videos = range(self._n_videos)               # (the videos the keys cover: one that joined since brings its keys in _sync_videos)
+        dead = getattr(self.s, "_dead", ())          # (a removed video has no key, under a new split either)
+        videos = [j for j in range(self._n_videos) if j not in dead]     # (the videos the keys cover: one that joined since brings its keys in _sync_videos)
         self.keys += [(j, k[0], k[1]) for j in videos for k in new] if not self.keys else [(j, k[0], k[1]) for k in new for j in videos]
         self._split_id = np.concatenate([self._split_id, np.asarray(ids, dtype=np.int64)])
 
     def _video_keys(self, lo: int, hi: int) -> List:
         """Videos lo .. hi - 1 joined: one key per (new video, known split), new videos outermost."""
-        return [(j, k[0], k[1]) for j in range(lo, hi) for k in self.splits]
+        dead = getattr(self.s, "_dead", ())          # (a video that joined and left again before the index looked brings none)
+        return [(j, k[0], k[1]) for j in range(lo, hi) if j not in dead for k in self.splits]
+
+    def _forget_videos(self, gone) -> None:
+        """The keys of the videos `gone` leave the key list the planners walk, slot_of -- their slots are free at once: the eager fill of _sync_videos and the lazy
+        admission of _begin_pass take any slot no key holds --, the recency stamps and the host tier (HostTier.forget: a later restore cannot resurrect them)."""
+        mine = [k for k in self.keys if k[0] in gone]
+        if not mine:
+            return
+        self.keys = [k for k in self.keys if k[0] not in gone]
+        for k in mine:
+            if self.slot_of.pop(k, None) is not None:
+                self.removed_stats["slots_freed"] += 1
+            self._stamp.pop(k, None)
+            if self.host is not None and self.host.forget(k):
+                self.removed_stats["records_forgotten"] += 1
 
     def prefix_len(self, key) -> int:
         j, pre, post = key
@@ -837,6 +905,15 @@ class GalleryIndex(_PrefixIndex):
         N = len(self.s.video)
         stage = self.s.tvg_gallery(texts)
         st = self.shortlist_stats
+        if getattr(self.s, "_dead", None):           #  index-space columns, NaN in a removed one; the prior is looked up for live videos only
+            lv = np.nonzero(self.s.live)[0]
+            st["queries"] += len(texts); st["passes"] += 1; st["pairs"] += len(np.unique(texts)) * len(lv)
+            if cpn:
+                prior = self._t2v_prior(texts, np.tile(lv, (len(texts), 1)))
+                out = np.full(stage.shape, np.nan, dtype=np.result_type(stage, prior))
+                out[:, lv] = stage[:, lv] - alpha[0] * prior
+                stage = out
+            return stage
         st["queries"] += len(texts); st["passes"] += 1; st["pairs"] += len(np.unique(texts)) * N
         if cpn:
             stage = stage - alpha[0] * self._t2v_prior(texts, np.tile(np.arange(N), (len(texts), 1)))
@@ -844,17 +921,18 @@ class GalleryIndex(_PrefixIndex):
 
     @staticmethod
     def _best(stage: np.ndarray, k: int):
-        """One text's stage-1 row [N] -> (the best min(k, N) videos, their values): descending, ties to the lower video index."""
-        order = np.argsort(-stage, kind="stable")[:max(min(int(k), len(stage)), 0)]
+        """One text's stage-1 row [N] -> (the best min(k, N) videos, their values): descending, ties to the lower video index.  A removed video's column is NaN
+        (section 24): it sorts behind every value and is cut off, so N counts the live columns and a removed index is never returned."""
+        order = np.argsort(-stage, kind="stable")[:max(min(int(k), len(stage) - int(np.isnan(stage).sum())), 0)]
         return order.astype(np.int64), stage[order]
 
     def shortlist(self, texts, k: int, cpn: bool = False, alpha=(0.0, 0.0)):
         """The whole gallery ranked by the TVG candidate term of each text: -> (cand [Q, min(k, N)] video indices, best first; their stage-1 scores)."""
-        k, _ = check_shortlist(k, None, len(self.s.video))
+        k, _ = check_shortlist(k, None, self.s.n_live)
         texts = np.asarray(texts, dtype=np.int64).reshape(-1)
         stage = self._stage1(texts, cpn, alpha)
         best = [self._best(row, k) for row in stage]
-        k = min(int(k), stage.shape[1])
+        k = min(int(k), self.s.n_live)
         return (np.stack([b[0] for b in best]) if best else np.zeros((0, k), np.int64),
                 np.stack([b[1] for b in best]) if best else np.zeros((0, k), stage.dtype))
 
@@ -870,10 +948,12 @@ class GalleryIndex(_PrefixIndex):
             if len(within) != len(texts):
                 raise ValueError(f"prefilter: within holds {len(within)} sets for {len(texts)} texts")
             sets = [check_within(w, len(self.s.video)) for w in within]
+            for w in sets:
+                self.s._need_live(w)
             k0s = [check_shortlist(None, k0, len(w))[1] for w in sets]
             self.within_stats["queries"] += len(texts); self.within_stats["candidates"] += int(sum(len(w) for w in sets))
             return self._stage0(texts, k0s, cpn, alpha, within=sets)
-        _, k0 = check_shortlist(None, k0, len(self.s.video))
+        _, k0 = check_shortlist(None, k0, self.s.n_live)
         kept = self._stage0(texts, [k0] * len(texts), cpn, alpha)
         return np.stack(kept) if kept else np.zeros((0, k0), np.int64)
 
@@ -932,13 +1012,14 @@ class GalleryIndex(_PrefixIndex):
                 if r.shortlist is None:
                     raise ValueError("search_requests: within confines a shortlist: the request needs its K")
                 w = check_within(r.within, N)
+                self.s._need_live(w)
                 K, K0 = check_shortlist(r.shortlist, r.prefilter, len(w))
                 reqs.append(SearchRequest(int(r.text), shortlist=K, prefilter=K0, within=w))
                 continue
             if (r.cand is None) == (r.shortlist is None):
                 raise ValueError("search_requests: a request takes candidates or a shortlist K, one of the two")
             if r.shortlist is not None:
-                K, K0 = check_shortlist(r.shortlist, r.prefilter, N)
+                K, K0 = check_shortlist(r.shortlist, r.prefilter, self.s.n_live)     # (K0 clipped to the videos that are left)
                 if r.first_stage is not None:
                     raise ValueError("search_requests: a first stage is parallel to a request's candidates; a shortlist request has none")
                 reqs.append(SearchRequest(int(r.text), shortlist=K, prefilter=K0))
@@ -946,6 +1027,7 @@ class GalleryIndex(_PrefixIndex):
                 cand = np.asarray(r.cand, dtype=np.int64).reshape(-1)
                 if len(cand) == 0:
                     raise ValueError("search_requests: a request has no candidates")
+                self.s._need_live(cand)
                 reqs.append(SearchRequest(int(r.text), cand, r.first_stage))
         if not finetuned and any(r.shortlist is not None for r in reqs):
             raise ValueError("search_requests: a shortlist ranks by the TVG likelihood, which a zero-shot model does not have (finetuned=False)")
@@ -1044,7 +1126,8 @@ class TextGalleryIndex(_PrefixIndex):
 
     def _sync_videos(self, fill: bool = True) -> None:
         """A caption prompt holds no video: a video that joins brings no key here, and the video index follows it.  (The v2t prior is kept per (text, token count),
-        VTG-side: it does not depend on the vocabulary and is not dropped.)"""
+        VTG-side: it does not depend on the vocabulary and is not dropped.)  A video that leaves takes no key either: the call is passed
+        on, and the query entries refuse a removed video by name."""
         super()._sync_videos(fill)
         if fill and self.video_index is not None:
             self.video_index._sync_videos()
@@ -1122,6 +1205,7 @@ class TextGalleryIndex(_PrefixIndex):
             self._prior, self._prior_state = {}, state
         n_vid = lambda j: int(np.prod(s.video[int(j)].shape[-3:-1]))
         videos = np.asarray(videos, dtype=np.int64).reshape(-1)
+        s._need_live(videos)                                 # (a miss is scored over its query video: never over a tombstone)
         cand = np.asarray(cand, dtype=np.int64).reshape(len(videos), -1)
         keys = [(int(i), n_vid(j)) for j, row in zip(videos, cand) for i in row]
         first: Dict[Tuple[int, int], int] = {}
@@ -1142,6 +1226,7 @@ class TextGalleryIndex(_PrefixIndex):
         (log P(video | text)).  Zero-shot: the likelihood term is the (debiased) candidate likelihood alone and no TVG call is made, as there.
         -> (order [Q, k] of candidate text ids, best first; blended scores in that order)."""
         videos, cand, pairs = grid_pairs(videos, cand, query_col=0)
+        self.s._need_live(videos)
         v2t_cand = self.vtg_pairs(pairs).reshape(cand.shape)
         fs = np.zeros(cand.shape) if first_stage is None else np.asarray(first_stage).reshape(cand.shape)
         if cpn:
@@ -1206,6 +1291,7 @@ class TextGalleryIndex(_PrefixIndex):
         -> (cand int64 [Q, min(k0, texts)] text indices, best first: descending, ties to the lower text index; val f32, their values).  ValueError as
         check_shortlist (K0 clipped to the texts); a text without a TVG row is refused by name."""
         videos = np.asarray(videos, dtype=np.int64).reshape(-1)
+        self.s._need_live(videos)
         n = len(self.s.tvg_split)
         _, k0 = check_shortlist(None, k0, n)
         if not len(videos):
@@ -1227,6 +1313,7 @@ class TextGalleryIndex(_PrefixIndex):
         (section 22): ONE prefilter() pass for all videos first, and each video's pass runs over its K0 survivors only, in ascending text order.
         -> (cand [Q, min(k, texts)] text indices, best first; their stage-1 scores)."""
         videos = np.asarray(videos, dtype=np.int64).reshape(-1)
+        self.s._need_live(videos)
         n = len(self.s.tvg_split)
         k = min(check_shortlist(k, prefilter, n)[0], n)
         kept = None if prefilter is None else np.sort(self.prefilter(videos, prefilter)[0], axis=1)
@@ -1241,6 +1328,7 @@ class TextGalleryIndex(_PrefixIndex):
     def rerank_shortlist(self, videos, k: int, cpn: bool = False, alpha=(0.0, 0.0), c=(1.0, 1.0, 1.0, 1.0), prefilter: Optional[int] = None):
         """rerank(videos, shortlist(videos, k), finetuned=True) without a first stage, the query likelihood of the blend being the shortlist's stage-1 value: the TVG
         term is not computed a second time.  prefilter = K0: shortlist's.  -> (order [Q, k] of text ids, best first; blended scores in that order)."""
+        self.s._need_live(videos)
         cand, stage = self.shortlist(videos, k) if prefilter is None else self.shortlist(videos, k, prefilter)
         videos, cand, pairs = grid_pairs(videos, cand, query_col=0)
         v2t_cand = self.vtg_pairs(pairs).reshape(cand.shape)

@@ -113,6 +113,7 @@ class PairScorer(CalibrationMixin):
     """Fused scoring of arbitrary (video, text) pairs.  See the module docstring for what is shared."""
     vocab_version = 0        # (instance state, set by the constructor; here for the indexes' sake: a scorer that never grew reads as version 0)
     has_vocab = False
+    _dead = frozenset()      # the indices remove_videos took out (video[j] is None there); empty for a scorer that never removed anything
 
     def __init__(self, model, vtg_ids, vtg_masks, vtg_labels, tvg_ids, tvg_masks, tvg_labels, video: Sequence, video_vocab,
                  tvg_video_labels, num_clips: int, max_tokens: int = 24576, precise_tvg: bool = True, feat_chunk: int = 64):
@@ -220,8 +221,9 @@ class PairScorer(CalibrationMixin):
         import torch
         videos = list(videos)
         C = self.num_clips
-        ndim = len(self.video[0].shape) if self.video else 3
-        width = int(self.video[0].shape[-1]) if self.video else None
+        ref = next((v for v in self.video if v is not None), None)       # (a removed video is a tombstone: the first live one gives the shapes)
+        ndim = len(ref.shape) if ref is not None else 3
+        width = int(ref.shape[-1]) if ref is not None else None
         for n, v in enumerate(videos):
             shape = tuple(getattr(v, "shape", ()))
             if len(shape) != ndim or len(shape) < 3:
@@ -259,13 +261,87 @@ class PairScorer(CalibrationMixin):
         self.video += videos
         self.tvg_video_labels = np.concatenate([self.tvg_video_labels, labels]).astype(np.int32)
         if vocab_rows is not None and (self._vocab_src is None or int(vocab_rows.shape[0])):
-            src = vocab_rows if self._vocab_src is None else torch.cat([torch.as_tensor(self._vocab_src).to(torch.float32).cpu(), vocab_rows.to(torch.float32).cpu()], dim=0)
-            self._vocab_src, self.n_vocab = src, int(src.shape[0])
-            if self.split_tvg and hasattr(self.engine, "set_video_vocab"):
-                self.engine.set_video_vocab(src)
-                self._vocab_key = self.engine._vocab_key
-            else:
-                self.vocab_cm = _clip_major_vocab(src, self.device, self.m.dtype)
+            self._register_vocab(vocab_rows if self._vocab_src is None else
+                                 torch.cat([torch.as_tensor(self._vocab_src).to(torch.float32).cpu(), vocab_rows.to(torch.float32).cpu()], dim=0))
+        self.vocab_version += 1
+
+    def _register_vocab(self, src) -> None:
+        """The whole vocabulary (float32 source rows [n, clips, M]) registered: with the engine as hi + lo operands, or as the clip-major 16-bit copy."""
+        self._vocab_src, self.n_vocab = src, int(src.shape[0])
+        if self.split_tvg and hasattr(self.engine, "set_video_vocab"):
+            self.engine.set_video_vocab(src)
+            self._vocab_key = self.engine._vocab_key
+        else:
+            self.vocab_cm = _clip_major_vocab(src, self.device, self.m.dtype)
+
+    # ---- videos that leave (DESIGN.md section 24)
+    @property
+    def live(self) -> np.ndarray:
+        """bool [len(video)]: False where remove_videos left a tombstone.  len(video) stays the index space."""
+        out = np.ones(len(self.video), dtype=bool)
+        if self._dead:
+            out[sorted(self._dead)] = False
+        return out
+
+    @property
+    def n_live(self) -> int:
+        return len(self.video) - len(self._dead)
+
+    def _need_live(self, videos) -> None:
+        """ValueError that names the first removed video among `videos` (any array of video indices)."""
+        if self._dead:
+            for j in np.unique(np.asarray(videos, dtype=np.int64)):
+                if int(j) in self._dead:
+                    raise ValueError(f"video {int(j)} was removed")
+
+    def check_removal(self, indices) -> np.ndarray:
+        """remove_videos' checks, changing nothing: -> the indices, int64; ValueError names the rule."""
+        items = list(indices.reshape(-1)) if isinstance(indices, np.ndarray) else list(indices) if isinstance(indices, (list, tuple, range)) else None
+        if items is None or any(isinstance(j, (bool, np.bool_)) or not isinstance(j, (int, np.integer)) for j in items):
+            raise ValueError("remove_videos: a list of integer video indices")
+        idx = np.asarray(items, dtype=np.int64).reshape(-1)
+        N = len(self.video)
+        if len(idx) and (idx.min() < 0 or idx.max() >= N):
+            raise ValueError(f"remove_videos: video index {int(idx.min() if idx.min() < 0 else idx.max())} outside 0 .. {N - 1}")
+        srt = np.sort(idx)
+        if (srt[1:] == srt[:-1]).any():
+            raise ValueError(f"remove_videos: video index {int(srt[1:][srt[1:] == srt[:-1]][0])} named twice")
+        gone = [int(j) for j in idx if int(j) in self._dead]
+        if gone:
+            raise ValueError(f"remove_videos: video {gone[0]} was removed already")
+        if len(idx) >= self.n_live:
+            raise ValueError(f"remove_videos: {len(idx)} of {self.n_live} videos: at least one video must remain")
+        return idx
+
+    def remove_videos(self, indices) -> None:
+        """Videos that leave the scorer, the mirror image of add_videos.  Every index is checked before anything changes (check_removal).
+        TOMBSTONES: a removed index is never reused and no other index moves -- video[j] becomes None, its cached projected rows are dropped, tvg_video_labels[j]
+        becomes -1, `live` / `n_live` say what is left.  A vocabulary entry leaves with its last live video: the float32 source rows of the surviving entries, in
+        their order, are registered again whole (the path _join_videos takes), the surviving labels are compacted to 0 .. n_vocab - 1 in their old order, and
+        vocab_version is bumped -- gallery_feats(), _label_inverse and every memo of a TVG value keyed by it are computed again, over the gallery as it now is.  A
+        scorer built without a vocabulary removes the videos without touching one.  Every entry that takes video indices refuses a removed one by name."""
+        import torch
+        idx = self.check_removal(indices)
+        if not len(idx):
+            return
+        labels = np.asarray(self.tvg_video_labels, dtype=np.int32).copy()
+        old = labels[idx]
+        for j in idx:
+            self.video[int(j)] = None
+            self._vfeat.pop((int(j), True), None); self._vfeat.pop((int(j), False), None)
+        labels[idx] = -1
+        self._dead = self._dead | frozenset(int(j) for j in idx)
+        self._upcoming, self._upcoming_pos = {}, {}                         # (a look-ahead order may name what just left)
+        if self.has_vocab and self._vocab_src is not None:
+            still = set(labels[labels >= 0].tolist())
+            keep = np.ones(self.n_vocab, dtype=bool)
+            keep[[int(l) for l in old if 0 <= int(l) < self.n_vocab and int(l) not in still]] = False
+            if not keep.all():
+                new_of = np.cumsum(keep) - 1                                 # old entry -> its place among the survivors
+                at = (labels >= 0) & (labels < self.n_vocab)
+                labels[at] = new_of[labels[at]]
+                self._register_vocab(torch.as_tensor(self._vocab_src).to(torch.float32).cpu()[torch.from_numpy(np.nonzero(keep)[0])])
+        self.tvg_video_labels = labels.astype(np.int32)
         self.vocab_version += 1
 
     def _need_tvg(self, texts) -> None:
@@ -284,6 +360,8 @@ class PairScorer(CalibrationMixin):
         per-video call; what changes is the fixed cost -- one upload + six launches per video was 0.4 ms x N on EVERY rank of a sharded
         evaluation (every rank needs the clip features of nearly all videos), the part of the job that did not shrink with the world size."""
         key = (int(j), bool(tvg))
+        if key[0] in self._dead:
+            raise ValueError(f"video {key[0]} was removed")
         f = self._vfeat.get(key)
         if f is None:
             self._project_chunk(int(j), bool(tvg))
@@ -293,6 +371,7 @@ class PairScorer(CalibrationMixin):
     def expect(self, video_ids, tvg: bool) -> None:
         """Order in which the pass being planned will first ask for its videos (chunked projection looks ahead along it)."""
         ids = np.asarray(video_ids, dtype=np.int64)
+        self._need_live(ids)
         _, first = np.unique(ids, return_index=True)
         self._upcoming[bool(tvg)] = [int(v) for v in ids[np.sort(first)]]
         self._upcoming_pos[bool(tvg)] = 0
@@ -305,6 +384,8 @@ class PairScorer(CalibrationMixin):
         in shape or no process group is up; then video_feat() projects on demand as before."""
         import torch
         if (world <= 1 and not dist_utils.force_collective()) or not dist_utils.is_dist_avail_and_initialized() or not hasattr(self.m, "project_many"):
+            return False
+        if self._dead:                                                       # (row blocks are cut over index space: a scorer with tombstones projects on demand)
             return False
         N = len(self.video)
         if len({tuple(v.shape) for v in self.video}) != 1:
@@ -331,7 +412,7 @@ class PairScorer(CalibrationMixin):
         rows}, e.g. an earlier evaluation's, handed in by the caller) -- what the all-gather would have delivered; the all-gather's own time is NOT part of
         an emulated rank's clock.  Rows of another width (another TVG mode) are not adopted; such videos are projected on demand as before."""
         N = len(self.video)
-        if world <= 1 or not peers or len({tuple(v.shape) for v in self.video}) != 1:
+        if world <= 1 or not peers or self._dead or len({tuple(v.shape) for v in self.video}) != 1:
             return False
         s_, e_ = dist_utils.row_block(N, world, rank)
         self.expect(np.arange(s_, e_), True)
@@ -391,6 +472,8 @@ class PairScorer(CalibrationMixin):
 
     def _vtg_items(self, pairs: np.ndarray, cpn: bool, base: int):
         """Groups of one VTG pass: (video j or None for a prior, its token count, texts, output slots per text), output slot of pair p = base + p."""
+        if len(pairs):
+            self._need_live(pairs[:, 0])
         if cpn:
             texts, inv = np.unique(pairs[:, 1], return_inverse=True)
             # the prior masks the video keys but keeps their positions: every video must contribute the same number of tokens,
@@ -425,6 +508,8 @@ class PairScorer(CalibrationMixin):
         the position of the prefix's last token in `rows`).  The group itself keeps the in-batch prefix: a slot is readable from the next call on."""
         st = _PackState(self, "vtg", slots)
         for (j, nv, texts_g, outs_g) in items:
+            if j is not None and j in self._dead:
+                raise ValueError(f"video {j} was removed")
             pre, post, _ = self.vtg_split[texts_g[0]]
             slot = -1 if slots is None or j is None else slots.slot_of.get((j, pre.tobytes(), post.tobytes()), -1)
             if j is None:
@@ -497,6 +582,7 @@ class PairScorer(CalibrationMixin):
         st = box[0]
         if len(pairs):
             self._need_tvg(pairs[:, 1])
+            self._need_live(pairs[:, 0])                                     # (a tombstone's label is -1: it never reaches the engine)
         # The continuations of one prefix -- the C - 1 clip tokens of every candidate video of a text (prior: last prompt token + clip tokens) -- are
         # packed into ONE sequence whose segments do not see each other (blim_batch.own_start): the 32-query attention blocks are dense instead of
         # holding 3 - 4 queries each (2,919 -> ~500 blocks per 13,700-token call at the reference's shapes) and the planner adds one sequence per
@@ -596,16 +682,17 @@ class PairScorer(CalibrationMixin):
         return SEG_MAX // max(self.num_clips - 1, 1)
 
     def gallery_feats(self):
-        """The TVG feature rows of every video as ONE device tensor [N * C, Hw], video j's rows at j * C as video_feat(j, True) lays them out (its own values:
-        a concatenation).  Built once per (weights version, split_tvg, vocab_version) and dropped when one changes (add_videos bumps the last: the cached per-video rows
+        """The TVG feature rows of every live video as ONE device tensor [n_live * C, Hw], the rows of the p-th live video (ascending index; video j itself in a
+        scorer without tombstones) at p * C as video_feat(j, True) lays them out (its own values: a concatenation).  Built once per (weights version, split_tvg, vocab_version) and dropped when one changes (add_videos bumps the last: the cached per-video rows
         stay, the concatenation is made again); a call of iter_tvg_gallery names it as its feature rows."""
         import torch
         key = (getattr(self.engine, "weights_version", None), bool(self.split_tvg), self.vocab_version)
         memo = getattr(self, "_gfeat", None)
         if memo is None or memo[0] != key:
-            N, C = len(self.video), self.num_clips
-            self.expect(np.arange(N), True)
-            rows = [self.video_feat(j, True) for j in range(N)]
+            C = self.num_clips
+            lv = np.nonzero(self.live)[0]                                    # (the live videos, ascending: the p-th of them has its rows at p * C)
+            self.expect(lv, True)
+            rows = [self.video_feat(int(j), True) for j in lv]
             if any(int(r.shape[0]) != C for r in rows):
                 raise ValueError(f"tvg_gallery: every video must project to num_clips = {C} TVG rows")
             memo = self._gfeat = (key, torch.cat(rows, dim=0))
@@ -626,10 +713,14 @@ class PairScorer(CalibrationMixin):
         if not len(texts) or not N:
             return
         self._need_tvg(texts)
+        # the fixed chunks are cut over the LIVE videos in ascending index order: a scorer with tombstones plans the calls of a scorer built
+        # from the survivors, and only the output slots are index space
+        lv = np.nonzero(self.live)[0] if self._dead else np.arange(N)
+        L = len(lv)
         longest = max(len(self.tvg_split[int(i)]) for i in texts)
-        if longest + min(chunk, N) * (C - 1) > self.max_tokens:
-            raise ValueError(f"tvg_gallery: max_tokens = {self.max_tokens} cannot hold one caption prompt ({longest} tokens) and one chunk of {min(chunk, N)} videos "
-                             f"({min(chunk, N) * (C - 1)} tokens)")
+        if longest + min(chunk, L) * (C - 1) > self.max_tokens:
+            raise ValueError(f"tvg_gallery: max_tokens = {self.max_tokens} cannot hold one caption prompt ({longest} tokens) and one chunk of {min(chunk, L)} videos "
+                             f"({min(chunk, L) * (C - 1)} tokens)")
         feats = self.gallery_feats()
         clip = np.arange(C - 1)
         st = _GalleryCall(self, feats)
@@ -637,24 +728,26 @@ class PairScorer(CalibrationMixin):
             pr = self.tvg_split[int(i)]
             plen = len(pr)
             p0 = None
-            for v0 in range(0, N, chunk):
-                n = min(chunk, N - v0)
+            for v0 in range(0, L, chunk):
+                n = min(chunk, L - v0)
                 if st.n_tok and st.n_tok + (plen if p0 is None else 0) + n * (C - 1) > self.max_tokens:
                     yield st.finish(); st = _GalleryCall(self, feats); p0 = None
                 if p0 is None:                           # the prompt is packed once per engine call; every merged sequence of the text names it
                     p0 = st.add_seq(pr, np.arange(plen), None, (0, 0))
-                v = np.arange(v0, v0 + n)
+                at = np.arange(v0, v0 + n)                   # places among the live videos: where gallery_feats() holds their rows
+                v = lv[at]
                 rows = np.full((n, C), p0 + plen - 1, np.int64)
                 if C > 1:
-                    s0 = st.add_seq(-(1 + v[:, None] * C + clip[None, :]).reshape(-1), np.tile(plen + clip, n), np.repeat(np.arange(n) * (C - 1), C - 1), (p0, plen))
+                    s0 = st.add_seq(-(1 + at[:, None] * C + clip[None, :]).reshape(-1), np.tile(plen + clip, n), np.repeat(np.arange(n) * (C - 1), C - 1), (p0, plen))
                     rows[:, 1:] = s0 + np.arange(n)[:, None] * (C - 1) + clip[None, :]
                 st.add_pairs(rows, self.tvg_video_labels[v], q * N + v)
         if st.n_pairs:
             yield st.finish()
 
     def tvg_gallery(self, texts, chunk: Optional[int] = None) -> np.ndarray:
-        """log P(video j | text) of each text against every video -> f32 [Q, N] in video-index order.  Each distinct text is planned once, in ascending index
-        order (iter_tvg_gallery); a value does not depend on which texts are asked for together, in which order, or on where max_tokens cuts the calls."""
+        """log P(video j | text) of each text against every live video -> f32 [Q, N] in video-index order, NaN in the column of a removed video.  Each distinct text
+        is planned once, in ascending index order (iter_tvg_gallery); a value does not depend on which texts are asked for together, in which order, or on where
+        max_tokens cuts the calls."""
         texts = np.asarray(texts, dtype=np.int64).reshape(-1)
         N = len(self.video)
         uniq, inv = np.unique(texts, return_inverse=True)
@@ -691,19 +784,31 @@ class PairScorer(CalibrationMixin):
             yield st.finish()
 
     def _label_inverse(self):
-        """-> (device int64 [n_vocab]: the video of each vocabulary entry, device int64 [N]: tvg_video_labels), memoised per vocab_version with their host copies
-        (_label_inverse_host).  The rank kernel ranks VOCABULARY entries; they name videos only when tvg_video_labels is a permutation of arange(N)."""
+        """-> (device int64 [n_vocab]: the video of each vocabulary entry, device int64 [n_live]: the live videos' labels, ascending by video -- tvg_video_labels
+        itself in a scorer without tombstones), memoised per vocab_version with their host copies (_label_inverse_host: the inverse, and tvg_video_labels in index
+        space).  The rank kernel ranks VOCABULARY entries; they name videos only when the live videos' labels are a permutation of arange(n_vocab)."""
         import torch
         memo = getattr(self, "_label_inv", None)
         if memo is None or memo[0] != self.vocab_version:
             lab = np.asarray(self.tvg_video_labels, dtype=np.int64)
             N = len(self.video)
-            if len(lab) != N or self.n_vocab != N or not np.array_equal(np.sort(lab), np.arange(N)):
-                raise ValueError(f"tvg_first: tvg_video_labels must be a permutation of arange({N}) -- one vocabulary entry per video ({self.n_vocab} entries, "
-                                 f"{len(np.unique(lab))} distinct labels)")
-            inv = np.empty(N, dtype=np.int64)
-            inv[lab] = np.arange(N)
-            memo = self._label_inv = (self.vocab_version, torch.from_numpy(inv).to(self.device), torch.from_numpy(lab).to(self.device), inv, lab)
+            if self._dead:                                                   # (DESIGN.md section 24) the rule over what is left: inv names live videos only
+                at = np.nonzero(self.live)[0]
+                N = len(at)
+                if len(lab) != len(self.video) or self.n_vocab != N or not np.array_equal(np.sort(lab[at]), np.arange(N)):
+                    raise ValueError(f"tvg_first: the live videos' tvg_video_labels must be a permutation of arange({N}) -- one vocabulary entry per live video "
+                                     f"({self.n_vocab} entries, {len(np.unique(lab[at]))} distinct labels)")
+                inv = np.empty(N, dtype=np.int64)
+                inv[lab[at]] = at
+                dev_lab = lab[at]                                            # the labels of the live videos, ascending by video: the live columns of a `full` result
+            else:
+                dev_lab = lab
+                if len(lab) != N or self.n_vocab != N or not np.array_equal(np.sort(lab), np.arange(N)):
+                    raise ValueError(f"tvg_first: tvg_video_labels must be a permutation of arange({N}) -- one vocabulary entry per video ({self.n_vocab} entries, "
+                                     f"{len(np.unique(lab))} distinct labels)")
+                inv = np.empty(N, dtype=np.int64)
+                inv[lab] = np.arange(N)
+            memo = self._label_inv = (self.vocab_version, torch.from_numpy(inv).to(self.device), torch.from_numpy(dev_lab).to(self.device), inv, lab)
         return memo[1], memo[2]
 
     def _label_inverse_host(self):
@@ -718,7 +823,8 @@ class PairScorer(CalibrationMixin):
         within: one array of video indices per text -- text q is ranked inside its own set alone (Engine.score_tvg_first_within).  Each set is made unique and
         sorted by vocabulary entry, so the kernel's position order is the tie order above and the result is the whole-gallery order filtered to the set, every
         value the same bits (the normaliser stays over the whole vocabulary).  Text q gets min(k, len(within[q])) real places, the rest are -1 / NaN; k is then
-        bounded by TVG_RANK_MAX_K alone.  Texts with one prompt still share one packed row."""
+        bounded by TVG_RANK_MAX_K alone.  Texts with one prompt still share one packed row.  After remove_videos nothing changes here: the kernels rank vocabulary
+        entries, so a removed video cannot appear; lp keeps index-space columns [Q, len(video)], NaN in a removed one, and a set that names one is refused."""
         texts = np.asarray(texts, dtype=np.int64).reshape(-1)
         N, k = self.n_vocab, int(k)
         if within is not None:
@@ -729,14 +835,19 @@ class PairScorer(CalibrationMixin):
         idx = np.zeros((len(texts), k), dtype=np.int64)
         val = np.zeros((len(texts), k), dtype=np.float32)
         lp = np.zeros((len(texts), N), dtype=np.float32) if full else None
+        cols = None
+        if full and self._dead:                                              # index-space columns, NaN where a video was removed
+            lp, cols = np.full((len(texts), len(self.video)), np.nan, dtype=np.float32), np.nonzero(self.live)[0]
         done = [(p.out_index, self.run(p, k=k, alpha=float(alpha), full=full)) for p in self.iter_tvg_first(texts, cpn)]
         for out_index, res in done:
             vi, vv = inv[res[0].long()].cpu().numpy(), res[1].cpu().numpy()
             vl = res[2][:, lab].cpu().numpy() if full else None
             for r, outs in enumerate(out_index):
                 idx[outs], val[outs] = vi[r], vv[r]
-                if full:
+                if full and cols is None:
                     lp[outs] = vl[r]
+                elif full:
+                    lp[np.asarray(outs, dtype=np.int64)[:, None], cols[None, :]] = vl[r][None, :]
         return (idx, val, lp) if full else (idx, val)
 
     def _tvg_first_within(self, texts, k: int, cpn: bool, alpha: float, full: bool, within):
@@ -749,13 +860,14 @@ class PairScorer(CalibrationMixin):
             raise ValueError(f"tvg_first: k = {k} outside 1 .. TVG_RANK_MAX_K = {TVG_RANK_MAX_K}")
         if len(within) != len(texts):
             raise ValueError(f"tvg_first: within holds {len(within)} sets for {len(texts)} texts")
-        N = self.n_vocab
+        N = len(self.video) if self._dead else self.n_vocab                  # (the index space; without tombstones the permutation rule makes the two one number)
         inv, lab = self._label_inverse_host()
         entries = []                                                         # per text: its set as vocabulary entries, unique and ascending
         for q, w in enumerate(within):
             w = np.asarray(w, dtype=np.int64).reshape(-1)
             if len(w) and (w.min() < 0 or w.max() >= N):
                 raise ValueError(f"tvg_first: within[{q}] names a video outside 0 .. {N - 1}")
+            self._need_live(w)
             entries.append(np.unique(lab[w]))
         idx = np.full((len(texts), k), -1, dtype=np.int64)
         val = np.full((len(texts), k), np.nan, dtype=np.float32)

@@ -64,10 +64,21 @@ Inside a set of the caller's.  A request may carry `"with
 default K under `--candidates tvg`), with `"prefilter": K0` or the `--prefilter` default optional: the shortlist -- and the prefilter in front of it -- rank the
 videos of the set alone, K and K0 clipped to its size M, and the answer gains `"within": M`.  The clip-0 values are the whole gallery's (the normaliser still runs
 over every registered video, which keeps a score equal to the evaluation's), so the result is the unfiltered order filtered to the set, at the cost of the unfiltered
-request.  A caller can hide taken-down videos this way; removing a video from the gallery is not built.  Both forms at once, `within` with `candidates` /
+request.  A caller can hide a video this way without changing any score; a video that is gone for good is removed (below).  Both forms at once, `within` with `candidates` /
 `candidate_idx` / `first_stage`, `within` with neither a shortlist nor `--candidates tvg`, an empty list, an unknown id and a repeated id each get an error line;
 an `add_video` request refuses the keys as it refuses other query keys, and a set behind the barrier may name the new video.  One-shot: `--within_ids FILE` (one
 video id per line; t2v, `--candidates tvg`) confines every query of the run.  A `within:` stderr line counts the requests that carried a set and the videos named.
+
+Videos leave a running gallery.  A request `{"id", "remove_video": VID}` is answered with {"id", "removed": VID, "index": j, "videos": <live
+count>}; it is validated in full first (an unknown id, an id removed already, the last video of the gallery, a request that also carries query keys and a value that
+is no JSON scalar each get an error line) and it is a barrier exactly as `add_video` is: the requests in front of it are scored against the old gallery and answered
+first, those behind it see the new one, a micro-batch never spans it.  Indices never move: the removed index stays a tombstone, its id and its content digest are
+forgotten -- the same features may join again, under the same or another id, at a new index --, `candidates` / `within` that name it get the "unknown video id"
+words and `candidate_idx` / `within_idx` "video j was removed"; `--candidates all` means the videos that are left, `iv2` the top-k of the first-stage row among
+them.  The vocabulary is registered again without the video's entry, so every later TVG score is that of an evaluation over the gallery as it now is; the cache slot
+of its prefix is free at once, and under `--gallery_fill eager` the next `add_video` is filled into it even with `--gallery_spare 0`.  The EOF `serve:` line gains
+`videos_removed`, and a `removed:` stderr line counts the videos, the slots freed and the host records forgotten -- both only when a removal happened.  There is no
+one-shot flag: a one-shot run simply does not load the video.
 """
 from __future__ import annotations
 
@@ -362,17 +373,23 @@ def query_video_features(files, args, featuriser=None):
             own.close()
 
 
-def default_candidates(mode: str, row, n: int, k: int):
+def default_candidates(mode: str, row, n: int, k: int, live=None):
     """The candidates of a query that names none, under `--candidates iv2 | all` -> (candidate indices, their first-stage scores or None).  row: the query's
     first-stage row, or None for a query that has none (free text, raw rows, a video outside the dataset): then `all` has no first-stage term, and `iv2` is the
-    caller's refusal.  iv2: the stable top-k of the row.  all: the whole gallery of n, the row padded with zeros for the entries that joined at run time."""
+    caller's refusal.  iv2: the stable top-k of the row.  all: the whole gallery of n, the row padded with zeros for the entries that joined at run time.
+    live (bool [n]): the videos that are left -- `all` is those, `iv2` the top-k of the row among them."""
     import numpy as np
     if row is not None:
         row = np.asarray(row, dtype=np.float32)
+    if live is not None:
+        live = np.asarray(live, dtype=bool).reshape(-1)
     if mode == "iv2":
-        cand = np.argsort(-row, kind="stable")[:min(k, n)]
+        order = np.argsort(-row, kind="stable")
+        if live is not None:
+            order = order[live[order]]
+        cand = order[:min(k, n)]
     else:
-        cand = np.arange(n)
+        cand = np.arange(n) if live is None else np.nonzero(live)[0]
         if row is not None:
             row = np.concatenate([row, np.zeros(max(n - len(row), 0), np.float32)])
     return cand, None if row is None else row[cand]
@@ -412,7 +429,8 @@ class Server:
         self.content_hash = content_hash           # feature tensor -> a digest of its content (engine.hash_device on the device copy), or None: contents are not compared
         self.content_of = {}                       # digest -> the id of the run-time video that has this content
         self.featuriser = featuriser               # raw frames uint8 [num_frames, H, W, 3] -> the video's feature tensor (FrameFeaturiser), or None: `frames` is refused
-        self.requests = self.batches = self.errors = self.texts_added = self.videos_added = 0
+        self.requests = self.batches = self.errors = self.texts_added = self.videos_added = self.videos_removed = 0
+        self.removed_ids = set()                   # ids that left and have not joined again: a second removal is refused by name
 
     # ---- one request
     def _rows(self, req):
@@ -455,6 +473,17 @@ class Server:
             self.texts_added += 1
         return t, (f"query:{req['text']}" if "text" in req else f"rows:{t}")
 
+    def _live(self):
+        """-> the scorer's live mask once a video was removed, else None (every caller then does what it always did)."""
+        return self.s.live if getattr(self.s, "_dead", None) else None
+
+    def _refuse_removed(self, idx) -> None:
+        dead = getattr(self.s, "_dead", None)
+        if dead:
+            gone = [int(j) for j in idx if int(j) in dead]
+            if gone:
+                raise BadRequest(f"video {gone[0]} was removed")
+
     def _candidates(self, req, t: int, is_caption: bool):
         """-> (candidate video indices, first-stage scores or None, None), or (None, None, K): the candidates are the best K of the gallery's TVG ranking."""
         np = self.np
@@ -481,6 +510,7 @@ class Server:
             else:
                 if any(isinstance(j, bool) or not isinstance(j, int) or not 0 <= j < N for j in given):
                     raise BadRequest(f"candidate_idx must hold indices in 0 .. {N - 1}")
+                self._refuse_removed(given)
                 cand = given
             if len(set(cand)) != len(cand):
                 raise BadRequest("the candidate list names a video twice")
@@ -491,7 +521,8 @@ class Server:
             row = self.t2v_iv2[t] if self.t2v_iv2 is not None and is_caption else None
             if row is None and self.args.candidates == "iv2":
                 raise BadRequest("a text / rows query has no first-stage row (--candidates iv2): send candidates")
-            cand, fs = default_candidates(self.args.candidates, row, N, self.args.topk)
+            live = self._live()
+            cand, fs = default_candidates(self.args.candidates, row, N, self.args.topk, **({} if live is None else {"live": live}))
         if "first_stage" in req:
             try:
                 fs = np.asarray(req["first_stage"], dtype=np.float32).reshape(-1)
@@ -539,6 +570,7 @@ class Server:
             N = len(self.vids)
             if any(isinstance(j, bool) or not isinstance(j, int) or not 0 <= j < N for j in given):
                 raise BadRequest(f"within_idx must hold indices in 0 .. {N - 1}")
+            self._refuse_removed(given)
             idx = given
         if len(set(idx)) != len(idx):
             raise BadRequest("the within list names a video twice")
@@ -558,7 +590,7 @@ class Server:
         if shortlist is None:
             return None
         try:
-            check_shortlist(shortlist, K0, len(self.vids) if n_videos is None else n_videos)
+            check_shortlist(shortlist, K0, (len(self.vids) - len(getattr(self.s, "_dead", ()))) if n_videos is None else n_videos)
         except ValueError as e:
             raise BadRequest(str(e)) from None
         return K0
@@ -579,6 +611,8 @@ class Server:
                 raise BadRequest("id must be a JSON scalar")
             if "add_video" in req:
                 return self._add_request(rid, req)
+            if "remove_video" in req:
+                return self._remove_request(rid, req)
             topk = req.get("topk")
             if topk is not None and (isinstance(topk, bool) or not isinstance(topk, int) or topk < 1):
                 raise BadRequest("topk must be a positive integer")
@@ -599,11 +633,13 @@ class Server:
             e.id = rid
             raise
 
+    QUERY_KEYS = ("caption", "text", "rows", "candidates", "candidate_idx", "first_stage", "shortlist", "prefilter", "topk", "within", "within_idx")
+
     # ---- a video that joins
     def _add_request(self, rid, req):
         """`{"id", "add_video": {"vid", "features" | "frames"}}`, validated in full before anything changes -> dict(id, add: (vid, tensor, digest)).  `frames` (a
         .npy stack of raw frames) goes through the vision tower first and is a `features` request from there on."""
-        if any(k in req for k in ("caption", "text", "rows", "candidates", "candidate_idx", "first_stage", "shortlist", "prefilter", "topk", "within", "within_idx")):
+        if any(k in req for k in self.QUERY_KEYS + ("remove_video",)):
             raise BadRequest("an add_video request carries no query")
         a = req["add_video"]
         if not isinstance(a, dict) or set(a) not in ({"vid", "features"}, {"vid", "frames"}):
@@ -641,11 +677,54 @@ class Server:
             return
         self.vids.append(vid if isinstance(vid, str) else str(vid))
         self.vid_at[str(vid)] = j
+        self.removed_ids.discard(str(vid))
         self.n_vid = self.np.append(self.n_vid, int(self.np.prod(feat.shape[-3:-1])))
         if digest is not None:
             self.content_of[digest] = self.vids[-1]
         self.videos_added += 1
-        write(json.dumps({"id": item["id"], "added": self.vids[-1], "index": j, "videos": len(self.vids)}))
+        write(json.dumps({"id": item["id"], "added": self.vids[-1], "index": j, "videos": int(self.s.n_live)}))      # (the videos the gallery holds: the index space less the removed ones)
+
+    # ---- a video that leaves
+    def _remove_request(self, rid, req):
+        """`{"id", "remove_video": VID}`, validated in full before anything changes -> dict(id, remove: (VID as the gallery names it, its index))."""
+        if any(k in req for k in self.QUERY_KEYS):
+            raise BadRequest("a remove_video request carries no query")
+        vid = req["remove_video"]
+        if isinstance(vid, (bool, dict, list)) or vid is None or str(vid) == "":
+            raise BadRequest("remove_video takes the id of a video of the gallery: a non-empty string or a number")
+        key = str(vid)
+        if key not in self.vid_at:
+            raise BadRequest(f"video id {vid!r} was removed already" if key in self.removed_ids else f"unknown video id {vid!r}")
+        if self.s.n_live <= 1:
+            raise BadRequest(f"video id {vid!r} is the last video of the gallery: at least one video must remain")
+        j = self.vid_at[key]
+        try:
+            self.s.check_removal([j])
+        except ValueError as e:
+            raise BadRequest(str(e)) from None
+        return {"id": rid, "remove": (key, j)}
+
+    def _remove(self, item, write) -> None:
+        """The video leaves: the scorer (a tombstone; its vocabulary registered again without the entry), the id map and the content digests -- the same features
+        may join again, under the same or another id, at a new index; the index follows before its next pass (_PrefixIndex._follow_removed)."""
+        key, j = item["remove"]
+        try:
+            self.s.remove_videos([j])
+        except ValueError as e:                    # (parse checked it already: what it did not foresee)
+            self.errors += 1
+            write(json.dumps({"id": item["id"], "error": str(e)}))
+            return
+        del self.vid_at[key]
+        self.removed_ids.add(key)
+        for j2, v in enumerate(self.vids):         # (an id that appears twice names its first video: now the next one that is left)
+            if str(v) == key and j2 not in self.s._dead:
+                self.vid_at[key] = j2
+                self.removed_ids.discard(key)
+                break
+        self.n_vid[j] = 0                          # (a tombstone adds nothing to the longest prefix a request may meet)
+        self.content_of = {d: v for d, v in self.content_of.items() if str(v) != key or key in self.vid_at}
+        self.videos_removed += 1
+        write(json.dumps({"id": item["id"], "removed": self.vids[j], "index": j, "videos": int(self.s.n_live)}))
 
     # ---- one batch
     def _score(self, reqs):
@@ -668,11 +747,11 @@ class Server:
                 item = self.parse(ln)
             except BadRequest as e:
                 item = e
-            if isinstance(item, dict) and "add" in item:
+            if isinstance(item, dict) and ("add" in item or "remove" in item):
                 self._answer(items, write)
                 items = []
                 self.requests += 1
-                self._add(item, write)
+                (self._add if "add" in item else self._remove)(item, write)
             else:
                 items.append(item)
         self._answer(items, write)
@@ -708,6 +787,8 @@ class Server:
 
     def summary(self):
         more = {"videos_added": self.videos_added} if self.videos_added else {}             # (a stream without an add_video request: the line it always was)
+        if self.videos_removed:                                                             # (likewise without a remove_video request)
+            more["videos_removed"] = self.videos_removed
         return {"requests": self.requests, "batches": self.batches, "mean_batch": self.requests / self.batches if self.batches else 0.0, "errors": self.errors,
                 "texts_added": self.texts_added, **more}
 
@@ -861,9 +942,9 @@ def gallery_banner(args, indexes, ready: float) -> str:
             f"tvg mode {s.tvg_mode}, {narrow}, built in {tg.build_seconds:.2f}s {ready}")
 
 
-def report_lines(indexes, serve_summary=None, shortlist_stats=None, prefilter_stats=None, within_stats=None):
+def report_lines(indexes, serve_summary=None, shortlist_stats=None, prefilter_stats=None, within_stats=None, removed_stats=None):
     """The closing stderr lines of a run over `indexes` ([(name, index)]: "gallery", and "text gallery" under v2t), in one order: what the caches did, what their
-    host tiers did (where there is one), `serve:`, `shortlist:` and `prefilter:` (where a pass of theirs ran), `within:` (where a request carried a set)."""
+    host tiers did (where there is one), `serve:`, `shortlist:` and `prefilter:` (where a pass of theirs ran), `within:` (where a request carried a set), `removed:` (where a video left the gallery)."""
     tier = lambda h: json.dumps(dict(h.stats.as_dict(), records=h.n_records, record_bytes=h.record_bytes))
     lines = ["; ".join(f"{name} stats: {json.dumps(ix.stats.as_dict())}" for name, ix in indexes)]
     if any(ix.host is not None for _, ix in indexes):
@@ -876,6 +957,8 @@ def report_lines(indexes, serve_summary=None, shortlist_stats=None, prefilter_st
         lines.append(f"prefilter: {json.dumps(_prefilter_line(prefilter_stats))}")
     if within_stats is not None and within_stats["queries"]:
         lines.append(f"within: {json.dumps(_within_line(within_stats))}")
+    if removed_stats is not None and removed_stats["videos"]:
+        lines.append(f"removed: {json.dumps(_removed_line(removed_stats))}")
     return lines
 
 
@@ -892,6 +975,11 @@ def _prefilter_line(stats):
 def _within_line(stats):
     """The `within:` stderr line: queries confined to a set of the caller's, and the videos those sets held."""
     return {"queries": int(stats["queries"]), "candidates": int(stats["candidates"])}
+
+
+def _removed_line(stats):
+    """The `removed:` stderr line: videos that left the gallery, the cache slots their prefixes gave back and the host records forgotten with them."""
+    return {"videos": int(stats["videos"]), "slots_freed": int(stats["slots_freed"]), "records_forgotten": int(stats["records_forgotten"])}
 
 
 def read_within_ids(path, vids):
@@ -932,6 +1020,8 @@ def run_serve(gal, vids, t2v_iv2, args, write, lines, build_rows=None, content_h
     featuriser = FrameFeaturiser(args)             # (the tower is created when the first add_video request brings frames)
     server = Server(gal, vids, len(gal.s.vtg_split), t2v_iv2, args, finetuned=bool(args.resume), build_rows=build_rows, content_hash=content_hash, featuriser=featuriser)
     summary = serve(lines, write, server, args.batch_queries, args.batch_wait_ms)
+    if server.videos_removed:                      # (a removal no pass came after: the index follows it now, so that the `removed:` line counts it)
+        gal._follow_removed()
     featuriser.close()
     return summary
 
@@ -1018,7 +1108,7 @@ def main(args):
     else:
         run_t2v(gal, vids, p.t2v_iv2, args, write, within)
     close_output()
-    for line in report_lines(indexes, summary, shortlisted, prefiltered, getattr(gal, "within_stats", None)):
+    for line in report_lines(indexes, summary, shortlisted, prefiltered, getattr(gal, "within_stats", None), getattr(gal, "removed_stats", None)):
         print(line, file=sys.stderr, flush=True)
     for _, ix in reversed(indexes):
         ix.close()

@@ -73,6 +73,17 @@ in one process and checked bit-equal (a tvg_gallery query too), with the engine'
 
     python tools/gallery_bench.py --grow 8 --modes none --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r24_gallery_grow.json
 
+`--grow K --remove` (t2v): videos that leave a running gallery, with r24's protocol.  Scorers over all N videos, with an eager index (no spare
+slot) and gallery_feats() made, lose K videos spread over the gallery through PairScorer.remove_videos -- one video per call on one scorer, all K in one call on
+another -- timed per removed video: remove_videos (the checks, the tombstones, the vocabulary registered again), the re-registration alone (Engine.set_video_vocab over
+the surviving rows), the gallery_feats() rebuild and the index sync (_sync_videos: keys, stamps and slots dropped).  Then a REPLACEMENT on the eager index with no spare
+slot -- remove one video, add one, sync: the new prefix is filled into the freed slot -- against the only alternative without removal, measured in the same script: the
+model loaded again and the index built again over the new set.  Then the stream of Q queries x top-k (candidates among the survivors) over the index after K removals
+against an index built from the survivors, alternated `--reps` times in one process and checked bit-equal through the index map (a tvg_gallery query too), with the
+engine's timing classes of one stream each.
+
+    python tools/gallery_bench.py --grow 8 --remove --modes none --n 1000 --queries 55 --k 16 --synthetic_7b --out profiles/r29_gallery_remove.json
+
 `--shortlist K --prefilter K0 [K0 ...]` (t2v): `--shortlist`'s protocol (the fine-tuned blend, the narrow options on auto, one eager index,
 `--gallery_gb` caps it) for the shortlist of K alone -- the parent's `--candidates tvg`, stage 1 over the whole gallery -- against the cascade at each K0: stage 0
 (GalleryIndex._stage0: one logits row per query, ranked on the device), stage 1 (PairScorer.tvg over the K0 survivors), stage 2 (the cached VTG rerank of the best K),
@@ -135,6 +146,7 @@ def main():
     ap.add_argument("--rank_kernel", action="store_true", help="--prefilter: also the rank kernel alone against the copy to the host plus np.argsort")
     ap.add_argument("--gallery_gb", type=float, default=None, help="--prefilter: device memory for the prefix cache (default: every video)")
     ap.add_argument("--grow", type=int, default=None, metavar="K", help="the index built over N - K videos and grown by K (PairScorer.add_videos) against one built over all N (t2v)")
+    ap.add_argument("--remove", action="store_true", help="--grow K: the other way round -- K videos leave an index built over all N (PairScorer.remove_videos) against one built from the survivors")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dims = synth.ModelDims() if a.synthetic_7b else synth.ModelDims(vocab_size=151700, hidden_size=256, intermediate_size=512, num_layers=2, num_heads=2,
@@ -154,6 +166,8 @@ def main():
         return main_narrow_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc, option="narrow_qkv" if a.narrow_qkv else "narrow_lo6")
     if a.direction == "v2t":
         return main_v2t(a, dims, model, prob, vtg, tvg, video, q, tpc)
+    if a.grow and a.remove:
+        return main_remove(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.grow:
         return main_grow(a, dims, model, prob, vtg, tvg, video, q, tpc)
     if a.shortlist and a.prefilter:
@@ -559,6 +573,141 @@ def main_grow(a, dims, model, prob, vtg, tvg, video, q, tpc):
         print(json.dumps({mode: r}), flush=True)
         gal1.close(); ref_gal.close()
         del sc1, sc2, whole
+        torch.cuda.empty_cache()
+    if a.out:
+        os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+    model.engine.close()
+
+
+def main_remove(a, dims, model, prob, vtg, tvg, video, q, tpc):
+    """`--grow K --remove`: K videos leave a gallery built over all N, against one built from the survivors (see the module text)."""
+    e = model.engine
+    N, K = a.n, int(a.grow)
+    med = lambda x: float(np.median(x))
+    spread = lambda x: float((max(x) - min(x)) / np.median(x)) if len(x) > 1 else 0.0
+    ms = lambda x: [1e3 * float(t) for t in x]
+    vocab = torch.from_numpy(prob.video_vocab)
+    gone = np.unique(np.linspace(1, N - 2, K).round().astype(np.int64))            # the videos that leave: spread over the gallery, never a query's own
+    gone = np.array([j for j in gone if j not in set(q.tolist())], dtype=np.int64)
+    K = len(gone)
+    keep = np.array([j for j in range(N) if j not in set(gone.tolist())], dtype=np.int64)
+    place = -np.ones(N, dtype=np.int64); place[keep] = np.arange(len(keep))         # a survivor's index in the gallery built from the survivors
+    sims = prob.t2v_sims[q].copy(); sims[:, gone] = -np.inf
+    cand = np.argsort(-sims, axis=1, kind="stable")[:, :a.k]                        # candidates among the survivors
+    res = {"remove": K, "removed": gone.tolist(), "n": N, "queries": a.queries, "k": a.k, "dtype": a.dtype, "dims": "7B" if a.synthetic_7b else "tiny", "video_tokens": 4 * tpc,
+           "reps": a.reps, "modes": {}}
+
+    def scorer(ids):
+        ids = [int(j) for j in ids]
+        sc = RU.PairScorer(DDPLike(model), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], [video[j] for j in ids], vocab[ids], torch.arange(len(ids)), dims.num_clips,
+                           max_tokens=a.max_tokens)
+        sc.set_vtg_mode(model.vtg_mode())
+        sc.set_tvg_mode(model.tvg_mode())
+        return sc
+
+    for mode in a.modes.split(","):
+        model.vtg_precise = None if mode == "none" else mode
+        model.tvg_precise = a.tvg_modes.split(",")[0]
+        model.clear_cache()
+        fresh = scorer(keep)
+        fresh.vtg(np.stack([np.arange(8), np.full(8, q[0])], axis=1))               # warm-up: workspaces sized
+        ref_gal = GalleryIndex(fresh)
+        t_build, _ = timed(ref_gal.build)
+        t_feats, _ = timed(fresh.gallery_feats)
+        r = {"from_survivors": {"build_s": t_build, "slots": len(ref_gal.slot_of), "gallery_feats_s": t_feats}}
+
+        def shrunk(batch):
+            """A scorer over all N videos with its eager index built and gallery_feats() made, losing K videos one at a time or in one call."""
+            sc = scorer(range(N))
+            eager = GalleryIndex(sc, spare_slots=0)
+            tb, _ = timed(eager.build)
+            sc.gallery_feats()
+            steps = [gone.tolist()] if batch else [[int(j)] for j in gone]
+            t = {"remove_videos": [], "gallery_feats": [], "index_sync": []}
+            for js in steps:
+                dt, _ = timed(lambda: sc.remove_videos(js)); t["remove_videos"].append(dt / len(js))
+                dt, _ = timed(sc.gallery_feats); t["gallery_feats"].append(dt / len(js))
+                dt, _ = timed(eager._sync_videos); t["index_sync"].append(dt / len(js))
+                assert not any(k[0] in js for k in eager.keys) and not any(k[0] in js for k in eager.slot_of)
+            assert eager.removed_stats == {"videos": K, "slots_freed": K, "records_forgotten": 0} and sc.n_live == N - K
+            out = {"build_s": tb, "calls": len(steps), **{k + "_ms_per_video": {"median": med(ms(v)), "min": min(ms(v)), "max": max(ms(v)), "first_call": ms(v)[0]} for k, v in t.items()}}
+            return sc, eager, out
+
+        sc1, gal1, r["one_at_a_time"] = shrunk(False)
+        sc2, gal2, r["one_batch"] = shrunk(True)
+        gal2.close()
+        # the re-registration alone: the surviving rows through the engine's split
+        t_reg = [timed(lambda: e.set_video_vocab(sc1._vocab_src))[0] for _ in range(max(a.reps, 3))]
+        r["set_video_vocab_ms"] = {"rows": int(sc1.n_vocab), "bytes": int(sc1._vocab_src.numel() * 4), "median": med(ms(t_reg)), "min": min(ms(t_reg)), "spread": spread(t_reg)}
+        # the same stream after the removals and from the survivors
+        stream = lambda gal, at: [gal.rerank([int(t)], at[cand[i]][None]) for i, t in enumerate(q)]
+        ident = np.arange(N)
+        ref = stream(ref_gal, place); stream(gal1, ident)
+        ts = {"removed": [], "from_survivors": []}
+        for _ in range(a.reps):
+            for leg, gal, at in (("removed", gal1, ident), ("from_survivors", ref_gal, place)):
+                dt, got = timed(lambda: stream(gal, at)); ts[leg].append(dt)
+                back = ident if leg == "removed" else keep
+                assert all(np.array_equal(back[o], keep[o1]) and np.array_equal(b, b1) for (o, b), (o1, b1) in zip(got, ref)), f"{leg}: the stream's results differ"
+        classes = {}
+        for leg, gal, at in (("removed", gal1, ident), ("from_survivors", ref_gal, place)):
+            e.timing_enable(True); e.timing_report()
+            stream(gal, at)
+            classes[leg] = {k: x for k, x in e.timing_report().items() if x["calls"]}
+            e.timing_enable(False)
+        same = {k: x["calls"] for k, x in classes["removed"].items()} == {k: x["calls"] for k, x in classes["from_survivors"].items()}
+        tokens = {leg: int(sum(p.n_tokens for i, t in enumerate(q) for p in gal.iter_plans(np.stack([at[cand[i]], np.full(a.k, t)], axis=1))))
+                  for leg, gal, at in (("removed", gal1, ident), ("from_survivors", ref_gal, place))}
+        r["stream"] = {leg: {"s": ts[leg], "ms_per_query": 1e3 * med(ts[leg]) / len(q), "spread": spread(ts[leg]), "packed_tokens": tokens[leg]} for leg in ts}
+        r["stream"].update(ratio_removed_to_from_survivors=med(ts["removed"]) / med(ts["from_survivors"]), same_classes_and_calls=bool(same), classes=classes,
+                           stats_removed=gal1.stats.as_dict(), stats_from_survivors=ref_gal.stats.as_dict())
+        texts = [int(q[0]), int(q[-1])]
+        dt1, g1 = timed(lambda: sc1.tvg_gallery(texts)); dt2, g2 = timed(lambda: fresh.tvg_gallery(texts))
+        assert np.array_equal(g1[:, keep], g2) and np.isnan(g1[:, gone]).all(), "tvg_gallery over the scorer with removals differs from the survivors' scorer's"
+        r["tvg_gallery_two_texts_ms"] = {"removed": 1e3 * dt1, "from_survivors": 1e3 * dt2, "bit_equal": True}
+        # a replacement on the eager index with no spare slot, against the model loaded and the index built again over the new set
+        out_j = int(keep[len(keep) // 2])
+        t_rep = {}
+        t_rep["remove_videos"], _ = timed(lambda: sc1.remove_videos([out_j]))
+        t_rep["add_videos"], new = timed(lambda: sc1.add_videos([video[int(gone[0])]], vocab[[int(gone[0])]]))
+        t_rep["index_sync_and_fill"], _ = timed(gal1._sync_videos)
+        new_key = [k for k in gal1.keys if k[0] == int(new[0])]
+        assert new_key and all(k in gal1.slot_of for k in new_key), "the new video's prefix was not filled into the freed slot"
+        pairs = np.stack([np.full(4, int(new[0])), q[:4]], axis=1)
+        before = gal1.stats.as_dict()
+        t_rep["first_query_of_the_new_video"], got = timed(lambda: gal1.vtg_pairs(pairs))
+        assert gal1.stats.hits - before["hits"] == len(new_key) and gal1.stats.misses == before["misses"], "the new video was not served from a cached slot"
+        after = [j for j in keep if j != out_j] + [int(gone[0])]
+
+        def rebuild():
+            """-> (seconds of the model load, seconds of the scorer and the index build, the new video's scores)."""
+            torch.cuda.synchronize()
+            t_start = time.perf_counter()
+            m2 = BlimModel(dims, dtype=a.dtype)
+            m2.engine.init_synthetic_weights(0)
+            m2.set_tvg_prefix_length(prob.tvg_prefix_length)
+            m2.vtg_precise, m2.tvg_precise = model.vtg_precise, model.tvg_precise
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            s2 = RU.PairScorer(DDPLike(m2), vtg[0], vtg[2], vtg[1], tvg[0], tvg[2], tvg[1], [video[j] for j in after], vocab[[int(j) for j in after]], torch.arange(len(after)),
+                               dims.num_clips, max_tokens=a.max_tokens)
+            s2.set_vtg_mode(m2.vtg_mode())
+            g2_ = GalleryIndex(s2).build()
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            want = g2_.vtg_pairs(np.stack([np.full(4, len(after) - 1), q[:4]], axis=1))
+            g2_.close(); m2.engine.close()
+            return t0 - t_start, dt, want
+        t_load, t_index, want = rebuild()
+        assert np.array_equal(got, want), "the replaced video's scores differ from a rebuilt gallery's"
+        r["replacement"] = {"removed": out_j, "added_as": int(new[0]), **{k + "_ms": 1e3 * v for k, v in t_rep.items()},
+                            "total_ms": 1e3 * (t_rep["remove_videos"] + t_rep["add_videos"] + t_rep["index_sync_and_fill"]),
+                            "rebuild": {"model_load_s": t_load, "scorer_and_index_build_s": t_index, "total_s": t_load + t_index}, "bit_equal": True}
+        res["modes"][mode] = r
+        print(json.dumps({mode: r}), flush=True)
+        gal1.close(); ref_gal.close()
+        del sc1, sc2, fresh
         torch.cuda.empty_cache()
     if a.out:
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
