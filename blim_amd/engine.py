@@ -612,7 +612,7 @@ class Engine:
     def score_vtg(self, batch: PackedBatch, embeds, rows, labels, row_start, **cached):
         return self._score("blim_score_vtg", batch, embeds, rows, (_ptr(labels), rows.shape[0], _ptr(row_start)), row_start.shape[0] - 1, **cached)
 
-    # ---- gallery prefix cache (blim.h: blim_prefix_cache_*; blim_amd/gallery.py)
+    # ---- gallery prefix cache (blim.h: blim_prefix_cache_*; blim_amd/prefix_index.py)
     def prefix_cache_bytes(self, n_slots: int, max_len: int, compensated: bool) -> int:
         return int(self.lib.blim_prefix_cache_bytes(self.h, int(n_slots), int(max_len), int(bool(compensated))))
 
@@ -749,7 +749,7 @@ class PrefixCache:
     def slot_len(self, slot: int) -> int:
         return int(self.lib.blim_prefix_cache_slot_len(self.h, int(slot)))
 
-    # ---- slot export / import (blim.h: blim_prefix_cache_export / _import; blim_amd/gallery.py: HostTier)
+    # ---- slot export / import (blim.h: blim_prefix_cache_export / _import; blim_amd/prefix_index.py: HostTier)
     def record_bytes(self, length: int) -> int:
         """Bytes of the packed record of a slot with `length` filled positions (a multiple of 256; -1: length outside 1 .. max_len)."""
         return int(self.lib.blim_prefix_cache_record_bytes(self.h, int(length)))

@@ -41,7 +41,7 @@ class Plan:
     out_index: np.ndarray      # host: which requested pair each scored pair answers (many-to-one allowed)
     n_tokens: int
     n_rows: int
-    pfx_slot: Optional[object] = None            # planned over a prefix source (blim_amd/gallery.py): device int32 per sequence, the cache slot of its prefix (-1: in the batch)
+    pfx_slot: Optional[object] = None            # planned over a prefix source (blim_amd/prefix_index.py): device int32 per sequence, the cache slot of its prefix (-1: in the batch)
     slots_used: Optional[np.ndarray] = None      # ... host int32: every slot the call reads
     admits: Optional[np.ndarray] = None          # ... host int32 [n, 5] = (seq, slot, start, len, row): in-batch prefixes the call also captures into slots (a source with `admit`)
     prefix_tokens: int = 0                       # ... of n_tokens, those of in-batch prefix sequences
@@ -287,6 +287,15 @@ class PairScorer(CalibrationMixin):
     def n_live(self) -> int:
         return len(self.video) - len(self._dead)
 
+    @property
+    def removed(self) -> frozenset:
+        """The indices remove_videos took out: what other modules ask instead of the storage."""
+        return frozenset(self._dead)
+
+    def live_videos(self) -> np.ndarray:
+        """int64, ascending: the indices of the videos that are left."""
+        return np.nonzero(self.live)[0]
+
     def _need_live(self, videos) -> None:
         """ValueError that names the first removed video among `videos` (any array of video indices)."""
         if self._dead:
@@ -502,7 +511,7 @@ class PairScorer(CalibrationMixin):
         return items
 
     def _pack_vtg(self, items, slots=None):
-        """Packs groups into super-batches.  slots: a prefix source (blim_amd/gallery.py: `slot_of` {(video, pre, post): slot} and `cache.slot_len`) -- a group whose
+        """Packs groups into super-batches.  slots: a prefix source (blim_amd/prefix_index.py: `slot_of` {(video, pre, post): slot} and `cache.slot_len`) -- a group whose
         prefix it holds packs no prefix sequence: its sequences name the slot and each pair's first row is -(slot + 1).  A source with an `admit(key)` hook (a lazy
         index) is offered every prefix that had to be packed: when it returns a slot, the plan records the admission of that prefix sequence (Plan.admits; its row is
         the position of the prefix's last token in `rows`).  The group itself keeps the in-batch prefix: a slot is readable from the next call on."""
@@ -576,7 +585,7 @@ class PairScorer(CalibrationMixin):
 
     def _plan_tvg(self, pairs: np.ndarray, cpn: bool, box, base: int, slots=None):
         """Plans one TVG pass into the pack state box[0] (replaced whenever a call is full and yielded); output slot of pair p = base + p.  slots: a prefix source
-        (blim_amd/gallery.py: `slot_of` {caption prompt bytes: slot} and `cache.slot_len`) -- a text whose prompt it holds packs no prompt: its merged sequences name
+        (blim_amd/prefix_index.py: `slot_of` {caption prompt bytes: slot} and `cache.slot_len`) -- a text whose prompt it holds packs no prompt: its merged sequences name
         the slot and each pair's first row is -(slot + 1).  The priors (cpn) have no cached form."""
         C = self.num_clips
         st = box[0]
@@ -892,7 +901,7 @@ class PairScorer(CalibrationMixin):
     # ---- execution (device) ---------------------------------------------------------------------
     @contextmanager
     def _call_options(self, kind: str):
-        """The engine options every call of `kind` runs under, for the length of the call.  A prefix cache's fills run under it too (blim_amd/gallery.py): the
+        """The engine options every call of `kind` runs under, for the length of the call.  A prefix cache's fills run under it too (blim_amd/prefix_index.py): the
         engine refuses a slot whose fill ran under other options than the call that reads it."""
         if kind == "vtg":
             comp = self.vtg_mode in VTG_SPLIT_MODES                          # None | "full" | "select"

@@ -406,6 +406,14 @@ def answer_line(query: str, ranked_as: str, ranked, scores, shortlisted=None, pr
     return json.dumps({**(head or {}), "query": query, ranked_as: list(ranked), "scores": [float(x) for x in scores], **more})
 
 
+def video_index_of(vids) -> dict:
+    """The id map, stated once: {str(id): video index}; an id that appears twice names its first video."""
+    at = {}
+    for j, v in enumerate(vids):
+        at.setdefault(str(v), j)
+    return at
+
+
 class BadRequest(ValueError):
     """A request that gets an error line; the process goes on."""
 
@@ -420,9 +428,7 @@ class Server:
         self.np = np
         self.gal, self.s = gal, gal.s
         self.vids = [v for v in vids]
-        self.vid_at = {}
-        for j, v in enumerate(self.vids):          # (an id that appears twice names its first video)
-            self.vid_at.setdefault(str(v), j)
+        self.vid_at = video_index_of(self.vids)
         self.n_captions, self.t2v_iv2, self.args, self.finetuned, self.build_rows = int(n_captions), t2v_iv2, args, bool(finetuned), build_rows
         self.n_vid = np.array([int(np.prod(v.shape[-3:-1])) for v in self.s.video], dtype=np.int64)      # video tokens of each prefix, as the planner counts them
         self.text_of = {}                          # row bytes -> text index
@@ -473,16 +479,32 @@ class Server:
             self.texts_added += 1
         return t, (f"query:{req['text']}" if "text" in req else f"rows:{t}")
 
-    def _live(self):
-        """-> the scorer's live mask once a video was removed, else None (every caller then does what it always did)."""
-        return self.s.live if getattr(self.s, "_dead", None) else None
-
     def _refuse_removed(self, idx) -> None:
-        dead = getattr(self.s, "_dead", None)
-        if dead:
-            gone = [int(j) for j in idx if int(j) in dead]
-            if gone:
-                raise BadRequest(f"video {gone[0]} was removed")
+        """Names the first removed index in the request's own order (PairScorer._need_live names the lowest)."""
+        removed = self.s.removed
+        gone = [int(j) for j in idx if int(j) in removed]
+        if gone:
+            raise BadRequest(f"video {gone[0]} was removed")
+
+    def _named(self, req, ids_key: str, idx_key: str, word: str, opens: str = ""):
+        """The id-list rule, stated once: req[ids_key] (video ids as printed in `videos`) or req[idx_key] (indices) -> video indices in the request's order, a
+        list.  An unknown id, an index that is no integer of 0 .. N - 1, a removed index and a video named twice are refused; `word` names the list in the
+        messages and `opens` opens the unknown-id one."""
+        given = req.get(ids_key, req.get(idx_key))
+        if ids_key in req:
+            unknown = [v for v in given if str(v) not in self.vid_at]
+            if unknown:
+                raise BadRequest(f"{opens}unknown video id {unknown[0]!r}")
+            idx = [self.vid_at[str(v)] for v in given]
+        else:
+            N = len(self.vids)
+            if any(isinstance(j, bool) or not isinstance(j, int) or not 0 <= j < N for j in given):
+                raise BadRequest(f"{idx_key} must hold indices in 0 .. {N - 1}")
+            self._refuse_removed(given)
+            idx = given
+        if len(set(idx)) != len(idx):
+            raise BadRequest(f"the {word} list names a video twice")
+        return idx
 
     def _candidates(self, req, t: int, is_caption: bool):
         """-> (candidate video indices, first-stage scores or None, None), or (None, None, K): the candidates are the best K of the gallery's TVG ranking."""
@@ -502,27 +524,14 @@ class Server:
             given = req.get("candidates", req.get("candidate_idx"))
             if not isinstance(given, list) or not given:
                 raise BadRequest("the candidate list is empty")
-            if "candidates" in req:
-                unknown = [v for v in given if str(v) not in self.vid_at]
-                if unknown:
-                    raise BadRequest(f"unknown video id {unknown[0]!r}")
-                cand = [self.vid_at[str(v)] for v in given]
-            else:
-                if any(isinstance(j, bool) or not isinstance(j, int) or not 0 <= j < N for j in given):
-                    raise BadRequest(f"candidate_idx must hold indices in 0 .. {N - 1}")
-                self._refuse_removed(given)
-                cand = given
-            if len(set(cand)) != len(cand):
-                raise BadRequest("the candidate list names a video twice")
-            cand = np.asarray(cand, dtype=np.int64)
+            cand = np.asarray(self._named(req, "candidates", "candidate_idx", "candidate"), dtype=np.int64)
         elif self.args.candidates == "tvg":
             return self._shortlisted(req, t, shortlist_k(self.args))
         else:
             row = self.t2v_iv2[t] if self.t2v_iv2 is not None and is_caption else None
             if row is None and self.args.candidates == "iv2":
                 raise BadRequest("a text / rows query has no first-stage row (--candidates iv2): send candidates")
-            live = self._live()
-            cand, fs = default_candidates(self.args.candidates, row, N, self.args.topk, **({} if live is None else {"live": live}))
+            cand, fs = default_candidates(self.args.candidates, row, N, self.args.topk, live=self.s.live)
         if "first_stage" in req:
             try:
                 fs = np.asarray(req["first_stage"], dtype=np.float32).reshape(-1)
@@ -559,22 +568,9 @@ class Server:
             raise BadRequest("within / within_idx must be a list")
         if not given:
             raise BadRequest("the within list is empty")
-        if "within" in req:
-            if any(isinstance(v, (dict, list)) for v in given):
-                raise BadRequest("within must hold video ids")
-            unknown = [v for v in given if str(v) not in self.vid_at]
-            if unknown:
-                raise BadRequest(f"within: unknown video id {unknown[0]!r}")
-            idx = [self.vid_at[str(v)] for v in given]
-        else:
-            N = len(self.vids)
-            if any(isinstance(j, bool) or not isinstance(j, int) or not 0 <= j < N for j in given):
-                raise BadRequest(f"within_idx must hold indices in 0 .. {N - 1}")
-            self._refuse_removed(given)
-            idx = given
-        if len(set(idx)) != len(idx):
-            raise BadRequest("the within list names a video twice")
-        return np.sort(np.asarray(idx, dtype=np.int64))
+        if "within" in req and any(isinstance(v, (dict, list)) for v in given):
+            raise BadRequest("within must hold video ids")
+        return np.sort(np.asarray(self._named(req, "within", "within_idx", "within", opens="within: "), dtype=np.int64))
 
     def _prefilter(self, req, shortlist, n_videos=None):
         """-> the K0 of a shortlisted request: its own `"prefilter"`, else --prefilter for a request that takes the default K; None: not prefiltered.  The
@@ -590,7 +586,7 @@ class Server:
         if shortlist is None:
             return None
         try:
-            check_shortlist(shortlist, K0, (len(self.vids) - len(getattr(self.s, "_dead", ()))) if n_videos is None else n_videos)
+            check_shortlist(shortlist, K0, (len(self.vids) - len(self.s.removed)) if n_videos is None else n_videos)
         except ValueError as e:
             raise BadRequest(str(e)) from None
         return K0
@@ -717,7 +713,7 @@ class Server:
         del self.vid_at[key]
         self.removed_ids.add(key)
         for j2, v in enumerate(self.vids):         # (an id that appears twice names its first video: now the next one that is left)
-            if str(v) == key and j2 not in self.s._dead:
+            if str(v) == key and j2 not in self.s.removed:
                 self.vid_at[key] = j2
                 self.removed_ids.discard(key)
                 break
@@ -990,9 +986,7 @@ def read_within_ids(path, vids):
             ids = [ln.strip() for ln in f if ln.strip()]
     except OSError as e:
         raise SystemExit(f"search: --within_ids: {e}") from None
-    at = {}
-    for j, v in enumerate(vids):
-        at.setdefault(str(v), j)
+    at = video_index_of(vids)
     if not ids:
         raise SystemExit(f"search: --within_ids {path}: an empty set of videos")
     unknown = [v for v in ids if v not in at]
